@@ -1,6 +1,12 @@
 """Benchmark of the PT-RWM hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --full                            (also every other reading below)
+    python bench.py ... --dump-outputs DIR                (also the arrays of the last timed step, DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value, unit, ms_per_step, dtype,
+config, ranks).  `--full` adds the objects described below (roofline, other_single_gpu_readings, cpu_baseline,
+summary), which take runs and passes of their own.
 
 A bench "step" is ONE launch of the fused kernel over the rank's whole batch: `--inner` Metropolis steps
 (default 2000 = 200 swap periods, ~0.11 s per launch, so that the driver's 20-launch timed region is > 2 s of steady
@@ -12,7 +18,13 @@ disjoint blocks of global ladder ids, no collective on the data path; one summar
 metric = chain-MH-steps/s: one unit = one (ladder, temperature) replica advancing one Metropolis step.
 Inputs are resident in HBM before the timed region (state is generated on the device).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+--dump-outputs DIR: after the timed steps (before any --full reading touches the run), rank 0 writes what a caller of
+run.advance() holds after the last timed step: state [L, T, D] float32, logp [L, T] float32 and the per-replica
+statistics n_accept, sq_jump, swap_accept, last_swap_ordinal [L, T] as float64, for L ladders - all of them, or a fixed
+seeded sample when the whole batch is above 48 MiB (ladder ids in ladder_index.npy).  Inputs are seeded (Philox seed
+42, NumPy seed 1234), so the same arguments give the same inputs on every run.
+
+Rank 0 prints ONE JSON line; with --full it carries these extra objects (and other_single_gpu_readings, summary):
   roofline     dominant kernel (ptrwm_step_kernel).  The kernel keeps the state in registers for the whole launch, so
                the BINDING resource is VALU issue, not HBM: bound = "valu_issue", achieved = wave-level VALU
                instructions per second (SQ_INSTS_VALU per launch, from the rocprofv3 PMC pass of this same command
@@ -53,9 +65,43 @@ def parse():
     ap.add_argument("--swap-order", default="sequential", choices=["sequential", "even_odd"])
     ap.add_argument("--workload", default="cfg3", choices=["cfg2", "cfg3", "cfg4", "cfg5", "pt", "rwm"],
                     help="BASELINE.json configs[1..4] (cfg3 = configs[2], the headline); pt = cfg3, rwm = cfg2")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra single-GPU readings (configs[1], even/odd)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, the other single-GPU readings, the CPU baseline and the run summary")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays of the last timed step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0,
+                    help="budget of the CPU baseline sample (0 = skip; --full only)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="skip the extra single-GPU readings (configs[1], even/odd; --full only)")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 48 << 20  # bytes of --dump-outputs
+
+
+def dump_outputs(run, out_dir):
+    """The arrays a caller of run.advance() holds after the last timed step (module docstring), for every ladder or a
+    fixed seeded sample of them."""
+    import numpy as np
+    import torch
+
+    C, T, D = run.n_replicas, run.n_temps, run.dim
+    per_ladder = T * D * run.state.element_size() + T * 4 + 4 * T * 8
+    n = min(C, max(1, DUMP_BUDGET // per_ladder))
+    idx = np.arange(C) if n == C else np.sort(np.random.default_rng(20241016).choice(C, n, replace=False))
+    sel = torch.from_numpy(idx).to(run.state.device)
+
+    def take(t, dtype):
+        return t.index_select(0, sel).to(dtype).cpu().numpy()
+
+    state_dtype = torch.float64 if run.state.dtype == torch.float64 else torch.float32
+    arrays = {"state": take(run.state, state_dtype), "logp": take(run.logp, torch.float32),
+              "n_accept": take(run.n_accept, torch.float64), "sq_jump": take(run.sq_jump, torch.float64),
+              "swap_accept": take(run.swap_accept, torch.float64),
+              "last_swap_ordinal": take(run.last_ord, torch.float64), "ladder_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def _cpu_worker(job):
@@ -138,7 +184,7 @@ def main():
 
     # CPU baseline first: it spawns worker processes, which must happen before this process touches the GPU
     cpu = None
-    if world == 1 and args.cpu_seconds > 0:
+    if args.full and world == 1 and args.cpu_seconds > 0:
         wl0 = {"pt": "cfg3", "rwm": "cfg2"}.get(args.workload, args.workload)
         cpu = cpu_baseline(args.dim, 1 if wl0 == "cfg2" else args.temps, args.cpu_seconds)
         cpu["c_oracle_chain_steps_per_s_1core"] = c_oracle_rate(args.dim, 1 if wl0 == "cfg2" else args.temps,
@@ -236,6 +282,8 @@ def main():
         t = torch.tensor([elapsed], device=coll_dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(run, args.dump_outputs)
     launch_ms = sorted(a.elapsed_time(b) for a, b in ev)
     kernel_ms = sum(launch_ms) / len(launch_ms)
     # Per-rank record for the N > 1 line (gathered below): which physical device each rank ran on and its own launch times,
@@ -265,7 +313,7 @@ def main():
     # (median of 3 repeats of >= 1 s each), the north star's one-step-per-launch formulation (HBM-streaming
     # bound), BASELINE configs[1] (RWM, 65 536 chains, one temperature) and configs[2] with even/odd swaps.
     others, inner1 = None, None
-    if world == 1 and wl == "cfg3" and not args.no_extras:
+    if args.full and world == 1 and wl == "cfg3" and not args.no_extras:
         def timed_launches(r, n, inner):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
@@ -416,7 +464,7 @@ def main():
 
     # HBM copy probe (the measured copy bandwidth as a second denominator): 1 GiB device-to-device
     copy_gbps = None
-    if rank == 0:
+    if args.full and rank == 0:
         src = torch.empty(1 << 28, device=dev, dtype=torch.float32).normal_()
         dst = torch.empty_like(src)
         dst.copy_(src)
@@ -429,116 +477,117 @@ def main():
         copy_gbps = 10 * 2 * src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3) / 1e9
         del src, dst
 
-    summary = allreduce_summary(run.summary(), coll_dev)  # the only collective: whole-job acceptance / ESJD
+    summary = allreduce_summary(run.summary(), coll_dev) if args.full else None  # the only collective: acceptance / ESJD
     units_per_launch = C * T * args.inner            # per GPU
     value = world * units_per_launch * args.steps / elapsed
     alg_bytes = (8 * dim + 24) * units_per_launch
     achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
 
     if rank == 0:
-        # Counters of the SAME command from the committed rocprofv3 PMC passes (profiles/traffic.json: FETCH_SIZE /
-        # WRITE_SIZE / GRBM_GUI_ACTIVE / SQ_* collected in separate passes, FETCH doubled per the gfx950 note).  They are
-        # properties of the code object: the record carries the sha256 of the library it was measured on and the line
-        # says whether that is the library being timed now.
-        import hashlib
+        if args.full:
+            # Counters of the SAME command from the committed rocprofv3 PMC passes (profiles/traffic.json: FETCH_SIZE /
+            # WRITE_SIZE / GRBM_GUI_ACTIVE / SQ_* collected in separate passes, FETCH doubled per the gfx950 note).  They are
+            # properties of the code object: the record carries the sha256 of the library it was measured on and the line
+            # says whether that is the library being timed now.
+            import hashlib
 
-        import ptrwm_hip
+            import ptrwm_hip
 
-        with open(ptrwm_hip.LIB_PATH, "rb") as f:
-            lib_sha = hashlib.sha256(f.read()).hexdigest()
-        traffic, rec = None, {}
-        tfile = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tfile):
-            with open(tfile) as f:
-                tj = json.load(f)
-            key = f"{'rwm' if T == 1 else 'pt'}_d{dim}_T{T}_C{C}" if wl in ("cfg2", "cfg3") else wl
-            rec = tj.get(key, {})
-            traffic = rec.get("hbm_bytes_per_launch")  # state in / state out: does not depend on the steps per launch
-            rec1 = tj.get(key + "_inner1", {})
-            if inner1 is not None and rec1:
-                inner1["traffic"] = rec1.get("hbm_bytes_per_launch")
-                inner1["traffic_source"] = rec1.get("source")
-                inner1["profiled_kernel_ms"] = rec1.get("profiled_kernel_ms")
-                inner1["traffic_of_this_build"] = rec1.get("lib_sha256") == lib_sha
-                if inner1["traffic_of_this_build"] and inner1["traffic"]:
-                    inner1["achieved_counters"] = inner1["traffic"] / (inner1["kernel_ms_mean"] * 1e-3) / 1e9
-                    inner1["frac_counters"] = inner1["achieved_counters"] / HBM_PEAK_GBPS
-        clock_ghz = rec.get("shader_clock_ghz", 2.4)
-        valu_peak = 1024 * clock_ghz * 1e9 / 2  # 1024 SIMDs, one wave64 VALU instruction per 2 cycles each
-        if "valu_insts_per_launch" in rec:
-            # the instruction count of a launch is proportional to its Metropolis steps (prologue and epilogue are
-            # < 0.1 % at >= 100 steps); the record states the steps it was collected at
-            valu_launch = rec["valu_insts_per_launch"] * args.inner / rec.get("mh_steps_per_launch", args.inner)
-            valu_rate = valu_launch / (kernel_ms * 1e-3)
-            roof = {"bound": "valu_issue", "achieved": valu_rate / 1e9, "peak": valu_peak / 1e9, "unit": "Gwave-instr/s",
-                    "frac": valu_rate / valu_peak, "traffic": traffic,
-                    "valu_wave_insts_per_launch": valu_launch,
-                    "valu_wave_insts_per_wave_step": valu_launch * 64 / units_per_launch,
-                    "counters_collected_at_mh_steps_per_launch": rec.get("mh_steps_per_launch"),
-                    "shader_clock_ghz": clock_ghz, "counters_source": rec.get("source"),
-                    "counters_lib_sha256": rec.get("lib_sha256"), "counters_match_this_build": rec.get("lib_sha256") == lib_sha}
-        else:  # no PMC record for this configuration: the fraction cannot be stated
-            roof = {"bound": "valu_issue", "achieved": None, "peak": valu_peak / 1e9, "unit": "Gwave-instr/s", "frac": None,
-                    "traffic": traffic, "note_counters": f"no PMC record {key!r} in profiles/traffic.json"}
-        # The ceiling of THIS instruction mix, measured two ways (profiles/r04_issue_model.json):
-        #  (a) tools/mix_probe.py: the step path of the shipped kernel - the same instructions with the same operand forms -
-        #      replayed with every dependency removed, at the kernel's own residency (four waves per SIMD, 8 192 workgroups):
-        #      the rate at which this hardware issues this mix when nothing but issue limits it.  peak_measured_mix is that
-        #      rate (the better of two orders), frac_of_measured_mix = achieved / that.
-        #  (b) tools/issue_model.py: the sum over the path of each opcode's stand-alone issue cost (tools/issue_cost.hip, cycles
-        #      of the clock measured inside each microbenchmark launch; an SGPR source operand halves a full-rate opcode's
-        #      rate): sum_of_standalone_costs.
-        # Both say the nominal 2-cycle peak (frac) is out of reach for this mix whatever its schedule: only 47 % of the
-        # step's VALU instructions are full-rate all-VGPR ones.
-        imf = os.path.join(ROOT, "profiles", "r04_issue_model.json")
-        if wl == "cfg3" and os.path.exists(imf) and roof.get("achieved"):
-            with open(imf) as f:
-                im = json.load(f)
-            mm = im.get("measured_mix") or {}
-            per_inst = im.get("floor_cycles_per_valu_instruction")
-            if mm.get("ns_of_simd_time_per_wave_step") and mm.get("valu_per_iteration"):
-                peak_mix = 1024 * mm["valu_per_iteration"] / mm["ns_of_simd_time_per_wave_step"]  # Gwave-instr/s
-                roof["peak_measured_mix"] = peak_mix
-                roof["frac_of_measured_mix"] = roof["achieved"] / peak_mix
-                roof["measured_mix"] = {
-                    "replay_ns_of_simd_time_per_wave_step": mm["ns_of_simd_time_per_wave_step"],
-                    "replay_program_order_ns": mm.get("program_order_ns"), "replay_spread_evenly_ns": mm.get("spread_evenly_ns"),
-                    "kernel_ns_of_simd_time_per_wave_step_without_swap_events": im.get("ns_per_wave_step"),
-                    "valu_on_step_path": im.get("valu_on_path"), "class_counts": im.get("class_counts"),
-                    "sum_of_standalone_costs_cycles_per_wave_step": im.get("floor_cycles_per_wave_step"),
-                    "sum_of_standalone_costs_cycles_per_valu_instruction": per_inst,
-                    "kernel_cycles_per_wave_step_without_swap_events": im.get("measured_cycles_per_wave_step"),
-                    "pmc_check": im.get("pmc_check"), "model_of_this_build": im.get("lib_sha256") == lib_sha,
-                    "source": "profiles/r04_issue_model.txt / .json (tools/issue_model.py), profiles/r04_mix_probe.json "
-                              "(tools/mix_probe.py), profiles/r04_issue_costs.json (tools/issue_cost.hip), "
-                              "profiles/r04_residency.json (tools/residency_probe.hip)",
-                    "note": "frac (nominal) prices every VALU instruction at 2 cycles.  The replay of this kernel's own step "
-                            "path without dependencies takes 3 480-3 530 cycles of SIMD time per wave-step, the sum of the "
-                            "stand-alone opcode costs is 3 610, the kernel itself takes 3 360 (a launch without swap "
-                            "events): the kernel issues its mix 3-4 % FASTER than the dependency-free replay does, so "
-                            "frac_of_measured_mix is slightly above one.  Read: the step is at the issue ceiling of its "
-                            "instruction mix; no schedule of these instructions is faster on this hardware; only a "
-                            "different mix (fewer or cheaper instructions) is."}
-        roof.update({
-            "kernel": rec.get("kernel") or f"fused step kernel <{type(target).__name__}, {alg.proposal_dist.get_name()}, dim {dim}, "
-                                           "production>, form chosen by the C ABI",
-            "kernel_ms": kernel_ms, "lib_sha256": lib_sha,
-            "hbm_counter_traffic": None if traffic is None else {
-                "bytes_per_launch": traffic, "GBps": traffic / (kernel_ms * 1e-3) / 1e9,
-                "frac_of_hbm_peak": traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
-            "hbm_streaming_accounting": {
-                "algorithmic_bytes_per_launch": alg_bytes, "GBps": achieved, "ratio_to_hbm_peak": achieved / HBM_PEAK_GBPS,
-                "measured_copy_GBps": copy_gbps,
-                "note": "SURVEY 8(d) accounting: (8*dim+24) B per chain-MH-step as if every step streamed its state through "
-                        "HBM.  The fused kernel never moves those bytes (state stays in registers for the whole launch), "
-                        "so a ratio above 1 is possible and is NOT a roofline fraction."},
-            "hbm_stream_inner1": inner1,
-        })
-        if inner1 is not None and copy_gbps:
-            # the same box's plain device-to-device copy (torch's copy_ of 1 GiB) as a second denominator: the
-            # bytes really moved against the bytes a copy moves in the same time
-            inner1["frac_of_measured_copy"] = inner1["achieved_touched"] / copy_gbps
-            inner1["frac_of_measured_copy_algorithmic"] = inner1["achieved"] / copy_gbps
+            with open(ptrwm_hip.LIB_PATH, "rb") as f:
+                lib_sha = hashlib.sha256(f.read()).hexdigest()
+            traffic, rec = None, {}
+            tfile = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tfile):
+                with open(tfile) as f:
+                    tj = json.load(f)
+                key = f"{'rwm' if T == 1 else 'pt'}_d{dim}_T{T}_C{C}" if wl in ("cfg2", "cfg3") else wl
+                rec = tj.get(key, {})
+                traffic = rec.get("hbm_bytes_per_launch")  # state in / state out: does not depend on the steps per launch
+                rec1 = tj.get(key + "_inner1", {})
+                if inner1 is not None and rec1:
+                    inner1["traffic"] = rec1.get("hbm_bytes_per_launch")
+                    inner1["traffic_source"] = rec1.get("source")
+                    inner1["profiled_kernel_ms"] = rec1.get("profiled_kernel_ms")
+                    inner1["traffic_of_this_build"] = rec1.get("lib_sha256") == lib_sha
+                    if inner1["traffic_of_this_build"] and inner1["traffic"]:
+                        inner1["achieved_counters"] = inner1["traffic"] / (inner1["kernel_ms_mean"] * 1e-3) / 1e9
+                        inner1["frac_counters"] = inner1["achieved_counters"] / HBM_PEAK_GBPS
+            clock_ghz = rec.get("shader_clock_ghz", 2.4)
+            valu_peak = 1024 * clock_ghz * 1e9 / 2  # 1024 SIMDs, one wave64 VALU instruction per 2 cycles each
+            if "valu_insts_per_launch" in rec:
+                # the instruction count of a launch is proportional to its Metropolis steps (prologue and epilogue are
+                # < 0.1 % at >= 100 steps); the record states the steps it was collected at
+                valu_launch = rec["valu_insts_per_launch"] * args.inner / rec.get("mh_steps_per_launch", args.inner)
+                valu_rate = valu_launch / (kernel_ms * 1e-3)
+                roof = {"bound": "valu_issue", "achieved": valu_rate / 1e9, "peak": valu_peak / 1e9, "unit": "Gwave-instr/s",
+                        "frac": valu_rate / valu_peak, "traffic": traffic,
+                        "valu_wave_insts_per_launch": valu_launch,
+                        "valu_wave_insts_per_wave_step": valu_launch * 64 / units_per_launch,
+                        "counters_collected_at_mh_steps_per_launch": rec.get("mh_steps_per_launch"),
+                        "shader_clock_ghz": clock_ghz, "counters_source": rec.get("source"),
+                        "counters_lib_sha256": rec.get("lib_sha256"), "counters_match_this_build": rec.get("lib_sha256") == lib_sha}
+            else:  # no PMC record for this configuration: the fraction cannot be stated
+                roof = {"bound": "valu_issue", "achieved": None, "peak": valu_peak / 1e9, "unit": "Gwave-instr/s", "frac": None,
+                        "traffic": traffic, "note_counters": f"no PMC record {key!r} in profiles/traffic.json"}
+            # The ceiling of THIS instruction mix, measured two ways (profiles/r04_issue_model.json):
+            #  (a) tools/mix_probe.py: the step path of the shipped kernel - the same instructions with the same operand forms -
+            #      replayed with every dependency removed, at the kernel's own residency (four waves per SIMD, 8 192 workgroups):
+            #      the rate at which this hardware issues this mix when nothing but issue limits it.  peak_measured_mix is that
+            #      rate (the better of two orders), frac_of_measured_mix = achieved / that.
+            #  (b) tools/issue_model.py: the sum over the path of each opcode's stand-alone issue cost (tools/issue_cost.hip, cycles
+            #      of the clock measured inside each microbenchmark launch; an SGPR source operand halves a full-rate opcode's
+            #      rate): sum_of_standalone_costs.
+            # Both say the nominal 2-cycle peak (frac) is out of reach for this mix whatever its schedule: only 47 % of the
+            # step's VALU instructions are full-rate all-VGPR ones.
+            imf = os.path.join(ROOT, "profiles", "r04_issue_model.json")
+            if wl == "cfg3" and os.path.exists(imf) and roof.get("achieved"):
+                with open(imf) as f:
+                    im = json.load(f)
+                mm = im.get("measured_mix") or {}
+                per_inst = im.get("floor_cycles_per_valu_instruction")
+                if mm.get("ns_of_simd_time_per_wave_step") and mm.get("valu_per_iteration"):
+                    peak_mix = 1024 * mm["valu_per_iteration"] / mm["ns_of_simd_time_per_wave_step"]  # Gwave-instr/s
+                    roof["peak_measured_mix"] = peak_mix
+                    roof["frac_of_measured_mix"] = roof["achieved"] / peak_mix
+                    roof["measured_mix"] = {
+                        "replay_ns_of_simd_time_per_wave_step": mm["ns_of_simd_time_per_wave_step"],
+                        "replay_program_order_ns": mm.get("program_order_ns"), "replay_spread_evenly_ns": mm.get("spread_evenly_ns"),
+                        "kernel_ns_of_simd_time_per_wave_step_without_swap_events": im.get("ns_per_wave_step"),
+                        "valu_on_step_path": im.get("valu_on_path"), "class_counts": im.get("class_counts"),
+                        "sum_of_standalone_costs_cycles_per_wave_step": im.get("floor_cycles_per_wave_step"),
+                        "sum_of_standalone_costs_cycles_per_valu_instruction": per_inst,
+                        "kernel_cycles_per_wave_step_without_swap_events": im.get("measured_cycles_per_wave_step"),
+                        "pmc_check": im.get("pmc_check"), "model_of_this_build": im.get("lib_sha256") == lib_sha,
+                        "source": "profiles/r04_issue_model.txt / .json (tools/issue_model.py), profiles/r04_mix_probe.json "
+                                  "(tools/mix_probe.py), profiles/r04_issue_costs.json (tools/issue_cost.hip), "
+                                  "profiles/r04_residency.json (tools/residency_probe.hip)",
+                        "note": "frac (nominal) prices every VALU instruction at 2 cycles.  The replay of this kernel's own step "
+                                "path without dependencies takes 3 480-3 530 cycles of SIMD time per wave-step, the sum of the "
+                                "stand-alone opcode costs is 3 610, the kernel itself takes 3 360 (a launch without swap "
+                                "events): the kernel issues its mix 3-4 % FASTER than the dependency-free replay does, so "
+                                "frac_of_measured_mix is slightly above one.  Read: the step is at the issue ceiling of its "
+                                "instruction mix; no schedule of these instructions is faster on this hardware; only a "
+                                "different mix (fewer or cheaper instructions) is."}
+            roof.update({
+                "kernel": rec.get("kernel") or f"fused step kernel <{type(target).__name__}, {alg.proposal_dist.get_name()}, dim {dim}, "
+                                               "production>, form chosen by the C ABI",
+                "kernel_ms": kernel_ms, "lib_sha256": lib_sha,
+                "hbm_counter_traffic": None if traffic is None else {
+                    "bytes_per_launch": traffic, "GBps": traffic / (kernel_ms * 1e-3) / 1e9,
+                    "frac_of_hbm_peak": traffic / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS},
+                "hbm_streaming_accounting": {
+                    "algorithmic_bytes_per_launch": alg_bytes, "GBps": achieved, "ratio_to_hbm_peak": achieved / HBM_PEAK_GBPS,
+                    "measured_copy_GBps": copy_gbps,
+                    "note": "SURVEY 8(d) accounting: (8*dim+24) B per chain-MH-step as if every step streamed its state through "
+                            "HBM.  The fused kernel never moves those bytes (state stays in registers for the whole launch), "
+                            "so a ratio above 1 is possible and is NOT a roofline fraction."},
+                "hbm_stream_inner1": inner1,
+            })
+            if inner1 is not None and copy_gbps:
+                # the same box's plain device-to-device copy (torch's copy_ of 1 GiB) as a second denominator: the
+                # bytes really moved against the bytes a copy moves in the same time
+                inner1["frac_of_measured_copy"] = inner1["achieved_touched"] / copy_gbps
+                inner1["frac_of_measured_copy_algorithmic"] = inner1["achieved"] / copy_gbps
         out = {
             "metric": "chain-MH-steps/sec", "value": value, "unit": "chain-MH-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -553,15 +602,16 @@ def main():
             },
             # one entry per rank: its device and its own launch times (value uses the MAX wall clock over ranks)
             "ranks": ranks, "distinct_devices": distinct,
-            "roofline": roof,
-            "summary": {
+        }
+        if args.full:
+            out["roofline"] = roof
+            out["summary"] = {
                 "acceptance_rate_cold": float(summary["acceptance_rate"][0]),
                 "acceptance_rate_hot": float(summary["acceptance_rate"][-1]),
                 "esjd_cold": float(summary["esjd"][0]),
                 "swap_acceptance_rate": summary["swap_acceptance_rate"],
                 "replicas": summary["n_replicas"],
-            },
-        }
+            }
         if others is not None:
             out["other_single_gpu_readings"] = others
         if cpu is not None:

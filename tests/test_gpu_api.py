@@ -978,8 +978,8 @@ def test_long_run_statistics_of_the_other_baseline_families(device, family):
 
 
 def test_bench_emits_the_contract_line(device):
-    """bench.py as the driver runs it (a child process; N = 1, few steps): exactly one JSON line with the contract's
-    keys, the roofline and cpu_baseline objects, and sane values."""
+    """bench.py --full as the driver runs it (a child process; N = 1, few steps): exactly one JSON line with the
+    contract's keys, the roofline and cpu_baseline objects, and sane values."""
     import json
     import os
     import subprocess
@@ -987,7 +987,8 @@ def test_bench_emits_the_contract_line(device):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
-                          "--cpu-seconds", "1", "--inner", "200"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--full", "--cpu-seconds", "1", "--inner", "200"], capture_output=True, text=True, timeout=600,
+                         cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -7,12 +7,14 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARGS = ["--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--no-extras", "--inner", "300"]
+# --full: the summary and roofline objects these tests read are not part of a plain run
+ARGS = ["--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "0", "--no-extras", "--inner", "300"]
 
 
 def _bench(cmd, env_extra, timeout=600):
@@ -62,3 +64,37 @@ def test_bench_under_torchrun_over_rccl():
     assert out["config"]["world_size"] == 1 and out["distinct_devices"] == 1 and len(out["ranks"]) == 1
     r0 = out["ranks"][0]
     assert r0["rank"] == 0 and r0["pci"] and r0["kernel_ms_mean"] == pytest.approx(out["roofline"]["kernel_ms"], rel=1e-6)
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """A plain run (no --full): the headline line without the --full objects, `--steps` timed launches, and with
+    --dump-outputs the arrays of the last timed step - float32 / float64, within 64 MB - identical in a second run
+    with the same arguments."""
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--inner", "200"]
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        line = _bench([sys.executable, "bench.py"] + args + ["--dump-outputs", str(d)], {})
+        names = {p.stem for p in d.glob("*.npy")}
+        runs.append((line, {n: np.load(d / f"{n}.npy") for n in names}))
+    line, a = runs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config", "ranks"):
+        assert k in line, k
+    for k in ("roofline", "summary", "other_single_gpu_readings", "cpu_baseline"):
+        assert k not in line, k
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 1e9
+    units = line["config"]["ladders_per_gpu"] * line["config"]["temps"] * line["config"]["mh_steps_per_launch"]
+    assert line["value"] == pytest.approx(units / (line["ms_per_step"] * 1e-3), rel=1e-6)
+    C, T, D = line["config"]["ladders_per_gpu"], line["config"]["temps"], line["config"]["dim"]
+    assert set(a) == {"state", "logp", "n_accept", "sq_jump", "swap_accept", "last_swap_ordinal", "ladder_index"}
+    L = len(a["ladder_index"])
+    assert 0 < L <= C and a["state"].shape == (L, T, D) and a["state"].dtype == np.float32
+    assert a["logp"].shape == (L, T) and a["logp"].dtype == np.float32
+    for n in ("n_accept", "sq_jump", "swap_accept", "last_swap_ordinal"):
+        assert a[n].shape == (L, T) and a[n].dtype == np.float64, n
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    # warm-up and timed launches: 3 x 200 Metropolis steps per replica, burn-in 0
+    assert np.isfinite(a["state"]).all() and np.isfinite(a["logp"]).all()
+    assert 0 < a["n_accept"].sum() and a["n_accept"].max() <= 3 * 200
+    for n, x in runs[1][1].items():
+        assert np.array_equal(x, a[n]), n

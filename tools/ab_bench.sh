@@ -2,6 +2,8 @@
 # A/B on ONE box: the shipped library against alternative builds (PTRWM_LIB), alternating, bench.py main reading only.
 #   tools/ab_bench.sh <name>=<lib path> ...    (development aid; output under gpurun_out/ab_*.json)
 mkdir -p gpurun_out
+# the readout below takes kernel_ms from the roofline object, which only a --full run prints
+AB_ARGS="--full ${AB_ARGS}"
 for rep in 1 2; do
   for spec in "cur=" "$@"; do
     name=${spec%%=*}; lib=${spec#*=}

@@ -42,12 +42,12 @@ prof cfg2 20 4 --workload cfg2
 prof cfg4 10 3 --workload cfg4 --inner 500
 prof cfg5 10 3 --workload cfg5 --inner 200
 cd /root/repo
-timeout -k 10 500 python3 bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+timeout -k 10 500 python3 bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 echo "bench done"
 python3 tools/profile_summary.py "$TAG" "$OUT"
 # cost-weighted issue model of the headline kernel (recompiles one translation unit with -save-temps: ~1 min of CPU)
 python3 tools/issue_model.py --from-traffic pt_d30_T32_C65536_noswap --costs profiles/${TAG}_issue_costs.json \
     --json profiles/${TAG}_issue_model.json > profiles/${TAG}_issue_model.txt 2>&1 || tail -5 profiles/${TAG}_issue_model.txt
 # second bench run so that the committed line carries the counters of THIS build (traffic.json was just rewritten)
-timeout -k 10 500 python3 bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+timeout -k 10 500 python3 bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 cp "$OUT/bench_n1.json" profiles/${TAG}_bench_n1.json
