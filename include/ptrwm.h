@@ -195,6 +195,17 @@ enum {
 };
 int32_t ptrwm_last_launch_kind(void);
 
+/* Which specialisation of the target's functor the calling thread's most recent successful ptrwm_run used
+ * (introspection for tests; 0 before the first call): the general functor, the specialised one (RoughCarpet: the
+ * smallest mixture term proven negligible; ThreeMixture: means that differ in the first coordinate only), or the
+ * folded RoughCarpet (modes -m, 0, +m). */
+enum {
+  PTRWM_FUNCTOR_GENERAL = 0,
+  PTRWM_FUNCTOR_SPECIALISED = 1,
+  PTRWM_FUNCTOR_FOLDED = 2
+};
+int32_t ptrwm_last_launch_functor(void);
+
 /* Number of raw random numbers one MH proposal consumes from `ext_prop`
  * (NORMAL: dim normals; LAPLACE: dim uniforms in [0,1); UNIFORM_RADIUS: dim
  * normals then one uniform). */

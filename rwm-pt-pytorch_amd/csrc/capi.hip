@@ -1,5 +1,8 @@
 // C ABI of the PT-RWM engine (include/ptrwm.h): argument validation, variant
 // dispatch and launch.  No allocation, no synchronisation, no retained pointers.
+#include <algorithm>
+#include <cmath>
+
 #include "../../include/ptrwm.h"
 #include "variants.h"
 
@@ -127,6 +130,7 @@ constexpr long long kStreamMinBytes = 192ll << 20, kStreamMaxBytes = 448ll << 20
 
 // what the calling thread's most recent ptrwm_run launched (ptrwm_last_launch_kind: tests and the benchmark's record)
 static thread_local int t_last_launch_kind = 0;
+static thread_local int t_last_launch_functor = 0;  // ... and with which functor (ptrwm_last_launch_functor)
 
 static bool stream_layout_ok(const ptrwm_run_args *args, int dim, int cpw) {
   return args->n_temps <= 64 && args->n_chains % cpw == 0 && ((long long)cpw * args->n_temps * dim) % 4 == 0 &&
@@ -169,12 +173,14 @@ static bool auto_prefers_lane_split(int dim, int n_temps, long long n_chains, lo
 #endif
 
 
-// alt: the specialised functor of the kind - RoughCarpet2 (the host proved the third mixture term negligible,
-// rough_carpet_two_term) or ThreeMixture1 (the caller declared means that differ in the first coordinate only, ip[0] = 1)
-static const QuadVariants &quad_variants(int kind, bool alt) {
+// alt: the specialised functor of the kind (0: none) - for RoughCarpet 1 = RoughCarpet2 (the host proved the third
+// mixture term negligible, rough_carpet_two_term), 2 = RoughCarpetSym (also modes -m, 0, +m, rough_carpet_fold); for
+// ThreeMixture 1 = ThreeMixture1 (the caller declared means that differ in the first coordinate only, ip[0] = 1)
+static const QuadVariants &quad_variants(int kind, int alt) {
   switch (kind) {
-    case PTRWM_TARGET_ROUGH_CARPET: return alt ? rough_carpet2_variants_quad() : rough_carpet_variants_quad();
-    case PTRWM_TARGET_THREE_MIXTURE: return alt ? three_mixture1_variants_quad() : three_mixture_variants_quad();
+    case PTRWM_TARGET_ROUGH_CARPET:
+      return alt == 2 ? rough_carpet_sym_variants_quad() : (alt == 1 ? rough_carpet2_variants_quad() : rough_carpet_variants_quad());
+    case PTRWM_TARGET_THREE_MIXTURE: return alt != 0 ? three_mixture1_variants_quad() : three_mixture_variants_quad();
     case PTRWM_TARGET_FULL_ROSENBROCK: return full_rosenbrock_variants_quad();
     case PTRWM_TARGET_EVEN_ROSENBROCK: return even_rosenbrock_variants_quad();
     case PTRWM_TARGET_HYBRID_ROSENBROCK: return hybrid_rosenbrock_variants_quad();
@@ -186,11 +192,14 @@ static const QuadVariants &quad_variants(int kind, bool alt) {
   }
 }
 
-static VariantPair target_variants(int kind, bool alt = false) {
+static VariantPair target_variants(int kind, int alt = 0) {
 #define PTRWM_PAIR(SYMBOL) VariantPair{&SYMBOL##_narrow(), &SYMBOL##_wide()}
   switch (kind) {
-    case PTRWM_TARGET_ROUGH_CARPET: return alt ? PTRWM_PAIR(rough_carpet2_variants) : PTRWM_PAIR(rough_carpet_variants);
-    case PTRWM_TARGET_THREE_MIXTURE: return alt ? PTRWM_PAIR(three_mixture1_variants) : PTRWM_PAIR(three_mixture_variants);
+    case PTRWM_TARGET_ROUGH_CARPET:
+      // (the folded tables have no wide object: nothing of theirs lives above width 64)
+      return alt == 2 ? VariantPair{&rough_carpet_sym_variants_narrow(), &rough_carpet_sym_variants_narrow()}
+                      : (alt == 1 ? PTRWM_PAIR(rough_carpet2_variants) : PTRWM_PAIR(rough_carpet_variants));
+    case PTRWM_TARGET_THREE_MIXTURE: return alt != 0 ? PTRWM_PAIR(three_mixture1_variants) : PTRWM_PAIR(three_mixture_variants);
     case PTRWM_TARGET_FULL_ROSENBROCK: return PTRWM_PAIR(full_rosenbrock_variants);
     case PTRWM_TARGET_EVEN_ROSENBROCK: return PTRWM_PAIR(even_rosenbrock_variants);
     case PTRWM_TARGET_HYBRID_ROSENBROCK: return PTRWM_PAIR(hybrid_rosenbrock_variants);
@@ -269,6 +278,41 @@ static bool rough_carpet_two_term(const float *p) {
       gmin = v < gmin ? v : gmin;
     }
   return gmin > 27.0;
+}
+
+// RoughCarpet, folded form (targets.h rc_fold_dim_term): may the kernel evaluate only the middle mode and the outer mode
+// on the coordinate's own side?  Needs the two-term property (the three-term form's smallest term drops out, so the
+// fold is compared with the two-term form), fp32-exact symmetry - one mode +-0, the other two exact negatives of each
+// other, in any order - and that the FAR outer mode, wherever it is not the smallest of the three, lies more than 27
+// (log2 units) below the largest.  On the side s x >= 0 the far mode is -m and every difference a_k - a_far is linear
+// and increasing in s x (a common curvature; slope log2(e) (m_k + m) > 0 for k != far), so max_k a_k - a_far is
+// increasing there and the bound at s x = 0 holds on the whole side; the other side is the mirror image.  On success
+// `perm` holds the target's indices of the modes -m, 0, +m: the order the kernel reads p[0..2] / p[3..5] in.
+static bool rough_carpet_fold(const float *p, int perm[3]) {
+  for (int i = 0; i < 6; ++i)
+    if (!std::isfinite(p[i])) return false;
+  int z = -1;
+  for (int i = 0; i < 3 && z < 0; ++i)
+    if (p[i] == 0.0f) z = i;
+  if (z < 0) return false;
+  const int i = (z + 1) % 3, j = (z + 2) % 3;
+  if (p[i] == 0.0f || p[i] != -p[j]) return false;
+  perm[0] = p[i] < 0.0f ? i : j;
+  perm[1] = z;
+  perm[2] = p[i] < 0.0f ? j : i;
+  if (!rough_carpet_two_term(p)) return false;
+  const double l2e = 1.4426950408889634, m = p[perm[2]];
+  const double a_neg = l2e * ((double)p[3 + perm[0]] - 0.5 * m * m), a_mid = l2e * (double)p[3 + perm[1]],
+               a_pos = l2e * ((double)p[3 + perm[2]] - 0.5 * m * m);
+  return std::max(a_mid, a_pos) - a_neg > 27.0 && std::max(a_mid, a_neg) - a_pos > 27.0;
+}
+
+// the specialised functor of a run's target (the `alt` of target_variants / quad_variants); fills `perm` for the folded
+// rough carpet
+static int specialised_form(const ptrwm_target_desc *t, int perm[3]) {
+  if (t->kind == PTRWM_TARGET_ROUGH_CARPET) return rough_carpet_fold(t->p, perm) ? 2 : (rough_carpet_two_term(t->p) ? 1 : 0);
+  if (t->kind == PTRWM_TARGET_THREE_MIXTURE) return t->ip[0] == 1 ? 1 : 0;
+  return 0;
 }
 
 static TParams make_tparams(const ptrwm_target_desc *t) {
@@ -606,6 +650,8 @@ int32_t ptrwm_set_stream_mode(int32_t mode) {
 
 int32_t ptrwm_last_launch_kind(void) { return t_last_launch_kind; }
 
+int32_t ptrwm_last_launch_functor(void) { return t_last_launch_functor; }
+
 int32_t ptrwm_has_stream_variant(int32_t target_kind, int32_t proposal_kind, int32_t dim) {
   if (ptrwm_has_thread_variant(target_kind, proposal_kind, dim) == 0) return 0;
   const int dpi = width_index_for_dim(dim, target_kind);
@@ -696,15 +742,26 @@ int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *pr
 
   const int dpi = width_index_for_dim(target->dim, target->kind);
   if (dpi < 0) return PTRWM_E_DIM;
-  const bool two_term = (target->kind == PTRWM_TARGET_ROUGH_CARPET && rough_carpet_two_term(target->p)) ||
-                        (target->kind == PTRWM_TARGET_THREE_MIXTURE && target->ip[0] == 1);  // the kind's specialised functor
-  RunLaunchFn fn = target_variants(target->kind, two_term).run(proposal->kind, dpi);  // null above width 64
+  int rc_perm[3] = {0, 1, 2};
+  int alt = specialised_form(target, rc_perm);  // the kind's specialised functor
+  if (alt == 2) {
+    // the folded tables hold no state_f64 kernels (quad_rough_carpet_sym.hip): where they lack a kernel that the
+    // two-term tables have for this launch, the two-term functor runs (the same bits)
+    const int qi = quad_index_for(target->dim, args->n_temps, target->kind);
+    const QuadVariants &q2 = quad_variants(target->kind, 2), &q1 = quad_variants(target->kind, 1);
+    const bool thread_ok = target_variants(target->kind, 2).run(proposal->kind, dpi) != nullptr ||
+                           target_variants(target->kind, 1).run(proposal->kind, dpi) == nullptr;
+    const bool quad_ok = qi < 0 || (f64 ? q2.run_f64 : q2.run)[proposal->kind][qi] != nullptr ||
+                         (f64 ? q1.run_f64 : q1.run)[proposal->kind][qi] == nullptr;
+    if (!thread_ok || !quad_ok) alt = 1;
+  }
+  RunLaunchFn fn = target_variants(target->kind, alt).run(proposal->kind, dpi);  // null above width 64
   // lane-split form? (bit-identical results: a speed decision, see g_kernel_form - except above dim 64, where it is the
   // only form)
   bool quad = false;
   {
     const int qi = quad_index_for(target->dim, args->n_temps, target->kind);
-    const QuadVariants &qv = quad_variants(target->kind, two_term);
+    const QuadVariants &qv = quad_variants(target->kind, alt);
     const RunLaunchFn qfn = qi >= 0 ? (f64 ? qv.run_f64 : qv.run)[proposal->kind][qi] : nullptr;
     const int form = __atomic_load_n(&g_kernel_form, __ATOMIC_RELAXED);
     if (f64) {
@@ -751,6 +808,8 @@ int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *pr
   k.k0 = (unsigned)(args->seed & 0xffffffffull);
   k.k1 = (unsigned)(args->seed >> 32);
   k.tp = make_tparams(target);
+  if (target->kind == PTRWM_TARGET_ROUGH_CARPET && alt == 2)  // the folded form reads the modes as -m, 0, +m
+    for (int i = 0; i < 3; ++i) k.tp.p[i] = target->p[rc_perm[i]], k.tp.p[3 + i] = target->p[3 + rc_perm[i]];
   k.pp.dim_scale = proposal->dim_scale;
   k.pp.inv_dim = proposal->inv_dim;
   k.full.trace = args->trace;
@@ -787,6 +846,7 @@ int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *pr
   if (kMaxStepsPerLaunch < 1) kMaxStepsPerLaunch = 1;
   if (kMaxStepsPerLaunch > (1 << 16)) kMaxStepsPerLaunch = 1 << 16;
   t_last_launch_kind = quad ? PTRWM_LAUNCH_QUAD : (stream ? PTRWM_LAUNCH_STREAM : PTRWM_LAUNCH_THREAD);
+  t_last_launch_functor = alt;
   const long long te = args->trace_every > 1 ? args->trace_every : 1;
   k.full.trace_every = (int)te;
   const long long reps = args->n_chains * args->n_temps;
@@ -956,7 +1016,7 @@ int32_t ptrwm_logdensity(const ptrwm_target_desc *target, const float *x, float 
   if (dpi < 0) return PTRWM_E_DIM;
   // (RoughCarpet: the three-term functor always - the two-term one has the same bits where it applies; ThreeMixture1: a
   // different summation order, so a target declared that way is evaluated that way everywhere)
-  const LogpLaunchFn fn = target_variants(target->kind, target->kind == PTRWM_TARGET_THREE_MIXTURE && target->ip[0] == 1).logp(dpi);
+  const LogpLaunchFn fn = target_variants(target->kind, target->kind == PTRWM_TARGET_THREE_MIXTURE && target->ip[0] == 1 ? 1 : 0).logp(dpi);
   if (fn == nullptr) return PTRWM_E_NOVARIANT;
   const hipError_t err = fn(x, out, n, target->dim, make_tparams(target), (hipStream_t)stream);
   return err == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;

@@ -279,7 +279,7 @@ struct QUniformRadius {
 // ---- targets ---------------------------------------------------------------------------------------------------------
 // logp(y_local, lane, D, params) -> the replica's log-density, the same bits on all four lanes.  Each functor restates
 // the per-dimension arithmetic of its twin in targets.h on the lane's own range and combines canonically.
-template <int W, int MIN_OWN, bool TWO_TERM>
+template <int W, int MIN_OWN, int FORM>
 struct QRoughCarpetT {
   static constexpr int kKind = PTRWM_TARGET_ROUGH_CARPET;
   template <bool SCALED>
@@ -287,14 +287,24 @@ struct QRoughCarpetT {
     const float m0 = -(tp.p[0] * kRcScale), m1 = -(tp.p[1] * kRcScale), m2 = -(tp.p[2] * kRcScale);  // (targets.h)
     [[maybe_unused]] const float *sc_v = SCALED ? tp.vec0 + l.d0 : nullptr;
     const float w0 = tp.p[3] * kLog2e, w1 = tp.p[4] * kLog2e, w2 = tp.p[5] * kLog2e;
+    // kRcFold: the VOP3 fma's kRcScale in a VGPR (targets.h RoughCarpetT::logp_fold)
+    [[maybe_unused]] float kv = kRcScale;
+    if constexpr (FORM == kRcFold) PTRWM_VALUE_BARRIER("+v"(kv));
     float sm = 0.0f, pr = 1.0f;
 #pragma unroll
     for (int j = 0; j < W; ++j) {
       if (q_valid<MIN_OWN>(l, j)) {
-        const float sc = SCALED ? sc_v[j] * kRcScale : kRcScale;
-        const float d0 = fmaf(y[j], sc, m0), d1 = fmaf(y[j], sc, m1), d2 = fmaf(y[j], sc, m2);
         float mx, s;
-        rc_dim_term<false, TWO_TERM>(d0, d1, d2, w0, w1, w2, mx, s);
+        if constexpr (FORM == kRcFold) {  // modes (-m, 0, +m) in this order (capi.hip rough_carpet_fold)
+          const float sc = SCALED ? sc_v[j] * kRcScale : kv;
+          const float d1 = SCALED ? mul_rn(y[j], sc) : mul_rn(y[j], kRcScale);
+          const float dn = fmaf(__builtin_fabsf(y[j]), SCALED ? __builtin_fabsf(sc) : kv, m2);
+          rc_fold_dim_term(d1, dn, w1, w0, w2, mx, s);
+        } else {
+          const float sc = SCALED ? sc_v[j] * kRcScale : kRcScale;
+          const float d0 = fmaf(y[j], sc, m0), d1 = fmaf(y[j], sc, m1), d2 = fmaf(y[j], sc, m2);
+          rc_dim_term<false, FORM == kRcTwo>(d0, d1, d2, w0, w1, w2, mx, s);
+        }
         sm = add_rn(sm, mx);
         pr = mul_rn(pr, s);
       }
@@ -310,9 +320,11 @@ struct QRoughCarpetT {
   }
 };
 template <int W, int MIN_OWN>
-using QRoughCarpet = QRoughCarpetT<W, MIN_OWN, false>;
+using QRoughCarpet = QRoughCarpetT<W, MIN_OWN, kRcThree>;
 template <int W, int MIN_OWN>
-using QRoughCarpet2 = QRoughCarpetT<W, MIN_OWN, true>;
+using QRoughCarpet2 = QRoughCarpetT<W, MIN_OWN, kRcTwo>;
+template <int W, int MIN_OWN>
+using QRoughCarpetSym = QRoughCarpetT<W, MIN_OWN, kRcFold>;
 
 template <int W, int MIN_OWN>
 struct QThreeMixture {

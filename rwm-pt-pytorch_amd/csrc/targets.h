@@ -68,7 +68,37 @@ __device__ __forceinline__ void rc_dim_term(float d0, float d1, float d2, float 
 #define PTRWM_RC_FENCE_MASK 15
 #endif
 
-template <int DP, bool TWO_TERM>
+// The three compiled forms of the rough carpet's fused-kernel evaluation (capi.hip picks one per run; the stand-alone
+// log-density kernel always evaluates the three-term form).
+enum RcForm { kRcThree = 0, kRcTwo = 1, kRcFold = 2 };
+
+// kRcFold: one dimension when the modes are (-m, 0, +m) exactly, in that order on the host (rough_carpet_fold).
+// d1 = kRcScale s x is the centred coordinate of the middle mode; dn = fma(|x|, |sc|, -kRcScale m) that of the NEAR outer
+// mode: on the side s x >= 0 it is d2 of the three-term form bit for bit, on the other side it is -d0 exactly (round to
+// nearest is sign-symmetric) and it is only squared.  The sign of d1 picks the near mode's weight (v_ashrrev_i32 +
+// v_bitop3_b32, gfx950's bit-field insert:
+// at d1 = +-0 either side is taken, and the host proved the far mode negligible there too).  With a1, an the two
+// exponents, mx = max(a1, an) and s = 1 + 2^-|a1 - an|.
+// Exactness: where the far mode's exponent is the smallest of the three (for |x| beyond the midpoints always: it is
+// the -inf one when a square overflows), max / med of the three-term form are max(a1, an) / min(a1, an), and
+// min - max = -|a1 - an| exactly: the same mx and s bits.  Where it is not the smallest, the host proved it below the
+// largest by more than 27 (log2 units), so 2^(med - max) and 2^(min(a1, an) - max) both vanish beside 1 and s = 1 either
+// way, mx unchanged.  Special inputs: x = +-inf or NaN give a1 = an = -inf or NaN, so the three-term form's med - max and
+// a1 - an are both NaN, the log-density is NaN, and the Metropolis test rejects it (mh_accept: NaN compares false) -
+// the same decision and state as before; a NaN log-density is never stored.
+__device__ __forceinline__ void rc_fold_dim_term(float d1, float dn, float wmid, float wneg, float wpos, float &mx, float &s) {
+  // all ones on the negative side (v_ashrrev_i32).  Opaque: seen through, the and/or below is matched as a select and
+  // becomes v_cmp + s_nop + v_cndmask (half rate, and a hazard nop) instead of one all-VGPR v_bitop3_b32
+  unsigned neg = (unsigned)(__float_as_int(d1) >> 31);
+  PTRWM_VALUE_BARRIER("+v"(neg));
+  const float wn = __uint_as_float((neg & __float_as_uint(wneg)) | (~neg & __float_as_uint(wpos)));  // v_bitop3_b32 0xe4
+  const float a1 = fmaf(-d1, d1, wmid);
+  const float an = fmaf(-dn, dn, wn);
+  mx = __builtin_fmaxf(a1, an);
+  s = 1.0f + hw_exp2(-__builtin_fabsf(sub_rn(a1, an)));
+}
+
+template <int DP, int FORM>
 struct RoughCarpetT {
   static constexpr int kKind = PTRWM_TARGET_ROUGH_CARPET;
   // STRICT: all three exponents can be -inf only for |x| > ~1e19; torch.logsumexp then returns -inf where the
@@ -110,17 +140,55 @@ struct RoughCarpetT {
     // p[6] = log_jacobian, p[7] = -dim * log(sqrt(2 pi)) folded on the host
     return add_rn(fmaf(add_rn(sum_mx, lg), kLn2, tp.p[7]), tp.p[6]);
   }
+  // kRcFold (kernel variant RoughCarpetSym): modes (-m, 0, +m) in this order and weights with them (p[3..5]), see
+  // rc_fold_dim_term.  Same canonical four-range sums, same fences, same closing arithmetic as logp_impl.
+  template <bool SCALED>
+  __device__ __forceinline__ static float logp_fold(const float (&y)[DP], int D, const TParams &tp) {
+    const float mn = -(tp.p[2] * kRcScale);  // the near outer mode on the scaled axis, negated
+    [[maybe_unused]] const const_float_ptr uv0 = SCALED ? uniform_vec(tp.vec0) : nullptr;
+    const float wneg = tp.p[3] * kLog2e, wmid = tp.p[4] * kLog2e, wpos = tp.p[5] * kLog2e;
+    // kRcScale as a VOP3 operand of the fma below: in a VGPR (an SGPR source halves a full-rate opcode's issue rate)
+    [[maybe_unused]] float kv = kRcScale;
+    PTRWM_VALUE_BARRIER("+v"(kv));
+    constexpr int W = canon_width(DP);
+    float sm[4] = {0.0f, 0.0f, 0.0f, 0.0f}, pr[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    PTRWM_DIM_LOOP(d, DP, D, {
+      // d1 = kRcScale s x: the three-term form's fma(x, sc, -0.0) is the same rounding of the same product
+      const float sc = SCALED ? uv0[d] * kRcScale : kv;
+      const float d1 = SCALED ? mul_rn(y[d], sc) : mul_rn(y[d], kRcScale);
+      const float dn = fmaf(__builtin_fabsf(y[d]), SCALED ? __builtin_fabsf(sc) : kv, mn);
+      float mx, s;
+      rc_fold_dim_term(d1, dn, wmid, wneg, wpos, mx, s);
+#ifdef PTRWM_RC_PROD_FIRST
+      pr[d / W] = mul_rn(pr[d / W], s);
+      sm[d / W] = add_rn(sm[d / W], mx);
+#else
+      sm[d / W] = add_rn(sm[d / W], mx);
+      pr[d / W] = mul_rn(pr[d / W], s);
+#endif
+      if ((d & PTRWM_RC_FENCE_MASK) == PTRWM_RC_FENCE_MASK) sched_fence_soft();
+    })
+    const float sum_mx = tree4_add(sm);
+    const float lg = add_rn(hw_log2(mul_rn(pr[0], pr[1])), hw_log2(mul_rn(pr[2], pr[3])));
+    return add_rn(fmaf(add_rn(sum_mx, lg), kLn2, tp.p[7]), tp.p[6]);
+  }
   template <bool STRICT = false>
   __device__ __forceinline__ static float logp(const float (&y)[DP], int D, const TParams &tp) {
-    // wave-uniform branches per evaluation instead of per dimension
-    constexpr bool two = TWO_TERM && !STRICT;
-    return tp.vec0 != nullptr ? logp_impl<true, STRICT, two>(y, D, tp) : logp_impl<false, STRICT, two>(y, D, tp);
+    // wave-uniform branches per evaluation instead of per dimension; STRICT (ptrwm_logdensity) is always three-term
+    if constexpr (FORM == kRcFold && !STRICT) {
+      return tp.vec0 != nullptr ? logp_fold<true>(y, D, tp) : logp_fold<false>(y, D, tp);
+    } else {
+      constexpr bool two = FORM == kRcTwo && !STRICT;
+      return tp.vec0 != nullptr ? logp_impl<true, STRICT, two>(y, D, tp) : logp_impl<false, STRICT, two>(y, D, tp);
+    }
   }
 };
 template <int DP>
-using RoughCarpet = RoughCarpetT<DP, false>;
+using RoughCarpet = RoughCarpetT<DP, kRcThree>;
 template <int DP>
-using RoughCarpet2 = RoughCarpetT<DP, true>;
+using RoughCarpet2 = RoughCarpetT<DP, kRcTwo>;
+template <int DP>
+using RoughCarpetSym = RoughCarpetT<DP, kRcFold>;
 
 // ThreeMixtureDistributionTorch.log_density, multimodal_torch.py:173-242.  cov_invs
 // is always the identity (:87-98) so the [B,D]x[D,D] matmul at :234 is skipped.

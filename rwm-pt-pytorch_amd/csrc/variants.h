@@ -364,12 +364,29 @@ constexpr RunLaunchFn quad_f64_entry() {
     return v;                                                                          \
   }
 
+// A translation unit of a specialisation that only the fused step runs may define, before including this header,
+// PTRWM_TU_NO_LOGP: its table has no stand-alone log-density kernels (ptrwm_logdensity never selects it), and
+// PTRWM_TU_NO_F64: its lane-split table has no state_f64 twins (capi.hip then runs the general functor).
+#ifdef PTRWM_TU_NO_LOGP
+#undef PTRWM_X_LOGP
+#define PTRWM_X_LOGP(W, E) nullptr,
+#endif
+#ifdef PTRWM_TU_NO_F64
+#undef PTRWM_X_QRUN64_N
+#undef PTRWM_X_QRUN64_L
+#undef PTRWM_X_QRUN64_U
+#define PTRWM_X_QRUN64_N(W, E, M) nullptr,
+#define PTRWM_X_QRUN64_L(W, E, M) nullptr,
+#define PTRWM_X_QRUN64_U(W, E, M) nullptr,
+#endif
+
 #define PTRWM_DECLARE_TARGET_VARIANTS(SYMBOL) \
   const TargetVariants &SYMBOL##_narrow();    \
   const TargetVariants &SYMBOL##_wide();      \
   const QuadVariants &SYMBOL##_quad();
 PTRWM_DECLARE_TARGET_VARIANTS(rough_carpet_variants)
 PTRWM_DECLARE_TARGET_VARIANTS(rough_carpet2_variants)  // two-term specialisation, see targets.h
+PTRWM_DECLARE_TARGET_VARIANTS(rough_carpet_sym_variants)  // folded specialisation (modes -m, 0, +m), see targets.h
 PTRWM_DECLARE_TARGET_VARIANTS(three_mixture_variants)
 PTRWM_DECLARE_TARGET_VARIANTS(three_mixture1_variants)  // means differing in the first coordinate only, see targets.h
 PTRWM_DECLARE_TARGET_VARIANTS(full_rosenbrock_variants)

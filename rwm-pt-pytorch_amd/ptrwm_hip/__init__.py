@@ -129,6 +129,7 @@ SYMBOLS = {
     "ptrwm_set_stream_mode": (C.c_int32, [C.c_int32]),
     "ptrwm_has_stream_variant": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
     "ptrwm_last_launch_kind": (C.c_int32, []),
+    "ptrwm_last_launch_functor": (C.c_int32, []),
     "ptrwm_has_quad_variant": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "ptrwm_has_thread_variant": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
     "ptrwm_auto_form": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
@@ -353,6 +354,15 @@ LAUNCH_THREAD, LAUNCH_QUAD, LAUNCH_STREAM = 1, 2, 3
 def last_launch_kind() -> int:
     """Which kernel this thread's most recent ptrwm_run enqueued (LAUNCH_THREAD / LAUNCH_QUAD / LAUNCH_STREAM)."""
     return load_library().ptrwm_last_launch_kind()
+
+
+FUNCTOR_GENERAL, FUNCTOR_SPECIALISED, FUNCTOR_FOLDED = 0, 1, 2
+
+
+def last_launch_functor() -> int:
+    """Which functor of the target this thread's most recent ptrwm_run used (FUNCTOR_GENERAL / FUNCTOR_SPECIALISED /
+    FUNCTOR_FOLDED, include/ptrwm.h)."""
+    return load_library().ptrwm_last_launch_functor()
 
 
 def has_stream_variant(target_kind: int, proposal_kind: int, dim: int) -> bool:
