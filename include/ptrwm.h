@@ -286,6 +286,48 @@ typedef struct ptrwm_run_args {
 int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
                   const ptrwm_run_args *args, void *stream);
 
+/* ---- posterior moments pooled over every replica ------------------------------------------------------------------
+ * A moments accumulator covers the first `temps` temperatures (1 = the cold chain only, n_temps = all).  For each such
+ * temperature t, over every local chain, at every step whose step_counter > burn_in and step_counter % every == 0:
+ *   sum[t, d] += x_d,   sum_sq[t, d] += x_d * x_d,   sum_logp[t] += logp,   count[t] += 1
+ * where x / logp are the replica's state and log-density after the whole step (MH move and that step's swap event) - the
+ * values a trace with trace_every = every records at that step.  Sums are fp64 and only ever added to (+=), so launches,
+ * calls and shards compose; the order of the additions is unspecified (atomics), so two runs may differ in the last bits
+ * of a sum.  ptrwm_swap_sweep events are not steps and add nothing.  No other output of the run changes: state, logp and
+ * every counter are bit-identical to the same run without moments.
+ * Limits:
+ *  - the accumulators must be ordinary device memory of the current device (hipMalloc / a torch tensor): they are
+ *    added to with hardware fp64 atomics, which fine-grained host memory does not support;
+ *  - ptrwm_run_with_moments runs the fixture / trace twin of the step kernel (never the streaming form) and keeps the
+ *    partial sums in LDS: temps * (2 dim + 1) doubles per exchange group (a wavefront of up to 64 / n_temps ladders in the
+ *    thread form, of up to 16 / n_temps ladders in the lane-split form; the whole workgroup for longer ladders), on top
+ *    of what the kernel already holds, at most 160 KiB per workgroup.  Cold-only (temps = 1) fits every shape; all
+ *    temperatures fit e.g. dim 30 with up to 64 temperatures in the thread form.  A shape that does not fit returns
+ *    PTRWM_E_ARG before anything is enqueued (use fewer temps, or pin the other form with ptrwm_set_kernel_form);
+ *  - partial sums are flushed once per launch (ptrwm_run splits requests of more than 2^16 steps into several). */
+typedef struct ptrwm_moments_args {
+  uint32_t struct_size; /* sizeof(ptrwm_moments_args) */
+  int32_t temps;        /* 1..n_temps: the first `temps` temperatures */
+  int32_t every;        /* >= 1: thinning period of the accumulated steps */
+  double *sum;          /* [temps, dim] device, += (required) */
+  double *sum_sq;       /* [temps, dim] device, += (required) */
+  double *sum_logp;     /* [temps] device, +=, or NULL */
+  int64_t *count;       /* [temps] device, +=, or NULL: the number of (chain, step) pairs added per temperature */
+} ptrwm_moments_args;
+
+/* ptrwm_run, and the moments of `moments` accumulated over the steps it performs.  moments == NULL: exactly ptrwm_run.
+ * PTRWM_E_STRUCT for a wrong struct_size; PTRWM_E_ARG for temps outside 1..n_temps, every < 1, or an accumulator too
+ * big for the kernel's LDS (above); PTRWM_E_NULL for a NULL sum / sum_sq. */
+int32_t ptrwm_run_with_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                               const ptrwm_run_args *args, const ptrwm_moments_args *moments, void *stream);
+
+/* Split steps: the moments of the step ptrwm_split_accept just performed (enqueue it after ptrwm_split_accept, which
+ * includes the step's swap event).  Reads from `args`: n_temps, n_chains, state, logp, burn_in, step0, device_step.  The
+ * step is args->step0, or *device_step + step0 in device-step mode - read on the device, so the call can sit inside a
+ * captured block of split steps.  A step that does not count adds nothing.  Same argument checks as
+ * ptrwm_run_with_moments (no LDS limit: a small stand-alone kernel). */
+int32_t ptrwm_split_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm_moments_args *moments, void *stream);
+
 /* One stand-alone swap event over the current states: what the reference's
  * ParallelTemperingRWM_GPU_Optimized._attempt_all_swaps() does when called on its own
  * (pt_rwm_gpu_optimized.py:594-633; tests/debug_pt_performance.py:156).  Exactly the swap part of a ptrwm_run step:

@@ -10,6 +10,13 @@ Shared by `RandomWalkMH_GPU_Optimized` (one temperature) and `ParallelTemperingR
     swap_accept  int64   [n_replicas, n_temps]        accepted swaps of pair (t, t+1)
     last_ord     int64   [n_replicas, n_temps]        attempt ordinal of the pair's last accepted swap
 
+and, when moments are on (moments_temps > 0), pooled over every replica of the shard:
+
+    mom_sum      float64 [moments_temps, dim]         sum of x over the accumulated steps (include/ptrwm.h ptrwm_moments_args)
+    mom_sum_sq   float64 [moments_temps, dim]         sum of x^2
+    mom_sum_logp float64 [moments_temps]              sum of the log-density
+    mom_count    int64   [moments_temps]              (replica, step) pairs added
+
 `n_replicas` is the axis the reference does not have: independent copies of the whole chain /
 ladder, one Philox subsequence each (global replica id = chain_offset + local index), so a run is
 invariant to how replicas are sharded over GPUs.
@@ -41,7 +48,7 @@ class EngineRun:
     def __init__(self, *, target_dist, proposal: "ptrwm_hip.Proposal", beta_ladder: Sequence[float], dim: int,
                  device: torch.device, n_replicas: int, initial_state: np.ndarray, burn_in: int, swap_every: int,
                  swap_mode: str, swap_order: str, seed: Optional[int], chain_offset: int = 0,
-                 dtype: torch.dtype = torch.float32):
+                 dtype: torch.dtype = torch.float32, moments_temps: int = 0, moments_every: int = 1):
         if swap_mode not in ptrwm_hip.SWAP_MODES:
             raise ValueError(f"swap_mode must be one of {sorted(ptrwm_hip.SWAP_MODES)}, got {swap_mode!r}")
         if swap_order not in ptrwm_hip.SWAP_ORDERS:
@@ -113,6 +120,20 @@ class EngineRun:
             swap_every=self.swap_every, swap_mode=self.swap_mode, swap_order=self.swap_order, seed=self.seed,
             chain_offset=self.chain_offset, n_accept=self.n_accept, sq_jump=self.sq_jump,
             swap_accept=self.swap_accept, last_swap_ordinal=self.last_ord)
+        # posterior moments accumulated inside the step kernels (0: off)
+        if not 0 <= int(moments_temps) <= n_temps:
+            raise ValueError(f"moments_temps must be in 0..{n_temps}, got {moments_temps}")
+        if int(moments_every) < 1:
+            raise ValueError(f"moments_every must be >= 1, got {moments_every}")
+        self.moments_temps, self.moments_every = int(moments_temps), int(moments_every)
+        if self.moments_temps:
+            mt = self.moments_temps
+            self.mom_sum = torch.zeros(mt, dim, device=device, dtype=torch.float64)
+            self.mom_sum_sq = torch.zeros(mt, dim, device=device, dtype=torch.float64)
+            self.mom_sum_logp = torch.zeros(mt, device=device, dtype=torch.float64)
+            self.mom_count = torch.zeros(mt, device=device, dtype=torch.int64)
+            self._plan.set_moments(self.mom_sum, self.mom_sum_sq, sum_logp=self.mom_sum_logp, count=self.mom_count,
+                                   every=self.moments_every)
 
     def _density(self, rows: torch.Tensor) -> torch.Tensor:
         """log-density of every row [n, dim] -> float32 [n] on the device."""
@@ -161,6 +182,7 @@ class EngineRun:
         props = self._plan.split_propose(offset)
         lp_new = self._density(props.view(-1, D)).view(C, T)
         self._plan.split_accept(offset, lp_new, swap_event_offset=self.manual_sweeps, no_sweep=no_sweep)
+        self._plan.split_moments(offset)  # (decides on the device whether this step counts; no-op without moments)
         if advance:
             self._plan.split_advance(advance)
 
@@ -247,6 +269,7 @@ class EngineRun:
             props = self._plan.split_propose(s)
             lp_new = self._density(props.view(-1, D)).view(C, T)
             self._plan.split_accept(s, lp_new, swap_event_offset=self.manual_sweeps)
+            self._plan.split_moments(s)
             self.steps_done += 1
             if trace is not None and self.steps_done % trace_every == 0:
                 tc, tt = trace.shape[1], trace.shape[2]
@@ -282,6 +305,20 @@ class EngineRun:
         # events are numbered from 0: even-numbered events take the even pairs
         return ((ev + 1) // 2) * n_even + (ev // 2) * n_odd
 
+    def moments(self) -> Optional[dict]:
+        """The raw moment sums of this shard (device tensors, no synchronisation), or None when moments are off:
+        sum / sum_sq [temps, dim] float64, sum_logp [temps] float64, count [temps] int64, every."""
+        if not self.moments_temps:
+            return None
+        return {"sum": self.mom_sum, "sum_sq": self.mom_sum_sq, "sum_logp": self.mom_sum_logp, "count": self.mom_count,
+                "every": self.moments_every}
+
+    def reset_moments(self) -> None:
+        """Zero the moment accumulators (the chains keep their states)."""
+        if self.moments_temps:
+            for t in (self.mom_sum, self.mom_sum_sq, self.mom_sum_logp, self.mom_count):
+                t.zero_()
+
     def summary(self) -> dict:
         """Whole-shard sums, as plain Python numbers / CPU tensors (one device sync)."""
         acc = self.n_accept.sum(0).cpu()
@@ -294,4 +331,79 @@ class EngineRun:
             "sq_jump_sum": sq,              # [T] float64
             "swap_accept_count": sw,        # [T] int64 (last entry unused)
             "swap_attempts": self.swap_attempts_per_replica() * self.n_replicas,
+        }
+
+
+# ---- posterior moments of the drop-in classes ------------------------------------------------------------------
+MOMENT_MODES = (None, "cold", "all")
+
+
+def moments_temps(mode, n_temps: int, every) -> int:
+    """Temperatures a `moments=` mode covers (0: off); raises on a bad mode or thinning period."""
+    if mode not in MOMENT_MODES:
+        raise ValueError(f"moments must be None, 'cold' or 'all', got {mode!r}")
+    if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
+        raise ValueError(f"moments_every must be an integer >= 1, got {every!r}")
+    return {None: 0, "cold": 1, "all": n_temps}[mode]
+
+
+class PosteriorMoments:
+    """Estimates from the moments accumulated inside the step kernels (include/ptrwm.h ptrwm_moments_args), pooled over
+    every replica of the run.  The host class sets `_moments_mode` / `_moments_every` and owns `_run` (an EngineRun).
+    Every read synchronises."""
+
+    def _moment_sums(self) -> dict:
+        if getattr(self, "_moments_mode", None) is None:
+            raise RuntimeError("posterior moments are off: construct the sampler with moments='cold' or 'all'")
+        run = getattr(self, "_run", None)
+        if run is None:  # nothing run yet, or reset(): empty sums (the next run starts from zero)
+            mt = moments_temps(self._moments_mode, len(getattr(self, "beta_ladder", [1.0])), self._moments_every)
+            z = torch.zeros(mt, self.dim, device=self.device, dtype=torch.float64)
+            return {"sum": z, "sum_sq": z.clone(), "sum_logp": torch.zeros(mt, device=self.device, dtype=torch.float64),
+                    "count": torch.zeros(mt, device=self.device, dtype=torch.int64), "every": self._moments_every}
+        return run.moments()
+
+    def _check_temperature(self, temperature: int, m: dict) -> int:
+        mt = m["sum"].shape[0]
+        if not isinstance(temperature, (int, np.integer)) or not 0 <= temperature < mt:
+            raise ValueError(f"temperature must be in 0..{mt - 1} (the moments cover the first {mt}), got {temperature!r}")
+        return int(temperature)
+
+    @property
+    def moment_count(self) -> torch.Tensor:
+        """(replica, step) pairs accumulated per covered temperature: int64 [temps] on the device."""
+        return self._moment_sums()["count"]
+
+    def posterior_mean(self, temperature: int = 0) -> torch.Tensor:
+        """sum x / n over every replica of `temperature` and every accumulated step: float64 [dim] on the device."""
+        m = self._moment_sums()
+        t = self._check_temperature(temperature, m)
+        return m["sum"][t] / m["count"][t].double()
+
+    def posterior_variance(self, temperature: int = 0) -> torch.Tensor:
+        """sum x^2 / n - mean^2 (per coordinate): float64 [dim] on the device."""
+        m = self._moment_sums()
+        t = self._check_temperature(temperature, m)
+        n = m["count"][t].double()
+        mean = m["sum"][t] / n
+        return m["sum_sq"][t] / n - mean * mean
+
+    def mean_log_density(self) -> torch.Tensor:
+        """sum logp / n per covered temperature: float64 [temps] on the device."""
+        m = self._moment_sums()
+        return m["sum_logp"] / m["count"].double()
+
+    def _moments_diagnostics(self) -> dict:
+        if getattr(self, "_moments_mode", None) is None:
+            return {}
+        m = self._moment_sums()
+        n = m["count"].double()
+        mean = m["sum"] / n[:, None]
+        return {
+            "moments": self._moments_mode,
+            "moments_every": self._moments_every,
+            "moment_count": m["count"].cpu(),
+            "posterior_mean": mean.cpu(),
+            "posterior_variance": (m["sum_sq"] / n[:, None] - mean * mean).cpu(),
+            "mean_log_density": (m["sum_logp"] / n).cpu(),
         }

@@ -30,7 +30,7 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import EngineRun, resolve_device
+from ._engine_core import EngineRun, PosteriorMoments, moments_temps, resolve_device
 
 
 def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
@@ -43,7 +43,7 @@ def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
     return [float(beta_min ** (t / (n_temps - 1))) for t in range(n_temps)]
 
 
-class ParallelTemperingRWM_GPU_Optimized(MHAlgorithm):
+class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
     def __init__(self, dim: int, var: float, target_dist=None, symmetric: bool = True, beta_ladder: list = None,
                  iterative_temp_spacing: bool = False, geom_temp_spacing: bool = False,
                  swap_acceptance_rate: float = 0.234, beta_min_iterative: float = 0.01, N_samples_swap_est: int = 3000,
@@ -54,8 +54,11 @@ class ParallelTemperingRWM_GPU_Optimized(MHAlgorithm):
                  pre_allocate_steps: int = None, dtype: torch.dtype = torch.float32, *,
                  num_replicas: int = 1, proposal_distribution: Optional[ProposalDistribution] = None,
                  swap_mode: str = "exchange", swap_order: str = "sequential", seed: Optional[int] = None,
-                 chain_offset: int = 0, trace: str = "all", thin: int = 1):
+                 chain_offset: int = 0, trace: str = "all", thin: int = 1, moments: Optional[str] = None,
+                 moments_every: int = 1):
         super().__init__(dim, var, target_dist, symmetric)
+        moments_temps(moments, 1, moments_every)  # (checked before anything is built)
+        self._moments_mode, self._moments_every = moments, int(moments_every)
         self.device = resolve_device(device)
         # dtype=torch.float64 (experiment_pt_GPU.py:236 --use_double_precision; pt_rwm_gpu_optimized.py:134,431-449): states,
         # proposals x + scale * z, stored chains and jump distances in double (the engine's state_f64 mode: lane-split
@@ -224,7 +227,8 @@ class ParallelTemperingRWM_GPU_Optimized(MHAlgorithm):
             beta_ladder=self.beta_ladder, dim=self.dim, device=self.device, n_replicas=self.num_replicas,
             initial_state=self._initial_state, burn_in=self.burn_in, swap_every=self.swap_every,
             swap_mode=self._swap_mode, swap_order=self._swap_order, seed=self._seed, chain_offset=self._chain_offset,
-            dtype=self.dtype)
+            dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
+            moments_every=self._moments_every)
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
         self.current_log_densities = self._run.logp[0] if self.num_replicas == 1 else self._run.logp
@@ -415,6 +419,7 @@ class ParallelTemperingRWM_GPU_Optimized(MHAlgorithm):
             "clone_free_swaps": "swaps are LDS exchanges inside one wavefront / workgroup (no HBM traffic)",
             "kernel_fusion": "proposal, log-density, accept, update, swaps and statistics in one HIP kernel",
             "memory_allocated_mb": torch.cuda.memory_allocated() / 1e6 if self.device.type == "cuda" else 0,
+            **self._moments_diagnostics(),
         }
 
     def performance_summary(self):

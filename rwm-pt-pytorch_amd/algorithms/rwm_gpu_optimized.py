@@ -22,7 +22,7 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import EngineRun, resolve_device
+from ._engine_core import EngineRun, PosteriorMoments, moments_temps, resolve_device
 
 
 def ultra_fused_mcmc_step_basic(current_state, current_log_density, increment, random_val, beta, log_density_proposed):
@@ -52,11 +52,14 @@ def _rebuild_proposal(p: ProposalDistribution, dim, beta, device, dtype, rng):
     )
 
 
-class RandomWalkMH_GPU_Optimized(MHAlgorithm):
+class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
     def __init__(self, dim: int, var: float = None, target_dist=None, symmetric: bool = True, beta: float = 1.0,
                  burn_in: int = 0, device: str = None, pre_allocate_steps: int = None, use_efficient_rng: bool = True,
                  compile_mode: str = None, proposal_distribution: ProposalDistribution = None, *,
-                 num_chains: int = 1, seed: Optional[int] = None, chain_offset: int = 0, thin: int = 1):
+                 num_chains: int = 1, seed: Optional[int] = None, chain_offset: int = 0, thin: int = 1,
+                 moments: Optional[str] = None, moments_every: int = 1):
+        moments_temps(moments, 1, moments_every)  # (checked before anything is built)
+        self._moments_mode, self._moments_every = moments, int(moments_every)
         if proposal_distribution is None and var is None:
             raise ValueError("Either var (backward compatibility) or proposal_distribution must be provided")
         super().__init__(dim, 1.0 if proposal_distribution is not None else var, target_dist, symmetric)
@@ -148,7 +151,8 @@ class RandomWalkMH_GPU_Optimized(MHAlgorithm):
             target_dist=self.target_dist, proposal=self.proposal_dist.engine_proposal(), beta_ladder=[self.beta],
             dim=self.dim, device=self.device, n_replicas=self.num_chains, initial_state=self.chain[-1],
             burn_in=self.burn_in, swap_every=1, swap_mode="exchange", swap_order="sequential", seed=self._seed,
-            chain_offset=self._chain_offset,
+            chain_offset=self._chain_offset, moments_temps=moments_temps(self._moments_mode, 1, self._moments_every),
+            moments_every=self._moments_every,
         )
         self.current_state = self._run.state[0, 0]  # views: always the live values
         self.log_target_density_current = self._run.logp[0, 0]
@@ -234,6 +238,7 @@ class RandomWalkMH_GPU_Optimized(MHAlgorithm):
             "memory_allocated_mb": torch.cuda.memory_allocated() / 1e6 if self.device.type == "cuda" else 0,
             "memory_efficiency": "state in registers for the whole launch; HBM touched at launch start/end",
             "random_generation": "Philox4x32-10 in-kernel (no precomputed random tensors)",
+            **self._moments_diagnostics(),
         }
 
     def performance_comparison_summary(self):

@@ -67,3 +67,24 @@ def allreduce_summary(summary: dict, device, group: Optional[dist.ProcessGroup] 
         world = dist.get_world_size(group)
         dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=group)
     return unpack_summary(vec, n_temps, world)
+
+
+def allreduce_moments(moments: dict, group: Optional[dist.ProcessGroup] = None) -> dict:
+    """Whole-job moment sums from every rank's shard (EngineRun.moments(): sum / sum_sq [temps, dim], sum_logp and count
+    [temps]): one SUM all-reduce of a float64 vector, separate from the summary's (pack_summary keeps its layout).
+    Returns new tensors on the shards' device; the inputs are not modified.  Counts are exact below 2^53."""
+    s, q, lp, n = moments["sum"], moments["sum_sq"], moments["sum_logp"], moments["count"]
+    temps, dim = s.shape
+    vec = torch.cat([s.reshape(-1).double(), q.reshape(-1).double(), lp.reshape(-1).double(), n.reshape(-1).double()])
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=group)
+    td = temps * dim
+    out = {
+        "sum": vec[:td].view(temps, dim),
+        "sum_sq": vec[td:2 * td].view(temps, dim),
+        "sum_logp": vec[2 * td:2 * td + temps],
+        "count": vec[2 * td + temps:].round().to(torch.int64),
+    }
+    if "every" in moments:
+        out["every"] = moments["every"]
+    return out

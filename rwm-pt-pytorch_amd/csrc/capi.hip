@@ -615,9 +615,64 @@ static int32_t launch_sweep(const ptrwm_run_args *args, int32_t dim, int64_t eve
   return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 
+// Moments of one split step (ptrwm_split_moments): the state / log-density after the step, summed over a tile of
+// kSplitMomChains chains per workgroup - thread k owns element k of the first temps * dim floats of every chain's run
+// (contiguous: coalesced reads chain after chain) and keeps its two sums in registers - then one no-return fp64 atomic
+// per element and workgroup.
+constexpr int kSplitMomChains = 256;
+struct SplitMomentsArgs {
+  const float *state, *logp;
+  double *sum, *sum_sq, *sum_logp;
+  long long *count;
+  long long n_chains, step, burn_in, every;
+  const long long *device_step;
+  int n_temps, dim, temps;
+};
+
+__global__ void __launch_bounds__(256) split_moments_kernel(SplitMomentsArgs a) {
+  const long long step = a.device_step != nullptr ? *a.device_step + a.step : a.step;
+  const long long sc = step + 1;  // step_counter of the step just performed
+  if (!(sc > a.burn_in && sc % a.every == 0)) return;  // (grid-uniform)
+  const long long c0 = (long long)blockIdx.x * kSplitMomChains;
+  const long long c1 = (a.n_chains - c0 < kSplitMomChains) ? a.n_chains : c0 + kSplitMomChains;
+  const int td = a.temps * a.dim;
+  const long long run = (long long)a.n_temps * a.dim;
+  for (int k = threadIdx.x; k < td; k += blockDim.x) {
+    double s = 0.0, q = 0.0;
+    for (long long c = c0; c < c1; ++c) {
+      const double v = (double)a.state[c * run + k];
+      s += v;
+      q += v * v;
+    }
+    unsafeAtomicAdd(a.sum + k, s);
+    unsafeAtomicAdd(a.sum_sq + k, q);
+  }
+  if (a.sum_logp != nullptr) {
+    for (int t = threadIdx.x; t < a.temps; t += blockDim.x) {
+      double s = 0.0;
+      for (long long c = c0; c < c1; ++c) s += (double)a.logp[c * a.n_temps + t];
+      unsafeAtomicAdd(a.sum_logp + t, s);
+    }
+  }
+  if (a.count != nullptr)
+    for (int t = threadIdx.x; t < a.temps; t += blockDim.x) count_add(&a.count[t], c1 - c0);
+}
+
 }  // namespace ptrwm
 
 using namespace ptrwm;
+
+// ptrwm_moments_args checks shared by ptrwm_run_with_moments and ptrwm_split_moments (args already checked); NULL: none
+static int32_t check_moments(const ptrwm_run_args *args, const ptrwm_moments_args *m) {
+  if (m == nullptr) return PTRWM_OK;
+  if (m->struct_size != sizeof(ptrwm_moments_args)) return PTRWM_E_STRUCT;
+  if (m->temps < 1 || m->temps > args->n_temps || m->every < 1) return PTRWM_E_ARG;
+  if (m->sum == nullptr || m->sum_sq == nullptr) return PTRWM_E_NULL;
+  return PTRWM_OK;
+}
+
+static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                        const ptrwm_moments_args *mom, void *hip_stream);
 
 extern "C" {
 
@@ -717,11 +772,24 @@ int32_t ptrwm_has_variant(int32_t target_kind, int32_t proposal_kind, int32_t di
 
 int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                   void *hip_stream) {
+  return run_impl(target, proposal, args, nullptr, hip_stream);
+}
+
+int32_t ptrwm_run_with_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                               const ptrwm_run_args *args, const ptrwm_moments_args *moments, void *stream) {
+  return run_impl(target, proposal, args, moments, stream);
+}
+
+}  // extern "C"
+
+static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                        const ptrwm_moments_args *mom, void *hip_stream) {
   if (proposal == nullptr || args == nullptr) return PTRWM_E_NULL;
   if (int rc = check_target(target)) return rc;
   if (args->struct_size != sizeof(ptrwm_run_args)) return PTRWM_E_STRUCT;
   if (proposal->kind < 0 || proposal->kind >= PTRWM_PROPOSAL_COUNT) return PTRWM_E_KIND;
   if (args->n_temps < 1 || args->n_temps > PTRWM_MAX_TEMPS) return PTRWM_E_TEMPS;
+  if (int rc = check_moments(args, mom)) return rc;
   if (args->n_chains < 0 || args->n_steps < 0 || args->step0 < 0 || args->burn_in < 0 || args->swap_every < 1)
     return PTRWM_E_ARG;
   if (args->swap_mode != PTRWM_SWAP_EXCHANGE && args->swap_mode != PTRWM_SWAP_REFERENCE_COPY) return PTRWM_E_ARG;
@@ -775,7 +843,8 @@ int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *pr
   }
   if (fn == nullptr) return PTRWM_E_NOVARIANT;
   const long long se = args->swap_every;
-  const bool full = ext || args->trace != nullptr || args->accept_flags != nullptr;
+  // moments are accumulated by the fixture / trace twin (kernel.h FullArgs)
+  const bool full = ext || args->trace != nullptr || args->accept_flags != nullptr || mom != nullptr;
   // swap events before step_counter sc = multiples m*se with burn_in < m*se <= sc
   auto events_upto = [&](long long sc) -> long long {
     const long long e = sc / se - args->burn_in / se;
@@ -817,6 +886,22 @@ int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *pr
   k.full.trace_chains = args->trace != nullptr ? args->trace_chains : 0;
   k.full.trace_temps = args->trace_temps;
   k.full.n_raw_ext = ptrwm_ext_raw_per_step(proposal->kind, target->dim);
+  k.full.mom_sum = nullptr;
+  k.full.mom_sum_sq = nullptr;
+  k.full.mom_sum_logp = nullptr;
+  k.full.mom_count = nullptr;
+  k.full.mom_steps = 0;
+  k.full.mom_temps = mom != nullptr ? mom->temps : 0;
+  k.full.mom_every = mom != nullptr ? mom->every : 1;
+  k.full.steps_to_mom = 0;
+  if (mom != nullptr) {
+    // the whole workgroup's LDS: what the kernel holds anyway and the moments regions behind it (variants.h)
+    const int block = quad ? quad_block_threads(args->n_temps) : (wide ? ((args->n_temps + 63) & ~63) : kBlockThreads);
+    const unsigned base = quad ? quad_kernel_lds_bytes(block, canon_width(target->dim), f64)
+                               : step_kernel_lds_bytes(block, kWidths[dpi].dp) + (wide ? kWideVoteBytes : 0u);
+    k.dim = target->dim;
+    if (base + moments_lds_bytes(k, block, quad) > kMaxLdsBytes) return PTRWM_E_ARG;
+  }
 
   // the streaming form for short launches of the one-thread-per-replica kernel (see kStreamMaxSteps above)
   bool stream = false;
@@ -871,12 +956,26 @@ int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *pr
     // traced steps are those whose step_counter is a multiple of trace_every: rows before this launch
     k.full.trace_row0 = args->trace_row0 + (step0 / te - args->step0 / te);
     k.full.steps_to_trace = (int)(te - step0 % te);
+    if (mom != nullptr) {
+      // accumulated steps of this launch: step_counter in (max(step0, burn_in), step0 + n], a multiple of every
+      const long long me = mom->every, lo = args->burn_in > step0 ? args->burn_in : step0;
+      const long long m = (step0 + n) / me - lo / me;
+      const bool on = m > 0;  // (a launch with none leaves the accumulators and its LDS alone)
+      k.full.mom_steps = on ? m : 0;
+      k.full.mom_sum = on ? mom->sum : nullptr;
+      k.full.mom_sum_sq = mom->sum_sq;
+      k.full.mom_sum_logp = mom->sum_logp;
+      k.full.mom_count = (long long *)mom->count;
+      k.full.steps_to_mom = (int)(me - step0 % me);
+    }
     const hipError_t err = fn(k, (unsigned)n_blocks, full ? kRunFull : (stream ? kRunStream : kRunProd), (hipStream_t)hip_stream);
     if (err != hipSuccess) return PTRWM_E_LAUNCH;
     done += n;
   }
   return PTRWM_OK;
 }
+
+extern "C" {
 
 int32_t ptrwm_swap_sweep(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
                          void *stream) {
@@ -996,6 +1095,34 @@ int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *propo
   // the swap event of this step: event number as ptrwm_run counts them, swap uniforms from the fused kernel's stream
   const long long ev = sc / args->swap_every - args->burn_in / args->swap_every - 1 + args->swap_event_offset;
   return launch_sweep(args, dim, ev, (int)kStreamSwap, proposals, args->sq_jump, (hipStream_t)stream);
+}
+
+int32_t ptrwm_split_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm_moments_args *moments, void *stream) {
+  if (int rc = split_common_checks(args, dim)) return rc;
+  if (moments == nullptr) return PTRWM_E_NULL;
+  if (int rc = check_moments(args, moments)) return rc;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->state == nullptr || args->logp == nullptr) return PTRWM_E_NULL;
+  if (args->device_step == nullptr && !(args->step0 + 1 > args->burn_in && (args->step0 + 1) % moments->every == 0))
+    return PTRWM_OK;  // (known on the host: nothing to add)
+  SplitMomentsArgs a;
+  a.state = args->state;
+  a.logp = args->logp;
+  a.sum = moments->sum;
+  a.sum_sq = moments->sum_sq;
+  a.sum_logp = moments->sum_logp;
+  a.count = (long long *)moments->count;
+  a.n_chains = args->n_chains;
+  a.step = args->step0;
+  a.burn_in = args->burn_in;
+  a.every = moments->every;
+  a.device_step = (const long long *)args->device_step;
+  a.n_temps = args->n_temps;
+  a.dim = dim;
+  a.temps = moments->temps;
+  const unsigned grid = (unsigned)((args->n_chains + kSplitMomChains - 1) / kSplitMomChains);
+  hipLaunchKernelGGL(split_moments_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 
 int32_t ptrwm_split_advance(const ptrwm_run_args *args, void *stream) {

@@ -60,7 +60,18 @@ struct FullArgs {
   int trace_temps, n_raw_ext;
   int trace_every;     // thinning period (>= 1)
   int steps_to_trace;  // steps until the first traced step of this launch (1 = the first step)
+  // moments accumulator (include/ptrwm.h ptrwm_moments_args; NULL mom_sum = off): fp64 partial sums in a region of the
+  // dynamic LDS per exchange group, added to at every accumulated step and flushed to HBM once at the end of the launch
+  double *__restrict__ mom_sum;       // [mom_temps, dim]
+  double *__restrict__ mom_sum_sq;    // [mom_temps, dim]
+  double *__restrict__ mom_sum_logp;  // [mom_temps] or NULL
+  long long *__restrict__ mom_count;  // [mom_temps] or NULL
+  long long mom_steps;                // accumulated steps in this launch: count[t] += live ladders x mom_steps
+  int mom_temps, mom_every;
+  int steps_to_mom;                   // steps until the first step whose step_counter % mom_every == 0 (1 = the first step)
 };
+
+typedef const __attribute__((address_space(4))) FullArgs *kargs_full_ptr;
 
 struct KArgs {
   float *__restrict__ state;
@@ -311,6 +322,46 @@ __device__ __forceinline__ void count_add(long long *p, long long v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// The moments region of one exchange group: [mom_temps * dim] sums of x, [mom_temps * dim] sums of x^2, [mom_temps] sums
+// of the log-density, as doubles, behind everything else the kernel keeps in its dynamic LDS.  One region per group:
+// narrow groups (one wave) never meet at a workgroup barrier, so they cannot share one.
+constexpr unsigned moments_region_doubles(int temps, int dim) { return (unsigned)(temps * (2 * dim + 1)); }
+
+__device__ __forceinline__ void moments_zero(double *reg, int n, int tid, int nthr) {
+  for (int i = tid; i < n; i += nthr) reg[i] = 0.0;
+}
+// ds_add_f64: lanes of one wave with equal temperature (the ladders of a narrow group) hit the same address - the LDS
+// atomic unit serialises them
+__device__ __forceinline__ void moments_add(double *p, double v) {
+  (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// one no-return global_atomic_add_f64 per non-zero partial sum (device memory: include/ptrwm.h), and the counts
+// (the pointers come from the kernarg segment, late_args: loaded here, not held across the step loop)
+__device__ __forceinline__ void moments_flush(const double *reg, kargs_full_ptr f, int dim, long long live_ladders, int tid,
+                                              int nthr) {
+  const int temps = f->mom_temps;
+  const int td = temps * dim;
+  double *const sum = f->mom_sum, *const sum_sq = f->mom_sum_sq, *const sum_logp = f->mom_sum_logp;
+  const int n = 2 * td + (sum_logp != nullptr ? temps : 0);
+  for (int i = tid; i < n; i += nthr) {
+    const double v = reg[i];
+    if (v != 0.0) unsafeAtomicAdd(i < td ? sum + i : (i < 2 * td ? sum_sq + (i - td) : sum_logp + (i - 2 * td)), v);
+  }
+  long long *const count = f->mom_count;
+  const long long add = live_ladders * f->mom_steps;
+  if (count != nullptr)
+    for (int i = tid; i < temps; i += nthr) count_add(&count[i], add);
+}
+
+// the thread form's moments region: behind the rows and parked words of every group of the workgroup (and a wide
+// group's vote word); one per wave in narrow workgroups, one per workgroup for a wide ladder
+template <int DP>
+__device__ __forceinline__ double *thread_moments_region(float *s_dyn, bool wide, int gthreads, int wave, int stride) {
+  float *const base = s_dyn + (wide ? gthreads * (DP + kLdsExtraPerThread) + (int)(kWideVoteBytes / 4u)
+                                    : kBlockThreads * (DP + kLdsExtraPerThread));
+  return reinterpret_cast<double *>(base) + (wide ? 0 : wave * stride);
+}
+
 template <bool EXACT>
 __device__ __forceinline__ int fresh_dim(int d0) {
   if constexpr (!EXACT) PTRWM_VALUE_BARRIER("+s"(d0));
@@ -530,6 +581,12 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       stage_copy<true>(s_stage, gs, stage_total, tid, nthr);
       row_head = stage_head(gs);
       if (wide) reinterpret_cast<int *>(s_dyn)[nthr * (DP + kLdsExtraPerThread)] = 0;  // no objection yet (kWideVoteBytes)
+      if constexpr (FULL) {
+        if (a.full.mom_sum != nullptr) {  // (ordered before the first add by the barrier below)
+          const int n_mom = (int)moments_region_doubles(a.full.mom_temps, D0);
+          moments_zero(thread_moments_region<DP>(s_dyn, wide, nthr, wave, n_mom), n_mom, tid, nthr);
+        }
+      }
     }
     // (streaming form: the run is landing in slab `cur` by LDS-DMA.  The compiler does not order LDS reads behind it:
     // this wait does - every DMA of this wave, and nothing younger than a whole step, see flush_pending)
@@ -597,6 +654,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       FULL && live && a.full.trace != nullptr && (chain < a.full.trace_chains) && (t < a.full.trace_temps);
   int to_swap = a.steps_to_swap;
   int to_trace = FULL ? a.full.steps_to_trace : 0;
+  [[maybe_unused]] int to_mom = FULL ? a.full.steps_to_mom : 0;
   int trace_rows = 0;    // rows of the trace written by this launch
   int swap_in_call = 0;  // swap events already done in this launch
   const int ev_par0 = (int)(a.first_swap_event & 1);
@@ -792,6 +850,24 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
         if (a.full.trace_logp != nullptr) a.full.trace_logp[row] = lp;
       }
       trace_rows += trace_now ? 1 : 0;
+      if (a.full.mom_sum != nullptr) {  // wave-uniform countdown, as the trace's; the state after the whole step
+        --to_mom;
+        const bool mom_now = (to_mom == 0);
+        if (mom_now) to_mom = a.full.mom_every;
+        if (mom_now && count_on && live && t < a.full.mom_temps) {
+          const int mt = a.full.mom_temps;
+          double *const reg = thread_moments_region<DP>(s_dyn, wide, wide ? ((T + 63) & ~63) : 64, wave,
+                                                        (int)moments_region_doubles(mt, D));
+          double *const rs = reg + t * D;
+          double *const rq = reg + (mt + t) * D;
+          PTRWM_DIM_LOOP(d, DP, D, {
+            const double v = (double)x[d];
+            moments_add(rs + d, v);
+            moments_add(rq + d, v * v);
+          })
+          moments_add(reg + 2 * mt * D + t, (double)lp);
+        }
+      }
     }
   }
 
@@ -828,6 +904,13 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     }
     sync_group();
     const int nthr = wide2 ? ((T2 + 63) & ~63) : 64;
+    if constexpr (FULL) {
+      // every add of the launch is behind the barrier above: the group's partial sums go to HBM, once
+      const kargs_full_ptr fa = &ae->full;
+      if (fa->mom_sum != nullptr)
+        moments_flush(thread_moments_region<DP>(s_dyn, wide2, nthr, wave, (int)moments_region_doubles(fa->mom_temps, D2)),
+                      fa, D2, live_chains, tid2, nthr);
+    }
     if constexpr (STREAM) {
       // whole aligned vectors only (capi.hip): slab -> registers now, registers -> HBM in flush_pending
       const pf_vec4 *__restrict__ lv = reinterpret_cast<const pf_vec4 *>(rows2);

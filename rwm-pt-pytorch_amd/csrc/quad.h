@@ -601,6 +601,12 @@ constexpr unsigned quad_kernel_lds_bytes(int threads, int w, bool f64 = false) {
 // temperatures: up to 256 VGPRs).  (Until round 4 the W >= 20 classes also existed for 1024 threads: 128 VGPRs, 40 of
 // them spilled inside the step loop - retired, variants.h.)
 constexpr int kQuadThreads = 512;
+// the lane-split form's moments region (kernel.h moments_region_doubles): behind the slabs of every group of the
+// workgroup; one per wave in narrow workgroups, one per workgroup for wide ladders
+template <int W, bool F64>
+__device__ __forceinline__ double *quad_moments_region(float *s_dyn, bool wide, int wave, int stride) {
+  return reinterpret_cast<double *>(s_dyn + (int)blockDim.x * (W * (F64 ? 2 : 1) + 2)) + (wide ? 0 : wave * stride);
+}
 
 // double-precision pieces of the F64 form: IEEE ops the compiler must not contract (the state update x + scale * z is then
 // bit-identical to the reference's two float64 torch ops), and the canonical quad combination on 64-bit values
@@ -707,6 +713,12 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
     float *__restrict__ gs = a.state + chain0 * T * (long long)D * SW;
     stage_copy<true>(rows_f, gs, stage_total, tid, gthreads);
     s_landed[nslots + slot_raw] = 0;  // the ladders' swap-form objections (wide groups: the vote of a swap event, below)
+    if constexpr (FULL) {
+      if (a.full.mom_sum != nullptr) {  // (ordered before the first add by the barrier below)
+        const int n_mom = (int)moments_region_doubles(a.full.mom_temps, D);
+        moments_zero(quad_moments_region<W, F64>(s_dyn, wide, (int)(threadIdx.x >> 6), n_mom), n_mom, tid, gthreads);
+      }
+    }
     sync_group();
     const state_t *seg = reinterpret_cast<const state_t *>(rows_f + stage_head(gs)) + slot * D + l.d0;
 #pragma unroll
@@ -747,6 +759,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
       FULL && live && a.full.trace != nullptr && (chain < a.full.trace_chains) && (t < a.full.trace_temps);
   int to_swap = a.steps_to_swap;
   int to_trace = FULL ? a.full.steps_to_trace : 0;
+  [[maybe_unused]] int to_mom = FULL ? a.full.steps_to_mom : 0;
   int trace_rows = 0;
   int swap_in_call = 0;
   const int ev_par0 = (int)(a.first_swap_event & 1);
@@ -986,6 +999,26 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
         if (a.full.trace_logp != nullptr && l.q == 0) a.full.trace_logp[row] = lp;
       }
       trace_rows += trace_now ? 1 : 0;
+      if (a.full.mom_sum != nullptr) {  // wave-uniform countdown, as the trace's; the state after the whole step
+        --to_mom;
+        const bool mom_now = (to_mom == 0);
+        if (mom_now) to_mom = a.full.mom_every;
+        if (mom_now && count_on && live && t < a.full.mom_temps) {
+          const int mt = a.full.mom_temps;
+          double *const reg = quad_moments_region<W, F64>(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(mt, D));
+          double *const rs = reg + t * D + l.d0;
+          double *const rq = reg + (mt + t) * D + l.d0;
+#pragma unroll
+          for (int j = 0; j < W; ++j) {
+            if (q_valid<MIN_OWN>(l, j)) {
+              const double v = (double)x[j];
+              moments_add(rs + j, v);
+              moments_add(rq + j, v * v);
+            }
+          }
+          if (l.q == 0) moments_add(reg + 2 * mt * D + t, (double)lp);
+        }
+      }
     }
   }
 
@@ -1004,6 +1037,13 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
         if (q_valid<MIN_OWN>(l, j)) seg[j] = x[j];
     }
     sync_group();
+    if constexpr (FULL) {
+      // every add of the launch is behind the barrier above: the group's partial sums go to HBM, once
+      const kargs_full_ptr fa = &ae->full;
+      if (fa->mom_sum != nullptr)
+        moments_flush(quad_moments_region<W, F64>(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(fa->mom_temps, D)),
+                      fa, D, live_chains, tid, gthreads);
+    }
     stage_copy<false>(rows_f, gs, stage_total, tid, gthreads);
   }
   if (live && l.q == 0) {

@@ -117,6 +117,16 @@ inline int device_cus() {
   return n;
 }
 
+// LDS of a CU (MI355X: 160 KiB), the most one workgroup may declare
+constexpr unsigned kMaxLdsBytes = 160u * 1024u;
+// dynamic LDS bytes of the moments regions of a FULL-twin workgroup of `block` threads: one region per exchange group -
+// per wave of a narrow workgroup, one for a wide ladder (thread form: T > 64; lane-split form: 4 T > 64)
+inline unsigned moments_lds_bytes(const KArgs &a, int block, bool lane_split) {
+  const bool wide = lane_split ? 4 * a.n_temps > 64 : a.n_temps > 64;
+  const int groups = wide ? 1 : block / 64;
+  return (unsigned)groups * moments_region_doubles(a.full.mom_temps, a.dim) * 8u;
+}
+
 // The streaming twin: a grid sized to the device - as many workgroups as are resident at once (occupancy of THIS kernel on
 // THIS device, asked once), trimmed so that every wave walks the same number of groups (+-1).
 template <class Target, class Proposal, int DP, bool EXACT>
@@ -170,7 +180,17 @@ hipError_t launch_run(const KArgs &a, unsigned grid, int mode, hipStream_t strea
                                            (int)(step_kernel_lds_bytes(kBlockThreads, DP) + kWideVoteBytes), raised_mask);
     if (e != hipSuccess) return e;
   }
-  if (full)
+  if (full && a.full.mom_sum != nullptr) {
+    // the moments regions behind (kernel.h thread_moments_region); the fixture twin's allowance alone is raised to all
+    // of a CU's LDS (the C ABI refuses what does not fit: moments_lds_bytes)
+    const unsigned lds_m = lds + moments_lds_bytes(a, (int)block, false);
+    if (lds_m > 48u * 1024u) {
+      static unsigned long long raised_mask_m = 0;
+      const hipError_t e = raise_dynamic_lds((const void *)kfull, (const void *)kfull, (int)kMaxLdsBytes, raised_mask_m);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kfull, dim3(grid), dim3(block), lds_m, stream, a);
+  } else if (full)
     hipLaunchKernelGGL(kfull, dim3(grid), dim3(block), lds, stream, a);
   else
     hipLaunchKernelGGL(kprod, dim3(grid), dim3(block), lds, stream, a);
@@ -285,7 +305,15 @@ hipError_t launch_run_quad(const KArgs &a, unsigned grid, int mode, hipStream_t 
                                            (int)quad_kernel_lds_bytes(MAXT, W, F64), raised_mask);
     if (e != hipSuccess) return e;
   }
-  if (full)
+  if (full && a.full.mom_sum != nullptr) {  // (as launch_run: the moments regions behind the slabs, quad_moments_region)
+    const unsigned lds_m = lds + moments_lds_bytes(a, (int)block, true);
+    if (lds_m > 48u * 1024u) {
+      static unsigned long long raised_mask_m = 0;
+      const hipError_t e = raise_dynamic_lds((const void *)kfull, (const void *)kfull, (int)kMaxLdsBytes, raised_mask_m);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kfull, dim3(grid), dim3(block), lds_m, stream, a);
+  } else if (full)
     hipLaunchKernelGGL(kfull, dim3(grid), dim3(block), lds, stream, a);
   else
     hipLaunchKernelGGL(kprod, dim3(grid), dim3(block), lds, stream, a);

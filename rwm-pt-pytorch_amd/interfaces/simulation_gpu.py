@@ -117,6 +117,16 @@ class MCMCSimulation_GPU:
         post = chain[self.burn_in:]
         return np.mean(np.sum((post[1:] - post[:-1]) ** 2, axis=1))
 
+    def posterior_mean(self, temperature: int = 0):
+        """The sampler's posterior mean pooled over every replica (needs moments='cold' or 'all', forwarded to it)."""
+        self._require_run()
+        return self.algorithm.posterior_mean(temperature)
+
+    def posterior_variance(self, temperature: int = 0):
+        """The sampler's posterior variance pooled over every replica (needs moments='cold' or 'all')."""
+        self._require_run()
+        return self.algorithm.posterior_variance(temperature)
+
     def pt_expected_squared_jump_distance(self):
         self._require_run()
         return self.algorithm.pt_esjd

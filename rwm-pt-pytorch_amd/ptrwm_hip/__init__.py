@@ -119,6 +119,19 @@ class RunArgs(C.Structure):
     ]
 
 
+class MomentsArgs(C.Structure):
+    """ptrwm_moments_args: fp64 moment sums of the first ``temps`` temperatures (include/ptrwm.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("temps", C.c_int32),
+        ("every", C.c_int32),
+        ("sum", C.c_void_p),
+        ("sum_sq", C.c_void_p),
+        ("sum_logp", C.c_void_p),
+        ("count", C.c_void_p),
+    ]
+
+
 # every symbol include/ptrwm.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "ptrwm_abi_version": (C.c_int32, []),
@@ -138,6 +151,10 @@ SYMBOLS = {
     "ptrwm_source_hash": (C.c_char_p, []),
     "ptrwm_form_table_source_hash": (C.c_char_p, []),
     "ptrwm_run": (C.c_int32, [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.c_void_p]),
+    "ptrwm_run_with_moments": (
+        C.c_int32,
+        [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.c_void_p]),
+    "ptrwm_split_moments": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(MomentsArgs), C.c_void_p]),
     "ptrwm_swap_sweep": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "ptrwm_split_propose": (
         C.c_int32, [C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -530,6 +547,52 @@ class RunPlan:
         self._plain = True  # no per-launch buffers set in _a
         self._last_trace = (None, None, None)  # (trace, trace_logp, trace_every) marshalled into _a by the last launch
         self._guard = on_device(self.device)  # (after the checks above: they reject CPU tensors first)
+        self._mom = None  # (MomentsArgs, byref, tensors) of set_moments
+
+    def set_moments(self, sum: Optional[torch.Tensor], sum_sq: Optional[torch.Tensor] = None, *,
+                    sum_logp: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                    every: int = 1) -> None:
+        """Accumulate posterior moments (include/ptrwm.h ptrwm_moments_args) in every following ``launch`` and
+        ``split_moments``: ``sum`` / ``sum_sq`` [temps, dim] float64, ``sum_logp`` [temps] float64 and ``count`` [temps]
+        int64 (both optional), all on the run's device and added to (+=).  ``temps`` (the first temperatures covered) is
+        the first extent of ``sum``.  ``set_moments(None)`` switches it off."""
+        if sum is None:
+            self._mom = None
+            return
+        Cn, T, D = self.shape
+        if sum.dim() != 2 or sum.shape[1] != D or not 1 <= sum.shape[0] <= T:
+            raise ValueError(f"moments sum must be [temps, {D}] with 1 <= temps <= {T}")
+        temps = sum.shape[0]
+        if sum_sq is None or tuple(sum_sq.shape) != (temps, D):
+            raise ValueError(f"moments sum_sq must be [{temps}, {D}]")
+        for name, t in (("sum_logp", sum_logp), ("count", count)):
+            if t is not None and tuple(t.shape) != (temps,):
+                raise ValueError(f"moments {name} must be [{temps}]")
+        if int(every) < 1:
+            raise ValueError("moments every must be >= 1")
+        for name, t in (("sum", sum), ("sum_sq", sum_sq), ("sum_logp", sum_logp), ("count", count)):
+            if t is not None and t.device != self.device:
+                raise ValueError(f"moments {name} is on {t.device}, state on {self.device}")
+        m = MomentsArgs()
+        m.struct_size = C.sizeof(MomentsArgs)
+        m.temps = temps
+        m.every = int(every)
+        m.sum = _require_device(sum, "moments sum", torch.float64)
+        m.sum_sq = _require_device(sum_sq, "moments sum_sq", torch.float64)
+        m.sum_logp = _opt(sum_logp, "moments sum_logp", torch.float64)
+        m.count = _opt(count, "moments count", torch.int64)
+        self._mom = (m, C.byref(m), (sum, sum_sq, sum_logp, count))
+
+    def split_moments(self, step: int) -> None:
+        """Moments of the split step ``step`` just performed (ptrwm_split_moments; device-step mode: counter + step).
+        Enqueue after ``split_accept``.  No-op without ``set_moments``."""
+        if self._mom is None:
+            return
+        self._a.step0 = step
+        with self._guard:
+            rc = self._lib.ptrwm_split_moments(self._refs[4], self.shape[2], self._mom[1], _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_split_moments")
 
     def launch(
         self,
@@ -596,10 +659,14 @@ class RunPlan:
             self._plain = plain
             if trace is not None and ext_prop is None and ext_u is None and ext_swap_u is None and accept_flags is None:
                 self._last_trace = (trace, trace_logp, trace_every)
-        with self._guard:
-            rc = self._lib.ptrwm_run(self._refs[2], self._refs[3], self._refs[4], _stream(self.device))
+        if self._mom is None:
+            with self._guard:
+                rc = self._lib.ptrwm_run(self._refs[2], self._refs[3], self._refs[4], _stream(self.device))
+        else:
+            with self._guard:
+                rc = self._lib.ptrwm_run_with_moments(self._refs[2], self._refs[3], self._refs[4], self._mom[1], _stream(self.device))
         if rc != 0:
-            raise PTRWMError(rc, "ptrwm_run")
+            raise PTRWMError(rc, "ptrwm_run_with_moments" if self._mom is not None else "ptrwm_run")
 
     def _split_buffers(self):
         if getattr(self, "_split", None) is None:
