@@ -660,52 +660,13 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
   const int ev_par0 = (int)(a.first_swap_event & 1);
   unsigned long long s = (unsigned long long)a.step0;  // 0-based global step index
 
-  for (int i = 0; i < a.n_steps; ++i, ++s) {
-    const bool count_on = i >= a.burn_left;
-    --to_swap;
-    const bool multiple = (to_swap == 0);
-    if (multiple) to_swap = a.swap_every;
-    const bool swap_due = multiple && count_on && (T > 1);
-
-    rc.c0hi = (uint32_t)(s >> 32) << 16;
-    rc.c1 = (uint32_t)s;
-    rc.c3 = c3_base | (kStreamMH << 8);
-    // (at the register cap the chain word is made opaque per step: its product with the Philox multiplier is otherwise
-    // hoisted out of the step loop as a 64-bit pair, which THERE is spilled and fetched back from scratch at the top of
-    // every step - one v_mad_u64_u32 per step instead.  Only there: every kernel with registers to spare keeps the hoisted
-    // product and runs 2-5 % faster for it - dims 24 / 48 / 50 in profiles/r04_scratch_ab.txt, table 6)
-#ifndef PTRWM_NO_C2_OPAQUE
-    if constexpr (step_loop_at_register_cap(DP, STREAM)) asm volatile("" : "+v"(rc.c2));
-#endif
-
-    long long srep = 0;
-    const float *ext_raw = nullptr;
-    float ext_u = 0.0f;
-    if constexpr (FULL) {
-      srep = ((long long)i * a.n_chains + chain) * T + t;
-      if (ext) {
-        ext_raw = a.full.ext_prop + srep * a.full.n_raw_ext;
-        ext_u = a.full.ext_u[srep];
-      }
-    }
-
-    constexpr int W = canon_width(DP);
-    float jump = 0.0f;  // the squared length of the increment, if the proposal knows it (proposals.h)
-    int jump_kind;      // (a constant in production kernels)
-    const float u_acc = Proposal::propose(y, x, fresh_dim<EXACT>(D0), tscale, a.pp, rc, ext_raw, ext_u, jump, jump_kind);
-    const float lp_new = Target::template logp<false>(y, fresh_dim<EXACT>(D0), a.tp);
-    const int D = fresh_dim<EXACT>(D0);
-
-    // ultra_fused_mcmc_step_basic / ultra_fused_parallel_mcmc_step:
-    //   r = beta (l' - l);  accept = (r > 0) | (u < exp r)
-    const bool acc = mh_accept(beta_t, lp_new, lp, u_acc);
-    const float lp_mh = acc ? lp_new : lp;
-    if constexpr (FULL) {
-      if (a.full.accept_flags != nullptr && live) a.full.accept_flags[srep] = acc ? 1 : 0;
-    }
-
+  constexpr int W = canon_width(DP);
+  // The move of a step without a swap event, x[d] = acc ? y[d] : x[d], and its squared jump.  It is committed IN PLACE, one
+  // select per dimension: the loop below is shaped so that no path on which the old state is still needed meets this one
+  // before the next step begins (see there).
+  auto commit_plain = [&](bool acc, float jump, int jump_kind, int D) __attribute__((always_inline)) -> float {
     float j2;
-    if (!swap_due && jump_kind != kJumpNone) {
+    if (jump_kind != kJumpNone) {
       // the proposal knows the length of its own increment: the move itself is one select per dimension.  Replicas whose
       // state is too large for that to equal |y - x|^2 (jump_trusted, decided at the start of the launch: none, normally -
       // the branch is skipped) take it from the states
@@ -724,8 +685,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
         if ((d & PTRWM_J2_FENCE_MASK) == PTRWM_J2_FENCE_MASK) sched_fence_soft();
       })
       j2 = acc ? (jump_trusted ? jump : from_states) : 0.0f;
-      lp = lp_mh;
-    } else if (!swap_due) {
+    } else {
       float j2p[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // squared jump in the canonical four-range order (philox.h)
 #ifdef PTRWM_J2_SEPARATE
 #pragma unroll
@@ -749,6 +709,126 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
 #endif
       j2 = tree4_add(j2p);
       if (!acc) j2 = 0.0f;
+    }
+    return j2;
+  };
+  // what every step ends with: the launch's statistics, and the trace / moments of the fixture twin
+  auto finish_step = [&](bool count_on, bool acc, float j2, int D) __attribute__((always_inline)) {
+    if (count_on) {
+      n_acc += acc ? 1u : 0u;
+#ifdef PTRWM_NO_SQ_LDS
+      sq_reg += (double)j2;
+#else
+      const int tid_q = thread_index_now(wave);  // (the slot's address is rebuilt here, not carried across the step)
+      const int gt_q = wide ? ((T + 63) & ~63) : 64;
+      double *const sq_slot = reinterpret_cast<double *>(
+                                  STREAM ? s_dyn + wave * kWaveFloats + kExtra0 + 6 * 64
+                                         : s_dyn + (wide ? 0 : wave * (64 * (DP + kLdsExtraPerThread))) + gt_q * (DP + 6)) +
+                              (wide ? tid_q : (tid_q & 63));
+      (void)__hip_atomic_fetch_add(sq_slot, (double)j2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+#endif
+    }
+    if constexpr (FULL) {
+      bool trace_now = false;
+      if (a.full.trace != nullptr) {  // wave-uniform thinning countdown
+        --to_trace;
+        trace_now = (to_trace == 0);
+        if (trace_now) to_trace = a.full.trace_every;
+      }
+      if (trace_now && trace_on) {
+        const long long row = ((a.full.trace_row0 + trace_rows) * a.full.trace_chains + chain) * a.full.trace_temps + t;
+        float *__restrict__ tr = a.full.trace + row * D;
+        PTRWM_DIM_LOOP(d, DP, D, { tr[d] = x[d]; })
+        if (a.full.trace_logp != nullptr) a.full.trace_logp[row] = lp;
+      }
+      trace_rows += trace_now ? 1 : 0;
+      if (a.full.mom_sum != nullptr) {  // wave-uniform countdown, as the trace's; the state after the whole step
+        --to_mom;
+        const bool mom_now = (to_mom == 0);
+        if (mom_now) to_mom = a.full.mom_every;
+        if (mom_now && count_on && live && t < a.full.mom_temps) {
+          const int mt = a.full.mom_temps;
+          double *const reg = thread_moments_region<DP>(s_dyn, wide, wide ? ((T + 63) & ~63) : 64, wave,
+                                                        (int)moments_region_doubles(mt, D));
+          double *const rs = reg + t * D;
+          double *const rq = reg + (mt + t) * D;
+          PTRWM_DIM_LOOP(d, DP, D, {
+            const double v = (double)x[d];
+            moments_add(rs + d, v);
+            moments_add(rq + d, v * v);
+          })
+          moments_add(reg + 2 * mt * D + t, (double)lp);
+        }
+      }
+    }
+  };
+
+  // The step loop is two loops.  The INNER one holds nothing but Metropolis steps: it runs up to the next step whose counter
+  // is a multiple of swap_every (or the end of the launch) and leaves, with that step's proposal decided but not committed,
+  // to the OUTER one, which commits it - with a swap event if one is due - and starts the next run.  As one loop, an
+  // ordinary step's commit met the swap path again before the latch (the compiler linearises the divergent parts of a
+  // loop body into `if (!swap) commit; if (swap) exchange;`): the new state and the old one the exchange still needs were
+  // both live there, so every select wrote a temporary and DP + 1 v_mov_b32 copied them back at the end of EVERY step -
+  // 62 of the 977 VALU instructions of a dim-30 step (profiles/r06_commit_in_place.txt).  Step for step the same work in the
+  // same order: count_on / burn_left, to_swap, the countdowns of the fixture twin and swap_in_call keep their meaning.
+  int i = 0;
+  while (i < a.n_steps) {
+    const int left = a.n_steps - i;
+    const bool to_multiple = to_swap <= left;      // this run ends on a multiple of swap_every (else: with the launch)
+    int run = to_multiple ? to_swap : left;        // its steps, the last one included (>= 1)
+    to_swap = to_multiple ? a.swap_every : to_swap - left;
+    bool count_on, acc;
+    float lp_mh;
+    float jump;     // the squared length of the increment, if the proposal knows it (proposals.h)
+    int jump_kind;  // (a constant in production kernels)
+    int D;
+    for (;; ++i, ++s) {
+      count_on = i >= a.burn_left;
+      rc.c0hi = (uint32_t)(s >> 32) << 16;
+      rc.c1 = (uint32_t)s;
+      rc.c3 = c3_base | (kStreamMH << 8);
+      // (at the register cap the chain word is made opaque per step: its product with the Philox multiplier is otherwise
+      // hoisted out of the step loop as a 64-bit pair, which THERE is spilled and fetched back from scratch at the top of
+      // every step - one v_mad_u64_u32 per step instead.  Only there: every kernel with registers to spare keeps the hoisted
+      // product and runs 2-5 % faster for it - dims 24 / 48 / 50 in profiles/r04_scratch_ab.txt, table 6)
+#ifndef PTRWM_NO_C2_OPAQUE
+      if constexpr (step_loop_at_register_cap(DP, STREAM)) asm volatile("" : "+v"(rc.c2));
+#endif
+
+      long long srep = 0;
+      const float *ext_raw = nullptr;
+      float ext_u = 0.0f;
+      if constexpr (FULL) {
+        srep = ((long long)i * a.n_chains + chain) * T + t;
+        if (ext) {
+          ext_raw = a.full.ext_prop + srep * a.full.n_raw_ext;
+          ext_u = a.full.ext_u[srep];
+        }
+      }
+
+      jump = 0.0f;
+      const float u_acc = Proposal::propose(y, x, fresh_dim<EXACT>(D0), tscale, a.pp, rc, ext_raw, ext_u, jump, jump_kind);
+      const float lp_new = Target::template logp<false>(y, fresh_dim<EXACT>(D0), a.tp);
+      D = fresh_dim<EXACT>(D0);
+
+      // ultra_fused_mcmc_step_basic / ultra_fused_parallel_mcmc_step:
+      //   r = beta (l' - l);  accept = (r > 0) | (u < exp r)
+      acc = mh_accept(beta_t, lp_new, lp, u_acc);
+      lp_mh = acc ? lp_new : lp;
+      if constexpr (FULL) {
+        if (a.full.accept_flags != nullptr && live) a.full.accept_flags[srep] = acc ? 1 : 0;
+      }
+
+      if (--run == 0) break;  // the last step of the run is committed below
+      const float j2 = commit_plain(acc, jump, jump_kind, D);
+      lp = lp_mh;
+      finish_step(count_on, acc, j2, D);
+    }
+    const bool swap_due = to_multiple && count_on && (T > 1);
+
+    float j2;
+    if (!swap_due) {
+      j2 = commit_plain(acc, jump, jump_kind, D);
       lp = lp_mh;
     } else {
       // ---- temperature swaps on the post-MH log-densities (pt_rwm_gpu_optimized.py:594-633) ----
@@ -821,54 +901,9 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       lp = my_l;
       ++swap_in_call;
     }
-
-    if (count_on) {
-      n_acc += acc ? 1u : 0u;
-#ifdef PTRWM_NO_SQ_LDS
-      sq_reg += (double)j2;
-#else
-      const int tid_q = thread_index_now(wave);  // (the slot's address is rebuilt here, not carried across the step)
-      const int gt_q = wide ? ((T + 63) & ~63) : 64;
-      double *const sq_slot = reinterpret_cast<double *>(
-                                  STREAM ? s_dyn + wave * kWaveFloats + kExtra0 + 6 * 64
-                                         : s_dyn + (wide ? 0 : wave * (64 * (DP + kLdsExtraPerThread))) + gt_q * (DP + 6)) +
-                              (wide ? tid_q : (tid_q & 63));
-      (void)__hip_atomic_fetch_add(sq_slot, (double)j2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#endif
-    }
-    if constexpr (FULL) {
-      bool trace_now = false;
-      if (a.full.trace != nullptr) {  // wave-uniform thinning countdown
-        --to_trace;
-        trace_now = (to_trace == 0);
-        if (trace_now) to_trace = a.full.trace_every;
-      }
-      if (trace_now && trace_on) {
-        const long long row = ((a.full.trace_row0 + trace_rows) * a.full.trace_chains + chain) * a.full.trace_temps + t;
-        float *__restrict__ tr = a.full.trace + row * D;
-        PTRWM_DIM_LOOP(d, DP, D, { tr[d] = x[d]; })
-        if (a.full.trace_logp != nullptr) a.full.trace_logp[row] = lp;
-      }
-      trace_rows += trace_now ? 1 : 0;
-      if (a.full.mom_sum != nullptr) {  // wave-uniform countdown, as the trace's; the state after the whole step
-        --to_mom;
-        const bool mom_now = (to_mom == 0);
-        if (mom_now) to_mom = a.full.mom_every;
-        if (mom_now && count_on && live && t < a.full.mom_temps) {
-          const int mt = a.full.mom_temps;
-          double *const reg = thread_moments_region<DP>(s_dyn, wide, wide ? ((T + 63) & ~63) : 64, wave,
-                                                        (int)moments_region_doubles(mt, D));
-          double *const rs = reg + t * D;
-          double *const rq = reg + (mt + t) * D;
-          PTRWM_DIM_LOOP(d, DP, D, {
-            const double v = (double)x[d];
-            moments_add(rs + d, v);
-            moments_add(rq + d, v * v);
-          })
-          moments_add(reg + 2 * mt * D + t, (double)lp);
-        }
-      }
-    }
+    finish_step(count_on, acc, j2, D);
+    ++i;
+    ++s;
   }
 
   // ---- state store: rows -> LDS slab -> coalesced HBM writes -----------------------------------------------

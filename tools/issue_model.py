@@ -106,20 +106,24 @@ def kernel_blocks(asm_path, flt):
     return name, blocks, order
 
 
-def features(b):
+def features(b, depth=1):
+    """`depth`: nesting depth of the step loop (1 until round 6; 2 since the Metropolis steps between two swap events run in
+    a loop of their own, kernel.h)."""
     ops = [o for o, _ in b["ins"]]
     return {
         # (LDS traffic marks the swap event - except the no-return ds_add_f64 that every counted step adds its squared jump with)
         "lds": sum(o.startswith("ds_") and not o.startswith("ds_add_f64") for o in ops), "barrier": sum(o == "s_barrier" for o in ops),
-        "sload": sum(o.startswith("s_load") for o in ops), "inner": int("Depth=2" in b["notes"] or "Depth 2" in b["notes"] and "Child" not in b["notes"]),
+        "sload": sum(o.startswith("s_load") for o in ops), "inner": int(f"Depth={depth + 1}" in b["notes"] or f"Depth {depth + 1}" in b["notes"] and "Child" not in b["notes"]),
         "global": sum(o.startswith(("global_", "flat_", "buffer_", "scratch_")) for o in ops),
         "cold": int("ptrwm-cold-path" in b["notes"]),  # PTRWM_COLD_PATH() of philox.h
     }
 
 
 def step_path(blocks, order):
-    loops = [b for b in order if "This Loop Header: Depth=1" in blocks[b]["notes"]]
+    # the step loop: the loop, at whatever depth, whose header holds the Philox multiplies
+    loops = [b for b in order if re.search(r"This (Inner )?Loop Header: Depth=\d", blocks[b]["notes"])]
     header = max(loops, key=lambda b: sum(o == "v_mad_u64_u32" for o, _ in blocks[b]["ins"]) * 1000 + len(blocks[b]["ins"]))
+    depth = int(re.search(r"Loop Header: Depth=(\d)", blocks[header]["notes"]).group(1))
     in_loop = {b for b in order if f"Header={header.replace('.L', '')}" in blocks[b]["notes"].replace(" ", "")} | {header}
     # Among the paths from the header back to itself that avoid the swap event: least penalty, then most VALU work.  The
     # loop body without its back edge and without inner loops is a DAG: one memoised pass (generic kernels have > 1000 blocks).
@@ -128,7 +132,7 @@ def step_path(blocks, order):
     memo, visiting = {}, set()
 
     def cost(t):
-        f = features(blocks[t])
+        f = features(blocks[t], depth)
         return 10 * f["lds"] + 1000 * f["barrier"] + 3 * f["sload"] + 1000 * f["inner"] + 5 * f["global"] + 100 * f["cold"]
 
     def best_from(b):
@@ -141,8 +145,9 @@ def step_path(blocks, order):
         out = (INF[0], 0, None)
         falls_cold = any(k == "fall" and features(blocks[t])["cold"] for k, t in blocks[b]["succ"])
         for kind, t in blocks[b]["succ"]:
-            if kind.startswith("s_cbranch_exec") and not falls_cold:
+            if kind.startswith("s_cbranch_execz") and not falls_cold:
                 continue  # a skip over a block for waves without live lanes: not taken (but taken over a cold block)
+            # (s_cbranch_execnz IS taken by a wave with live lanes: the nested step loop's back edge is one)
             if t == header:
                 cand = (0, 0, header)
             elif t in in_loop:
