@@ -895,12 +895,9 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   k.full.mom_every = mom != nullptr ? mom->every : 1;
   k.full.steps_to_mom = 0;
   if (mom != nullptr) {
-    // the whole workgroup's LDS: what the kernel holds anyway and the moments regions behind it (variants.h)
-    const int block = quad ? quad_block_threads(args->n_temps) : (wide ? ((args->n_temps + 63) & ~63) : kBlockThreads);
-    const unsigned base = quad ? quad_kernel_lds_bytes(block, canon_width(target->dim), f64)
-                               : step_kernel_lds_bytes(block, kWidths[dpi].dp) + (wide ? kWideVoteBytes : 0u);
-    k.dim = target->dim;
-    if (base + moments_lds_bytes(k, block, quad) > kMaxLdsBytes) return PTRWM_E_ARG;
+    // the workgroup's LDS with the moments regions behind it, as the launcher will ask for it (variants.h LaunchShape)
+    const LaunchShape sh = quad ? quad_launch_shape(k, canon_width(target->dim), f64) : thread_launch_shape(k, kWidths[dpi].dp);
+    if (sh.lds_moments > kMaxLdsBytes) return PTRWM_E_ARG;
   }
 
   // the streaming form for short launches of the one-thread-per-replica kernel (see kStreamMaxSteps above)

@@ -25,27 +25,77 @@ namespace ptrwm {
 #endif
 constexpr int kBlockThreads = PTRWM_BLOCK_THREADS;
 constexpr int kWavesPerBlock = kBlockThreads / 64;
-// dynamic LDS bytes of a step-kernel workgroup of `threads` threads with register width dp: one row of dp floats
-// per thread plus its log-density, swap-uniform and swap-outcome slots, three words that live for the whole
-// launch but are touched only in swap events and the epilogue (parked in LDS to keep them out of the VGPR budget
-// of the MH part: without that the compiler spilled five VGPRs to scratch, 42 MB of HBM traffic per launch) and the
-// launch's sum of squared jumps (a double: two words, added to by ds_add_f64 - profiles/r04_scratch_ab.txt)
-constexpr int kLdsExtraPerThread = 8;  // s_l, s_u, landed (swap-event scratch); c3, swap count, last event, the squared-jump sum (a double) (whole launch)
-// (the streaming form, STREAM below, keeps TWO slabs of rows per wave: the one its current group lives in and the one the
-// next group's state is landing in)
-// and two small landing zones for the next group's log-densities (one float per thread), squared-jump sums (one double) and
-// acceptance counts (one 64-bit integer)
-constexpr int kLdsStreamStatPerThread = 5;  // floats per thread and landing zone
-constexpr int kStreamSlabs = 2;
-constexpr int lds_floats_per_thread(int dp, bool stream) {
-  return (stream ? kStreamSlabs * (dp + kLdsStreamStatPerThread) : dp) + kLdsExtraPerThread;
+// The dynamic LDS of a ptrwm_step_kernel<.., DP, .., STREAM> workgroup, described ONCE: the kernel takes every pointer and
+// the host (variants.h, capi.hip) every size from here.  Offsets in floats; gt = threads of the exchange group: 64 (narrow:
+// a workgroup is kBlockThreads / 64 one-wave groups, kWaveFloats apart) or the workgroup (wide: one ladder, n_temps > 64).
+//   classic, per group:  [rows: gt x DP][s_l][s_u][landed][c3][swap count][last event][squared-jump sums: gt doubles]
+//                        behind ALL groups: [wide only: the ladder's vote word][FULL twin with moments: the regions]
+//   streaming, per wave: [slab 0: 64 x DP][slab 1][s_l .. squared-jump sums, gt = 64][zone 0][zone 1]
+//                        zone: [64 log-densities][64 squared-jump sums (double)][64 acceptance counts (64-bit)]
+// rows: up to DP floats per thread, packed (row stride = dim) for the coalesced state copy and a swap's row exchange; the
+// streaming form has TWO slabs - the current group's and the one the next group's state lands in by LDS-DMA - and landing
+// zones for that group's log-densities and statistics.  s_l / s_u / landed: log-density, swap uniform, outcome of a swap
+// sweep.  Parked for the whole launch, touched only in swap events and the epilogue (out of the VGPR budget of the MH part:
+// five VGPRs spilled to scratch otherwise, 42 MB of HBM traffic per launch): the Philox word with the temperature index,
+// the accepted swaps of pair (t, t+1), the last event it accepted in, the sum of squared jumps (a double, ds_add_f64 -
+// profiles/r04_scratch_ab.txt).  Vote word: a wide ladder's objection to the threshold form of a swap event.
+struct StepLdsWords {  // what does not depend on the register width
+  static constexpr int kSwapWords = 3;                                  // s_l, s_u, landed
+  static constexpr int kParkedInts = 3;                                 // c3, swap count, last event
+  static constexpr int kExtraPerThread = kSwapWords + kParkedInts + 2;  // ... and the squared-jump sum, a double
+  static constexpr int kStreamSlabs = 2;
+  static constexpr int kStreamStatPerThread = 5;  // floats per thread and landing zone: a float, a double, a 64-bit integer
+  static constexpr unsigned kVoteBytes = 16u;
+  static constexpr int floats_per_thread(int dp, bool stream) { return (stream ? kStreamSlabs * (dp + kStreamStatPerThread) : dp) + kExtraPerThread; }
+  // what a launch of `threads` threads asks for (the moments regions of a FULL twin come on top)
+  static constexpr unsigned bytes(int threads, int dp, bool stream, bool wide) { return (unsigned)(threads * floats_per_thread(dp, stream)) * 4u + (wide ? kVoteBytes : 0u); }
+};
+template <int DP, bool STREAM = false>
+struct StepLds : StepLdsWords {
+  static constexpr int kWaveFloats = 64 * floats_per_thread(DP, STREAM);  // the wave stride of a narrow workgroup
+  static constexpr int kSlabFloats = 64 * DP;                             // streaming form: slab `cur` at cur * kSlabFloats
+  static constexpr int kSlabVectorsPerLane = (kSlabFloats + 255) / 256;   // 16-byte vectors per lane that fill a slab
+  static constexpr int s_l(int gt) { return STREAM ? kStreamSlabs * kSlabFloats : gt * DP; }  // these four: from the group's base (classic) / the wave's (streaming)
+  static constexpr int parked(int gt) { return STREAM ? s_l(64) + kSwapWords * 64 : gt * (DP + kSwapWords); }
+  static constexpr int sq_jump(int gt) { return STREAM ? s_l(64) + (kSwapWords + kParkedInts) * 64 : gt * (DP + (kSwapWords + kParkedInts)); }
+  static constexpr int vote(int gt) { return gt * (DP + kExtraPerThread); }  // wide: behind the one group
+  static constexpr int kSu = 1, kLanded = 2, kParked = kSwapWords, kVote = kExtraPerThread;  // from s_l, in units of gt
+  static constexpr int kSwapCount = 1, kLastEvent = 2, kSqJump = kParkedInts;  // from the parked block, in units of gt (ints; doubles from there on)
+  static constexpr int kZoneFloats = 64 * kStreamStatPerThread;  // streaming landing zones, from the wave's base; the arrays of a zone, from its start
+  static constexpr int zone(int slab) { return s_l(64) + 64 * kExtraPerThread + slab * kZoneFloats; }
+  static constexpr int kZoneLogp = 0, kZoneSqJump = 64, kZoneAccept = 64 + 2 * 64;
+  // the moments regions (FULL twin), from s_dyn, behind all of the above: `stride` doubles per wave (narrow), one region for a wide ladder
+  static constexpr int moments(bool wide, int gt) { return wide ? gt * (DP + kExtraPerThread) + (int)(kVoteBytes / 4u) : kBlockThreads * (DP + kExtraPerThread); }
+  __device__ __forceinline__ static double *moments_region(float *s_dyn, bool wide, int gt, int wave, int stride) {
+    return reinterpret_cast<double *>(s_dyn + moments(wide, gt)) + (wide ? 0 : wave * stride);
+  }
+  static constexpr unsigned bytes(int threads, bool wide) { return StepLdsWords::bytes(threads, DP, STREAM, wide); }
+};
+namespace lds_check {
+using C = StepLds<30>;
+using S = StepLds<30, true>;
+static_assert(C::s_l(256) == 256 * 30 && C::parked(256) == C::s_l(256) + C::kParked * 256 &&
+                  C::sq_jump(256) == C::parked(256) + C::kSqJump * 256 && C::vote(256) == C::sq_jump(256) + 2 * 256 &&
+                  C::vote(256) == C::s_l(256) + C::kVote * 256 && C::moments(true, 256) * 4 == (int)C::bytes(256, true) &&
+                  C::moments(false, 64) * 4 == (int)C::bytes(kBlockThreads, false) && C::kWaveFloats == C::vote(64) && 0 < C::kSu &&
+                  C::kSu < C::kLanded && C::kLanded < C::kParked && 0 < C::kSwapCount && C::kSwapCount < C::kLastEvent && C::kLastEvent < C::kSqJump,
+              "classic layout: rows, swap scratch, parked ints, squared-jump doubles, vote word, moments regions: disjoint, in this order");
+static_assert(S::s_l(64) == 2 * S::kSlabFloats && S::parked(64) == S::s_l(64) + 3 * 64 && S::sq_jump(64) == S::parked(64) + 3 * 64 &&
+                  S::zone(0) == S::sq_jump(64) + 2 * 64 && S::zone(1) == S::zone(0) + S::kZoneFloats &&
+                  S::zone(1) + S::kZoneFloats == S::kWaveFloats && S::kZoneSqJump == S::kZoneLogp + 64 &&
+                  S::kZoneAccept == S::kZoneSqJump + 2 * 64 && S::kZoneAccept + 2 * 64 == S::kZoneFloats,
+              "streaming layout: two slabs, swap scratch, parked words, two landing zones of three arrays");
+template <int DP>  // doubles / 64-bit integers start 8-byte aligned; wave strides, slabs and landing zones (16-byte copies, DMA) 16-byte
+constexpr bool aligned(bool ok = true) {
+  using A = StepLds<DP>;
+  using B = StepLds<DP, true>;
+  for (int gt = 64; gt <= 256; gt += 64) ok = ok && A::sq_jump(gt) % 2 == 0 && A::moments(true, gt) % 2 == 0 && A::moments(false, gt) % 2 == 0;
+  for (int z = 0; z < 2; ++z) ok = ok && B::zone(z) % 4 == 0 && (B::zone(z) + B::kZoneSqJump) % 4 == 0 && (B::zone(z) + B::kZoneAccept) % 4 == 0;
+  return ok && A::kWaveFloats % 4 == 0 && B::kWaveFloats % 4 == 0 && B::kSlabFloats % 4 == 0 && B::sq_jump(64) % 2 == 0;
 }
-constexpr unsigned step_kernel_lds_bytes(int threads, int dp, bool stream = false) {
-  return (unsigned)(threads * lds_floats_per_thread(dp, stream)) * 4u;
-}
-// a wide group (one ladder = the workgroup, n_temps > 64) has one more word behind all of that: the ladder's objection to
-// the threshold form of a swap event (ptrwm_step_kernel, the swap section)
-constexpr unsigned kWideVoteBytes = 16u;
+static_assert(aligned<2>() && aligned<3>() && aligned<5>() && aligned<9>() && aligned<29>() && aligned<30>() && aligned<50>() && aligned<64>(), "alignment");
+static_assert(C::bytes(256, false) == 38912u && S::bytes(256, false) == 79872u && C::bytes(256, true) == 38928u, "LDS bytes, as before the layout had a name");
+}  // namespace lds_check
 
 // Arguments only the fixture / trace variant of the kernel (FULL = true) reads.  Keeping them out
 // of the production variant keeps its wave-uniform state inside the 100-odd SGPRs of a wave.
@@ -353,15 +403,6 @@ __device__ __forceinline__ void moments_flush(const double *reg, kargs_full_ptr 
     for (int i = tid; i < temps; i += nthr) count_add(&count[i], add);
 }
 
-// the thread form's moments region: behind the rows and parked words of every group of the workgroup (and a wide
-// group's vote word); one per wave in narrow workgroups, one per workgroup for a wide ladder
-template <int DP>
-__device__ __forceinline__ double *thread_moments_region(float *s_dyn, bool wide, int gthreads, int wave, int stride) {
-  float *const base = s_dyn + (wide ? gthreads * (DP + kLdsExtraPerThread) + (int)(kWideVoteBytes / 4u)
-                                    : kBlockThreads * (DP + kLdsExtraPerThread));
-  return reinterpret_cast<double *>(base) + (wide ? 0 : wave * stride);
-}
-
 template <bool EXACT>
 __device__ __forceinline__ int fresh_dim(int d0) {
   if constexpr (!EXACT) PTRWM_VALUE_BARRIER("+s"(d0));
@@ -453,13 +494,10 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
   // wave, not only across waves.  The next group's log-densities and squared-jump sums travel the same way into two
   // small landing zones: an ordinary load to a VGPR anywhere in this loop would make the compiler drain every
   // outstanding DMA and store (vmcnt(0)) at its first use.
-  // LDS of a wave, in floats: [slab 0: 64 DP][slab 1: 64 DP][swap scratch + parked words: 6 x 64][zone 0: 5 x 64][zone 1]
-  // (a zone: 64 log-densities, 64 squared-jump sums, 64 acceptance counts)
   typedef float pf_vec4 __attribute__((ext_vector_type(4)));
-  constexpr int NV = STREAM ? (DP + 3) / 4 : 1;  // 16-byte vectors per lane and group
-  constexpr int kWaveFloats = 64 * lds_floats_per_thread(DP, STREAM);
-  constexpr int kExtra0 = 64 * kStreamSlabs * DP;  // streaming form: swap scratch and parked words behind the slab(s)
-  constexpr int kZone0 = kExtra0 + 64 * kLdsExtraPerThread, kZoneFloats = 64 * kLdsStreamStatPerThread;
+  typedef StepLds<DP, STREAM> L;  // where everything in the dynamic LDS lives
+  constexpr int NV = STREAM ? L::kSlabVectorsPerLane : 1;  // 16-byte vectors per lane and group
+  constexpr int kWaveFloats = L::kWaveFloats;
   [[maybe_unused]] int cur = 0;  // which slab / landing zone holds the current group (streaming form; wave-uniform)
   typedef const __attribute__((address_space(1))) void *dma_src;
   typedef __attribute__((address_space(3))) void *dma_dst;
@@ -471,18 +509,18 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     float *const wbase = s_dyn + wave * kWaveFloats;
     // log-densities: one dword per lane (idle lanes re-read replica 0 of the group)
     const long long r0 = g * n_live;
-    float *const zone = wbase + kZone0 + slab * kZoneFloats;
-    __builtin_amdgcn_global_load_lds((dma_src)(ap->logp + r0 + (tid < n_live ? tid : 0)), (dma_dst)(uintptr_t)zone, 4, 0, 0);
+    float *const zone = wbase + L::zone(slab);
+    __builtin_amdgcn_global_load_lds((dma_src)(ap->logp + r0 + (tid < n_live ? tid : 0)), (dma_dst)(uintptr_t)(zone + L::kZoneLogp), 4, 0, 0);
     // squared-jump sums: 16 bytes = two doubles per lane (n_live is even, capi.hip)
     if (ap->sq_jump != nullptr && 2 * tid < n_live)
-      __builtin_amdgcn_global_load_lds((dma_src)(ap->sq_jump + r0 + 2 * tid), (dma_dst)(uintptr_t)(zone + 64), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((dma_src)(ap->sq_jump + r0 + 2 * tid), (dma_dst)(uintptr_t)(zone + L::kZoneSqJump), 16, 0, 0);
     // acceptance counts likewise: read ahead and stored back as old + delta.  (The classic kernel adds them by no-return
     // atomics to keep a load off the end of a wave's life; here the old value is in LDS before the step begins, and plain
     // 8-byte stores stream at several times the rate the memory-side atomics do.)
     if (ap->n_accept != nullptr && 2 * tid < n_live)
-      __builtin_amdgcn_global_load_lds((dma_src)(ap->n_accept + r0 + 2 * tid), (dma_dst)(uintptr_t)(zone + 192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((dma_src)(ap->n_accept + r0 + 2 * tid), (dma_dst)(uintptr_t)(zone + L::kZoneAccept), 16, 0, 0);
     const pf_vec4 *__restrict__ gv = reinterpret_cast<const pf_vec4 *>(ap->state + g * cpw * T * (long long)D0);
-    float *const dst = wbase + slab * (64 * DP);
+    float *const dst = wbase + slab * L::kSlabFloats;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const int v = tid + 64 * k;
@@ -547,14 +585,9 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
   const long long chain = chain0 + cw;
   const long long rep = chain0 * T + (live ? tid : 0);  // cw * T + t == tid for a live thread
 
-  // ---- LDS (dynamic: group threads * (DP + kLdsExtraPerThread) floats per group, sized by the launch: step_kernel_lds_bytes) --
-  // s_stage: one row of up to DP floats per thread; the group packs its live replicas' rows back to back (row
-  // stride = dim) for the coalesced state load / store and exchanges rows through it in a swap.
-  // s_l / s_u / landed (behind the rows): per-thread log-density, swap uniform and swap outcome of a swap sweep.
-  // (streaming form: the slab of the current group; the swap scratch and the parked words sit behind BOTH slabs)
-  float *const s_stage = STREAM ? s_dyn + wave * kWaveFloats + cur * (64 * DP)
-                                : s_dyn + (wide ? 0 : (int)(threadIdx.x >> 6) * (64 * (DP + kLdsExtraPerThread)));
-  [[maybe_unused]] float *const s_extra = s_dyn + wave * kWaveFloats + kExtra0;  // streaming form only
+  // ---- LDS (dynamic, sized by the launch: StepLds).  s_stage: the group's rows (streaming form: the current group's slab)
+  float *const s_stage = STREAM ? s_dyn + wave * kWaveFloats + cur * L::kSlabFloats
+                                : s_dyn + (wide ? 0 : (int)(threadIdx.x >> 6) * kWaveFloats);
   // group-wide ordering of LDS accesses: the group is one wave (narrow) or the workgroup (wide)
   auto sync_group = [&]() {
     if (wide) {
@@ -580,11 +613,11 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     if constexpr (!STREAM) {
       stage_copy<true>(s_stage, gs, stage_total, tid, nthr);
       row_head = stage_head(gs);
-      if (wide) reinterpret_cast<int *>(s_dyn)[nthr * (DP + kLdsExtraPerThread)] = 0;  // no objection yet (kWideVoteBytes)
+      if (wide) reinterpret_cast<int *>(s_dyn)[L::vote(nthr)] = 0;  // no objection yet
       if constexpr (FULL) {
         if (a.full.mom_sum != nullptr) {  // (ordered before the first add by the barrier below)
           const int n_mom = (int)moments_region_doubles(a.full.mom_temps, D0);
-          moments_zero(thread_moments_region<DP>(s_dyn, wide, nthr, wave, n_mom), n_mom, tid, nthr);
+          moments_zero(L::moments_region(s_dyn, wide, nthr, wave, n_mom), n_mom, tid, nthr);
         }
       }
     }
@@ -601,10 +634,10 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
   [[maybe_unused]] long long acc_old = 0;
   if constexpr (STREAM) {
     {
-      const float *zone = s_dyn + wave * kWaveFloats + kZone0 + cur * kZoneFloats;
-      lp = zone[tid];
-      if (a.sq_jump != nullptr) sq_old = reinterpret_cast<const double *>(zone + 64)[tid < cpw * T ? tid : 0];
-      if (a.n_accept != nullptr) acc_old = reinterpret_cast<const long long *>(zone + 192)[tid < cpw * T ? tid : 0];
+      const float *zone = s_dyn + wave * kWaveFloats + L::zone(cur);
+      lp = (zone + L::kZoneLogp)[tid];
+      if (a.sq_jump != nullptr) sq_old = reinterpret_cast<const double *>(zone + L::kZoneSqJump)[tid < cpw * T ? tid : 0];
+      if (a.n_accept != nullptr) acc_old = reinterpret_cast<const long long *>(zone + L::kZoneAccept)[tid < cpw * T ? tid : 0];
     }
     // the previous group's results leave now, and behind them the next group's DMA is issued: the other slab is free,
     // the previous group's outgoing rows were read back into pend_o before this group began
@@ -633,21 +666,17 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
 
   unsigned n_acc = 0;
   {
-    // parked in LDS (see step_kernel_lds_bytes): the Philox word with the temperature index, the number of accepted
+    // parked in LDS (StepLds): the Philox word with the temperature index, the number of accepted
     // swaps of pair (t, t+1) and the index within this launch of the last swap event in which it accepted
     const int gt = wide ? ((T + 63) & ~63) : 64;
-    int *const park = reinterpret_cast<int *>(STREAM ? s_extra + 3 * gt : s_stage + gt * (DP + 3)) + tid;
+    int *const park = reinterpret_cast<int *>(STREAM ? s_dyn + wave * kWaveFloats + L::parked(gt) : s_stage + L::parked(gt)) + tid;
     park[0] = (int)c3_base;
-    park[gt] = 0;
-    park[2 * gt] = -1;
-    // ... and this launch's sum of squared jumps, a double behind them: added to by a no-return ds_add_f64 per counted
-    // step - the same IEEE additions in the same order as a register would see, without the two VGPRs of a double that
-    // lives across the whole step loop (the headline kernel sits at the 128-VGPR cap of four waves per SIMD)
-    reinterpret_cast<double *>(park - tid + 3 * gt)[tid] = 0.0;
+    park[L::kSwapCount * gt] = 0;
+    park[L::kLastEvent * gt] = -1;
+    // ... and this launch's sum of squared jumps behind them: a no-return ds_add_f64 per counted step - the same IEEE
+    // additions in the same order as a register would see, without two VGPRs across the step loop (at the 128-VGPR cap)
+    reinterpret_cast<double *>(park - tid + L::kSqJump * gt)[tid] = 0.0;
   }
-#ifdef PTRWM_NO_SQ_LDS
-  double sq_reg = 0.0;
-#endif
 
   const bool ext = FULL && a.full.ext_prop != nullptr;
   const bool trace_on =
@@ -687,26 +716,12 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       j2 = acc ? (jump_trusted ? jump : from_states) : 0.0f;
     } else {
       float j2p[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // squared jump in the canonical four-range order (philox.h)
-#ifdef PTRWM_J2_SEPARATE
-#pragma unroll
-      for (int d = 0; d < DP; ++d) {
-        if (d < D) {
-          const float dl = sub_rn(y[d], x[d]);
-          j2p[d / W] = fmaf(dl, dl, j2p[d / W]);
-        }
-        if ((d & PTRWM_J2_FENCE_MASK) == PTRWM_J2_FENCE_MASK) sched_fence_soft();
-      }
-#pragma unroll
-      for (int d = 0; d < DP; ++d)
-        if (d < D) x[d] = acc ? y[d] : x[d];
-#else
       PTRWM_DIM_LOOP(d, DP, D, {
         const float dl = sub_rn(y[d], x[d]);
         j2p[d / W] = fmaf(dl, dl, j2p[d / W]);
         x[d] = acc ? y[d] : x[d];
         if ((d & PTRWM_J2_FENCE_MASK) == PTRWM_J2_FENCE_MASK) sched_fence_soft();
       })
-#endif
       j2 = tree4_add(j2p);
       if (!acc) j2 = 0.0f;
     }
@@ -716,17 +731,13 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
   auto finish_step = [&](bool count_on, bool acc, float j2, int D) __attribute__((always_inline)) {
     if (count_on) {
       n_acc += acc ? 1u : 0u;
-#ifdef PTRWM_NO_SQ_LDS
-      sq_reg += (double)j2;
-#else
       const int tid_q = thread_index_now(wave);  // (the slot's address is rebuilt here, not carried across the step)
       const int gt_q = wide ? ((T + 63) & ~63) : 64;
       double *const sq_slot = reinterpret_cast<double *>(
-                                  STREAM ? s_dyn + wave * kWaveFloats + kExtra0 + 6 * 64
-                                         : s_dyn + (wide ? 0 : wave * (64 * (DP + kLdsExtraPerThread))) + gt_q * (DP + 6)) +
+                                  STREAM ? s_dyn + wave * kWaveFloats + L::sq_jump(64)
+                                         : s_dyn + (wide ? 0 : wave * kWaveFloats) + L::sq_jump(gt_q)) +
                               (wide ? tid_q : (tid_q & 63));
       (void)__hip_atomic_fetch_add(sq_slot, (double)j2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-#endif
     }
     if constexpr (FULL) {
       bool trace_now = false;
@@ -748,8 +759,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
         if (mom_now) to_mom = a.full.mom_every;
         if (mom_now && count_on && live && t < a.full.mom_temps) {
           const int mt = a.full.mom_temps;
-          double *const reg = thread_moments_region<DP>(s_dyn, wide, wide ? ((T + 63) & ~63) : 64, wave,
-                                                        (int)moments_region_doubles(mt, D));
+          double *const reg = L::moments_region(s_dyn, wide, wide ? ((T + 63) & ~63) : 64, wave, (int)moments_region_doubles(mt, D));
           double *const rs = reg + t * D;
           double *const rq = reg + (mt + t) * D;
           PTRWM_DIM_LOOP(d, DP, D, {
@@ -791,9 +801,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       // hoisted out of the step loop as a 64-bit pair, which THERE is spilled and fetched back from scratch at the top of
       // every step - one v_mad_u64_u32 per step instead.  Only there: every kernel with registers to spare keeps the hoisted
       // product and runs 2-5 % faster for it - dims 24 / 48 / 50 in profiles/r04_scratch_ab.txt, table 6)
-#ifndef PTRWM_NO_C2_OPAQUE
       if constexpr (step_loop_at_register_cap(DP, STREAM)) asm volatile("" : "+v"(rc.c2));
-#endif
 
       long long srep = 0;
       const float *ext_raw = nullptr;
@@ -837,11 +845,11 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       const int tid_s = thread_index_now(wave);
       const int slot = wide ? tid_s : (tid_s & 63);  // this thread's slot in s_l / s_u and its row in s_stage
       const int group_threads = wide ? ((T + 63) & ~63) : 64;
-      float *const rows = STREAM ? s_dyn + wave * kWaveFloats + cur * (64 * DP)
-                                 : s_dyn + (wide ? 0 : (tid_s >> 6) * (64 * (DP + kLdsExtraPerThread)));
-      float *const s_l = STREAM ? s_dyn + wave * kWaveFloats + kExtra0 : rows + group_threads * DP;
-      float *const s_u = s_l + group_threads;
-      int *const park = reinterpret_cast<int *>(s_l + 3 * group_threads) + slot;
+      float *const rows = STREAM ? s_dyn + wave * kWaveFloats + cur * L::kSlabFloats
+                                 : s_dyn + (wide ? 0 : (tid_s >> 6) * kWaveFloats);
+      float *const s_l = STREAM ? s_dyn + wave * kWaveFloats + L::s_l(64) : rows + L::s_l(group_threads);
+      float *const s_u = s_l + L::kSu * group_threads;
+      int *const park = reinterpret_cast<int *>(s_l + L::kParked * group_threads) + slot;
       const uint32_t c3_s = (uint32_t)park[0];
       const int t = (int)(c3_s & 0xffu);  // the temperature index, as the Philox counter holds it
       const int base = live ? slot - t : 0;            // slot of temperature 0 of this thread's ladder
@@ -866,7 +874,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       // for the last time before this event's row-exchange barrier, after which the next event may stamp it again)
       bool swap_plain;
       if (wide) {
-        int *const objection = reinterpret_cast<int *>(s_l + kLdsExtraPerThread * group_threads);
+        int *const objection = reinterpret_cast<int *>(s_l + L::kVote * group_threads);
         if (!pair_plain) *objection = swap_in_call + 1;
         sync_group();
         swap_plain = *objection != swap_in_call + 1;
@@ -875,10 +883,10 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
         sync_group();
       }
       swap_decide(T, t, base, slot, a.swap_mode, a.swap_order, (ev_par0 + swap_in_call) & 1, a.beta, beta_t, us, s_l, s_u,
-                  reinterpret_cast<int *>(s_u + group_threads), my_l, src, pair_acc, sync_group, swap_plain);
+                  reinterpret_cast<int *>(s_u + (L::kLanded - L::kSu) * group_threads), my_l, src, pair_acc, sync_group, swap_plain);
       if (pair_acc) {
-        park[group_threads] += 1;
-        park[2 * group_threads] = swap_in_call;
+        park[L::kSwapCount * group_threads] += 1;
+        park[L::kLastEvent * group_threads] = swap_in_call;
       }
       // commit MH move and swap in one pass: every thread publishes its post-MH vector as its slab row, then
       // fetches the row of slot `src` (rows exchanged through LDS: 2 LDS ops per dimension, no HBM)
@@ -915,8 +923,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     const bool wide2 = T2 > 64;
     const int tx2 = thread_index_now(wave);
     const int tid2 = wide2 ? tx2 : (tx2 & 63);
-    float *const rows2 = STREAM ? s_dyn + wave * kWaveFloats + cur * (64 * DP)
-                                : s_dyn + (wide2 ? 0 : wave * (64 * (DP + kLdsExtraPerThread)));
+    float *const rows2 = STREAM ? s_dyn + wave * kWaveFloats + cur * L::kSlabFloats : s_dyn + (wide2 ? 0 : wave * kWaveFloats);
     long long c0;
     if constexpr (STREAM) {
       c0 = group * cpw2;
@@ -943,8 +950,8 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       // every add of the launch is behind the barrier above: the group's partial sums go to HBM, once
       const kargs_full_ptr fa = &ae->full;
       if (fa->mom_sum != nullptr)
-        moments_flush(thread_moments_region<DP>(s_dyn, wide2, nthr, wave, (int)moments_region_doubles(fa->mom_temps, D2)),
-                      fa, D2, live_chains, tid2, nthr);
+        moments_flush(L::moments_region(s_dyn, wide2, nthr, wave, (int)moments_region_doubles(fa->mom_temps, D2)), fa, D2,
+                      live_chains, tid2, nthr);
     }
     if constexpr (STREAM) {
       // whole aligned vectors only (capi.hip): slab -> registers now, registers -> HBM in flush_pending
@@ -964,18 +971,14 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     const int T_o = fresh_dim<false>(T);
     const long long rep = c0_out * T_o + (T_o > 64 ? tid_o : (tid_o & 63));  // live: replica index in group == tid
     const int gt_o = T_o > 64 ? ((T_o + 63) & ~63) : 64;
-    const int *const park = reinterpret_cast<const int *>(STREAM ? s_dyn + wave * kWaveFloats + kExtra0 + 3 * 64
-                                                                 : s_dyn + (T_o > 64 ? 0 : (tid_o >> 6) * (64 * (DP + kLdsExtraPerThread)))
-                                                                       + gt_o * (DP + 3)) + (T_o > 64 ? tid_o : (tid_o & 63));
+    const int *const park = reinterpret_cast<const int *>(STREAM ? s_dyn + wave * kWaveFloats + L::parked(64)
+                                                                 : s_dyn + (T_o > 64 ? 0 : (tid_o >> 6) * kWaveFloats) + L::parked(gt_o)) +
+                            (T_o > 64 ? tid_o : (tid_o & 63));
     const int t = park[0] & 0xff;
-    const unsigned n_swap_acc = (unsigned)park[gt_o];
-    const int last_event = park[2 * gt_o];
+    const unsigned n_swap_acc = (unsigned)park[L::kSwapCount * gt_o];
+    const int last_event = park[L::kLastEvent * gt_o];
     const int tid_g = T_o > 64 ? tid_o : (tid_o & 63);
-#ifdef PTRWM_NO_SQ_LDS
-    const double sq = sq_reg;
-#else
-    const double sq = reinterpret_cast<const double *>(park - tid_g + 3 * gt_o)[tid_g];
-#endif
+    const double sq = reinterpret_cast<const double *>(park - tid_g + L::kSqJump * gt_o)[tid_g];
     if constexpr (STREAM) {
       // handed to flush_pending (the old squared-jump sum came in with the prefetch: the same double addition as the classic
       // kernel's read-modify-write, without a load)

@@ -25,14 +25,8 @@ namespace ptrwm {
 
 constexpr int kQuad = 4;
 
-// A lane runs two (dim 30) to seven Philox blocks per step: few enough to let the scheduler interleave them (at four
-// waves per SIMD the dependent rounds of ONE block do not hide their own latency); PTRWM_QUAD_FENCE_RNG restores the
-// per-block fences of the one-thread-per-replica kernel (needed there to bound the registers of eight-plus blocks).
-__device__ __forceinline__ void quad_rng_fence() {
-#ifdef PTRWM_QUAD_FENCE_RNG
-  __builtin_amdgcn_sched_barrier(0);
-#endif
-}
+// A lane runs two (dim 30) to seven Philox blocks per step: few enough to let the scheduler interleave them - no per-block
+// fences as in the one-thread-per-replica kernel (needed there to bound the registers of eight-plus blocks).
 
 // ---- DPP quad permutes (lane i of a quad reads lane SEL_i; full rate, no LDS) --------------------------------------
 constexpr int quad_ctrl(int s0, int s1, int s2, int s3) { return s0 | (s1 << 2) | (s2 << 4) | (s3 << 6); }
@@ -143,7 +137,6 @@ struct QNormal {
           }
           if ((int)(4 * cb) + 2 * h == w_a) u_loc = u01(ra);
         }
-        quad_rng_fence();
       }
     }
     if (c_a >= W) {  // dim = 4 W or 4 W - 1: the accept word opens block W, which no lane owns: all compute it
@@ -187,7 +180,6 @@ struct QLaplace {
           // when dim is compiled in), only the block is lane-dependent - one compare per block, not one per word
           if (k == (D & 3)) u_loc = ((int)cb == c_a) ? u01(pick(r, k)) : u_loc;
         }
-        quad_rng_fence();
       }
     }
     if (c_a >= W) {
@@ -238,7 +230,6 @@ struct QUniformRadius {
               ua_loc = u01(rb);
             }
           }
-          quad_rng_fence();
         }
       }
       if (c_a >= W) {
@@ -591,21 +582,44 @@ struct QNealFunnel {
 };
 
 // ---- the kernel ------------------------------------------------------------------------------------------------------
-// dynamic LDS bytes of a workgroup: per replica slot a row of up to 4 W state elements (float, or double in the F64 form)
-// plus the words of the swap machinery (per slot: log-density, swap uniform, outcome, the ladder's swap-form objection)
-// -> (W * words-per-element + 2) floats per thread
-constexpr unsigned quad_kernel_lds_bytes(int threads, int w, bool f64 = false) {
-  return (unsigned)(threads * (w * (f64 ? 2 : 1) + 2)) * 4u;
-}
+// The dynamic LDS of a ptrwm_quad_step_kernel<.., W, .., F64> workgroup, described once for kernel and host (as kernel.h
+// StepLds).  Offsets in floats; gthreads = threads of the exchange group (64: one-wave groups kWaveFloats apart; or the
+// workgroup), nslots = gthreads / 4.  Per group: [rows: nslots x 4 W state elements (float; F64: double)][s_l][s_u][outcome]
+// [objection], nslots words each (log-density, swap uniform, outcome of a swap sweep; the swap-form objection of the ladder
+// whose first slot it is: one word per thread; a second one is allocated, unused); behind ALL groups the FULL twin's moments regions.
+struct QuadLdsWords {  // what does not depend on the lane width
+  static constexpr int kExtraPerThread = 2;
+  static constexpr int floats_per_thread(int w, bool f64) { return w * (f64 ? 2 : 1) + kExtraPerThread; }
+  static constexpr unsigned bytes(int threads, int w, bool f64) { return (unsigned)(threads * floats_per_thread(w, f64)) * 4u; }
+};
+template <int W, bool F64 = false>
+struct QuadLds : QuadLdsWords {
+  static constexpr int SW = F64 ? 2 : 1;  // 32-bit words per state element
+  static constexpr int kFloatsPerThread = floats_per_thread(W, F64);
+  static constexpr int kWaveFloats = 64 * kFloatsPerThread;  // the wave stride of a narrow workgroup
+  static constexpr int s_l(int nslots) { return nslots * (4 * W * SW); }
+  static constexpr int kSu = 1, kLanded = 2, kObjection = 3;  // from s_l, in units of nslots
+  static constexpr int moments(int threads) { return threads * kFloatsPerThread; }  // from s_dyn
+  __device__ __forceinline__ static double *moments_region(float *s_dyn, bool wide, int wave, int stride) {
+    return reinterpret_cast<double *>(s_dyn + moments((int)blockDim.x)) + (wide ? 0 : wave * stride);
+  }
+  static constexpr unsigned bytes(int threads) { return QuadLdsWords::bytes(threads, W, F64); }
+};
+static_assert(QuadLds<8>::s_l(16) == 16 * 32 && QuadLds<8>::s_l(16) + (QuadLds<8>::kObjection + 1) * 16 <= QuadLds<8>::kWaveFloats && QuadLds<8, true>::s_l(16) == 16 * 64 &&
+                  QuadLds<8, true>::s_l(16) + (QuadLds<8, true>::kObjection + 1) * 16 <= QuadLds<8, true>::kWaveFloats && 0 < QuadLds<8>::kSu && QuadLds<8>::kSu < QuadLds<8>::kLanded && QuadLds<8>::kLanded < QuadLds<8>::kObjection &&
+                  QuadLds<8>::moments(256) * 4 == (int)QuadLds<8>::bytes(256) && QuadLds<8, true>::moments(512) * 4 == (int)QuadLds<8, true>::bytes(512),
+              "rows, s_l, s_u, outcome slots, objection words inside the group, in this order; moments regions behind all groups");
+static_assert(QuadLds<8>::kWaveFloats % 4 == 0 && QuadLds<8, true>::kWaveFloats % 4 == 0 && QuadLds<28>::kWaveFloats % 4 == 0 && QuadLds<8>::moments(64) % 2 == 0 &&
+                  QuadLds<20>::moments(64) % 2 == 0, "wave strides 16-byte aligned (16-byte row copies), moments regions (doubles) 8-byte aligned");
+static_assert(QuadLds<8>::bytes(256) == 10240u && QuadLds<8, true>::bytes(256) == 18432u, "LDS bytes, as before the layout had a name");
 // Widest workgroup = one ladder.  Every variant is compiled for workgroups of up to 512 threads (ladders of <= 128
 // temperatures: up to 256 VGPRs).  (Until round 4 the W >= 20 classes also existed for 1024 threads: 128 VGPRs, 40 of
 // them spilled inside the step loop - retired, variants.h.)
 constexpr int kQuadThreads = 512;
-// the lane-split form's moments region (kernel.h moments_region_doubles): behind the slabs of every group of the
-// workgroup; one per wave in narrow workgroups, one per workgroup for wide ladders
-template <int W, bool F64>
-__device__ __forceinline__ double *quad_moments_region(float *s_dyn, bool wide, int wave, int stride) {
-  return reinterpret_cast<double *>(s_dyn + (int)blockDim.x * (W * (F64 ? 2 : 1) + 2)) + (wide ? 0 : wave * stride);
+// MIN_OWN of the functors above: the number of dimensions the LAST lane owns when dim is compiled in (every lane owns at
+// least that); -1 marks the kernels that take dim at run time
+constexpr int quad_min_own(int w, int dexact) {
+  return dexact == 0 ? -1 : (dexact - 3 * w <= 0 ? 0 : (dexact - 3 * w > w ? w : dexact - 3 * w));
 }
 
 // double-precision pieces of the F64 form: IEEE ops the compiler must not contract (the state update x + scale * z is then
@@ -656,7 +670,8 @@ constexpr int quad_min_waves(int w, bool f64, bool full) { return (w >= 28 && !f
 template <class Target, class Proposal, int W, int DEXACT, int MAXT, bool FULL, bool F64 = false>
 __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad_step_kernel(const KArgs a) {
   typedef typename quad_state<F64>::type state_t;
-  constexpr int SW = F64 ? 2 : 1;  // 32-bit words per state element
+  typedef QuadLds<W, F64> L;  // where everything in the dynamic LDS lives
+  constexpr int SW = L::SW;   // 32-bit words per state element
   const int T = a.n_temps;
   const int D = DEXACT ? DEXACT : a.dim;
   const int cpw = a.chains_per_wave;  // ladders per exchange group (narrow: 16 / T per wave; wide: per workgroup)
@@ -686,11 +701,12 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
   const long long rep = chain0 * T + slot;
 
   extern __shared__ __attribute__((aligned(16))) float s_dyn[];
-  float *const rows_f = s_dyn + (wide ? 0 : (int)(threadIdx.x >> 6) * (64 * (W * SW + 2)));
+  float *const rows_f = s_dyn + (wide ? 0 : (int)(threadIdx.x >> 6) * L::kWaveFloats);
   state_t *const rows = reinterpret_cast<state_t *>(rows_f);
-  float *const s_l = rows_f + nslots * (4 * W * SW);
-  float *const s_u = s_l + nslots;
-  int *const s_landed = reinterpret_cast<int *>(s_u + nslots);
+  float *const s_l = rows_f + L::s_l(nslots);
+  float *const s_u = s_l + L::kSu * nslots;
+  int *const s_landed = reinterpret_cast<int *>(s_u + (L::kLanded - L::kSu) * nslots);
+  constexpr int kToObjection = L::kObjection - L::kLanded;  // s_landed[kToObjection * nslots + a ladder's first slot]: its word
   auto sync_group = [&]() {
     if (wide) {
       __syncthreads();
@@ -699,7 +715,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
       __builtin_amdgcn_wave_barrier();
     }
   };
-  constexpr int MIN_OWN = DEXACT ? (DEXACT - 3 * W > 0 ? (DEXACT - 3 * W > W ? W : DEXACT - 3 * W) : 0) : -1;
+  constexpr int MIN_OWN = quad_min_own(W, DEXACT);
 
   // ---- state load: the group's live replicas are one contiguous run of elements: coalesced copy into the slab (as 32-bit
   // words: two per element in the F64 form, whose runs start 8-byte aligned, so the slab offset stage_head is even),
@@ -712,11 +728,11 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
     const int stage_total = (int)live_chains * T * D * SW;
     float *__restrict__ gs = a.state + chain0 * T * (long long)D * SW;
     stage_copy<true>(rows_f, gs, stage_total, tid, gthreads);
-    s_landed[nslots + slot_raw] = 0;  // the ladders' swap-form objections (wide groups: the vote of a swap event, below)
+    s_landed[kToObjection * nslots + slot_raw] = 0;  // the ladders' swap-form objections (wide groups: the vote of a swap event, below)
     if constexpr (FULL) {
       if (a.full.mom_sum != nullptr) {  // (ordered before the first add by the barrier below)
         const int n_mom = (int)moments_region_doubles(a.full.mom_temps, D);
-        moments_zero(quad_moments_region<W, F64>(s_dyn, wide, (int)(threadIdx.x >> 6), n_mom), n_mom, tid, gthreads);
+        moments_zero(L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), n_mom), n_mom, tid, gthreads);
       }
     }
     sync_group();
@@ -897,9 +913,9 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
         // the published values - the one barrier below orders both, the vote has no barrier of its own - and nothing has
         // to be armed again: the stamp of an earlier event is not this event's.  (The word is read for the last time
         // before this event's row-exchange barrier, the next objection is written after it.)
-        if (!pair_plain) s_landed[nslots + base] = swap_in_call + 1;
+        if (!pair_plain) s_landed[kToObjection * nslots + base] = swap_in_call + 1;
         sync_group();
-        swap_plain = s_landed[nslots + base] != swap_in_call + 1;
+        swap_plain = s_landed[kToObjection * nslots + base] != swap_in_call + 1;
       }
       if (wide && a.swap_order == PTRWM_ORDER_SEQUENTIAL && a.swap_mode == PTRWM_SWAP_EXCHANGE) {
         // A wide ladder spans several wavefronts; the sequential sweep (kernel.h swap_decide: a scan over the ladder's
@@ -912,7 +928,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
           const int b0 = (int)threadIdx.x * T;
           float car_l = s_l[b0];
           int car_i = b0;
-          if (s_landed[nslots + b0] != swap_in_call + 1) {  // the verdict of ladder i (voted above), not of this lane's own ladder
+          if (s_landed[kToObjection * nslots + b0] != swap_in_call + 1) {  // the verdict of ladder i (voted above), not of this lane's own ladder
             // (the scanning lane builds each pair's threshold itself - they do not depend on the carried state, so the
             // logs and reciprocals of successive pairs overlap - instead of a third barrier to have them published)
 #pragma unroll 4
@@ -1005,7 +1021,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
         if (mom_now) to_mom = a.full.mom_every;
         if (mom_now && count_on && live && t < a.full.mom_temps) {
           const int mt = a.full.mom_temps;
-          double *const reg = quad_moments_region<W, F64>(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(mt, D));
+          double *const reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(mt, D));
           double *const rs = reg + t * D + l.d0;
           double *const rq = reg + (mt + t) * D + l.d0;
 #pragma unroll
@@ -1041,7 +1057,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
       // every add of the launch is behind the barrier above: the group's partial sums go to HBM, once
       const kargs_full_ptr fa = &ae->full;
       if (fa->mom_sum != nullptr)
-        moments_flush(quad_moments_region<W, F64>(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(fa->mom_temps, D)),
+        moments_flush(L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(fa->mom_temps, D)),
                       fa, D, live_chains, tid, gthreads);
     }
     stage_copy<false>(rows_f, gs, stage_total, tid, gthreads);

@@ -119,12 +119,38 @@ inline int device_cus() {
 
 // LDS of a CU (MI355X: 160 KiB), the most one workgroup may declare
 constexpr unsigned kMaxLdsBytes = 160u * 1024u;
-// dynamic LDS bytes of the moments regions of a FULL-twin workgroup of `block` threads: one region per exchange group -
-// per wave of a narrow workgroup, one for a wide ladder (thread form: T > 64; lane-split form: 4 T > 64)
-inline unsigned moments_lds_bytes(const KArgs &a, int block, bool lane_split) {
-  const bool wide = lane_split ? 4 * a.n_temps > 64 : a.n_temps > 64;
-  const int groups = wide ? 1 : block / 64;
-  return (unsigned)groups * moments_region_doubles(a.full.mom_temps, a.dim) * 8u;
+// What a step-kernel launch asks for: threads of a workgroup, its dynamic LDS bytes (kernel.h StepLds, quad.h QuadLds), and
+// those bytes with the FULL twin's moments regions behind them (one per wave of a narrow workgroup, one for a wide ladder).
+// ONE function per kernel form: the launcher launches with it, the C ABI refuses with it what does not fit (capi.hip).
+struct LaunchShape {
+  unsigned block, lds, lds_moments;
+};
+inline LaunchShape with_moments(unsigned block, unsigned lds, bool wide, const KArgs &a) {
+  return {block, lds, lds + (wide ? 1u : block / 64u) * moments_region_doubles(a.full.mom_temps, a.dim) * 8u};
+}
+// thread form.  Narrow ladders: four independent one-wave groups per workgroup; wide (n_temps > 64): the waves the ladder needs
+inline LaunchShape thread_launch_shape(const KArgs &a, int dp) {
+  const bool wide = a.n_temps > 64;
+  const unsigned block = wide ? (unsigned)((a.n_temps + 63) & ~63) : (unsigned)kBlockThreads;
+  return with_moments(block, StepLdsWords::bytes((int)block, dp, false, wide), wide, a);
+}
+using StepKernelFn = void (*)(const KArgs);
+// The common end of a launcher: the production kernel or its FULL twin with `sh` (with the moments regions when the launch
+// accumulates moments).  Above the default dynamic-LDS allowance the pair's is raised to `cap` bytes first (the most this
+// variant ever asks for), the twin's alone to a CU's whole LDS for moments.  raised / raised_m: the caller's per-instantiation statics.
+inline hipError_t launch_twins(StepKernelFn kfull, StepKernelFn kprod, const KArgs &a, unsigned grid, const LaunchShape &sh, bool full,
+                               unsigned cap, unsigned long long &raised, unsigned long long &raised_m, hipStream_t stream) {
+  if (sh.lds > 48u * 1024u) {
+    const hipError_t e = raise_dynamic_lds((const void *)kfull, (const void *)kprod, (int)cap, raised);
+    if (e != hipSuccess) return e;
+  }
+  const bool moments = full && a.full.mom_sum != nullptr;
+  if (moments && sh.lds_moments > 48u * 1024u) {
+    const hipError_t e = raise_dynamic_lds((const void *)kfull, (const void *)kfull, (int)kMaxLdsBytes, raised_m);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(full ? kfull : kprod, dim3(grid), dim3(sh.block), moments ? sh.lds_moments : sh.lds, stream, a);
+  return hipGetLastError();
 }
 
 // The streaming twin: a grid sized to the device - as many workgroups as are resident at once (occupancy of THIS kernel on
@@ -136,7 +162,7 @@ hipError_t launch_run_stream(const KArgs &a, hipStream_t stream) {
   } else {
     if (a.n_temps > 64) return hipErrorNotSupported;
     auto ks = ptrwm_step_kernel<Target, Proposal, DP, EXACT, false, true>;
-    const unsigned lds = step_kernel_lds_bytes(kBlockThreads, DP, true);
+    const unsigned lds = StepLds<DP, true>::bytes(kBlockThreads, false);
     constexpr int kMaxDevices = 64;
     static int wg_per_cu[kMaxDevices];  // 0 = not asked yet
     int dev = 0;
@@ -167,34 +193,10 @@ hipError_t launch_run_stream(const KArgs &a, hipStream_t stream) {
 template <class Target, class Proposal, int DP, bool EXACT>
 hipError_t launch_run(const KArgs &a, unsigned grid, int mode, hipStream_t stream) {
   if (mode == kRunStream) return launch_run_stream<Target, Proposal, DP, EXACT>(a, stream);
-  const bool full = mode == kRunFull;
-  // narrow ladders: four independent one-wave groups per workgroup; wide ones (n_temps > 64): as many waves as
-  // the ladder needs
-  const unsigned block = a.n_temps > 64 ? (unsigned)((a.n_temps + 63) & ~63) : (unsigned)kBlockThreads;
-  const unsigned lds = step_kernel_lds_bytes((int)block, DP) + (a.n_temps > 64 ? kWideVoteBytes : 0u);
-  auto kfull = ptrwm_step_kernel<Target, Proposal, DP, EXACT, true>;
-  auto kprod = ptrwm_step_kernel<Target, Proposal, DP, EXACT, false>;
-  if (lds > 48u * 1024u) {  // above the default dynamic-LDS allowance (wide ladders at large dim)
-    static unsigned long long raised_mask = 0;
-    const hipError_t e = raise_dynamic_lds((const void *)kfull, (const void *)kprod,
-                                           (int)(step_kernel_lds_bytes(kBlockThreads, DP) + kWideVoteBytes), raised_mask);
-    if (e != hipSuccess) return e;
-  }
-  if (full && a.full.mom_sum != nullptr) {
-    // the moments regions behind (kernel.h thread_moments_region); the fixture twin's allowance alone is raised to all
-    // of a CU's LDS (the C ABI refuses what does not fit: moments_lds_bytes)
-    const unsigned lds_m = lds + moments_lds_bytes(a, (int)block, false);
-    if (lds_m > 48u * 1024u) {
-      static unsigned long long raised_mask_m = 0;
-      const hipError_t e = raise_dynamic_lds((const void *)kfull, (const void *)kfull, (int)kMaxLdsBytes, raised_mask_m);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kfull, dim3(grid), dim3(block), lds_m, stream, a);
-  } else if (full)
-    hipLaunchKernelGGL(kfull, dim3(grid), dim3(block), lds, stream, a);
-  else
-    hipLaunchKernelGGL(kprod, dim3(grid), dim3(block), lds, stream, a);
-  return hipGetLastError();
+  static unsigned long long raised_mask = 0, raised_mask_m = 0;
+  return launch_twins(ptrwm_step_kernel<Target, Proposal, DP, EXACT, true>, ptrwm_step_kernel<Target, Proposal, DP, EXACT, false>, a,
+                      grid, thread_launch_shape(a, DP), mode == kRunFull, StepLds<DP>::bytes(kBlockThreads, true), raised_mask,
+                      raised_mask_m, stream);
 }
 
 template <class Target, int DP>
@@ -283,41 +285,21 @@ struct QuadVariants {
   RunLaunchFn run_f64[PTRWM_PROPOSAL_COUNT][kNumQuadWidths];  // state_f64 twins
 };
 
-// MIN_OWN of quad.h: the number of dimensions the LAST lane owns when dim is compiled in (every lane owns at least
-// that); -1 marks the kernels that take dim at run time
-constexpr int quad_min_own(int w, int dexact) {
-  return dexact == 0 ? -1 : (dexact - 3 * w <= 0 ? 0 : (dexact - 3 * w > w ? w : dexact - 3 * w));
+// lane-split form.  Narrow ladders (4 T <= 64): four independent one-wave groups per workgroup; wide: the workgroup is the group
+inline LaunchShape quad_launch_shape(const KArgs &a, int w, bool f64) {
+  const unsigned block = (unsigned)quad_block_threads(a.n_temps);
+  return with_moments(block, QuadLdsWords::bytes((int)block, w, f64), 4 * a.n_temps > 64, a);
 }
 
 template <class Target, class Proposal, int W, int DEXACT, int MAXT, bool F64 = false>
 hipError_t launch_run_quad(const KArgs &a, unsigned grid, int mode, hipStream_t stream) {
   if (mode == kRunStream) return hipErrorNotSupported;  // the lane-split form has no streaming twin
-  const bool full = mode == kRunFull;
-  // narrow ladders (4 T <= 64): four independent one-wave groups per workgroup; wide ones: one ladder per workgroup
-  const unsigned block = (unsigned)quad_block_threads(a.n_temps);
-  if ((int)block > MAXT) return hipErrorInvalidConfiguration;
-  const unsigned lds = quad_kernel_lds_bytes((int)block, W, F64);
-  auto kfull = ptrwm_quad_step_kernel<Target, Proposal, W, DEXACT, MAXT, true, F64>;
-  auto kprod = ptrwm_quad_step_kernel<Target, Proposal, W, DEXACT, MAXT, false, F64>;
-  if (lds > 48u * 1024u) {
-    static unsigned long long raised_mask = 0;
-    const hipError_t e = raise_dynamic_lds((const void *)kfull, (const void *)kprod,
-                                           (int)quad_kernel_lds_bytes(MAXT, W, F64), raised_mask);
-    if (e != hipSuccess) return e;
-  }
-  if (full && a.full.mom_sum != nullptr) {  // (as launch_run: the moments regions behind the slabs, quad_moments_region)
-    const unsigned lds_m = lds + moments_lds_bytes(a, (int)block, true);
-    if (lds_m > 48u * 1024u) {
-      static unsigned long long raised_mask_m = 0;
-      const hipError_t e = raise_dynamic_lds((const void *)kfull, (const void *)kfull, (int)kMaxLdsBytes, raised_mask_m);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kfull, dim3(grid), dim3(block), lds_m, stream, a);
-  } else if (full)
-    hipLaunchKernelGGL(kfull, dim3(grid), dim3(block), lds, stream, a);
-  else
-    hipLaunchKernelGGL(kprod, dim3(grid), dim3(block), lds, stream, a);
-  return hipGetLastError();
+  const LaunchShape sh = quad_launch_shape(a, W, F64);
+  if ((int)sh.block > MAXT) return hipErrorInvalidConfiguration;
+  static unsigned long long raised_mask = 0, raised_mask_m = 0;
+  return launch_twins(ptrwm_quad_step_kernel<Target, Proposal, W, DEXACT, MAXT, true, F64>,
+                      ptrwm_quad_step_kernel<Target, Proposal, W, DEXACT, MAXT, false, F64>, a, grid, sh, mode == kRunFull,
+                      QuadLds<W, F64>::bytes(MAXT), raised_mask, raised_mask_m, stream);
 }
 
 #define PTRWM_X_QRUN_N(W, E, M) launch_run_quad<QTGT<W, quad_min_own(W, E)>, QNormal<W, quad_min_own(W, E)>, W, E, M>,

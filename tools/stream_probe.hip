@@ -71,7 +71,7 @@ static void launch(KArgs k, const Bufs &b, long long step0, int n_steps, int se,
   k.burn_left = 0;
   k.first_swap_event = step0 / se;
   k.steps_to_swap = (int)(se - step0 % se);
-  const unsigned lds = step_kernel_lds_bytes(kBlockThreads, DP, STREAM);
+  const unsigned lds = StepLds<DP, STREAM>::bytes(kBlockThreads, false);
   hipLaunchKernelGGL((ptrwm_step_kernel<Tgt, Prop, DP, true, false, STREAM>), dim3(grid), dim3(kBlockThreads), lds, 0, k);
 }
 
@@ -144,7 +144,7 @@ int main(int argc, char **argv) {
   const long long waves = (n_groups + rounds - 1) / rounds;
   const unsigned grid_stream = (unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
 
-  const unsigned lds = step_kernel_lds_bytes(kBlockThreads, DP), lds_s = step_kernel_lds_bytes(kBlockThreads, DP, true);
+  const unsigned lds = StepLds<DP>::bytes(kBlockThreads, false), lds_s = StepLds<DP, true>::bytes(kBlockThreads, false);
   CK(hipFuncSetAttribute((const void *)ptrwm_step_kernel<Tgt, Prop, DP, true, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
   CK(hipFuncSetAttribute((const void *)ptrwm_step_kernel<Tgt, Prop, DP, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_s));
   int occ_c = 0, occ_s = 0;
