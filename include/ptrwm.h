@@ -328,6 +328,59 @@ int32_t ptrwm_run_with_moments(const ptrwm_target_desc *target, const ptrwm_prop
  * ptrwm_run_with_moments (no LDS limit: a small stand-alone kernel). */
 int32_t ptrwm_split_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm_moments_args *moments, void *stream);
 
+/* ---- posterior moments of every chain on its own: R-hat and ESS without a trace -----------------------------------------
+ * The same accumulation as ptrwm_moments_args, kept apart per local chain c (RWM: chain; PT: ladder) instead of pooled.
+ * For chain c and each of the first `temps` temperatures t, at every step whose step_counter > burn_in and
+ * step_counter % every == 0:
+ *   sum[c, t, d] += x_d,   sum_sq[c, t, d] += x_d * x_d,   sum_logp[c, t] += logp
+ * where x / logp are the state and log-density at position (c, t) after the whole step (MH move and that step's swap
+ * event) - exactly what a trace with trace_every = every records at that step - and count[t] += 1: the accumulated steps
+ * of every chain.  Everything is device memory and is added to (+=), so launches and calls compose.
+ * Determinism: each element is the SEQUENTIAL fp64 sum of its terms in step order (x_d * x_d is the exact fp64 product of
+ * the state element) - no atomics between chains, one exchange group owns each element.  It does not depend on where a run
+ * is cut into launches, on the kernel form (pinned or AUTO's choice) or on how chains are sharded over devices; two runs
+ * give the same bits.  No other output of the run changes: state, logp and every counter are bit-identical to the same run
+ * without moments.  ptrwm_swap_sweep events are not steps and add nothing.
+ * How: the fixture / trace twin of the step kernel (never the streaming form) loads its exchange group's part of the
+ * accumulators into LDS when a launch begins, adds to it there, and stores it back with plain stores when the launch ends;
+ * a launch without an accumulated step touches nothing.
+ * Limit: the LDS region is  L * temps * (2 dim + 1)  doubles per exchange group, L = ladders per group:
+ *   thread form, n_temps <= 64:       L = 64 / n_temps,  four groups (waves) per workgroup
+ *   thread form, n_temps  > 64:       L = 1,             one group per workgroup
+ *   lane-split form, n_temps <= 16:   L = 16 / n_temps,  four groups (waves) per workgroup
+ *   lane-split form, n_temps  > 16:   L = the whole ladders (4 n_temps lanes each) that best fill a workgroup of up to 256
+ *                                     threads (n_temps 20: 3; n_temps >= 33: 1), one group per workgroup
+ * and  groups per workgroup * region * 8 bytes  plus what the kernel already holds (thread form: 4 (DP + 8) bytes per thread,
+ * DP = register width >= dim; lane-split: 4 (W + 2) bytes per thread, W = ceil(dim / 4) rounded up to a compiled width,
+ * twice W for double states) must stay within 160 KiB per workgroup (RWM at dim 30, thread form: 4 x 64 chains x 61 doubles
+ * on top of 38 912 bytes is exactly 160 KiB - one workgroup per CU; lane-split form: 4 x 16 x 61 doubles on top of 10 240).
+ * Under PTRWM_FORM_AUTO, where both forms exist and the form AUTO would run needs more than half of that (or does not fit),
+ * the other form runs if it needs less - RWM at dim 30 runs the lane-split form; the forms give the same bits.
+ * PTRWM_E_ARG - before anything is enqueued - only when the pinned form, or neither form, fits. */
+typedef struct ptrwm_chain_moments_args {
+  uint32_t struct_size; /* sizeof(ptrwm_chain_moments_args) */
+  int32_t temps;        /* 1..n_temps: the first `temps` temperatures */
+  int32_t every;        /* >= 1: thinning period of the accumulated steps */
+  double *sum;          /* [n_chains, temps, dim] device, += (required) */
+  double *sum_sq;       /* [n_chains, temps, dim] device, += (required) */
+  double *sum_logp;     /* [n_chains, temps] device, +=, or NULL */
+  int64_t *count;       /* [temps] device, +=, or NULL: the accumulated steps per chain */
+} ptrwm_chain_moments_args;
+
+/* ptrwm_run, and the per-chain moments accumulated over the steps it performs.  chain_moments == NULL: exactly ptrwm_run.
+ * Checked before anything is enqueued, as ptrwm_run_with_moments: PTRWM_E_STRUCT for a wrong struct_size; PTRWM_E_ARG for
+ * temps outside 1..n_temps, every < 1, or a region too big for the kernel's LDS (above); PTRWM_E_NULL for a NULL sum / sum_sq. */
+int32_t ptrwm_run_with_chain_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                                     const ptrwm_run_args *args, const ptrwm_chain_moments_args *chain_moments, void *stream);
+
+/* Split steps: the per-chain moments of the step ptrwm_split_accept just performed (enqueue it after ptrwm_split_accept).
+ * Reads from `args` what ptrwm_split_moments reads; the step is args->step0, or *device_step + step0 in device-step mode -
+ * read on the device, so the call can sit inside a captured block of split steps.  A step that does not count adds
+ * nothing.  One thread per (chain, t < temps, d), a plain read-modify-write: the same sequential sums as the fused kernels.
+ * Same argument checks as ptrwm_run_with_chain_moments (no LDS limit). */
+int32_t ptrwm_split_chain_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm_chain_moments_args *chain_moments,
+                                  void *stream);
+
 /* One stand-alone swap event over the current states: what the reference's
  * ParallelTemperingRWM_GPU_Optimized._attempt_all_swaps() does when called on its own
  * (pt_rwm_gpu_optimized.py:594-633; tests/debug_pt_performance.py:156).  Exactly the swap part of a ptrwm_run step:

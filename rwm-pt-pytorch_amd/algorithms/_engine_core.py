@@ -17,6 +17,13 @@ and, when moments are on (moments_temps > 0), pooled over every replica of the s
     mom_sum_logp float64 [moments_temps]              sum of the log-density
     mom_count    int64   [moments_temps]              (replica, step) pairs added
 
+or, with moments_per_chain, kept apart per replica (include/ptrwm.h ptrwm_chain_moments_args; deterministic sums):
+
+    cmom_sum      float64 [n_replicas, moments_temps, dim]
+    cmom_sum_sq   float64 [n_replicas, moments_temps, dim]
+    cmom_sum_logp float64 [n_replicas, moments_temps]
+    cmom_count    int64   [moments_temps]             accumulated steps per replica
+
 `n_replicas` is the axis the reference does not have: independent copies of the whole chain /
 ladder, one Philox subsequence each (global replica id = chain_offset + local index), so a run is
 invariant to how replicas are sharded over GPUs.
@@ -48,7 +55,8 @@ class EngineRun:
     def __init__(self, *, target_dist, proposal: "ptrwm_hip.Proposal", beta_ladder: Sequence[float], dim: int,
                  device: torch.device, n_replicas: int, initial_state: np.ndarray, burn_in: int, swap_every: int,
                  swap_mode: str, swap_order: str, seed: Optional[int], chain_offset: int = 0,
-                 dtype: torch.dtype = torch.float32, moments_temps: int = 0, moments_every: int = 1):
+                 dtype: torch.dtype = torch.float32, moments_temps: int = 0, moments_every: int = 1,
+                 moments_per_chain: bool = False):
         if swap_mode not in ptrwm_hip.SWAP_MODES:
             raise ValueError(f"swap_mode must be one of {sorted(ptrwm_hip.SWAP_MODES)}, got {swap_mode!r}")
         if swap_order not in ptrwm_hip.SWAP_ORDERS:
@@ -126,7 +134,19 @@ class EngineRun:
         if int(moments_every) < 1:
             raise ValueError(f"moments_every must be >= 1, got {moments_every}")
         self.moments_temps, self.moments_every = int(moments_temps), int(moments_every)
-        if self.moments_temps:
+        self.moments_per_chain = bool(moments_per_chain)
+        if self.moments_per_chain and not self.moments_temps:
+            raise ValueError("moments_per_chain needs moments_temps >= 1")
+        if self.moments_per_chain:
+            # the per-chain arrays only: the pooled sums are their sum over the replicas (moments())
+            mt = self.moments_temps
+            self.cmom_sum = torch.zeros(n_replicas, mt, dim, device=device, dtype=torch.float64)
+            self.cmom_sum_sq = torch.zeros(n_replicas, mt, dim, device=device, dtype=torch.float64)
+            self.cmom_sum_logp = torch.zeros(n_replicas, mt, device=device, dtype=torch.float64)
+            self.cmom_count = torch.zeros(mt, device=device, dtype=torch.int64)
+            self._plan.set_chain_moments(self.cmom_sum, self.cmom_sum_sq, sum_logp=self.cmom_sum_logp,
+                                         count=self.cmom_count, every=self.moments_every)
+        elif self.moments_temps:
             mt = self.moments_temps
             self.mom_sum = torch.zeros(mt, dim, device=device, dtype=torch.float64)
             self.mom_sum_sq = torch.zeros(mt, dim, device=device, dtype=torch.float64)
@@ -183,6 +203,7 @@ class EngineRun:
         lp_new = self._density(props.view(-1, D)).view(C, T)
         self._plan.split_accept(offset, lp_new, swap_event_offset=self.manual_sweeps, no_sweep=no_sweep)
         self._plan.split_moments(offset)  # (decides on the device whether this step counts; no-op without moments)
+        self._plan.split_chain_moments(offset)
         if advance:
             self._plan.split_advance(advance)
 
@@ -270,6 +291,7 @@ class EngineRun:
             lp_new = self._density(props.view(-1, D)).view(C, T)
             self._plan.split_accept(s, lp_new, swap_event_offset=self.manual_sweeps)
             self._plan.split_moments(s)
+            self._plan.split_chain_moments(s)
             self.steps_done += 1
             if trace is not None and self.steps_done % trace_every == 0:
                 tc, tt = trace.shape[1], trace.shape[2]
@@ -310,13 +332,33 @@ class EngineRun:
         sum / sum_sq [temps, dim] float64, sum_logp [temps] float64, count [temps] int64, every."""
         if not self.moments_temps:
             return None
+        if self.moments_per_chain:  # pooled = the per-chain sums added over the replicas; count: (replica, step) pairs
+            return {"sum": self.cmom_sum.sum(0), "sum_sq": self.cmom_sum_sq.sum(0), "sum_logp": self.cmom_sum_logp.sum(0),
+                    "count": self.cmom_count * self.n_replicas, "every": self.moments_every}
         return {"sum": self.mom_sum, "sum_sq": self.mom_sum_sq, "sum_logp": self.mom_sum_logp, "count": self.mom_count,
                 "every": self.moments_every}
 
     def reset_moments(self) -> None:
         """Zero the moment accumulators (the chains keep their states)."""
-        if self.moments_temps:
+        if self.moments_per_chain:
+            self.reset_chain_moments()
+        elif self.moments_temps:
             for t in (self.mom_sum, self.mom_sum_sq, self.mom_sum_logp, self.mom_count):
+                t.zero_()
+
+    def chain_moments(self) -> Optional[dict]:
+        """The raw per-chain moment sums of this shard (device tensors, no synchronisation), or None when
+        moments_per_chain is off: sum / sum_sq [n_replicas, temps, dim] float64, sum_logp [n_replicas, temps] float64,
+        count [temps] int64 (accumulated steps per replica), every."""
+        if not self.moments_per_chain:
+            return None
+        return {"sum": self.cmom_sum, "sum_sq": self.cmom_sum_sq, "sum_logp": self.cmom_sum_logp, "count": self.cmom_count,
+                "every": self.moments_every}
+
+    def reset_chain_moments(self) -> None:
+        """Zero the per-chain accumulators (the chains keep their states)."""
+        if self.moments_per_chain:
+            for t in (self.cmom_sum, self.cmom_sum_sq, self.cmom_sum_logp, self.cmom_count):
                 t.zero_()
 
     def summary(self) -> dict:
@@ -345,6 +387,38 @@ def moments_temps(mode, n_temps: int, every) -> int:
     if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or every < 1:
         raise ValueError(f"moments_every must be an integer >= 1, got {every!r}")
     return {None: 0, "cold": 1, "all": n_temps}[mode]
+
+
+def chain_mean_var(sum: torch.Tensor, sum_sq: torch.Tensor, n) -> tuple:
+    """Mean and variance (ddof 1) of every chain from its sums over n draws: sum / sum_sq [chains, ...] float64."""
+    n = float(n)
+    mean = sum / n
+    var = (sum_sq - n * mean * mean) / (n - 1.0) if n >= 2 else torch.full_like(mean, float("nan"))
+    return mean, var
+
+
+def rhat_ess_from_chain_summary(m: float, s_mean: torch.Tensor, s_mean_sq: torch.Tensor, s_var: torch.Tensor, n) -> tuple:
+    """Gelman-Rubin R-hat and between-chain ESS from what sums over chains: M, sum_c m_c, sum_c m_c^2, sum_c s2_c (m_c / s2_c
+    the chain means / variances over n draws each).  See rhat_ess_from_chain_sums."""
+    m, n = float(m), float(n)
+    if m < 2 or n < 2:
+        nan = torch.full_like(s_mean, float("nan"))
+        return nan, nan.clone()
+    w = s_var / m
+    grand = s_mean / m
+    b = n * (s_mean_sq - m * grand * grand) / (m - 1.0)
+    var_plus = (n - 1.0) / n * w + b / n
+    rhat = torch.sqrt(var_plus / w)
+    ess = torch.clamp(m * n * var_plus / b, max=m * n)
+    return rhat, ess
+
+
+def rhat_ess_from_chain_sums(sum: torch.Tensor, sum_sq: torch.Tensor, n) -> tuple:
+    """(R-hat, ESS) per coordinate from per-chain sums: sum / sum_sq [M, ...] float64 (CPU or GPU), n draws per chain.
+    With m_c, s2_c the chain means and variances (ddof 1):  W = mean_c s2_c,  B = n var_c(m_c, ddof 1),
+    var+ = (n - 1) / n W + B / n,  R-hat = sqrt(var+ / W),  ESS = min(M n, M n var+ / B).  NaN when M < 2 or n < 2."""
+    mean, var = chain_mean_var(sum, sum_sq, n)
+    return rhat_ess_from_chain_summary(sum.shape[0], mean.sum(0), (mean * mean).sum(0), var.sum(0), n)
 
 
 class PosteriorMoments:
@@ -393,13 +467,49 @@ class PosteriorMoments:
         m = self._moment_sums()
         return m["sum_logp"] / m["count"].double()
 
+    # ---- per-chain estimates (moments_per_chain=True) -----------------------------------------------------------
+    def _chain_sums(self, temperature: int) -> tuple:
+        """(sum [chains, dim], sum_sq [chains, dim], draws per chain) of one covered temperature."""
+        if not getattr(self, "_moments_per_chain", False):
+            raise RuntimeError("per-chain moments are off: construct the sampler with moments_per_chain=True")
+        run = getattr(self, "_run", None)
+        if run is None:
+            raise RuntimeError("nothing has run yet: no per-chain moments")
+        cm = run.chain_moments()
+        t = self._check_temperature(temperature, {"sum": cm["sum"][0]})
+        return cm["sum"][:, t], cm["sum_sq"][:, t], int(cm["count"][t].item())
+
+    def chain_means(self, temperature: int = 0) -> torch.Tensor:
+        """Every chain's own mean of `temperature`: float64 [chains, dim] on the device."""
+        s, q, n = self._chain_sums(temperature)
+        return chain_mean_var(s, q, n)[0] if n >= 1 else torch.full_like(s, float("nan"))
+
+    def chain_variances(self, temperature: int = 0) -> torch.Tensor:
+        """Every chain's own variance (ddof 1) of `temperature`: float64 [chains, dim] on the device."""
+        s, q, n = self._chain_sums(temperature)
+        return chain_mean_var(s, q, n)[1] if n >= 1 else torch.full_like(s, float("nan"))
+
+    def rhat(self, temperature: int = 0) -> torch.Tensor:
+        """Gelman-Rubin R-hat per coordinate over the chains of `temperature` (rhat_ess_from_chain_sums): float64 [dim]."""
+        s, q, n = self._chain_sums(temperature)
+        return rhat_ess_from_chain_sums(s, q, n)[0]
+
+    def ess(self, temperature: int = 0) -> torch.Tensor:
+        """Between-chain effective sample size per coordinate, all chains together: float64 [dim]."""
+        s, q, n = self._chain_sums(temperature)
+        return rhat_ess_from_chain_sums(s, q, n)[1]
+
     def _moments_diagnostics(self) -> dict:
         if getattr(self, "_moments_mode", None) is None:
             return {}
         m = self._moment_sums()
         n = m["count"].double()
         mean = m["sum"] / n[:, None]
+        extra = {}
+        if getattr(self, "_moments_per_chain", False) and getattr(self, "_run", None) is not None:
+            extra = {"rhat_max": float(self.rhat().max().item()), "ess_min": float(self.ess().min().item())}
         return {
+            **extra,
             "moments": self._moments_mode,
             "moments_every": self._moments_every,
             "moment_count": m["count"].cpu(),

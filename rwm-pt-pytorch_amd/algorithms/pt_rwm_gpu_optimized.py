@@ -55,10 +55,13 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
                  num_replicas: int = 1, proposal_distribution: Optional[ProposalDistribution] = None,
                  swap_mode: str = "exchange", swap_order: str = "sequential", seed: Optional[int] = None,
                  chain_offset: int = 0, trace: str = "all", thin: int = 1, moments: Optional[str] = None,
-                 moments_every: int = 1):
+                 moments_every: int = 1, moments_per_chain: bool = False):
         super().__init__(dim, var, target_dist, symmetric)
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         self._moments_mode, self._moments_every = moments, int(moments_every)
+        if moments_per_chain and moments is None:
+            raise ValueError("moments_per_chain=True needs moments='cold' or 'all'")
+        self._moments_per_chain = bool(moments_per_chain)
         self.device = resolve_device(device)
         # dtype=torch.float64 (experiment_pt_GPU.py:236 --use_double_precision; pt_rwm_gpu_optimized.py:134,431-449): states,
         # proposals x + scale * z, stored chains and jump distances in double (the engine's state_f64 mode: lane-split
@@ -228,7 +231,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             initial_state=self._initial_state, burn_in=self.burn_in, swap_every=self.swap_every,
             swap_mode=self._swap_mode, swap_order=self._swap_order, seed=self._seed, chain_offset=self._chain_offset,
             dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
-            moments_every=self._moments_every)
+            moments_every=self._moments_every, moments_per_chain=self._moments_per_chain)
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
         self.current_log_densities = self._run.logp[0] if self.num_replicas == 1 else self._run.logp

@@ -57,9 +57,12 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
                  burn_in: int = 0, device: str = None, pre_allocate_steps: int = None, use_efficient_rng: bool = True,
                  compile_mode: str = None, proposal_distribution: ProposalDistribution = None, *,
                  num_chains: int = 1, seed: Optional[int] = None, chain_offset: int = 0, thin: int = 1,
-                 moments: Optional[str] = None, moments_every: int = 1):
+                 moments: Optional[str] = None, moments_every: int = 1, moments_per_chain: bool = False):
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         self._moments_mode, self._moments_every = moments, int(moments_every)
+        if moments_per_chain and moments is None:
+            raise ValueError("moments_per_chain=True needs moments='cold' or 'all'")
+        self._moments_per_chain = bool(moments_per_chain)
         if proposal_distribution is None and var is None:
             raise ValueError("Either var (backward compatibility) or proposal_distribution must be provided")
         super().__init__(dim, 1.0 if proposal_distribution is not None else var, target_dist, symmetric)
@@ -152,7 +155,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             dim=self.dim, device=self.device, n_replicas=self.num_chains, initial_state=self.chain[-1],
             burn_in=self.burn_in, swap_every=1, swap_mode="exchange", swap_order="sequential", seed=self._seed,
             chain_offset=self._chain_offset, moments_temps=moments_temps(self._moments_mode, 1, self._moments_every),
-            moments_every=self._moments_every,
+            moments_every=self._moments_every, moments_per_chain=self._moments_per_chain,
         )
         self.current_state = self._run.state[0, 0]  # views: always the live values
         self.log_target_density_current = self._run.logp[0, 0]

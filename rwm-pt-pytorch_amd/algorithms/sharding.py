@@ -88,3 +88,39 @@ def allreduce_moments(moments: dict, group: Optional[dist.ProcessGroup] = None) 
     if "every" in moments:
         out["every"] = moments["every"]
     return out
+
+
+def chain_summary(chain_moments: dict) -> dict:
+    """What of a shard's per-chain moments (EngineRun.chain_moments()) adds over shards, per (temperature, coordinate):
+    the number of chains M, sum_c m_c, sum_c m_c^2 and sum_c s2_c of the chain means m_c and variances s2_c (ddof 1).
+    `draws` [temps]: accumulated steps per chain (the same on every shard of a run)."""
+    from ._engine_core import chain_mean_var
+
+    s, q, n = chain_moments["sum"], chain_moments["sum_sq"], chain_moments["count"]
+    draws = [int(v) for v in n.tolist()]
+    means, variances = zip(*(chain_mean_var(s[:, t], q[:, t], draws[t]) if draws[t] >= 1 else
+                             (torch.full_like(s[:, t], float("nan")),) * 2 for t in range(s.shape[1])))
+    mean, var = torch.stack(means, 1), torch.stack(variances, 1)  # [M, temps, dim]
+    return {"n_chains": s.shape[0], "sum_mean": mean.sum(0), "sum_mean_sq": (mean * mean).sum(0), "sum_var": var.sum(0),
+            "draws": draws}
+
+
+def allreduce_chain_summary(chain_moments: dict, group: Optional[dist.ProcessGroup] = None) -> dict:
+    """Whole-job Gelman-Rubin R-hat and between-chain ESS from every rank's per-chain moments: each rank reduces its own
+    chains to chain_summary() - (M, sum m_c, sum m_c^2, sum s2_c) per (temperature, coordinate) - and ONE SUM all-reduce of
+    that float64 vector combines them; the per-chain arrays never leave their shard.  Returns rhat / ess [temps, dim]
+    (new tensors on the shards' device), n_chains (whole job) and draws."""
+    from ._engine_core import rhat_ess_from_chain_summary
+
+    cs = chain_summary(chain_moments)
+    temps, dim = cs["sum_mean"].shape
+    td = temps * dim
+    vec = torch.cat([cs["sum_mean"].reshape(-1), cs["sum_mean_sq"].reshape(-1), cs["sum_var"].reshape(-1),
+                     torch.tensor([float(cs["n_chains"])], dtype=torch.float64, device=cs["sum_mean"].device)])
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=group)
+    m = int(round(float(vec[3 * td].item())))
+    sm, sq, sv = (vec[i * td:(i + 1) * td].view(temps, dim) for i in range(3))
+    pairs = [rhat_ess_from_chain_summary(m, sm[t], sq[t], sv[t], cs["draws"][t]) for t in range(temps)]
+    return {"rhat": torch.stack([p[0] for p in pairs]), "ess": torch.stack([p[1] for p in pairs]), "n_chains": m,
+            "draws": cs["draws"]}

@@ -658,9 +658,45 @@ __global__ void __launch_bounds__(256) split_moments_kernel(SplitMomentsArgs a) 
     for (int t = threadIdx.x; t < a.temps; t += blockDim.x) count_add(&a.count[t], c1 - c0);
 }
 
+// Per-chain moments of one split step (ptrwm_split_chain_moments): one thread per (chain, t < temps, d), a plain
+// read-modify-write of its own two elements - the same sequential fp64 sums as the fused kernels' (v * v is exact in fp64).
+struct SplitChainMomentsArgs {
+  const float *state, *logp;
+  double *sum, *sum_sq, *sum_logp;
+  long long *count;
+  long long n_elems, step, burn_in, every;  // n_elems = n_chains * temps * dim
+  const long long *device_step;
+  int n_temps, dim, temps;
+};
+
+__global__ void __launch_bounds__(256) split_chain_moments_kernel(SplitChainMomentsArgs a) {
+  const long long step = a.device_step != nullptr ? *a.device_step + a.step : a.step;
+  const long long sc = step + 1;  // step_counter of the step just performed
+  if (!(sc > a.burn_in && sc % a.every == 0)) return;  // (grid-uniform)
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_elems) return;
+  const int td = a.temps * a.dim;
+  const long long c = i / td;
+  const int k = (int)(i - c * td), t = k / a.dim, d = k - t * a.dim;
+  const long long rep = c * a.n_temps + t;
+  const double v = (double)a.state[rep * a.dim + d];
+  a.sum[i] += v;
+  a.sum_sq[i] += v * v;
+  if (d == 0 && a.sum_logp != nullptr) a.sum_logp[c * a.temps + t] += (double)a.logp[rep];
+  if (i < a.temps && a.count != nullptr) a.count[i] += 1;
+}
+
 }  // namespace ptrwm
 
 using namespace ptrwm;
+
+// what run_impl accumulates: the pooled sums of ptrwm_moments_args or the per-chain ones of ptrwm_chain_moments_args
+struct MomSpec {
+  bool per_chain;
+  int32_t temps, every;
+  double *sum, *sum_sq, *sum_logp;
+  int64_t *count;
+};
 
 // ptrwm_moments_args checks shared by ptrwm_run_with_moments and ptrwm_split_moments (args already checked); NULL: none
 static int32_t check_moments(const ptrwm_run_args *args, const ptrwm_moments_args *m) {
@@ -671,8 +707,17 @@ static int32_t check_moments(const ptrwm_run_args *args, const ptrwm_moments_arg
   return PTRWM_OK;
 }
 
+// ... and the same for ptrwm_chain_moments_args
+static int32_t check_chain_moments(const ptrwm_run_args *args, const ptrwm_chain_moments_args *m) {
+  if (m == nullptr) return PTRWM_OK;
+  if (m->struct_size != sizeof(ptrwm_chain_moments_args)) return PTRWM_E_STRUCT;
+  if (m->temps < 1 || m->temps > args->n_temps || m->every < 1) return PTRWM_E_ARG;
+  if (m->sum == nullptr || m->sum_sq == nullptr) return PTRWM_E_NULL;
+  return PTRWM_OK;
+}
+
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const ptrwm_moments_args *mom, void *hip_stream);
+                        const ptrwm_moments_args *pooled, const ptrwm_chain_moments_args *per_chain, void *hip_stream);
 
 extern "C" {
 
@@ -772,24 +817,34 @@ int32_t ptrwm_has_variant(int32_t target_kind, int32_t proposal_kind, int32_t di
 
 int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                   void *hip_stream) {
-  return run_impl(target, proposal, args, nullptr, hip_stream);
+  return run_impl(target, proposal, args, nullptr, nullptr, hip_stream);
 }
 
 int32_t ptrwm_run_with_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
                                const ptrwm_run_args *args, const ptrwm_moments_args *moments, void *stream) {
-  return run_impl(target, proposal, args, moments, stream);
+  return run_impl(target, proposal, args, moments, nullptr, stream);
+}
+
+int32_t ptrwm_run_with_chain_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                                     const ptrwm_run_args *args, const ptrwm_chain_moments_args *chain_moments, void *stream) {
+  return run_impl(target, proposal, args, nullptr, chain_moments, stream);
 }
 
 }  // extern "C"
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const ptrwm_moments_args *mom, void *hip_stream) {
+                        const ptrwm_moments_args *pooled, const ptrwm_chain_moments_args *per_chain, void *hip_stream) {
   if (proposal == nullptr || args == nullptr) return PTRWM_E_NULL;
   if (int rc = check_target(target)) return rc;
   if (args->struct_size != sizeof(ptrwm_run_args)) return PTRWM_E_STRUCT;
   if (proposal->kind < 0 || proposal->kind >= PTRWM_PROPOSAL_COUNT) return PTRWM_E_KIND;
   if (args->n_temps < 1 || args->n_temps > PTRWM_MAX_TEMPS) return PTRWM_E_TEMPS;
-  if (int rc = check_moments(args, mom)) return rc;
+  if (int rc = check_moments(args, pooled)) return rc;
+  if (int rc = check_chain_moments(args, per_chain)) return rc;
+  MomSpec mom_spec = {};
+  if (pooled != nullptr) mom_spec = {false, pooled->temps, pooled->every, pooled->sum, pooled->sum_sq, pooled->sum_logp, pooled->count};
+  if (per_chain != nullptr) mom_spec = {true, per_chain->temps, per_chain->every, per_chain->sum, per_chain->sum_sq, per_chain->sum_logp, per_chain->count};
+  const MomSpec *const mom = (pooled != nullptr || per_chain != nullptr) ? &mom_spec : nullptr;
   if (args->n_chains < 0 || args->n_steps < 0 || args->step0 < 0 || args->burn_in < 0 || args->swap_every < 1)
     return PTRWM_E_ARG;
   if (args->swap_mode != PTRWM_SWAP_EXCHANGE && args->swap_mode != PTRWM_SWAP_REFERENCE_COPY) return PTRWM_E_ARG;
@@ -823,7 +878,9 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
                          (f64 ? q1.run_f64 : q1.run)[proposal->kind][qi] == nullptr;
     if (!thread_ok || !quad_ok) alt = 1;
   }
-  RunLaunchFn fn = target_variants(target->kind, alt).run(proposal->kind, dpi);  // null above width 64
+  const RunLaunchFn thread_fn = target_variants(target->kind, alt).run(proposal->kind, dpi);  // null above width 64
+  RunLaunchFn fn = thread_fn;
+  RunLaunchFn other_fn = nullptr;  // the form NOT chosen, where AUTO chose and both exist (per-chain moments: below)
   // lane-split form? (bit-identical results: a speed decision, see g_kernel_form - except above dim 64, where it is the
   // only form)
   bool quad = false;
@@ -839,6 +896,7 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
       quad = fn == nullptr || form == PTRWM_FORM_QUAD ||
              auto_prefers_lane_split(target->dim, args->n_temps, args->n_chains, device_simds((hipStream_t)hip_stream));
       if (quad) fn = qfn;
+      if (form == PTRWM_FORM_AUTO && thread_fn != nullptr) other_fn = quad ? thread_fn : qfn;
     }
   }
   if (fn == nullptr) return PTRWM_E_NOVARIANT;
@@ -871,9 +929,13 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   k.swap_mode = args->swap_mode;
   k.swap_order = args->swap_order;
   // exchange groups: one wavefront holding whole ladders, or ("wide") one workgroup per ladder
-  const int lanes_per_replica = quad ? kQuad : 1;
-  const bool wide = args->n_temps * lanes_per_replica > 64;
-  k.chains_per_wave = quad ? quad_ladders_per_group(args->n_temps) : (wide ? 1 : 64 / args->n_temps);
+  bool wide = false;
+  auto set_form = [&](bool q) {  // what of the launch depends on the kernel form
+    quad = q;
+    wide = args->n_temps * (q ? kQuad : 1) > 64;
+    k.chains_per_wave = q ? quad_ladders_per_group(args->n_temps) : (wide ? 1 : 64 / args->n_temps);
+  };
+  set_form(quad);
   k.k0 = (unsigned)(args->seed & 0xffffffffull);
   k.k1 = (unsigned)(args->seed >> 32);
   k.tp = make_tparams(target);
@@ -894,10 +956,28 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   k.full.mom_temps = mom != nullptr ? mom->temps : 0;
   k.full.mom_every = mom != nullptr ? mom->every : 1;
   k.full.steps_to_mom = 0;
+  k.full.mom_chain = (mom != nullptr && mom->per_chain) ? 1 : 0;
   if (mom != nullptr) {
     // the workgroup's LDS with the moments regions behind it, as the launcher will ask for it (variants.h LaunchShape)
-    const LaunchShape sh = quad ? quad_launch_shape(k, canon_width(target->dim), f64) : thread_launch_shape(k, kWidths[dpi].dp);
-    if (sh.lds_moments > kMaxLdsBytes) return PTRWM_E_ARG;
+    auto lds_need = [&]() {
+      return (quad ? quad_launch_shape(k, canon_width(target->dim), f64) : thread_launch_shape(k, kWidths[dpi].dp)).lds_moments;
+    };
+    unsigned need = lds_need();
+    // Per-chain regions grow with the ladders of a group.  Where AUTO chose the form and both exist, a workgroup that needs
+    // more than half of the CU's LDS (one workgroup resident: one wave per SIMD in the thread form) - or does not fit at
+    // all - hands over to the other form if that one needs less (the same bits).  A pinned form is taken as it is.
+    if (mom->per_chain && other_fn != nullptr && need > kMaxLdsBytes / 2u) {
+      const bool chosen = quad;
+      set_form(!chosen);
+      const unsigned other = lds_need();
+      if (other < need) {
+        fn = other_fn;
+        need = other;
+      } else {
+        set_form(chosen);
+      }
+    }
+    if (need > kMaxLdsBytes) return PTRWM_E_ARG;
   }
 
   // the streaming form for short launches of the one-thread-per-replica kernel (see kStreamMaxSteps above)
@@ -958,7 +1038,7 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
       const long long me = mom->every, lo = args->burn_in > step0 ? args->burn_in : step0;
       const long long m = (step0 + n) / me - lo / me;
       const bool on = m > 0;  // (a launch with none leaves the accumulators and its LDS alone)
-      k.full.mom_steps = on ? m : 0;
+      k.full.mom_steps = on ? m : 0;  // (per chain: count[t] += m; pooled: += live ladders x m)
       k.full.mom_sum = on ? mom->sum : nullptr;
       k.full.mom_sum_sq = mom->sum_sq;
       k.full.mom_sum_logp = mom->sum_logp;
@@ -1092,6 +1172,35 @@ int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *propo
   // the swap event of this step: event number as ptrwm_run counts them, swap uniforms from the fused kernel's stream
   const long long ev = sc / args->swap_every - args->burn_in / args->swap_every - 1 + args->swap_event_offset;
   return launch_sweep(args, dim, ev, (int)kStreamSwap, proposals, args->sq_jump, (hipStream_t)stream);
+}
+
+int32_t ptrwm_split_chain_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm_chain_moments_args *cm, void *stream) {
+  if (int rc = split_common_checks(args, dim)) return rc;
+  if (cm == nullptr) return PTRWM_E_NULL;
+  if (int rc = check_chain_moments(args, cm)) return rc;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->state == nullptr || args->logp == nullptr) return PTRWM_E_NULL;
+  if (args->device_step == nullptr && !(args->step0 + 1 > args->burn_in && (args->step0 + 1) % cm->every == 0))
+    return PTRWM_OK;  // (known on the host: this step does not count)
+  SplitChainMomentsArgs a;
+  a.state = args->state;
+  a.logp = args->logp;
+  a.sum = cm->sum;
+  a.sum_sq = cm->sum_sq;
+  a.sum_logp = cm->sum_logp;
+  a.count = (long long *)cm->count;
+  a.n_elems = args->n_chains * (long long)cm->temps * dim;
+  a.step = args->step0;
+  a.burn_in = args->burn_in;
+  a.every = cm->every;
+  a.device_step = (const long long *)args->device_step;
+  a.n_temps = args->n_temps;
+  a.dim = dim;
+  a.temps = cm->temps;
+  const long long grid = (a.n_elems + 255) / 256;
+  if (grid > 0x7fffffffll) return PTRWM_E_ARG;
+  hipLaunchKernelGGL(split_chain_moments_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 
 int32_t ptrwm_split_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm_moments_args *moments, void *stream) {

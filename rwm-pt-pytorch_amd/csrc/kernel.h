@@ -119,6 +119,10 @@ struct FullArgs {
   long long mom_steps;                // accumulated steps in this launch: count[t] += live ladders x mom_steps
   int mom_temps, mom_every;
   int steps_to_mom;                   // steps until the first step whose step_counter % mom_every == 0 (1 = the first step)
+  // 1: per-chain accumulators (include/ptrwm.h ptrwm_chain_moments_args): mom_sum / mom_sum_sq are [n_chains, mom_temps, dim],
+  // mom_sum_logp [n_chains, mom_temps]; the group's region has a row per (ladder of the group, temperature), is LOADED from
+  // them in the prologue and stored back with plain stores (one group owns each element); mom_count[t] += mom_steps
+  int mom_chain;
 };
 
 typedef const __attribute__((address_space(4))) FullArgs *kargs_full_ptr;
@@ -376,6 +380,9 @@ __device__ __forceinline__ void count_add(long long *p, long long v) {
 // of the log-density, as doubles, behind everything else the kernel keeps in its dynamic LDS.  One region per group:
 // narrow groups (one wave) never meet at a workgroup barrier, so they cannot share one.
 constexpr unsigned moments_region_doubles(int temps, int dim) { return (unsigned)(temps * (2 * dim + 1)); }
+// Rows of a region: pooled, one per covered temperature; per chain (FullArgs::mom_chain), one per (ladder of the exchange
+// group, covered temperature), row = ladder * temps + t - kernel and host (variants.h with_moments) size the region from here
+constexpr int moments_rows(bool per_chain, int ladders_per_group, int temps) { return per_chain ? ladders_per_group * temps : temps; }
 
 __device__ __forceinline__ void moments_zero(double *reg, int n, int tid, int nthr) {
   for (int i = tid; i < n; i += nthr) reg[i] = 0.0;
@@ -401,6 +408,26 @@ __device__ __forceinline__ void moments_flush(const double *reg, kargs_full_ptr 
   const long long add = live_ladders * f->mom_steps;
   if (count != nullptr)
     for (int i = tid; i < temps; i += nthr) count_add(&count[i], add);
+}
+
+// Per-chain accumulators: the region's live rows and the group's part of the global arrays are the same contiguous runs
+// (row0 = first chain of the group x temps; region: [rows x dim] sums, [rows x dim] sums of squares, [rows] log-densities).
+// LOAD: global -> region, in the prologue - each element then is the sequential fp64 sum over ALL steps so far, wherever
+// launches are cut; else region -> global, plain 8-byte stores: no other group touches these elements.
+template <bool LOAD>
+__device__ __forceinline__ void moments_chain_copy(double *reg, double *sum, double *sum_sq, double *sum_logp, int rows, int live_rows,
+                                                   int dim, long long row0, int tid, int nthr) {
+  const int n = live_rows * dim, rd = rows * dim;
+  double *const gs = sum + row0 * dim, *const gq = sum_sq + row0 * dim;
+  for (int i = tid; i < n; i += nthr) {
+    if (LOAD) reg[i] = gs[i], reg[rd + i] = gq[i];
+    else gs[i] = reg[i], gq[i] = reg[rd + i];
+  }
+  if (sum_logp != nullptr)
+    for (int i = tid; i < live_rows; i += nthr) {
+      if (LOAD) reg[2 * rd + i] = sum_logp[row0 + i];
+      else sum_logp[row0 + i] = reg[2 * rd + i];
+    }
 }
 
 template <bool EXACT>
@@ -616,8 +643,13 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       if (wide) reinterpret_cast<int *>(s_dyn)[L::vote(nthr)] = 0;  // no objection yet
       if constexpr (FULL) {
         if (a.full.mom_sum != nullptr) {  // (ordered before the first add by the barrier below)
-          const int n_mom = (int)moments_region_doubles(a.full.mom_temps, D0);
-          moments_zero(L::moments_region(s_dyn, wide, nthr, wave, n_mom), n_mom, tid, nthr);
+          const int mt = a.full.mom_temps, m_rows = moments_rows(a.full.mom_chain != 0, cpw, mt);
+          const int n_mom = (int)moments_region_doubles(m_rows, D0);
+          double *const reg = L::moments_region(s_dyn, wide, nthr, wave, n_mom);
+          if (a.full.mom_chain != 0)
+            moments_chain_copy<true>(reg, a.full.mom_sum, a.full.mom_sum_sq, a.full.mom_sum_logp, m_rows, (int)live_chains * mt, D0, chain0 * mt, tid, nthr);
+          else
+            moments_zero(reg, n_mom, tid, nthr);
         }
       }
     }
@@ -758,16 +790,17 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
         const bool mom_now = (to_mom == 0);
         if (mom_now) to_mom = a.full.mom_every;
         if (mom_now && count_on && live && t < a.full.mom_temps) {
-          const int mt = a.full.mom_temps;
-          double *const reg = L::moments_region(s_dyn, wide, wide ? ((T + 63) & ~63) : 64, wave, (int)moments_region_doubles(mt, D));
-          double *const rs = reg + t * D;
-          double *const rq = reg + (mt + t) * D;
+          const int mt = a.full.mom_temps, pc = a.full.mom_chain;
+          const int m_rows = moments_rows(pc != 0, cpw, mt), m_row = pc != 0 ? cw * mt + t : t;
+          double *const reg = L::moments_region(s_dyn, wide, wide ? ((T + 63) & ~63) : 64, wave, (int)moments_region_doubles(m_rows, D));
+          double *const rs = reg + m_row * D;
+          double *const rq = reg + (m_rows + m_row) * D;
           PTRWM_DIM_LOOP(d, DP, D, {
             const double v = (double)x[d];
             moments_add(rs + d, v);
             moments_add(rq + d, v * v);
           })
-          moments_add(reg + 2 * mt * D + t, (double)lp);
+          moments_add(reg + 2 * m_rows * D + m_row, (double)lp);
         }
       }
     }
@@ -949,9 +982,17 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     if constexpr (FULL) {
       // every add of the launch is behind the barrier above: the group's partial sums go to HBM, once
       const kargs_full_ptr fa = &ae->full;
-      if (fa->mom_sum != nullptr)
-        moments_flush(L::moments_region(s_dyn, wide2, nthr, wave, (int)moments_region_doubles(fa->mom_temps, D2)), fa, D2,
-                      live_chains, tid2, nthr);
+      if (fa->mom_sum != nullptr) {
+        const int mt = fa->mom_temps, m_rows = moments_rows(fa->mom_chain != 0, cpw2, mt);
+        double *const reg = L::moments_region(s_dyn, wide2, nthr, wave, (int)moments_region_doubles(m_rows, D2));
+        if (fa->mom_chain != 0) {
+          moments_chain_copy<false>(reg, fa->mom_sum, fa->mom_sum_sq, fa->mom_sum_logp, m_rows, (int)live_chains * mt, D2, c0 * mt, tid2, nthr);
+          if (c0 == 0 && fa->mom_count != nullptr)  // (the group of chain 0: steps per chain, once per launch)
+            for (int i = tid2; i < mt; i += nthr) count_add(&fa->mom_count[i], fa->mom_steps);
+        } else {
+          moments_flush(reg, fa, D2, live_chains, tid2, nthr);
+        }
+      }
     }
     if constexpr (STREAM) {
       // whole aligned vectors only (capi.hip): slab -> registers now, registers -> HBM in flush_pending

@@ -731,8 +731,13 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
     s_landed[kToObjection * nslots + slot_raw] = 0;  // the ladders' swap-form objections (wide groups: the vote of a swap event, below)
     if constexpr (FULL) {
       if (a.full.mom_sum != nullptr) {  // (ordered before the first add by the barrier below)
-        const int n_mom = (int)moments_region_doubles(a.full.mom_temps, D);
-        moments_zero(L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), n_mom), n_mom, tid, gthreads);
+        const int mt = a.full.mom_temps, m_rows = moments_rows(a.full.mom_chain != 0, cpw, mt);
+        const int n_mom = (int)moments_region_doubles(m_rows, D);
+        double *const reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), n_mom);
+        if (a.full.mom_chain != 0)  // (kernel.h: per-chain accumulators are loaded, not zeroed)
+          moments_chain_copy<true>(reg, a.full.mom_sum, a.full.mom_sum_sq, a.full.mom_sum_logp, m_rows, (int)live_chains * mt, D, chain0 * mt, tid, gthreads);
+        else
+          moments_zero(reg, n_mom, tid, gthreads);
       }
     }
     sync_group();
@@ -1020,10 +1025,11 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
         const bool mom_now = (to_mom == 0);
         if (mom_now) to_mom = a.full.mom_every;
         if (mom_now && count_on && live && t < a.full.mom_temps) {
-          const int mt = a.full.mom_temps;
-          double *const reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(mt, D));
-          double *const rs = reg + t * D + l.d0;
-          double *const rq = reg + (mt + t) * D + l.d0;
+          const int mt = a.full.mom_temps, pc = a.full.mom_chain;
+          const int m_rows = moments_rows(pc != 0, cpw, mt), m_row = pc != 0 ? cw * mt + t : t;
+          double *const reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(m_rows, D));
+          double *const rs = reg + m_row * D + l.d0;
+          double *const rq = reg + (m_rows + m_row) * D + l.d0;
 #pragma unroll
           for (int j = 0; j < W; ++j) {
             if (q_valid<MIN_OWN>(l, j)) {
@@ -1032,7 +1038,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
               moments_add(rq + j, v * v);
             }
           }
-          if (l.q == 0) moments_add(reg + 2 * mt * D + t, (double)lp);
+          if (l.q == 0) moments_add(reg + 2 * m_rows * D + m_row, (double)lp);
         }
       }
     }
@@ -1056,9 +1062,17 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
     if constexpr (FULL) {
       // every add of the launch is behind the barrier above: the group's partial sums go to HBM, once
       const kargs_full_ptr fa = &ae->full;
-      if (fa->mom_sum != nullptr)
-        moments_flush(L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(fa->mom_temps, D)),
-                      fa, D, live_chains, tid, gthreads);
+      if (fa->mom_sum != nullptr) {
+        const int mt = fa->mom_temps, m_rows = moments_rows(fa->mom_chain != 0, cpw, mt);
+        double *const reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(m_rows, D));
+        if (fa->mom_chain != 0) {
+          moments_chain_copy<false>(reg, fa->mom_sum, fa->mom_sum_sq, fa->mom_sum_logp, m_rows, (int)live_chains * mt, D, chain0 * mt, tid, gthreads);
+          if (chain0 == 0 && fa->mom_count != nullptr)  // (the group of chain 0: steps per chain, once per launch)
+            for (int i = tid; i < mt; i += gthreads) count_add(&fa->mom_count[i], fa->mom_steps);
+        } else {
+          moments_flush(reg, fa, D, live_chains, tid, gthreads);
+        }
+      }
     }
     stage_copy<false>(rows_f, gs, stage_total, tid, gthreads);
   }

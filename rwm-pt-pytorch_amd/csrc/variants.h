@@ -126,7 +126,8 @@ struct LaunchShape {
   unsigned block, lds, lds_moments;
 };
 inline LaunchShape with_moments(unsigned block, unsigned lds, bool wide, const KArgs &a) {
-  return {block, lds, lds + (wide ? 1u : block / 64u) * moments_region_doubles(a.full.mom_temps, a.dim) * 8u};
+  const int rows = moments_rows(a.full.mom_chain != 0, a.chains_per_wave, a.full.mom_temps);  // (per chain: a row per ladder of the group)
+  return {block, lds, lds + (wide ? 1u : block / 64u) * moments_region_doubles(rows, a.dim) * 8u};
 }
 // thread form.  Narrow ladders: four independent one-wave groups per workgroup; wide (n_temps > 64): the waves the ladder needs
 inline LaunchShape thread_launch_shape(const KArgs &a, int dp) {

@@ -127,6 +127,16 @@ class MCMCSimulation_GPU:
         self._require_run()
         return self.algorithm.posterior_variance(temperature)
 
+    def rhat(self, temperature: int = 0):
+        """Gelman-Rubin R-hat per coordinate over the sampler's chains (needs moments_per_chain=True, forwarded to it)."""
+        self._require_run()
+        return self.algorithm.rhat(temperature)
+
+    def ess(self, temperature: int = 0):
+        """Between-chain effective sample size per coordinate (needs moments_per_chain=True)."""
+        self._require_run()
+        return self.algorithm.ess(temperature)
+
     def pt_expected_squared_jump_distance(self):
         self._require_run()
         return self.algorithm.pt_esjd

@@ -132,6 +132,19 @@ class MomentsArgs(C.Structure):
     ]
 
 
+class ChainMomentsArgs(C.Structure):
+    """ptrwm_chain_moments_args: fp64 moment sums of every chain on its own (include/ptrwm.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("temps", C.c_int32),
+        ("every", C.c_int32),
+        ("sum", C.c_void_p),
+        ("sum_sq", C.c_void_p),
+        ("sum_logp", C.c_void_p),
+        ("count", C.c_void_p),
+    ]
+
+
 # every symbol include/ptrwm.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "ptrwm_abi_version": (C.c_int32, []),
@@ -155,6 +168,10 @@ SYMBOLS = {
         C.c_int32,
         [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.c_void_p]),
     "ptrwm_split_moments": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(MomentsArgs), C.c_void_p]),
+    "ptrwm_run_with_chain_moments": (
+        C.c_int32,
+        [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(ChainMomentsArgs), C.c_void_p]),
+    "ptrwm_split_chain_moments": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(ChainMomentsArgs), C.c_void_p]),
     "ptrwm_swap_sweep": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "ptrwm_split_propose": (
         C.c_int32, [C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -548,6 +565,7 @@ class RunPlan:
         self._last_trace = (None, None, None)  # (trace, trace_logp, trace_every) marshalled into _a by the last launch
         self._guard = on_device(self.device)  # (after the checks above: they reject CPU tensors first)
         self._mom = None  # (MomentsArgs, byref, tensors) of set_moments
+        self._cmom = None  # (ChainMomentsArgs, byref, tensors) of set_chain_moments
 
     def set_moments(self, sum: Optional[torch.Tensor], sum_sq: Optional[torch.Tensor] = None, *,
                     sum_logp: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
@@ -582,6 +600,54 @@ class RunPlan:
         m.sum_logp = _opt(sum_logp, "moments sum_logp", torch.float64)
         m.count = _opt(count, "moments count", torch.int64)
         self._mom = (m, C.byref(m), (sum, sum_sq, sum_logp, count))
+
+    def set_chain_moments(self, sum: Optional[torch.Tensor], sum_sq: Optional[torch.Tensor] = None, *,
+                          sum_logp: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                          every: int = 1) -> None:
+        """Accumulate the moments of every chain on its own (include/ptrwm.h ptrwm_chain_moments_args) in every following
+        ``launch`` and ``split_chain_moments``: ``sum`` / ``sum_sq`` [n_chains, temps, dim] float64, ``sum_logp``
+        [n_chains, temps] float64 and ``count`` [temps] int64 (both optional), all on the run's device and added to (+=).
+        A plan accumulates pooled moments or per-chain ones, not both: this switches ``set_moments`` off.
+        ``set_chain_moments(None)`` switches it off."""
+        if sum is None:
+            self._cmom = None
+            return
+        Cn, T, D = self.shape
+        if sum.dim() != 3 or sum.shape[0] != Cn or sum.shape[2] != D or not 1 <= sum.shape[1] <= T:
+            raise ValueError(f"chain moments sum must be [{Cn}, temps, {D}] with 1 <= temps <= {T}")
+        temps = sum.shape[1]
+        if sum_sq is None or tuple(sum_sq.shape) != (Cn, temps, D):
+            raise ValueError(f"chain moments sum_sq must be [{Cn}, {temps}, {D}]")
+        if sum_logp is not None and tuple(sum_logp.shape) != (Cn, temps):
+            raise ValueError(f"chain moments sum_logp must be [{Cn}, {temps}]")
+        if count is not None and tuple(count.shape) != (temps,):
+            raise ValueError(f"chain moments count must be [{temps}]")
+        if int(every) < 1:
+            raise ValueError("chain moments every must be >= 1")
+        for name, t in (("sum", sum), ("sum_sq", sum_sq), ("sum_logp", sum_logp), ("count", count)):
+            if t is not None and t.device != self.device:
+                raise ValueError(f"chain moments {name} is on {t.device}, state on {self.device}")
+        m = ChainMomentsArgs()
+        m.struct_size = C.sizeof(ChainMomentsArgs)
+        m.temps = temps
+        m.every = int(every)
+        m.sum = _require_device(sum, "chain moments sum", torch.float64)
+        m.sum_sq = _require_device(sum_sq, "chain moments sum_sq", torch.float64)
+        m.sum_logp = _opt(sum_logp, "chain moments sum_logp", torch.float64)
+        m.count = _opt(count, "chain moments count", torch.int64)
+        self._cmom = (m, C.byref(m), (sum, sum_sq, sum_logp, count))
+        self._mom = None
+
+    def split_chain_moments(self, step: int) -> None:
+        """Per-chain moments of the split step ``step`` just performed (ptrwm_split_chain_moments; device-step mode:
+        counter + step).  Enqueue after ``split_accept``.  No-op without ``set_chain_moments``."""
+        if self._cmom is None:
+            return
+        self._a.step0 = step
+        with self._guard:
+            rc = self._lib.ptrwm_split_chain_moments(self._refs[4], self.shape[2], self._cmom[1], _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_split_chain_moments")
 
     def split_moments(self, step: int) -> None:
         """Moments of the split step ``step`` just performed (ptrwm_split_moments; device-step mode: counter + step).
@@ -659,14 +725,18 @@ class RunPlan:
             self._plain = plain
             if trace is not None and ext_prop is None and ext_u is None and ext_swap_u is None and accept_flags is None:
                 self._last_trace = (trace, trace_logp, trace_every)
-        if self._mom is None:
+        if self._cmom is not None:
+            with self._guard:
+                rc = self._lib.ptrwm_run_with_chain_moments(self._refs[2], self._refs[3], self._refs[4], self._cmom[1], _stream(self.device))
+        elif self._mom is None:
             with self._guard:
                 rc = self._lib.ptrwm_run(self._refs[2], self._refs[3], self._refs[4], _stream(self.device))
         else:
             with self._guard:
                 rc = self._lib.ptrwm_run_with_moments(self._refs[2], self._refs[3], self._refs[4], self._mom[1], _stream(self.device))
         if rc != 0:
-            raise PTRWMError(rc, "ptrwm_run_with_moments" if self._mom is not None else "ptrwm_run")
+            raise PTRWMError(rc, "ptrwm_run_with_chain_moments" if self._cmom is not None else
+                             ("ptrwm_run_with_moments" if self._mom is not None else "ptrwm_run"))
 
     def _split_buffers(self):
         if getattr(self, "_split", None) is None:

@@ -1,9 +1,11 @@
 """Cost of the posterior-moments accumulator at the headline shape (65 536 ladders x 32 temperatures, folded RoughCarpet
-dim 30, Normal proposal, swaps every 10, 2 000 steps per launch): chain-steps/s of four runs of the same sampler -
+dim 30, Normal proposal, swaps every 10, 2 000 steps per launch): chain-steps/s of six runs of the same sampler -
   none        plain ptrwm_run (the production kernel)
   cold_trace  a cold trace of replica 0 at trace_every = 10 (the fixture / trace twin without moments)
   mom_cold    moments of the cold chain, every = 10 (ptrwm_run_with_moments, temps = 1)
   mom_all     moments of every temperature, every = 10 (temps = 32)
+  cmom_cold   per-chain moments of the cold chain, every = 10 (ptrwm_run_with_chain_moments, temps = 1)
+  cmom_all    per-chain moments of every temperature, every = 10 (temps = 32)
 Each: `--warmup` launches, then `--steps` launches timed with HIP events; one JSON line per run.  `--pkg DIR` imports
 ptrwm_hip from another tree (a build of an earlier commit: the runs it lacks are skipped), for before / after numbers."""
 import argparse
@@ -24,7 +26,7 @@ def main():
     ap.add_argument("--temps", type=int, default=32)
     ap.add_argument("--dim", type=int, default=30)
     ap.add_argument("--every", type=int, default=10)
-    ap.add_argument("--runs", default="none,cold_trace,mom_cold,mom_all")
+    ap.add_argument("--runs", default="none,cold_trace,mom_cold,mom_all,cmom_cold,cmom_all")
     args = ap.parse_args()
     sys.path.insert(0, args.pkg)
     import numpy as np
@@ -62,6 +64,14 @@ def main():
             sums = [torch.zeros(mt, D, device=dev, dtype=torch.float64) for _ in range(2)]
             plan.set_moments(sums[0], sums[1], sum_logp=torch.zeros(mt, device=dev, dtype=torch.float64),
                              count=torch.zeros(mt, device=dev, dtype=torch.int64), every=args.every)
+        elif run.startswith("cmom_"):
+            if not hasattr(plan, "set_chain_moments"):
+                print(json.dumps({"run": run, "skipped": "no per-chain moments in this build"}), flush=True)
+                continue
+            mt = 1 if run == "cmom_cold" else T
+            sums = [torch.zeros(Cn, mt, D, device=dev, dtype=torch.float64) for _ in range(2)]
+            plan.set_chain_moments(sums[0], sums[1], sum_logp=torch.zeros(Cn, mt, device=dev, dtype=torch.float64),
+                                   count=torch.zeros(mt, device=dev, dtype=torch.int64), every=args.every)
         elif run != "none":
             raise SystemExit(f"unknown run {run}")
         step, row, ms = 0, 0, []
