@@ -421,6 +421,47 @@ int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *propo
  * device-step mode. */
 int32_t ptrwm_split_advance(const ptrwm_run_args *args, void *stream);
 
+/* ---- starting points: over-dispersed starts for multi-chain runs ----------------------------------------------------
+ * Writes rows of `state` before step 0: each coordinate drawn uniformly from the box [lo[d], hi[d]], or copied from
+ * `fallback`.  R-hat over many chains (ptrwm_chain_moments_args) says something about mixing between modes only when the
+ * chains start over-dispersed; the draw lives here, keyed like every other random of a run by `seed` and the GLOBAL chain id
+ * chain_offset + c, so the starts - and with them the whole run - do not depend on how chains are sharded over devices.
+ *
+ * The draw.  For row (c, t) and coordinate d, with g = chain_offset + c and tt = per_temperature ? t : 0: one
+ * Philox4x32-10 block per four coordinates,
+ *   counter  c0 = (d / 4) | attempt << 16
+ *            c1 = 0
+ *            c2 = low 32 bits of g
+ *            c3 = tt | 3 << 8 | (g >> 32) << 12
+ *   key      (seed low, seed high)
+ * - stream 3 of the layout ptrwm_run uses (0: Metropolis moves, 1: swaps, 2: stand-alone sweeps) - and
+ *   u = (word d % 4 of the block >> 8) * 2^-24                    in [0, 1): the lattice of torch.rand(float32)
+ *   x = lo[d] + (hi[d] - lo[d]) * u                                in float, every operation rounded on its own (no fma)
+ * With state_f64 the stored value is that float, widened.  (x <= hi[d] up to the rounding of hi - lo and of the sum: a bound
+ * that is not a short binary fraction can be exceeded by one unit in the last place.)
+ *
+ * Redraw.  attempt = 0 writes every row.  attempt = a > 0 rewrites ONLY the rows whose args->logp[c, t] is not finite (NaN,
+ * +inf or -inf) - starts outside the support of the target - drawing with attempt number a; every other row keeps its
+ * bits.  The caller evaluates the density between attempts; a last call with `fallback` puts the rows still outside on
+ * a point known to be inside.
+ *
+ * Reads from `args`: n_temps, n_chains, chain_offset, state, seed, state_f64, and logp when attempt > 0.  Enqueues one small
+ * kernel (one wavefront per 64 rows); neither allocates nor synchronises.
+ * Checked, in this order, before anything is enqueued: PTRWM_E_NULL for a NULL args / init; PTRWM_E_STRUCT for a wrong
+ * struct_size of either; PTRWM_E_DIM / PTRWM_E_TEMPS as everywhere; PTRWM_E_ARG for attempt outside 0..65535,
+ * per_temperature or state_f64 outside 0..1 or a negative n_chains; an empty batch (n_chains = 0) returns PTRWM_OK; then
+ * PTRWM_E_NULL for a NULL state, lo or hi, and for a NULL logp with attempt > 0. */
+typedef struct ptrwm_init_args {
+  uint32_t struct_size;     /* sizeof(ptrwm_init_args) */
+  int32_t per_temperature;  /* 0: the temperatures of a ladder share the chain's draw; 1: every (chain, t) draws its own */
+  int32_t attempt;          /* 0: write every row.  a > 0: rewrite ONLY rows whose args->logp[c,t] is not finite
+                               (NaN, +inf or -inf), drawing with attempt number a; 0 <= attempt < 65536 */
+  const float *lo, *hi;     /* device [dim]: the box */
+  const float *fallback;    /* device [dim] or NULL.  Non-NULL: the rows this call writes get fallback[d] instead
+                               of a draw (used with attempt > 0 as the last resort) */
+} ptrwm_init_args;
+int32_t ptrwm_init_states(const ptrwm_run_args *args, int32_t dim, const ptrwm_init_args *init, void *stream);
+
 /* out[i] = log_density(x[i, :]) for i < n; x is device [n, dim], out device [n]. */
 int32_t ptrwm_logdensity(const ptrwm_target_desc *target, const float *x, float *out, int64_t n,
                          void *stream);

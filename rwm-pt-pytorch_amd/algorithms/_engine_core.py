@@ -51,12 +51,86 @@ def draw_seed() -> int:
     return int(torch.randint(0, 2**62, (1,)).item())
 
 
+# ---- starting points ------------------------------------------------------------------------------------------
+def start_shape(initial_state, dim: int, n_replicas: int, n_temps: int) -> int:
+    """Number of axes of a start: 1 for one point [dim] shared by every row, 2 for [n_replicas, dim] (the temperatures of a
+    ladder share their replica's row), 3 for [n_replicas, n_temps, dim].  NumPy array, sequence or torch tensor on any
+    device; ValueError for any other shape.  Host-only."""
+    shape = tuple(initial_state.shape) if torch.is_tensor(initial_state) else np.asarray(initial_state).shape
+    for want in ((dim,), (n_replicas, dim), (n_replicas, n_temps, dim)):
+        if shape == want:
+            return len(want)
+    raise ValueError(f"starting states must have shape [{dim}], [{n_replicas}, {dim}] or [{n_replicas}, {n_temps}, {dim}] "
+                     f"(dim / replicas, dim / replicas, temperatures, dim), got {list(shape)}")
+
+
+def check_init_box(init_box, dim: int) -> Optional[tuple]:
+    """`init_box` = (lo, hi), each bound a scalar or a [dim] vector, as two float32 [dim] arrays; None stays None.
+    ValueError unless both are finite and lo <= hi element-wise.  Host-only."""
+    if init_box is None:
+        return None
+    try:
+        lo, hi = init_box
+    except (TypeError, ValueError):
+        raise ValueError("init_box must be a pair (lo, hi)") from None
+    out = []
+    for name, b in (("lo", lo), ("hi", hi)):
+        b = np.asarray(b.detach().cpu() if torch.is_tensor(b) else b, dtype=np.float64)
+        if b.shape not in ((), (dim,)):
+            raise ValueError(f"init_box: {name} must be a scalar or a [{dim}] vector, got shape {list(b.shape)}")
+        if not np.all(np.isfinite(b)):
+            raise ValueError(f"init_box: {name} must be finite")
+        out.append(np.ascontiguousarray(np.broadcast_to(b, (dim,)).astype(np.float32)))
+    if not np.all(out[0] <= out[1]):
+        raise ValueError("init_box: lo <= hi must hold in every coordinate")
+    return out[0], out[1]
+
+
+def check_init_attempts(init_attempts) -> int:
+    if isinstance(init_attempts, bool) or not isinstance(init_attempts, (int, np.integer)) or not 1 <= init_attempts <= 65535:
+        raise ValueError(f"init_attempts must be an integer in 1..65535, got {init_attempts!r}")
+    return int(init_attempts)
+
+
+def check_class_starts(dim: int, n_replicas: int, n_temps: int, initial_states, init_box, init_attempts,
+                       init_per_temperature: bool = False) -> tuple:
+    """The constructor checks the sampler classes share (no GPU needed): returns (mode, states, box) with mode "point" /
+    "states" / "box", `states` a private copy of `initial_states` (the caller may go on changing the original - e.g. the
+    live `current_states` of an earlier sampler) and `box` the float32 bounds."""
+    check_init_attempts(init_attempts)
+    box = check_init_box(init_box, dim)
+    if initial_states is not None and box is not None:
+        raise ValueError("initial_states and init_box exclude each other: the starts are given, or drawn from the box")
+    if init_per_temperature and box is None:
+        raise ValueError("init_per_temperature=True needs init_box (it chooses how the box is drawn from)")
+    if initial_states is not None:
+        if not torch.is_tensor(initial_states):
+            initial_states = np.array(initial_states)
+        start_shape(initial_states, dim, n_replicas, n_temps)
+        states = initial_states.detach().clone() if torch.is_tensor(initial_states) else initial_states
+        return "states", states, None
+    return ("box" if box is not None else "point"), None, box
+
+
 class EngineRun:
+    """`initial_state`: one point [dim] for every replica and temperature, or [n_replicas, dim] (the temperatures of a ladder
+    share their replica's row), or [n_replicas, n_temps, dim] - a NumPy array or a torch tensor on any device (a device tensor
+    is copied on the device); the log-densities are evaluated from the states either way.
+
+    `init_box` = (lo, hi), each a scalar or a [dim] vector: over-dispersed starts drawn by the library (include/ptrwm.h
+    ptrwm_init_states: Philox stream 3, keyed by seed and global replica id, so a sharded run starts exactly where the
+    unsharded one does).  Attempt 0 draws every row; attempts 1 .. init_attempts - 1 redraw the rows whose log-density is not
+    finite (starts outside the target's support); what is still outside after that is put on `initial_state` (the one point).
+    Then ONE host synchronisation - at construction, never in the step loop - checks that every log-density is finite and
+    raises ValueError otherwise.  `init_per_temperature`: every temperature of a ladder draws its own point instead of sharing
+    the ladder's."""
+
     def __init__(self, *, target_dist, proposal: "ptrwm_hip.Proposal", beta_ladder: Sequence[float], dim: int,
                  device: torch.device, n_replicas: int, initial_state: np.ndarray, burn_in: int, swap_every: int,
                  swap_mode: str, swap_order: str, seed: Optional[int], chain_offset: int = 0,
                  dtype: torch.dtype = torch.float32, moments_temps: int = 0, moments_every: int = 1,
-                 moments_per_chain: bool = False):
+                 moments_per_chain: bool = False, init_box=None, init_per_temperature: bool = False,
+                 init_attempts: int = 8):
         if swap_mode not in ptrwm_hip.SWAP_MODES:
             raise ValueError(f"swap_mode must be one of {sorted(ptrwm_hip.SWAP_MODES)}, got {swap_mode!r}")
         if swap_order not in ptrwm_hip.SWAP_ORDERS:
@@ -69,6 +143,13 @@ class EngineRun:
                              f"temperatures, got {n_temps}")
         if not 1 <= dim <= ptrwm_hip.MAX_DIM:
             raise ValueError(f"dim must be in 1..{ptrwm_hip.MAX_DIM} for the fused kernel, got {dim}")
+        # the starts (host-side checks, before the device is asked for: bad arguments fail the same way without a GPU)
+        axes = start_shape(initial_state, dim, n_replicas, n_temps)
+        box = check_init_box(init_box, dim)
+        attempts = check_init_attempts(init_attempts)
+        if box is not None and axes != 1:
+            raise ValueError("init_box draws the starts: initial_state must then be the one point [dim] that rows still "
+                             "outside the target's support fall back to, not per-replica states")
         if device.type != "cuda":
             raise RuntimeError(
                 "The PT-RWM engine runs only on a ROCm GPU (device='cuda'); there is no CPU fallback. "
@@ -111,11 +192,24 @@ class EngineRun:
             raise NotImplementedError("dtype=torch.float64 needs a target with a fused kernel (split steps carry float32 "
                                       "states)")
         self.dtype = dtype  # float64: the engine's state_f64 mode (the reference's dtype=torch.float64)
-        x0 = torch.as_tensor(np.asarray(initial_state), dtype=dtype).to(device)
-        # every temperature (and replica) starts from the same point (pt_rwm_gpu_optimized.py:478-484)
-        self.state = x0.expand(n_replicas, n_temps, dim).contiguous()
-        # (log-densities are float32 in either mode: the density kernels evaluate the state rounded to float)
-        self.logp = self._density(self.state.view(-1, dim).to(torch.float32)).view(n_replicas, n_temps).contiguous()
+        self.init_mode = "box" if box is not None else ("point" if axes == 1 else "states")
+        if torch.is_tensor(initial_state):
+            x0 = initial_state.detach().to(device=device, dtype=dtype)  # (a device tensor never visits the host)
+        else:
+            x0 = torch.as_tensor(np.asarray(initial_state), dtype=dtype).to(device)
+        if box is not None:
+            self.state = torch.empty(n_replicas, n_temps, dim, device=device, dtype=dtype)
+            self.logp = torch.empty(n_replicas, n_temps, device=device, dtype=torch.float32)
+        else:
+            if axes == 1:
+                # every temperature (and replica) starts from the same point (pt_rwm_gpu_optimized.py:478-484)
+                self.state = x0.expand(n_replicas, n_temps, dim).contiguous()
+            else:
+                # a copy of its own: the caller's tensor (the live states of an earlier run, say) is never stepped in place
+                self.state = torch.empty(n_replicas, n_temps, dim, device=device, dtype=dtype)
+                self.state.copy_(x0[:, None, :] if axes == 2 else x0)
+            # (log-densities are float32 in either mode: the density kernels evaluate the state rounded to float)
+            self.logp = self._density(self.state.view(-1, dim).to(torch.float32)).view(n_replicas, n_temps).contiguous()
         shape = (n_replicas, n_temps)
         self.n_accept = torch.zeros(shape, device=device, dtype=torch.int64)
         self.sq_jump = torch.zeros(shape, device=device, dtype=torch.float64)
@@ -154,6 +248,30 @@ class EngineRun:
             self.mom_count = torch.zeros(mt, device=device, dtype=torch.int64)
             self._plan.set_moments(self.mom_sum, self.mom_sum_sq, sum_logp=self.mom_sum_logp, count=self.mom_count,
                                    every=self.moments_every)
+        if box is not None:
+            self._draw_starts(box, x0.to(torch.float32).contiguous(), bool(init_per_temperature), attempts)
+
+    def _draw_starts(self, box: tuple, point: torch.Tensor, per_temperature: bool, attempts: int) -> None:
+        """Starts from the box (class docstring): attempt 0 for every row, a redraw per further attempt for the rows the
+        density rejects, `point` for what is left - all enqueued; then the one synchronising check."""
+        lo, hi = (torch.from_numpy(b).to(self.device) for b in box)
+
+        def evaluate():
+            rows = self.state.view(-1, self.dim).to(torch.float32)
+            self.logp.copy_(self._density(rows).view(self.n_replicas, self.n_temps))
+
+        self._plan.init_states(lo, hi, attempt=0, per_temperature=per_temperature)
+        evaluate()
+        for a in range(1, attempts):
+            self._plan.init_states(lo, hi, attempt=a, per_temperature=per_temperature)
+            evaluate()
+        self._plan.init_states(lo, hi, attempt=attempts, per_temperature=per_temperature, fallback=point)
+        evaluate()
+        bad = int((~torch.isfinite(self.logp)).sum().item())
+        if bad:
+            raise ValueError(f"{bad} of {self.logp.numel()} starting rows have no finite log-density after {attempts} "
+                             "draw(s) from init_box and the fallback to initial_state: neither the box nor the point "
+                             "lies in the target's support")
 
     def _density(self, rows: torch.Tensor) -> torch.Tensor:
         """log-density of every row [n, dim] -> float32 [n] on the device."""

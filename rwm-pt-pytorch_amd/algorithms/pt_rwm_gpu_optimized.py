@@ -30,7 +30,7 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import EngineRun, PosteriorMoments, moments_temps, resolve_device
+from ._engine_core import EngineRun, PosteriorMoments, check_class_starts, moments_temps, resolve_device
 
 
 def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
@@ -55,7 +55,8 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
                  num_replicas: int = 1, proposal_distribution: Optional[ProposalDistribution] = None,
                  swap_mode: str = "exchange", swap_order: str = "sequential", seed: Optional[int] = None,
                  chain_offset: int = 0, trace: str = "all", thin: int = 1, moments: Optional[str] = None,
-                 moments_every: int = 1, moments_per_chain: bool = False):
+                 moments_every: int = 1, moments_per_chain: bool = False, initial_states=None, init_box=None,
+                 init_per_temperature: bool = False, init_attempts: int = 8):
         super().__init__(dim, var, target_dist, symmetric)
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         self._moments_mode, self._moments_every = moments, int(moments_every)
@@ -120,6 +121,18 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
                                  else f"{self.num_chains} temperatures") + "; states are kept in float32")
                 self.dtype = torch.float32
         self.num_replicas = int(num_replicas)
+        # where the ladders start (EngineRun's docstring): by default every replica and temperature from the reference's one
+        # point; `initial_states` [num_replicas, dim] (a ladder's temperatures share the row) or [num_replicas, T, dim] gives
+        # them their own - one ladder also as [T, dim], the shape of its `current_states`, so that a warm restart reads
+        # initial_states=previous.current_states; `init_box` = (lo, hi) draws over-dispersed starts in the library (per ladder,
+        # or per temperature with `init_per_temperature`), redrawing up to `init_attempts` times what falls outside the support
+        if initial_states is not None and not torch.is_tensor(initial_states):
+            initial_states = np.asarray(initial_states)
+        if initial_states is not None and self.num_replicas == 1 and tuple(initial_states.shape) == (self.num_chains, dim):
+            initial_states = initial_states[None]
+        self._init_mode, self._initial_states, self._init_box = check_class_starts(
+            dim, self.num_replicas, self.num_chains, initial_states, init_box, init_attempts, init_per_temperature)
+        self._init_attempts, self._init_per_temperature = int(init_attempts), bool(init_per_temperature)
         self.beta_tensor = torch.tensor(self.beta_ladder, device=self.device, dtype=torch.float32)
 
         if proposal_distribution is None:
@@ -228,7 +241,9 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
         self._run = EngineRun(
             target_dist=self.target_dist, proposal=self.proposal_dist.engine_proposal(self.beta_ladder),
             beta_ladder=self.beta_ladder, dim=self.dim, device=self.device, n_replicas=self.num_replicas,
-            initial_state=self._initial_state, burn_in=self.burn_in, swap_every=self.swap_every,
+            initial_state=self._initial_state if self._initial_states is None else self._initial_states,
+            init_box=self._init_box, init_per_temperature=self._init_per_temperature, init_attempts=self._init_attempts,
+            burn_in=self.burn_in, swap_every=self.swap_every,
             swap_mode=self._swap_mode, swap_order=self._swap_order, seed=self._seed, chain_offset=self._chain_offset,
             dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain)
@@ -408,6 +423,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             "algorithm": self.name,
             "num_chains": self.num_chains,
             "num_replicas": self.num_replicas,
+            "init": self._init_mode,
             "beta_ladder": self.beta_ladder,
             "swap_every": self.swap_every,
             "swap_mode": self._swap_mode,

@@ -22,7 +22,7 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import EngineRun, PosteriorMoments, moments_temps, resolve_device
+from ._engine_core import EngineRun, PosteriorMoments, check_class_starts, moments_temps, resolve_device
 
 
 def ultra_fused_mcmc_step_basic(current_state, current_log_density, increment, random_val, beta, log_density_proposed):
@@ -57,8 +57,17 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
                  burn_in: int = 0, device: str = None, pre_allocate_steps: int = None, use_efficient_rng: bool = True,
                  compile_mode: str = None, proposal_distribution: ProposalDistribution = None, *,
                  num_chains: int = 1, seed: Optional[int] = None, chain_offset: int = 0, thin: int = 1,
-                 moments: Optional[str] = None, moments_every: int = 1, moments_per_chain: bool = False):
+                 moments: Optional[str] = None, moments_every: int = 1, moments_per_chain: bool = False,
+                 initial_states=None, init_box=None, init_attempts: int = 8):
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
+        # where the chains start (EngineRun's docstring): by default all from the reference's one point; `initial_states`
+        # [num_chains, dim] (or [dim] / [num_chains, 1, dim]) gives every chain its own - a warm restart is
+        # initial_states=previous.current_states; `init_box` = (lo, hi) draws over-dispersed starts in the library, redrawing
+        # up to `init_attempts` times what falls outside the target's support
+        self._init_mode, self._initial_states, self._init_box = check_class_starts(
+            dim, int(num_chains), 1, initial_states, init_box, init_attempts)
+        self._init_attempts = int(init_attempts)
+        self._start_point = None
         self._moments_mode, self._moments_every = moments, int(moments_every)
         if moments_per_chain and moments is None:
             raise ValueError("moments_per_chain=True needs moments='cold' or 'all'")
@@ -112,6 +121,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             self.chain_index = None
         self._run: Optional[EngineRun] = None
         self.current_state = None
+        self.current_states = None  # every chain's current point, [num_chains, dim] (a live view once the run has started)
         self.log_target_density_current = None
 
     # counters live on the device; reading them synchronises
@@ -142,6 +152,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
         self._run = None
         self.total_steps = 0
         self.current_state = None
+        self.current_states = None
         self.log_target_density_current = None
         if self.pre_allocated_chain is not None:
             self.chain_index = 0
@@ -150,15 +161,25 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
     def _ensure_started(self):
         if self._run is not None:
             return
+        if self._init_mode == "point":
+            self._start_point = self.chain[-1]
+        elif self._start_point is None:
+            # kept across reset() - chain[0] becomes chain 0's drawn start below: a new run falls back to the same point
+            self._start_point = self.chain[-1]
         self._run = EngineRun(
             target_dist=self.target_dist, proposal=self.proposal_dist.engine_proposal(), beta_ladder=[self.beta],
-            dim=self.dim, device=self.device, n_replicas=self.num_chains, initial_state=self.chain[-1],
+            dim=self.dim, device=self.device, n_replicas=self.num_chains,
+            initial_state=self._start_point if self._initial_states is None else self._initial_states,
             burn_in=self.burn_in, swap_every=1, swap_mode="exchange", swap_order="sequential", seed=self._seed,
             chain_offset=self._chain_offset, moments_temps=moments_temps(self._moments_mode, 1, self._moments_every),
-            moments_every=self._moments_every, moments_per_chain=self._moments_per_chain,
+            moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, init_box=self._init_box,
+            init_attempts=self._init_attempts,
         )
         self.current_state = self._run.state[0, 0]  # views: always the live values
+        self.current_states = self._run.state[:, 0]
         self.log_target_density_current = self._run.logp[0, 0]
+        if self._init_mode != "point":
+            self.chain[-1] = self.current_state.cpu().numpy()  # the stored chain opens with chain 0's actual start
         if self.pre_allocated_chain is not None and self.chain_index == 0:
             self.pre_allocated_chain[0] = self.current_state
             self.pre_allocated_log_densities[0] = self.log_target_density_current
@@ -237,6 +258,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             "total_steps": self.total_steps,
             "acceptance_rate": self.acceptance_rate,
             "num_chains": self.num_chains,
+            "init": self._init_mode,
             "kernel_fusion": "Philox + proposal + log-density + accept + update + statistics in one HIP kernel",
             "memory_allocated_mb": torch.cuda.memory_allocated() / 1e6 if self.device.type == "cuda" else 0,
             "memory_efficiency": "state in registers for the whole launch; HBM touched at launch start/end",

@@ -686,6 +686,79 @@ __global__ void __launch_bounds__(256) split_chain_moments_kernel(SplitChainMome
   if (i < a.temps && a.count != nullptr) a.count[i] += 1;
 }
 
+// Starting points (ptrwm_init_states): row (c, t) of `state` drawn uniformly from the box [lo, hi], or set to `fallback`.
+// The draw is Philox stream kStreamInit (philox.h: the counter layout; include/ptrwm.h restates it), keyed by the GLOBAL chain
+// id like every other random of a run, so the starts do not depend on how chains are sharded over devices.
+struct InitStatesArgs {
+  void *state;                             // float (or double, F64) [n_reps, dim]
+  const float *logp, *lo, *hi, *fallback;  // logp: read when attempt > 0 only; fallback: NULL = draw
+  long long n_reps, chain_offset;
+  int n_temps, dim, per_temperature, attempt;
+  unsigned k0, k1;
+};
+
+// One wavefront per tile of 64 rows (64-thread workgroups), as the split-step kernels: every lane builds its own row in a
+// slab of LDS and the tile's run of 64 x dim floats leaves through stage_copy (coalesced 16-byte stores whatever the run's
+// alignment); double states are written element by element, consecutive lanes to consecutive doubles.
+// attempt > 0 rewrites only the rows whose log-density is not finite: a tile without one exits before it touches `state`;
+// a float tile with some stages itself in first, so that the rows it keeps go back bit for bit; a double tile stores
+// the rewritten rows only.
+template <bool F64>
+__global__ void __launch_bounds__(64) init_states_kernel(InitStatesArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float s_init[];
+  const int lane = (int)threadIdx.x;
+  const long long first = (long long)blockIdx.x * 64;
+  if (first >= a.n_reps) return;
+  const int D = a.dim;
+  const int n_rows = (a.n_reps - first < 64) ? (int)(a.n_reps - first) : 64;
+  const bool live = lane < n_rows;
+  const long long i = first + (live ? lane : 0);
+  bool mine = live;
+  if (a.attempt > 0) mine = live && (__float_as_uint(a.logp[i]) & 0x7f800000u) == 0x7f800000u;  // NaN, +inf or -inf
+  const unsigned long long todo = __ballot(mine);
+  if (todo == 0ull) return;  // (wave-uniform)
+  const unsigned long long all = n_rows == 64 ? ~0ull : (1ull << n_rows) - 1ull;
+  float *__restrict__ gf = reinterpret_cast<float *>(a.state) + first * D;  // (float states)
+  const int head = F64 ? 0 : stage_head(gf);
+  if (!F64 && todo != all) {
+    stage_copy<true>(s_init, gf, n_rows * D, lane, 64);
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (mine) {
+    float *__restrict__ row = s_init + head + lane * D;
+    if (a.fallback != nullptr) {
+      const const_float_ptr fb = uniform_vec(a.fallback);
+      for (int d = 0; d < D; ++d) row[d] = fb[d];
+    } else {
+      const const_float_ptr lo = uniform_vec(a.lo), hi = uniform_vec(a.hi);
+      const long long chain = i / a.n_temps;
+      const uint32_t t = a.per_temperature ? (uint32_t)(i - chain * a.n_temps) : 0u;
+      const unsigned long long g = (unsigned long long)(a.chain_offset + chain);
+      const uint32_t c2 = (uint32_t)g, c3 = t | (kStreamInit << 8) | ((uint32_t)(g >> 32) << 12);
+      for (int b = 0; 4 * b < D; ++b) {
+        const u32x4 r = philox4x32_10((uint32_t)b | ((uint32_t)a.attempt << 16), 0u, c2, c3, a.k0, a.k1);
+        const uint32_t w[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int d = 4 * b + k;
+          if (d < D) row[d] = add_rn(lo[d], mul_rn(sub_rn(hi[d], lo[d]), u01(w[k])));
+        }
+      }
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  if (!F64) {
+    stage_copy<false>(s_init, gf, n_rows * D, lane, 64);
+  } else {
+    double *__restrict__ gd = reinterpret_cast<double *>(a.state) + first * D;
+    const int total = n_rows * D;
+    for (int e = lane; e < total; e += 64)
+      if ((todo >> (e / D)) & 1ull) gd[e] = (double)s_init[e];
+  }
+}
+
 }  // namespace ptrwm
 
 using namespace ptrwm;
@@ -1237,6 +1310,41 @@ int32_t ptrwm_split_advance(const ptrwm_run_args *args, void *stream) {
   if (args->device_step == nullptr) return PTRWM_E_NULL;
   hipLaunchKernelGGL(split_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (long long *)args->device_step,
                      args->n_steps > 0 ? (long long)args->n_steps : 1ll);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}
+
+int32_t ptrwm_init_states(const ptrwm_run_args *args, int32_t dim, const ptrwm_init_args *init, void *stream) {
+  if (args == nullptr || init == nullptr) return PTRWM_E_NULL;
+  if (args->struct_size != sizeof(ptrwm_run_args) || init->struct_size != sizeof(ptrwm_init_args)) return PTRWM_E_STRUCT;
+  if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
+  if (args->n_temps < 1 || args->n_temps > PTRWM_MAX_TEMPS) return PTRWM_E_TEMPS;
+  if (args->n_chains < 0 || args->n_chains > 0x7fffffffll || (args->state_f64 != 0 && args->state_f64 != 1) ||
+      init->attempt < 0 || init->attempt > 65535 || (init->per_temperature != 0 && init->per_temperature != 1))
+    return PTRWM_E_ARG;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->state == nullptr || init->lo == nullptr || init->hi == nullptr || (init->attempt > 0 && args->logp == nullptr))
+    return PTRWM_E_NULL;
+  InitStatesArgs a;
+  a.state = args->state;
+  a.logp = args->logp;
+  a.lo = init->lo;
+  a.hi = init->hi;
+  a.fallback = init->fallback;
+  a.n_reps = args->n_chains * (long long)args->n_temps;
+  a.chain_offset = args->chain_offset;
+  a.n_temps = args->n_temps;
+  a.dim = dim;
+  a.per_temperature = init->per_temperature;
+  a.attempt = init->attempt;
+  a.k0 = (unsigned)(args->seed & 0xffffffffull);
+  a.k1 = (unsigned)(args->seed >> 32);
+  const long long grid = (a.n_reps + 63) / 64;  // one wavefront per tile of 64 rows
+  if (grid > 0x7fffffffll) return PTRWM_E_ARG;
+  const unsigned lds = split_tile_lds_bytes(dim);  // (at most 26 640 bytes: within the default dynamic-LDS allowance)
+  if (args->state_f64)
+    hipLaunchKernelGGL(init_states_kernel<true>, dim3((unsigned)grid), dim3(64), lds, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(init_states_kernel<false>, dim3((unsigned)grid), dim3(64), lds, (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 

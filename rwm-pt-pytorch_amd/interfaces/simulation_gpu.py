@@ -5,6 +5,9 @@ Drop-in for the non-plotting half of the reference's `MCMCSimulation_GPU`
 instantiates the sampler (dispatching on the 'GPU' / 'ParallelTempering' substrings of the class
 name, :81-83), seeds torch/numpy AFTER construction (:144-148), runs `generate_samples` and exposes
 acceptance rate / ESJD / PT-ESJD.  Plotting (traceplot, histograms, benchmark sweeps) is out of scope.
+
+`**kwargs` go to the sampler as they are: among them its starting points, `initial_states=` (given per chain / replica)
+or `init_box=(lo, hi)` with `init_attempts=` and, for the PT class, `init_per_temperature=` (drawn by the library).
 """
 import time
 from typing import Optional

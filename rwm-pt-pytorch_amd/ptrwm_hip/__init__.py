@@ -145,6 +145,18 @@ class ChainMomentsArgs(C.Structure):
     ]
 
 
+class InitArgs(C.Structure):
+    """ptrwm_init_args: starting points drawn from a box, or set to a fallback point (include/ptrwm.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("per_temperature", C.c_int32),
+        ("attempt", C.c_int32),
+        ("lo", C.c_void_p),
+        ("hi", C.c_void_p),
+        ("fallback", C.c_void_p),
+    ]
+
+
 # every symbol include/ptrwm.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "ptrwm_abi_version": (C.c_int32, []),
@@ -178,6 +190,7 @@ SYMBOLS = {
     "ptrwm_split_accept": (
         C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptrwm_split_advance": (C.c_int32, [C.POINTER(RunArgs), C.c_void_p]),
+    "ptrwm_init_states": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(InitArgs), C.c_void_p]),
     "ptrwm_logdensity": (C.c_int32, [C.POINTER(TargetDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "ptrwm_propose": (
         C.c_int32,
@@ -637,6 +650,29 @@ class RunPlan:
         m.count = _opt(count, "chain moments count", torch.int64)
         self._cmom = (m, C.byref(m), (sum, sum_sq, sum_logp, count))
         self._mom = None
+
+    def init_states(self, lo: torch.Tensor, hi: torch.Tensor, *, attempt: int = 0, per_temperature: bool = False,
+                    fallback: Optional[torch.Tensor] = None) -> None:
+        """Starting points (ptrwm_init_states): every row of ``state`` drawn uniformly from the box ``lo``..``hi`` ([dim]
+        float32 on the run's device) on Philox stream 3, keyed by the run's seed and the global chain id.  ``attempt`` > 0
+        rewrites only the rows whose ``logp`` is not finite, with a fresh draw, or with ``fallback`` ([dim] float32) when
+        that is given; ``per_temperature``: every temperature of a ladder draws its own point.  Enqueues only; the caller
+        evaluates ``logp`` afterwards."""
+        D = self.shape[2]
+        for name, t in (("lo", lo), ("hi", hi), ("fallback", fallback)):
+            if t is not None and (tuple(t.shape) != (D,) or t.device != self.device):
+                raise ValueError(f"init_states: {name} must be a [{D}] float32 tensor on {self.device}")
+        i = InitArgs()
+        i.struct_size = C.sizeof(InitArgs)
+        i.per_temperature = 1 if per_temperature else 0
+        i.attempt = int(attempt)
+        i.lo = _require_device(lo, "lo", torch.float32)
+        i.hi = _require_device(hi, "hi", torch.float32)
+        i.fallback = _opt(fallback, "fallback", torch.float32)
+        with self._guard:
+            rc = self._lib.ptrwm_init_states(self._refs[4], D, C.byref(i), _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_init_states")
 
     def split_chain_moments(self, step: int) -> None:
         """Per-chain moments of the split step ``step`` just performed (ptrwm_split_chain_moments; device-step mode:
