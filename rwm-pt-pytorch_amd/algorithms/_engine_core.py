@@ -10,19 +10,14 @@ Shared by `RandomWalkMH_GPU_Optimized` (one temperature) and `ParallelTemperingR
     swap_accept  int64   [n_replicas, n_temps]        accepted swaps of pair (t, t+1)
     last_ord     int64   [n_replicas, n_temps]        attempt ordinal of the pair's last accepted swap
 
-and, when moments are on (moments_temps > 0), pooled over every replica of the shard:
+and, when moments are on (moments_temps > 0), ONE set of accumulators (`_mom`, a dict) with the leading shape L = () -
+pooled over every replica of the shard (include/ptrwm.h ptrwm_moments_args) - or, with moments_per_chain, L = (n_replicas,) -
+kept apart per replica (ptrwm_chain_moments_args; deterministic sums):
 
-    mom_sum      float64 [moments_temps, dim]         sum of x over the accumulated steps (include/ptrwm.h ptrwm_moments_args)
-    mom_sum_sq   float64 [moments_temps, dim]         sum of x^2
-    mom_sum_logp float64 [moments_temps]              sum of the log-density
-    mom_count    int64   [moments_temps]              (replica, step) pairs added
-
-or, with moments_per_chain, kept apart per replica (include/ptrwm.h ptrwm_chain_moments_args; deterministic sums):
-
-    cmom_sum      float64 [n_replicas, moments_temps, dim]
-    cmom_sum_sq   float64 [n_replicas, moments_temps, dim]
-    cmom_sum_logp float64 [n_replicas, moments_temps]
-    cmom_count    int64   [moments_temps]             accumulated steps per replica
+    sum      float64 [*L, moments_temps, dim]         sum of x over the accumulated steps
+    sum_sq   float64 [*L, moments_temps, dim]         sum of x^2
+    sum_logp float64 [*L, moments_temps]              sum of the log-density
+    count    int64   [moments_temps]                  pooled: (replica, step) pairs added; per replica: accumulated steps
 
 `n_replicas` is the axis the reference does not have: independent copies of the whole chain /
 ladder, one Philox subsequence each (global replica id = chain_offset + local index), so a run is
@@ -231,23 +226,17 @@ class EngineRun:
         self.moments_per_chain = bool(moments_per_chain)
         if self.moments_per_chain and not self.moments_temps:
             raise ValueError("moments_per_chain needs moments_temps >= 1")
-        if self.moments_per_chain:
-            # the per-chain arrays only: the pooled sums are their sum over the replicas (moments())
-            mt = self.moments_temps
-            self.cmom_sum = torch.zeros(n_replicas, mt, dim, device=device, dtype=torch.float64)
-            self.cmom_sum_sq = torch.zeros(n_replicas, mt, dim, device=device, dtype=torch.float64)
-            self.cmom_sum_logp = torch.zeros(n_replicas, mt, device=device, dtype=torch.float64)
-            self.cmom_count = torch.zeros(mt, device=device, dtype=torch.int64)
-            self._plan.set_chain_moments(self.cmom_sum, self.cmom_sum_sq, sum_logp=self.cmom_sum_logp,
-                                         count=self.cmom_count, every=self.moments_every)
-        elif self.moments_temps:
-            mt = self.moments_temps
-            self.mom_sum = torch.zeros(mt, dim, device=device, dtype=torch.float64)
-            self.mom_sum_sq = torch.zeros(mt, dim, device=device, dtype=torch.float64)
-            self.mom_sum_logp = torch.zeros(mt, device=device, dtype=torch.float64)
-            self.mom_count = torch.zeros(mt, device=device, dtype=torch.int64)
-            self._plan.set_moments(self.mom_sum, self.mom_sum_sq, sum_logp=self.mom_sum_logp, count=self.mom_count,
-                                   every=self.moments_every)
+        self._mom = None
+        if self.moments_temps:
+            # per chain, the per-chain arrays only: the pooled sums are their sum over the replicas (moments())
+            mt, lead = self.moments_temps, ((n_replicas,) if self.moments_per_chain else ())
+            self._mom = {"sum": torch.zeros(*lead, mt, dim, device=device, dtype=torch.float64),
+                         "sum_sq": torch.zeros(*lead, mt, dim, device=device, dtype=torch.float64),
+                         "sum_logp": torch.zeros(*lead, mt, device=device, dtype=torch.float64),
+                         "count": torch.zeros(mt, device=device, dtype=torch.int64)}
+            bind = self._plan.set_chain_moments if self.moments_per_chain else self._plan.set_moments
+            bind(self._mom["sum"], self._mom["sum_sq"], sum_logp=self._mom["sum_logp"], count=self._mom["count"],
+                 every=self.moments_every)
         if box is not None:
             self._draw_starts(box, x0.to(torch.float32).contiguous(), bool(init_per_temperature), attempts)
 
@@ -321,7 +310,6 @@ class EngineRun:
         lp_new = self._density(props.view(-1, D)).view(C, T)
         self._plan.split_accept(offset, lp_new, swap_event_offset=self.manual_sweeps, no_sweep=no_sweep)
         self._plan.split_moments(offset)  # (decides on the device whether this step counts; no-op without moments)
-        self._plan.split_chain_moments(offset)
         if advance:
             self._plan.split_advance(advance)
 
@@ -409,7 +397,6 @@ class EngineRun:
             lp_new = self._density(props.view(-1, D)).view(C, T)
             self._plan.split_accept(s, lp_new, swap_event_offset=self.manual_sweeps)
             self._plan.split_moments(s)
-            self._plan.split_chain_moments(s)
             self.steps_done += 1
             if trace is not None and self.steps_done % trace_every == 0:
                 tc, tt = trace.shape[1], trace.shape[2]
@@ -450,34 +437,27 @@ class EngineRun:
         sum / sum_sq [temps, dim] float64, sum_logp [temps] float64, count [temps] int64, every."""
         if not self.moments_temps:
             return None
+        m = self._mom
         if self.moments_per_chain:  # pooled = the per-chain sums added over the replicas; count: (replica, step) pairs
-            return {"sum": self.cmom_sum.sum(0), "sum_sq": self.cmom_sum_sq.sum(0), "sum_logp": self.cmom_sum_logp.sum(0),
-                    "count": self.cmom_count * self.n_replicas, "every": self.moments_every}
-        return {"sum": self.mom_sum, "sum_sq": self.mom_sum_sq, "sum_logp": self.mom_sum_logp, "count": self.mom_count,
-                "every": self.moments_every}
+            return {"sum": m["sum"].sum(0), "sum_sq": m["sum_sq"].sum(0), "sum_logp": m["sum_logp"].sum(0),
+                    "count": m["count"] * self.n_replicas, "every": self.moments_every}
+        return {**m, "every": self.moments_every}
 
     def reset_moments(self) -> None:
         """Zero the moment accumulators (the chains keep their states)."""
-        if self.moments_per_chain:
-            self.reset_chain_moments()
-        elif self.moments_temps:
-            for t in (self.mom_sum, self.mom_sum_sq, self.mom_sum_logp, self.mom_count):
-                t.zero_()
+        for t in (self._mom or {}).values():
+            t.zero_()
 
     def chain_moments(self) -> Optional[dict]:
         """The raw per-chain moment sums of this shard (device tensors, no synchronisation), or None when
         moments_per_chain is off: sum / sum_sq [n_replicas, temps, dim] float64, sum_logp [n_replicas, temps] float64,
         count [temps] int64 (accumulated steps per replica), every."""
-        if not self.moments_per_chain:
-            return None
-        return {"sum": self.cmom_sum, "sum_sq": self.cmom_sum_sq, "sum_logp": self.cmom_sum_logp, "count": self.cmom_count,
-                "every": self.moments_every}
+        return {**self._mom, "every": self.moments_every} if self.moments_per_chain else None
 
     def reset_chain_moments(self) -> None:
         """Zero the per-chain accumulators (the chains keep their states)."""
         if self.moments_per_chain:
-            for t in (self.cmom_sum, self.cmom_sum_sq, self.cmom_sum_logp, self.cmom_count):
-                t.zero_()
+            self.reset_moments()
 
     def summary(self) -> dict:
         """Whole-shard sums, as plain Python numbers / CPU tensors (one device sync)."""

@@ -347,6 +347,12 @@ __global__ void philox_raw_kernel(uint32_t *__restrict__ out, long long n, uint3
   out[4 * i + 3] = r.w;
 }
 
+// Is the step with step_counter sc past burn-in and a multiple of `period`?  The one rule of what happens every so many
+// steps once burn-in is over - a swap event (swap_every), an accumulated step of the moments (every) - host and device.
+__host__ __device__ inline bool periodic_step_due(long long sc, long long burn_in, long long period) {
+  return sc > burn_in && sc % period == 0;
+}
+
 // Stand-alone swap event: one workgroup per ladder, thread t = temperature t.  The decision is swap_decide(), the
 // code the fused kernel runs; the row permutation goes through LDS in column chunks (a permutation of rows can be
 // applied to every block of columns independently), so any (n_temps, dim) fits the 32 KB static buffer.
@@ -375,7 +381,7 @@ __global__ void __launch_bounds__(256) swap_sweep_kernel(SweepArgs a) {
   if (a.device_step != nullptr) {
     // the swap event of step *device_step, if that step has one (ptrwm_split_accept's host-side rule, on the device)
     const long long s0 = *a.device_step + (long long)a.step, sc = s0 + 1;  // (a.step: this call's offset, include/ptrwm.h)
-    if (!(sc > a.burn_in && sc % a.swap_every == 0)) return;  // (grid-uniform)
+    if (!periodic_step_due(sc, a.burn_in, a.swap_every)) return;  // (grid-uniform)
     a.step = (unsigned long long)s0;
     a.event_index = sc / a.swap_every - a.burn_in / a.swap_every - 1 + a.event_offset;
   }
@@ -620,19 +626,19 @@ static int32_t launch_sweep(const ptrwm_run_args *args, int32_t dim, int64_t eve
 // (contiguous: coalesced reads chain after chain) and keeps its two sums in registers - then one no-return fp64 atomic
 // per element and workgroup.
 constexpr int kSplitMomChains = 256;
-struct SplitMomentsArgs {
+struct SplitMomentsArgs {  // (of both kernels)
   const float *state, *logp;
   double *sum, *sum_sq, *sum_logp;
   long long *count;
   long long n_chains, step, burn_in, every;
   const long long *device_step;
   int n_temps, dim, temps;
+  // is the step just performed an accumulated one?  (grid-uniform)
+  __device__ bool step_counts() const { return periodic_step_due((device_step != nullptr ? *device_step + step : step) + 1, burn_in, every); }
 };
 
 __global__ void __launch_bounds__(256) split_moments_kernel(SplitMomentsArgs a) {
-  const long long step = a.device_step != nullptr ? *a.device_step + a.step : a.step;
-  const long long sc = step + 1;  // step_counter of the step just performed
-  if (!(sc > a.burn_in && sc % a.every == 0)) return;  // (grid-uniform)
+  if (!a.step_counts()) return;
   const long long c0 = (long long)blockIdx.x * kSplitMomChains;
   const long long c1 = (a.n_chains - c0 < kSplitMomChains) ? a.n_chains : c0 + kSplitMomChains;
   const int td = a.temps * a.dim;
@@ -660,22 +666,11 @@ __global__ void __launch_bounds__(256) split_moments_kernel(SplitMomentsArgs a) 
 
 // Per-chain moments of one split step (ptrwm_split_chain_moments): one thread per (chain, t < temps, d), a plain
 // read-modify-write of its own two elements - the same sequential fp64 sums as the fused kernels' (v * v is exact in fp64).
-struct SplitChainMomentsArgs {
-  const float *state, *logp;
-  double *sum, *sum_sq, *sum_logp;
-  long long *count;
-  long long n_elems, step, burn_in, every;  // n_elems = n_chains * temps * dim
-  const long long *device_step;
-  int n_temps, dim, temps;
-};
-
-__global__ void __launch_bounds__(256) split_chain_moments_kernel(SplitChainMomentsArgs a) {
-  const long long step = a.device_step != nullptr ? *a.device_step + a.step : a.step;
-  const long long sc = step + 1;  // step_counter of the step just performed
-  if (!(sc > a.burn_in && sc % a.every == 0)) return;  // (grid-uniform)
+__global__ void __launch_bounds__(256) split_chain_moments_kernel(SplitMomentsArgs a) {
+  if (!a.step_counts()) return;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.n_elems) return;
   const int td = a.temps * a.dim;
+  if (i >= a.n_chains * td) return;
   const long long c = i / td;
   const int k = (int)(i - c * td), t = k / a.dim, d = k - t * a.dim;
   const long long rep = c * a.n_temps + t;
@@ -763,16 +758,25 @@ __global__ void __launch_bounds__(64) init_states_kernel(InitStatesArgs a) {
 
 using namespace ptrwm;
 
-// what run_impl accumulates: the pooled sums of ptrwm_moments_args or the per-chain ones of ptrwm_chain_moments_args
+// The two public accumulator structs are one layout: ptrwm_moments_args is the view through which both are checked and read,
+// and a MomSpec says which kind it holds (m == NULL: none).
+#define PTRWM_SAME_FIELD(f) \
+  (offsetof(ptrwm_moments_args, f) == offsetof(ptrwm_chain_moments_args, f) && sizeof(ptrwm_moments_args::f) == sizeof(ptrwm_chain_moments_args::f))
+static_assert(sizeof(ptrwm_moments_args) == sizeof(ptrwm_chain_moments_args) && PTRWM_SAME_FIELD(struct_size) && PTRWM_SAME_FIELD(temps) &&
+                  PTRWM_SAME_FIELD(every) && PTRWM_SAME_FIELD(sum) && PTRWM_SAME_FIELD(sum_sq) && PTRWM_SAME_FIELD(sum_logp) && PTRWM_SAME_FIELD(count),
+              "ptrwm_moments_args and ptrwm_chain_moments_args: the same fields at the same offsets");
+#undef PTRWM_SAME_FIELD
 struct MomSpec {
+  const ptrwm_moments_args *m;
   bool per_chain;
-  int32_t temps, every;
-  double *sum, *sum_sq, *sum_logp;
-  int64_t *count;
+  MomSpec() : m(nullptr), per_chain(false) {}
+  MomSpec(const ptrwm_moments_args *pooled) : m(pooled), per_chain(false) {}
+  MomSpec(const ptrwm_chain_moments_args *chain) : m(reinterpret_cast<const ptrwm_moments_args *>(chain)), per_chain(true) {}
 };
 
-// ptrwm_moments_args checks shared by ptrwm_run_with_moments and ptrwm_split_moments (args already checked); NULL: none
-static int32_t check_moments(const ptrwm_run_args *args, const ptrwm_moments_args *m) {
+// the accumulator checks shared by ptrwm_run_with_*moments and ptrwm_split_*moments (args already checked); none: ok
+static int32_t check_moments(const ptrwm_run_args *args, const MomSpec &mom) {
+  const ptrwm_moments_args *const m = mom.m;
   if (m == nullptr) return PTRWM_OK;
   if (m->struct_size != sizeof(ptrwm_moments_args)) return PTRWM_E_STRUCT;
   if (m->temps < 1 || m->temps > args->n_temps || m->every < 1) return PTRWM_E_ARG;
@@ -780,17 +784,9 @@ static int32_t check_moments(const ptrwm_run_args *args, const ptrwm_moments_arg
   return PTRWM_OK;
 }
 
-// ... and the same for ptrwm_chain_moments_args
-static int32_t check_chain_moments(const ptrwm_run_args *args, const ptrwm_chain_moments_args *m) {
-  if (m == nullptr) return PTRWM_OK;
-  if (m->struct_size != sizeof(ptrwm_chain_moments_args)) return PTRWM_E_STRUCT;
-  if (m->temps < 1 || m->temps > args->n_temps || m->every < 1) return PTRWM_E_ARG;
-  if (m->sum == nullptr || m->sum_sq == nullptr) return PTRWM_E_NULL;
-  return PTRWM_OK;
-}
-
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const ptrwm_moments_args *pooled, const ptrwm_chain_moments_args *per_chain, void *hip_stream);
+                        const MomSpec &spec, void *hip_stream);
+static int32_t split_moments_impl(const ptrwm_run_args *args, int32_t dim, const MomSpec &spec, void *stream);
 
 extern "C" {
 
@@ -890,34 +886,30 @@ int32_t ptrwm_has_variant(int32_t target_kind, int32_t proposal_kind, int32_t di
 
 int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                   void *hip_stream) {
-  return run_impl(target, proposal, args, nullptr, nullptr, hip_stream);
+  return run_impl(target, proposal, args, MomSpec(), hip_stream);
 }
 
 int32_t ptrwm_run_with_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
                                const ptrwm_run_args *args, const ptrwm_moments_args *moments, void *stream) {
-  return run_impl(target, proposal, args, moments, nullptr, stream);
+  return run_impl(target, proposal, args, moments, stream);
 }
 
 int32_t ptrwm_run_with_chain_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
                                      const ptrwm_run_args *args, const ptrwm_chain_moments_args *chain_moments, void *stream) {
-  return run_impl(target, proposal, args, nullptr, chain_moments, stream);
+  return run_impl(target, proposal, args, chain_moments, stream);
 }
 
 }  // extern "C"
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const ptrwm_moments_args *pooled, const ptrwm_chain_moments_args *per_chain, void *hip_stream) {
+                        const MomSpec &spec, void *hip_stream) {
   if (proposal == nullptr || args == nullptr) return PTRWM_E_NULL;
   if (int rc = check_target(target)) return rc;
   if (args->struct_size != sizeof(ptrwm_run_args)) return PTRWM_E_STRUCT;
   if (proposal->kind < 0 || proposal->kind >= PTRWM_PROPOSAL_COUNT) return PTRWM_E_KIND;
   if (args->n_temps < 1 || args->n_temps > PTRWM_MAX_TEMPS) return PTRWM_E_TEMPS;
-  if (int rc = check_moments(args, pooled)) return rc;
-  if (int rc = check_chain_moments(args, per_chain)) return rc;
-  MomSpec mom_spec = {};
-  if (pooled != nullptr) mom_spec = {false, pooled->temps, pooled->every, pooled->sum, pooled->sum_sq, pooled->sum_logp, pooled->count};
-  if (per_chain != nullptr) mom_spec = {true, per_chain->temps, per_chain->every, per_chain->sum, per_chain->sum_sq, per_chain->sum_logp, per_chain->count};
-  const MomSpec *const mom = (pooled != nullptr || per_chain != nullptr) ? &mom_spec : nullptr;
+  if (int rc = check_moments(args, spec)) return rc;
+  const ptrwm_moments_args *const mom = spec.m;
   if (args->n_chains < 0 || args->n_steps < 0 || args->step0 < 0 || args->burn_in < 0 || args->swap_every < 1)
     return PTRWM_E_ARG;
   if (args->swap_mode != PTRWM_SWAP_EXCHANGE && args->swap_mode != PTRWM_SWAP_REFERENCE_COPY) return PTRWM_E_ARG;
@@ -1029,7 +1021,7 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   k.full.mom_temps = mom != nullptr ? mom->temps : 0;
   k.full.mom_every = mom != nullptr ? mom->every : 1;
   k.full.steps_to_mom = 0;
-  k.full.mom_chain = (mom != nullptr && mom->per_chain) ? 1 : 0;
+  k.full.mom_chain = (mom != nullptr && spec.per_chain) ? 1 : 0;
   if (mom != nullptr) {
     // the workgroup's LDS with the moments regions behind it, as the launcher will ask for it (variants.h LaunchShape)
     auto lds_need = [&]() {
@@ -1039,7 +1031,7 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
     // Per-chain regions grow with the ladders of a group.  Where AUTO chose the form and both exist, a workgroup that needs
     // more than half of the CU's LDS (one workgroup resident: one wave per SIMD in the thread form) - or does not fit at
     // all - hands over to the other form if that one needs less (the same bits).  A pinned form is taken as it is.
-    if (mom->per_chain && other_fn != nullptr && need > kMaxLdsBytes / 2u) {
+    if (spec.per_chain && other_fn != nullptr && need > kMaxLdsBytes / 2u) {
       const bool chosen = quad;
       set_form(!chosen);
       const unsigned other = lds_need();
@@ -1248,60 +1240,11 @@ int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *propo
 }
 
 int32_t ptrwm_split_chain_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm_chain_moments_args *cm, void *stream) {
-  if (int rc = split_common_checks(args, dim)) return rc;
-  if (cm == nullptr) return PTRWM_E_NULL;
-  if (int rc = check_chain_moments(args, cm)) return rc;
-  if (args->n_chains == 0) return PTRWM_OK;
-  if (args->state == nullptr || args->logp == nullptr) return PTRWM_E_NULL;
-  if (args->device_step == nullptr && !(args->step0 + 1 > args->burn_in && (args->step0 + 1) % cm->every == 0))
-    return PTRWM_OK;  // (known on the host: this step does not count)
-  SplitChainMomentsArgs a;
-  a.state = args->state;
-  a.logp = args->logp;
-  a.sum = cm->sum;
-  a.sum_sq = cm->sum_sq;
-  a.sum_logp = cm->sum_logp;
-  a.count = (long long *)cm->count;
-  a.n_elems = args->n_chains * (long long)cm->temps * dim;
-  a.step = args->step0;
-  a.burn_in = args->burn_in;
-  a.every = cm->every;
-  a.device_step = (const long long *)args->device_step;
-  a.n_temps = args->n_temps;
-  a.dim = dim;
-  a.temps = cm->temps;
-  const long long grid = (a.n_elems + 255) / 256;
-  if (grid > 0x7fffffffll) return PTRWM_E_ARG;
-  hipLaunchKernelGGL(split_chain_moments_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+  return split_moments_impl(args, dim, cm, stream);
 }
 
 int32_t ptrwm_split_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm_moments_args *moments, void *stream) {
-  if (int rc = split_common_checks(args, dim)) return rc;
-  if (moments == nullptr) return PTRWM_E_NULL;
-  if (int rc = check_moments(args, moments)) return rc;
-  if (args->n_chains == 0) return PTRWM_OK;
-  if (args->state == nullptr || args->logp == nullptr) return PTRWM_E_NULL;
-  if (args->device_step == nullptr && !(args->step0 + 1 > args->burn_in && (args->step0 + 1) % moments->every == 0))
-    return PTRWM_OK;  // (known on the host: nothing to add)
-  SplitMomentsArgs a;
-  a.state = args->state;
-  a.logp = args->logp;
-  a.sum = moments->sum;
-  a.sum_sq = moments->sum_sq;
-  a.sum_logp = moments->sum_logp;
-  a.count = (long long *)moments->count;
-  a.n_chains = args->n_chains;
-  a.step = args->step0;
-  a.burn_in = args->burn_in;
-  a.every = moments->every;
-  a.device_step = (const long long *)args->device_step;
-  a.n_temps = args->n_temps;
-  a.dim = dim;
-  a.temps = moments->temps;
-  const unsigned grid = (unsigned)((args->n_chains + kSplitMomChains - 1) / kSplitMomChains);
-  hipLaunchKernelGGL(split_moments_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+  return split_moments_impl(args, dim, moments, stream);
 }
 
 int32_t ptrwm_split_advance(const ptrwm_run_args *args, void *stream) {
@@ -1407,3 +1350,35 @@ int32_t ptrwm_philox_raw(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, u
 }
 
 }  // extern "C"
+
+// ptrwm_split_moments / ptrwm_split_chain_moments: the same checks, the same arguments, one of the two kernels
+static int32_t split_moments_impl(const ptrwm_run_args *args, int32_t dim, const MomSpec &spec, void *stream) {
+  if (int rc = split_common_checks(args, dim)) return rc;
+  const ptrwm_moments_args *const m = spec.m;
+  if (m == nullptr) return PTRWM_E_NULL;
+  if (int rc = check_moments(args, spec)) return rc;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->state == nullptr || args->logp == nullptr) return PTRWM_E_NULL;
+  if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, m->every))
+    return PTRWM_OK;  // (known on the host: this step does not count)
+  SplitMomentsArgs a;
+  a.state = args->state;
+  a.logp = args->logp;
+  a.sum = m->sum;
+  a.sum_sq = m->sum_sq;
+  a.sum_logp = m->sum_logp;
+  a.count = (long long *)m->count;
+  a.n_chains = args->n_chains;
+  a.step = args->step0;
+  a.burn_in = args->burn_in;
+  a.every = m->every;
+  a.device_step = (const long long *)args->device_step;
+  a.n_temps = args->n_temps;
+  a.dim = dim;
+  a.temps = m->temps;
+  // pooled: a workgroup per tile of chains; per chain: a thread per element
+  const long long grid = spec.per_chain ? (args->n_chains * (long long)m->temps * dim + 255) / 256 : (args->n_chains + kSplitMomChains - 1) / kSplitMomChains;
+  if (grid > 0x7fffffffll) return PTRWM_E_ARG;
+  hipLaunchKernelGGL(spec.per_chain ? split_chain_moments_kernel : split_moments_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}

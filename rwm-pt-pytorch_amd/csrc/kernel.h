@@ -376,58 +376,95 @@ __device__ __forceinline__ void count_add(long long *p, long long v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// The moments region of one exchange group: [mom_temps * dim] sums of x, [mom_temps * dim] sums of x^2, [mom_temps] sums
-// of the log-density, as doubles, behind everything else the kernel keeps in its dynamic LDS.  One region per group:
+// The moments region of one exchange group: [rows * dim] sums of x, [rows * dim] sums of x^2, [rows] sums of the
+// log-density, as doubles, behind everything else the kernel keeps in its dynamic LDS.  One region per group:
 // narrow groups (one wave) never meet at a workgroup barrier, so they cannot share one.
-constexpr unsigned moments_region_doubles(int temps, int dim) { return (unsigned)(temps * (2 * dim + 1)); }
+constexpr unsigned moments_region_doubles(int rows, int dim) { return (unsigned)(rows * (2 * dim + 1)); }
 // Rows of a region: pooled, one per covered temperature; per chain (FullArgs::mom_chain), one per (ladder of the exchange
 // group, covered temperature), row = ladder * temps + t - kernel and host (variants.h with_moments) size the region from here
 constexpr int moments_rows(bool per_chain, int ladders_per_group, int temps) { return per_chain ? ladders_per_group * temps : temps; }
 
-__device__ __forceinline__ void moments_zero(double *reg, int n, int tid, int nthr) {
-  for (int i = tid; i < n; i += nthr) reg[i] = 0.0;
-}
 // ds_add_f64: lanes of one wave with equal temperature (the ladders of a narrow group) hit the same address - the LDS
 // atomic unit serialises them
 __device__ __forceinline__ void moments_add(double *p, double v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-// one no-return global_atomic_add_f64 per non-zero partial sum (device memory: include/ptrwm.h), and the counts
-// (the pointers come from the kernarg segment, late_args: loaded here, not held across the step loop)
-__device__ __forceinline__ void moments_flush(const double *reg, kargs_full_ptr f, int dim, long long live_ladders, int tid,
-                                              int nthr) {
-  const int temps = f->mom_temps;
-  const int td = temps * dim;
-  double *const sum = f->mom_sum, *const sum_sq = f->mom_sum_sq, *const sum_logp = f->mom_sum_logp;
-  const int n = 2 * td + (sum_logp != nullptr ? temps : 0);
-  for (int i = tid; i < n; i += nthr) {
-    const double v = reg[i];
-    if (v != 0.0) unsafeAtomicAdd(i < td ? sum + i : (i < 2 * td ? sum_sq + (i - td) : sum_logp + (i - 2 * td)), v);
-  }
-  long long *const count = f->mom_count;
-  const long long add = live_ladders * f->mom_steps;
-  if (count != nullptr)
-    for (int i = tid; i < temps; i += nthr) count_add(&count[i], add);
-}
 
-// Per-chain accumulators: the region's live rows and the group's part of the global arrays are the same contiguous runs
-// (row0 = first chain of the group x temps; region: [rows x dim] sums, [rows x dim] sums of squares, [rows] log-densities).
-// LOAD: global -> region, in the prologue - each element then is the sequential fp64 sum over ALL steps so far, wherever
-// launches are cut; else region -> global, plain 8-byte stores: no other group touches these elements.
-template <bool LOAD>
-__device__ __forceinline__ void moments_chain_copy(double *reg, double *sum, double *sum_sq, double *sum_logp, int rows, int live_rows,
-                                                   int dim, long long row0, int tid, int nthr) {
-  const int n = live_rows * dim, rd = rows * dim;
-  double *const gs = sum + row0 * dim, *const gq = sum_sq + row0 * dim;
-  for (int i = tid; i < n; i += nthr) {
-    if (LOAD) reg[i] = gs[i], reg[rd + i] = gq[i];
-    else gs[i] = reg[i], gq[i] = reg[rd + i];
+// The accumulator of one exchange group (FULL twins of both step kernels): the one place that knows the rows and the three
+// sub-arrays of a region, and how the pooled and the per-chain kind (FullArgs::mom_chain) differ - in the row a thread adds
+// to, and in how the region starts and ends a launch.  `reg` is set from the layout (StepLds / QuadLds::moments_region, which
+// places a narrow group's region by doubles()).  The arguments come as a pointer: &a.full in the prologue and the step,
+// late_args() in the epilogue (loaded there, not held across the step loop).
+struct MomentsAcc {
+  double *reg = nullptr;
+  int temps, rows, dim;
+  bool per_chain;
+  struct Row { double *sum, *sum_sq, *logp; };
+
+  template <class F>
+  __device__ __forceinline__ MomentsAcc(F f, int ladders_per_group, int dim_)
+      : temps(f->mom_temps), rows(moments_rows(f->mom_chain != 0, ladders_per_group, temps)), dim(dim_), per_chain(f->mom_chain != 0) {}
+  __device__ __forceinline__ int doubles() const { return (int)moments_region_doubles(rows, dim); }
+  // where the replica at (ladder cw of the group, temperature t < temps) adds: sum[d], sum_sq[d], d < dim, and *logp
+  __device__ __forceinline__ Row row(int cw, int t) const {
+    const int r = per_chain ? cw * temps + t : t;
+    return {reg + r * dim, reg + (rows + r) * dim, reg + 2 * rows * dim + r};
   }
-  if (sum_logp != nullptr)
-    for (int i = tid; i < live_rows; i += nthr) {
-      if (LOAD) reg[2 * rd + i] = sum_logp[row0 + i];
-      else sum_logp[row0 + i] = reg[2 * rd + i];
+  // Per chain, the region's live rows and the group's part of the global arrays are the same contiguous runs (row0 = first
+  // chain of the group x temps).  LOAD: global -> region - each element then is the sequential fp64 sum over ALL steps so
+  // far, wherever launches are cut; else region -> global, plain 8-byte stores: no other group touches these elements.
+  template <bool LOAD, class F>
+  __device__ __forceinline__ void chain_copy(F f, int live_ladders, long long chain0, int tid, int nthr) const {
+    const int live_rows = live_ladders * temps, n = live_rows * dim, rd = rows * dim;
+    const long long row0 = chain0 * temps;
+    double *const sum_logp = f->mom_sum_logp, *const gs = f->mom_sum + row0 * dim, *const gq = f->mom_sum_sq + row0 * dim;
+    for (int i = tid; i < n; i += nthr) {
+      if (LOAD) reg[i] = gs[i], reg[rd + i] = gq[i];
+      else gs[i] = reg[i], gq[i] = reg[rd + i];
     }
+    if (sum_logp != nullptr)
+      for (int i = tid; i < live_rows; i += nthr) {
+        if (LOAD) reg[2 * rd + i] = sum_logp[row0 + i];
+        else sum_logp[row0 + i] = reg[2 * rd + i];
+      }
+  }
+  // prologue (ordered before the first add by the group's barrier): per chain the region is loaded, pooled it starts at zero
+  template <class F>
+  __device__ __forceinline__ void begin(F f, int live_ladders, long long chain0, int tid, int nthr) const {
+    if (per_chain) chain_copy<true>(f, live_ladders, chain0, tid, nthr);
+    else
+      for (int i = tid; i < doubles(); i += nthr) reg[i] = 0.0;
+  }
+  // epilogue, behind the barrier after the launch's last add.  Per chain: stored back, and the group of chain 0 counts the
+  // steps per chain.  Pooled: one no-return global_atomic_add_f64 per non-zero partial sum (device memory: include/ptrwm.h)
+  // and count[t] += live ladders x steps.
+  template <class F>
+  __device__ __forceinline__ void end(F f, long long live_ladders, long long chain0, int tid, int nthr) const {
+    long long *const count = f->mom_count;
+    if (per_chain) {
+      chain_copy<false>(f, (int)live_ladders, chain0, tid, nthr);
+      if (chain0 != 0) return;
+    } else {
+      const int td = temps * dim;
+      double *const sum = f->mom_sum, *const sum_sq = f->mom_sum_sq, *const sum_logp = f->mom_sum_logp;
+      const int n = 2 * td + (sum_logp != nullptr ? temps : 0);
+      for (int i = tid; i < n; i += nthr) {
+        const double v = reg[i];
+        if (v != 0.0) unsafeAtomicAdd(i < td ? sum + i : (i < 2 * td ? sum_sq + (i - td) : sum_logp + (i - 2 * td)), v);
+      }
+    }
+    const long long add = (per_chain ? 1 : live_ladders) * f->mom_steps;
+    if (count != nullptr)
+      for (int i = tid; i < temps; i += nthr) count_add(&count[i], add);
+  }
+};
+
+// The wave-uniform thinning countdowns of the FULL twins (trace rows, accumulated steps): true at every period-th step
+__device__ __forceinline__ bool countdown_due(int &left, int period) {
+  --left;
+  const bool due = (left == 0);
+  if (due) left = period;
+  return due;
 }
 
 template <bool EXACT>
@@ -642,14 +679,10 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       row_head = stage_head(gs);
       if (wide) reinterpret_cast<int *>(s_dyn)[L::vote(nthr)] = 0;  // no objection yet
       if constexpr (FULL) {
-        if (a.full.mom_sum != nullptr) {  // (ordered before the first add by the barrier below)
-          const int mt = a.full.mom_temps, m_rows = moments_rows(a.full.mom_chain != 0, cpw, mt);
-          const int n_mom = (int)moments_region_doubles(m_rows, D0);
-          double *const reg = L::moments_region(s_dyn, wide, nthr, wave, n_mom);
-          if (a.full.mom_chain != 0)
-            moments_chain_copy<true>(reg, a.full.mom_sum, a.full.mom_sum_sq, a.full.mom_sum_logp, m_rows, (int)live_chains * mt, D0, chain0 * mt, tid, nthr);
-          else
-            moments_zero(reg, n_mom, tid, nthr);
+        if (a.full.mom_sum != nullptr) {
+          MomentsAcc m(&a.full, cpw, D0);
+          m.reg = L::moments_region(s_dyn, wide, nthr, wave, m.doubles());
+          m.begin(&a.full, (int)live_chains, chain0, tid, nthr);
         }
       }
     }
@@ -772,12 +805,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       (void)__hip_atomic_fetch_add(sq_slot, (double)j2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
     if constexpr (FULL) {
-      bool trace_now = false;
-      if (a.full.trace != nullptr) {  // wave-uniform thinning countdown
-        --to_trace;
-        trace_now = (to_trace == 0);
-        if (trace_now) to_trace = a.full.trace_every;
-      }
+      const bool trace_now = a.full.trace != nullptr && countdown_due(to_trace, a.full.trace_every);
       if (trace_now && trace_on) {
         const long long row = ((a.full.trace_row0 + trace_rows) * a.full.trace_chains + chain) * a.full.trace_temps + t;
         float *__restrict__ tr = a.full.trace + row * D;
@@ -785,23 +813,17 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
         if (a.full.trace_logp != nullptr) a.full.trace_logp[row] = lp;
       }
       trace_rows += trace_now ? 1 : 0;
-      if (a.full.mom_sum != nullptr) {  // wave-uniform countdown, as the trace's; the state after the whole step
-        --to_mom;
-        const bool mom_now = (to_mom == 0);
-        if (mom_now) to_mom = a.full.mom_every;
-        if (mom_now && count_on && live && t < a.full.mom_temps) {
-          const int mt = a.full.mom_temps, pc = a.full.mom_chain;
-          const int m_rows = moments_rows(pc != 0, cpw, mt), m_row = pc != 0 ? cw * mt + t : t;
-          double *const reg = L::moments_region(s_dyn, wide, wide ? ((T + 63) & ~63) : 64, wave, (int)moments_region_doubles(m_rows, D));
-          double *const rs = reg + m_row * D;
-          double *const rq = reg + (m_rows + m_row) * D;
-          PTRWM_DIM_LOOP(d, DP, D, {
-            const double v = (double)x[d];
-            moments_add(rs + d, v);
-            moments_add(rq + d, v * v);
-          })
-          moments_add(reg + 2 * m_rows * D + m_row, (double)lp);
-        }
+      // the state after the whole step
+      if (a.full.mom_sum != nullptr && countdown_due(to_mom, a.full.mom_every) && count_on && live && t < a.full.mom_temps) {
+        MomentsAcc m(&a.full, cpw, D);
+        m.reg = L::moments_region(s_dyn, wide, wide ? ((T + 63) & ~63) : 64, wave, m.doubles());
+        const MomentsAcc::Row r = m.row(cw, t);
+        PTRWM_DIM_LOOP(d, DP, D, {
+          const double v = (double)x[d];
+          moments_add(r.sum + d, v);
+          moments_add(r.sum_sq + d, v * v);
+        })
+        moments_add(r.logp, (double)lp);
       }
     }
   };
@@ -983,15 +1005,9 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       // every add of the launch is behind the barrier above: the group's partial sums go to HBM, once
       const kargs_full_ptr fa = &ae->full;
       if (fa->mom_sum != nullptr) {
-        const int mt = fa->mom_temps, m_rows = moments_rows(fa->mom_chain != 0, cpw2, mt);
-        double *const reg = L::moments_region(s_dyn, wide2, nthr, wave, (int)moments_region_doubles(m_rows, D2));
-        if (fa->mom_chain != 0) {
-          moments_chain_copy<false>(reg, fa->mom_sum, fa->mom_sum_sq, fa->mom_sum_logp, m_rows, (int)live_chains * mt, D2, c0 * mt, tid2, nthr);
-          if (c0 == 0 && fa->mom_count != nullptr)  // (the group of chain 0: steps per chain, once per launch)
-            for (int i = tid2; i < mt; i += nthr) count_add(&fa->mom_count[i], fa->mom_steps);
-        } else {
-          moments_flush(reg, fa, D2, live_chains, tid2, nthr);
-        }
+        MomentsAcc m(fa, cpw2, D2);
+        m.reg = L::moments_region(s_dyn, wide2, nthr, wave, m.doubles());
+        m.end(fa, live_chains, c0, tid2, nthr);
       }
     }
     if constexpr (STREAM) {

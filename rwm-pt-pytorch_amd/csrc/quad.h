@@ -730,14 +730,10 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
     stage_copy<true>(rows_f, gs, stage_total, tid, gthreads);
     s_landed[kToObjection * nslots + slot_raw] = 0;  // the ladders' swap-form objections (wide groups: the vote of a swap event, below)
     if constexpr (FULL) {
-      if (a.full.mom_sum != nullptr) {  // (ordered before the first add by the barrier below)
-        const int mt = a.full.mom_temps, m_rows = moments_rows(a.full.mom_chain != 0, cpw, mt);
-        const int n_mom = (int)moments_region_doubles(m_rows, D);
-        double *const reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), n_mom);
-        if (a.full.mom_chain != 0)  // (kernel.h: per-chain accumulators are loaded, not zeroed)
-          moments_chain_copy<true>(reg, a.full.mom_sum, a.full.mom_sum_sq, a.full.mom_sum_logp, m_rows, (int)live_chains * mt, D, chain0 * mt, tid, gthreads);
-        else
-          moments_zero(reg, n_mom, tid, gthreads);
+      if (a.full.mom_sum != nullptr) {  // (kernel.h MomentsAcc)
+        MomentsAcc m(&a.full, cpw, D);
+        m.reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), m.doubles());
+        m.begin(&a.full, (int)live_chains, chain0, tid, gthreads);
       }
     }
     sync_group();
@@ -1005,12 +1001,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
       sq += (double)j2;
     }
     if constexpr (FULL) {
-      bool trace_now = false;
-      if (a.full.trace != nullptr) {
-        --to_trace;
-        trace_now = (to_trace == 0);
-        if (trace_now) to_trace = a.full.trace_every;
-      }
+      const bool trace_now = a.full.trace != nullptr && countdown_due(to_trace, a.full.trace_every);
       if (trace_now && trace_on) {
         const long long row = ((a.full.trace_row0 + trace_rows) * a.full.trace_chains + chain) * a.full.trace_temps + t;
         state_t *__restrict__ tr = reinterpret_cast<state_t *>(a.full.trace) + row * D + l.d0;
@@ -1020,26 +1011,20 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
         if (a.full.trace_logp != nullptr && l.q == 0) a.full.trace_logp[row] = lp;
       }
       trace_rows += trace_now ? 1 : 0;
-      if (a.full.mom_sum != nullptr) {  // wave-uniform countdown, as the trace's; the state after the whole step
-        --to_mom;
-        const bool mom_now = (to_mom == 0);
-        if (mom_now) to_mom = a.full.mom_every;
-        if (mom_now && count_on && live && t < a.full.mom_temps) {
-          const int mt = a.full.mom_temps, pc = a.full.mom_chain;
-          const int m_rows = moments_rows(pc != 0, cpw, mt), m_row = pc != 0 ? cw * mt + t : t;
-          double *const reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(m_rows, D));
-          double *const rs = reg + m_row * D + l.d0;
-          double *const rq = reg + (m_rows + m_row) * D + l.d0;
+      // the state after the whole step: every lane adds its own range of the row, the first lane the log-density
+      if (a.full.mom_sum != nullptr && countdown_due(to_mom, a.full.mom_every) && count_on && live && t < a.full.mom_temps) {
+        MomentsAcc m(&a.full, cpw, D);
+        m.reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), m.doubles());
+        const MomentsAcc::Row r = m.row(cw, t);
 #pragma unroll
-          for (int j = 0; j < W; ++j) {
-            if (q_valid<MIN_OWN>(l, j)) {
-              const double v = (double)x[j];
-              moments_add(rs + j, v);
-              moments_add(rq + j, v * v);
-            }
+        for (int j = 0; j < W; ++j) {
+          if (q_valid<MIN_OWN>(l, j)) {
+            const double v = (double)x[j];
+            moments_add(r.sum + l.d0 + j, v);
+            moments_add(r.sum_sq + l.d0 + j, v * v);
           }
-          if (l.q == 0) moments_add(reg + 2 * m_rows * D + m_row, (double)lp);
         }
+        if (l.q == 0) moments_add(r.logp, (double)lp);
       }
     }
   }
@@ -1063,15 +1048,9 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
       // every add of the launch is behind the barrier above: the group's partial sums go to HBM, once
       const kargs_full_ptr fa = &ae->full;
       if (fa->mom_sum != nullptr) {
-        const int mt = fa->mom_temps, m_rows = moments_rows(fa->mom_chain != 0, cpw, mt);
-        double *const reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), (int)moments_region_doubles(m_rows, D));
-        if (fa->mom_chain != 0) {
-          moments_chain_copy<false>(reg, fa->mom_sum, fa->mom_sum_sq, fa->mom_sum_logp, m_rows, (int)live_chains * mt, D, chain0 * mt, tid, gthreads);
-          if (chain0 == 0 && fa->mom_count != nullptr)  // (the group of chain 0: steps per chain, once per launch)
-            for (int i = tid; i < mt; i += gthreads) count_add(&fa->mom_count[i], fa->mom_steps);
-        } else {
-          moments_flush(reg, fa, D, live_chains, tid, gthreads);
-        }
+        MomentsAcc m(fa, cpw, D);
+        m.reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), m.doubles());
+        m.end(fa, live_chains, chain0, tid, gthreads);
       }
     }
     stage_copy<false>(rows_f, gs, stage_total, tid, gthreads);

@@ -119,30 +119,25 @@ class RunArgs(C.Structure):
     ]
 
 
+_MOMENTS_FIELDS = [  # of both accumulator structs: they differ in the shapes of what the pointers point to
+    ("struct_size", C.c_uint32),
+    ("temps", C.c_int32),
+    ("every", C.c_int32),
+    ("sum", C.c_void_p),
+    ("sum_sq", C.c_void_p),
+    ("sum_logp", C.c_void_p),
+    ("count", C.c_void_p),
+]
+
+
 class MomentsArgs(C.Structure):
     """ptrwm_moments_args: fp64 moment sums of the first ``temps`` temperatures (include/ptrwm.h)."""
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("temps", C.c_int32),
-        ("every", C.c_int32),
-        ("sum", C.c_void_p),
-        ("sum_sq", C.c_void_p),
-        ("sum_logp", C.c_void_p),
-        ("count", C.c_void_p),
-    ]
+    _fields_ = _MOMENTS_FIELDS
 
 
 class ChainMomentsArgs(C.Structure):
     """ptrwm_chain_moments_args: fp64 moment sums of every chain on its own (include/ptrwm.h)."""
-    _fields_ = [
-        ("struct_size", C.c_uint32),
-        ("temps", C.c_int32),
-        ("every", C.c_int32),
-        ("sum", C.c_void_p),
-        ("sum_sq", C.c_void_p),
-        ("sum_logp", C.c_void_p),
-        ("count", C.c_void_p),
-    ]
+    _fields_ = _MOMENTS_FIELDS
 
 
 class InitArgs(C.Structure):
@@ -577,8 +572,48 @@ class RunPlan:
         self._plain = True  # no per-launch buffers set in _a
         self._last_trace = (None, None, None)  # (trace, trace_logp, trace_every) marshalled into _a by the last launch
         self._guard = on_device(self.device)  # (after the checks above: they reject CPU tensors first)
-        self._mom = None  # (MomentsArgs, byref, tensors) of set_moments
-        self._cmom = None  # (ChainMomentsArgs, byref, tensors) of set_chain_moments
+        self._mom = None  # the accumulator, pooled or per chain: (kind of _MOMENT_KINDS, struct, byref, tensors)
+
+    # kind of accumulator -> (words of its messages, struct, entry point of launch(), entry point of split_moments())
+    _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
+                     "chain": ("chain moments", ChainMomentsArgs, "ptrwm_run_with_chain_moments", "ptrwm_split_chain_moments")}
+
+    def _bind_moments(self, kind, lead, sum, sum_sq, sum_logp, count, every) -> None:
+        """The one accumulator of the plan: ``sum`` / ``sum_sq`` are [*lead, temps, dim], ``sum_logp`` [*lead, temps],
+        ``count`` [temps].  ``sum`` None switches an accumulator of this kind off; anything else replaces what was set."""
+        if sum is None:
+            if self._mom is not None and self._mom[0] == kind:
+                self._mom = None
+            return
+        what, struct = self._MOMENT_KINDS[kind][:2]
+        T, D = self.shape[1:]
+
+        def fmt(*shape):
+            return "[" + ", ".join(str(n) for n in lead + shape) + "]"
+
+        if sum.dim() != len(lead) + 2 or tuple(sum.shape[:-2]) != lead or sum.shape[-1] != D or not 1 <= sum.shape[-2] <= T:
+            raise ValueError(f"{what} sum must be {fmt('temps', D)} with 1 <= temps <= {T}")
+        temps = sum.shape[-2]
+        if sum_sq is None or tuple(sum_sq.shape) != lead + (temps, D):
+            raise ValueError(f"{what} sum_sq must be {fmt(temps, D)}")
+        if sum_logp is not None and tuple(sum_logp.shape) != lead + (temps,):
+            raise ValueError(f"{what} sum_logp must be {fmt(temps)}")
+        if count is not None and tuple(count.shape) != (temps,):
+            raise ValueError(f"{what} count must be [{temps}]")
+        if int(every) < 1:
+            raise ValueError(f"{what} every must be >= 1")
+        for name, t in (("sum", sum), ("sum_sq", sum_sq), ("sum_logp", sum_logp), ("count", count)):
+            if t is not None and t.device != self.device:
+                raise ValueError(f"{what} {name} is on {t.device}, state on {self.device}")
+        m = struct()
+        m.struct_size = C.sizeof(struct)
+        m.temps = temps
+        m.every = int(every)
+        m.sum = _require_device(sum, f"{what} sum", torch.float64)
+        m.sum_sq = _require_device(sum_sq, f"{what} sum_sq", torch.float64)
+        m.sum_logp = _opt(sum_logp, f"{what} sum_logp", torch.float64)
+        m.count = _opt(count, f"{what} count", torch.int64)
+        self._mom = (kind, m, C.byref(m), (sum, sum_sq, sum_logp, count))
 
     def set_moments(self, sum: Optional[torch.Tensor], sum_sq: Optional[torch.Tensor] = None, *,
                     sum_logp: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
@@ -586,70 +621,19 @@ class RunPlan:
         """Accumulate posterior moments (include/ptrwm.h ptrwm_moments_args) in every following ``launch`` and
         ``split_moments``: ``sum`` / ``sum_sq`` [temps, dim] float64, ``sum_logp`` [temps] float64 and ``count`` [temps]
         int64 (both optional), all on the run's device and added to (+=).  ``temps`` (the first temperatures covered) is
-        the first extent of ``sum``.  ``set_moments(None)`` switches it off."""
-        if sum is None:
-            self._mom = None
-            return
-        Cn, T, D = self.shape
-        if sum.dim() != 2 or sum.shape[1] != D or not 1 <= sum.shape[0] <= T:
-            raise ValueError(f"moments sum must be [temps, {D}] with 1 <= temps <= {T}")
-        temps = sum.shape[0]
-        if sum_sq is None or tuple(sum_sq.shape) != (temps, D):
-            raise ValueError(f"moments sum_sq must be [{temps}, {D}]")
-        for name, t in (("sum_logp", sum_logp), ("count", count)):
-            if t is not None and tuple(t.shape) != (temps,):
-                raise ValueError(f"moments {name} must be [{temps}]")
-        if int(every) < 1:
-            raise ValueError("moments every must be >= 1")
-        for name, t in (("sum", sum), ("sum_sq", sum_sq), ("sum_logp", sum_logp), ("count", count)):
-            if t is not None and t.device != self.device:
-                raise ValueError(f"moments {name} is on {t.device}, state on {self.device}")
-        m = MomentsArgs()
-        m.struct_size = C.sizeof(MomentsArgs)
-        m.temps = temps
-        m.every = int(every)
-        m.sum = _require_device(sum, "moments sum", torch.float64)
-        m.sum_sq = _require_device(sum_sq, "moments sum_sq", torch.float64)
-        m.sum_logp = _opt(sum_logp, "moments sum_logp", torch.float64)
-        m.count = _opt(count, "moments count", torch.int64)
-        self._mom = (m, C.byref(m), (sum, sum_sq, sum_logp, count))
+        the first extent of ``sum``.  A plan holds ONE accumulator, pooled or per chain: this replaces whichever was set.
+        ``set_moments(None)`` switches pooled moments off."""
+        self._bind_moments("pooled", (), sum, sum_sq, sum_logp, count, every)
 
     def set_chain_moments(self, sum: Optional[torch.Tensor], sum_sq: Optional[torch.Tensor] = None, *,
                           sum_logp: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
                           every: int = 1) -> None:
         """Accumulate the moments of every chain on its own (include/ptrwm.h ptrwm_chain_moments_args) in every following
-        ``launch`` and ``split_chain_moments``: ``sum`` / ``sum_sq`` [n_chains, temps, dim] float64, ``sum_logp``
+        ``launch`` and ``split_moments``: ``sum`` / ``sum_sq`` [n_chains, temps, dim] float64, ``sum_logp``
         [n_chains, temps] float64 and ``count`` [temps] int64 (both optional), all on the run's device and added to (+=).
-        A plan accumulates pooled moments or per-chain ones, not both: this switches ``set_moments`` off.
-        ``set_chain_moments(None)`` switches it off."""
-        if sum is None:
-            self._cmom = None
-            return
-        Cn, T, D = self.shape
-        if sum.dim() != 3 or sum.shape[0] != Cn or sum.shape[2] != D or not 1 <= sum.shape[1] <= T:
-            raise ValueError(f"chain moments sum must be [{Cn}, temps, {D}] with 1 <= temps <= {T}")
-        temps = sum.shape[1]
-        if sum_sq is None or tuple(sum_sq.shape) != (Cn, temps, D):
-            raise ValueError(f"chain moments sum_sq must be [{Cn}, {temps}, {D}]")
-        if sum_logp is not None and tuple(sum_logp.shape) != (Cn, temps):
-            raise ValueError(f"chain moments sum_logp must be [{Cn}, {temps}]")
-        if count is not None and tuple(count.shape) != (temps,):
-            raise ValueError(f"chain moments count must be [{temps}]")
-        if int(every) < 1:
-            raise ValueError("chain moments every must be >= 1")
-        for name, t in (("sum", sum), ("sum_sq", sum_sq), ("sum_logp", sum_logp), ("count", count)):
-            if t is not None and t.device != self.device:
-                raise ValueError(f"chain moments {name} is on {t.device}, state on {self.device}")
-        m = ChainMomentsArgs()
-        m.struct_size = C.sizeof(ChainMomentsArgs)
-        m.temps = temps
-        m.every = int(every)
-        m.sum = _require_device(sum, "chain moments sum", torch.float64)
-        m.sum_sq = _require_device(sum_sq, "chain moments sum_sq", torch.float64)
-        m.sum_logp = _opt(sum_logp, "chain moments sum_logp", torch.float64)
-        m.count = _opt(count, "chain moments count", torch.int64)
-        self._cmom = (m, C.byref(m), (sum, sum_sq, sum_logp, count))
-        self._mom = None
+        A plan holds ONE accumulator, pooled or per chain: this replaces whichever was set.
+        ``set_chain_moments(None)`` switches per-chain moments off."""
+        self._bind_moments("chain", (self.shape[0],), sum, sum_sq, sum_logp, count, every)
 
     def init_states(self, lo: torch.Tensor, hi: torch.Tensor, *, attempt: int = 0, per_temperature: bool = False,
                     fallback: Optional[torch.Tensor] = None) -> None:
@@ -674,27 +658,18 @@ class RunPlan:
         if rc != 0:
             raise PTRWMError(rc, "ptrwm_init_states")
 
-    def split_chain_moments(self, step: int) -> None:
-        """Per-chain moments of the split step ``step`` just performed (ptrwm_split_chain_moments; device-step mode:
-        counter + step).  Enqueue after ``split_accept``.  No-op without ``set_chain_moments``."""
-        if self._cmom is None:
-            return
-        self._a.step0 = step
-        with self._guard:
-            rc = self._lib.ptrwm_split_chain_moments(self._refs[4], self.shape[2], self._cmom[1], _stream(self.device))
-        if rc != 0:
-            raise PTRWMError(rc, "ptrwm_split_chain_moments")
-
     def split_moments(self, step: int) -> None:
-        """Moments of the split step ``step`` just performed (ptrwm_split_moments; device-step mode: counter + step).
-        Enqueue after ``split_accept``.  No-op without ``set_moments``."""
+        """Moments of the split step ``step`` just performed, pooled or per chain as set (ptrwm_split_moments /
+        ptrwm_split_chain_moments; device-step mode: counter + step).  Enqueue after ``split_accept``.  No-op without an
+        accumulator."""
         if self._mom is None:
             return
+        name = self._MOMENT_KINDS[self._mom[0]][3]
         self._a.step0 = step
         with self._guard:
-            rc = self._lib.ptrwm_split_moments(self._refs[4], self.shape[2], self._mom[1], _stream(self.device))
+            rc = getattr(self._lib, name)(self._refs[4], self.shape[2], self._mom[2], _stream(self.device))
         if rc != 0:
-            raise PTRWMError(rc, "ptrwm_split_moments")
+            raise PTRWMError(rc, name)
 
     def launch(
         self,
@@ -761,18 +736,12 @@ class RunPlan:
             self._plain = plain
             if trace is not None and ext_prop is None and ext_u is None and ext_swap_u is None and accept_flags is None:
                 self._last_trace = (trace, trace_logp, trace_every)
-        if self._cmom is not None:
-            with self._guard:
-                rc = self._lib.ptrwm_run_with_chain_moments(self._refs[2], self._refs[3], self._refs[4], self._cmom[1], _stream(self.device))
-        elif self._mom is None:
-            with self._guard:
-                rc = self._lib.ptrwm_run(self._refs[2], self._refs[3], self._refs[4], _stream(self.device))
-        else:
-            with self._guard:
-                rc = self._lib.ptrwm_run_with_moments(self._refs[2], self._refs[3], self._refs[4], self._mom[1], _stream(self.device))
+        # ptrwm_run, or the accumulator's entry point with its struct in front of the stream
+        name, mom = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
+        with self._guard:
+            rc = getattr(self._lib, name)(self._refs[2], self._refs[3], self._refs[4], *mom, _stream(self.device))
         if rc != 0:
-            raise PTRWMError(rc, "ptrwm_run_with_chain_moments" if self._cmom is not None else
-                             ("ptrwm_run_with_moments" if self._mom is not None else "ptrwm_run"))
+            raise PTRWMError(rc, name)
 
     def _split_buffers(self):
         if getattr(self, "_split", None) is None:

@@ -106,6 +106,17 @@ def test_new_symbols_exist_and_the_mirror_has_the_c_layout(engine, tmp_path):
     assert fs == ["struct_size", "temps", "every", "sum", "sum_sq", "sum_logp", "count"]
 
 
+def test_the_two_accumulator_structs_are_one_layout(engine):
+    """MomentsArgs and ChainMomentsArgs: the same size and the same fields - names, offsets, types (the library checks and
+    reads both through one view, csrc/capi.hip)."""
+    a, b = engine.MomentsArgs, engine.ChainMomentsArgs
+    assert a is not b and C.sizeof(a) == C.sizeof(b)
+    assert [f[0] for f in a._fields_] == [f[0] for f in b._fields_]
+    for (name, ta), (_, tb) in zip(a._fields_, b._fields_):
+        assert ta is tb, name
+        assert getattr(a, name).offset == getattr(b, name).offset and getattr(a, name).size == getattr(b, name).size, name
+
+
 def _run_args(engine, n_temps, n_chains=4, n_steps=10):
     ra = engine.RunArgs()
     ra.struct_size = C.sizeof(engine.RunArgs)

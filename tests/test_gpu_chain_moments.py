@@ -13,7 +13,7 @@ import torch
 import helpers as H  # noqa: F401  (tests/ on the path)
 import ptrwm_hip as E
 from test_gpu_moments import CASES as POOLED_CASES
-from test_gpu_moments import FIELDS, _proposal, _target
+from test_gpu_moments import FIELDS, _check_against_trace, _proposal, _target, _trace_sums
 
 pytestmark = pytest.mark.gpu
 
@@ -346,3 +346,71 @@ def test_ess_predicts_the_spread_of_independent_runs(device):
     tol = 5.0 * np.sqrt(2.0 / (K - 1)) / np.sqrt(dim)
     print(f"ess check: mean 1/ESS {predicted:.4e}, mean se^2/var {observed:.4e}, ratio {ratio:.4f}, tolerance {tol:.3f}")
     assert abs(ratio - 1.0) <= tol, (predicted, observed, ratio, tol)
+
+
+def test_a_plan_holds_one_accumulator_and_either_setter_replaces_it(device):
+    """One RunPlan, 12 steps as three launches of 4 with a full trace at every = 2: pooled moments in the first launch,
+    per-chain ones in the second, none in the third.  Each set of accumulators holds the sums of its own launch alone, and
+    state, log-density and counters are those of the same steps without an accumulator.  And on a fresh plan,
+    set_chain_moments followed by set_moments accumulates the pooled sums and leaves the per-chain arrays alone."""
+    from target_distributions import MultivariateNormalTorch
+
+    dim, T, Cn, se, every, n = 5, 3, 8, 2, 2, 4
+    target = MultivariateNormalTorch(dim, mean=np.linspace(-1.0, 1.0, dim).tolist(),
+                                     cov=np.diag(np.linspace(0.5, 2.0, dim)).tolist(), device=device)
+    tgt = target.engine_target()  # (DiagGaussian)
+    betas = np.array([1.0, 0.5, 0.25], np.float32)
+    prop = _proposal("Normal", dim, betas, device)
+    x0 = np.random.default_rng(5).normal(0.0, 1.5, size=(Cn, T, dim)).astype(np.float32)
+
+    def make():
+        st = torch.tensor(x0, device=device)
+        lp = E.logdensity(tgt, st.view(-1, dim)).view(Cn, T).contiguous()
+        stats = {k: torch.zeros(Cn, T, dtype=dt, device=device) for k, dt in
+                 (("n_accept", torch.int64), ("sq_jump", torch.float64), ("swap_accept", torch.int64),
+                  ("last_swap_ordinal", torch.int64))}
+        plan = E.RunPlan(tgt, prop, state=st, logp=lp, beta=torch.tensor(betas, device=device), burn_in=0, swap_every=se,
+                         seed=321, **stats)
+        return plan, dict(stats, state=st, logp=lp)
+
+    def accumulators(*lead):
+        return {"sum": torch.zeros(*lead, T, dim, device=device, dtype=torch.float64),
+                "sum_sq": torch.zeros(*lead, T, dim, device=device, dtype=torch.float64),
+                "sum_logp": torch.zeros(*lead, T, device=device, dtype=torch.float64),
+                "count": torch.zeros(T, device=device, dtype=torch.int64)}
+
+    def bind(setter, m):
+        setter(m["sum"], m["sum_sq"], sum_logp=m["sum_logp"], count=m["count"], every=every)
+
+    def host(m):
+        return {k: v.cpu().numpy() for k, v in m.items()}
+
+    plan, out = make()
+    pooled, chain = accumulators(), accumulators(Cn)
+    rows = n // every
+    trace = torch.zeros(3 * rows, Cn, T, dim, device=device)
+    trace_logp = torch.zeros(3 * rows, Cn, T, device=device)
+    for k, switch in enumerate((lambda: bind(plan.set_moments, pooled), lambda: bind(plan.set_chain_moments, chain),
+                                lambda: plan.set_chain_moments(None))):
+        switch()
+        plan.launch(k * n, n, trace=trace, trace_logp=trace_logp, trace_row0=k * rows, trace_every=every)
+    ref_plan, ref = make()
+    for k in range(3):
+        ref_plan.launch(k * n, n)
+    torch.cuda.synchronize()
+    tr, trl = trace.cpu().numpy(), trace_logp.cpu().numpy()
+    want_pooled = _trace_sums(tr[:rows], trl[:rows], every=every, burn=0, temps=T)
+    # (the final values: nothing was added to either set outside its own launch - launch 3 included)
+    _check_against_trace(host(pooled), want_pooled)
+    _assert_bit_equal(host(chain), _sequential_sums(tr[rows:2 * rows], trl[rows:2 * rows], every=every, burn=0, temps=T))
+    for f in FIELDS:
+        assert torch.equal(out[f], ref[f]), f
+
+    plan2, _ = make()
+    pooled2, chain2 = accumulators(), accumulators(Cn)
+    bind(plan2.set_chain_moments, chain2)
+    bind(plan2.set_moments, pooled2)
+    plan2.launch(0, n)
+    torch.cuda.synchronize()
+    _check_against_trace(host(pooled2), want_pooled)  # (the same first four steps)
+    assert not any(v.any().item() for v in chain2.values())
