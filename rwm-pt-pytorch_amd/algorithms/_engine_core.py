@@ -277,7 +277,7 @@ class EngineRun:
     # ---- stepping ---------------------------------------------------------------------------
     def traced_rows(self, n_steps: int, every: int) -> int:
         """Rows a trace with thinning period `every` receives from the next n_steps steps."""
-        return (self.steps_done + n_steps) // every - self.steps_done // every
+        return ptrwm_hip.periodic_steps_in(self.steps_done, self.steps_done + n_steps, every)
 
     def advance(self, n_steps: int, trace: Optional[torch.Tensor] = None, trace_logp: Optional[torch.Tensor] = None,
                 trace_row0: int = 0, trace_every: int = 1) -> None:
@@ -398,7 +398,7 @@ class EngineRun:
             self._plan.split_accept(s, lp_new, swap_event_offset=self.manual_sweeps)
             self._plan.split_moments(s)
             self.steps_done += 1
-            if trace is not None and self.steps_done % trace_every == 0:
+            if trace is not None and ptrwm_hip.periodic_steps_in(s, s + 1, trace_every):
                 tc, tt = trace.shape[1], trace.shape[2]
                 trace[row] = self.state[:tc, :tt]
                 if trace_logp is not None:
@@ -417,11 +417,12 @@ class EngineRun:
     # ---- summaries (each read synchronises) ---------------------------------------------------
     @property
     def post_burn_steps(self) -> int:
-        return max(0, self.steps_done - self.burn_in)
+        return ptrwm_hip.periodic_steps_in(0, self.steps_done, 1, self.burn_in)
 
     def swap_events(self) -> int:
-        e = self.steps_done // self.swap_every - self.burn_in // self.swap_every
-        return max(0, e) + self.manual_sweeps if self.n_temps > 1 else 0
+        if self.n_temps < 2:
+            return 0
+        return ptrwm_hip.periodic_steps_in(0, self.steps_done, self.swap_every, self.burn_in) + self.manual_sweeps
 
     def swap_attempts_per_replica(self) -> int:
         """Swap attempts one ladder has made so far (deterministic, needs no device read)."""

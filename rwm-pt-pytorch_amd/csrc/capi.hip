@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "../../include/ptrwm.h"
+#include "schedule.h"
 #include "variants.h"
 
 namespace ptrwm {
@@ -242,6 +243,20 @@ static int check_target(const ptrwm_target_desc *t) {
   return PTRWM_OK;
 }
 
+// Checks of ptrwm_run_args that several entry points make (each where it always has: the order of an entry point's checks is
+// the code a caller with two defects gets).
+static bool has_abi_size(const ptrwm_run_args *args) { return args->struct_size == sizeof(ptrwm_run_args); }
+static bool temps_in_range(int n_temps) { return n_temps >= 1 && n_temps <= PTRWM_MAX_TEMPS; }
+static bool is_flag(int v) { return v == 0 || v == 1; }
+static bool swap_rule_known(const ptrwm_run_args *args) {
+  return (args->swap_mode == PTRWM_SWAP_EXCHANGE || args->swap_mode == PTRWM_SWAP_REFERENCE_COPY) &&
+         (args->swap_order == PTRWM_ORDER_SEQUENTIAL || args->swap_order == PTRWM_ORDER_EVEN_ODD);
+}
+// a fused run or a stand-alone sweep: float or double states, none of the split steps' fields
+static bool fused_fields_ok(const ptrwm_run_args *args) {
+  return is_flag(args->state_f64) && args->split_flags == 0 && args->device_step == nullptr;
+}
+
 // RoughCarpet: is the smallest of the three per-dimension mixture terms always < 2^-27 of the largest?
 // In log2 units a_k(x) = -0.5 log2(e) (x - m_k)^2 + log2 w_k; the three parabolas share their curvature, so every
 // difference a_j - a_k is LINEAR in x and g(x) = max_k a_k - min_k a_k is the maximum of six lines: convex and
@@ -347,12 +362,6 @@ __global__ void philox_raw_kernel(uint32_t *__restrict__ out, long long n, uint3
   out[4 * i + 3] = r.w;
 }
 
-// Is the step with step_counter sc past burn-in and a multiple of `period`?  The one rule of what happens every so many
-// steps once burn-in is over - a swap event (swap_every), an accumulated step of the moments (every) - host and device.
-__host__ __device__ inline bool periodic_step_due(long long sc, long long burn_in, long long period) {
-  return sc > burn_in && sc % period == 0;
-}
-
 // Stand-alone swap event: one workgroup per ladder, thread t = temperature t.  The decision is swap_decide(), the
 // code the fused kernel runs; the row permutation goes through LDS in column chunks (a permutation of rows can be
 // applied to every block of columns independently), so any (n_temps, dim) fits the 32 KB static buffer.
@@ -383,7 +392,7 @@ __global__ void __launch_bounds__(256) swap_sweep_kernel(SweepArgs a) {
     const long long s0 = *a.device_step + (long long)a.step, sc = s0 + 1;  // (a.step: this call's offset, include/ptrwm.h)
     if (!periodic_step_due(sc, a.burn_in, a.swap_every)) return;  // (grid-uniform)
     a.step = (unsigned long long)s0;
-    a.event_index = sc / a.swap_every - a.burn_in / a.swap_every - 1 + a.event_offset;
+    a.event_index = swap_event_number(sc, a.burn_in, a.swap_every) + a.event_offset;
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char s_sweep[];
   __shared__ float s_l[256], s_u[256];
@@ -489,9 +498,9 @@ __global__ void __launch_bounds__(64) split_accept_kernel(SplitAcceptArgs a) {
   const long long first = (long long)blockIdx.x * 64;
   if (first >= a.n_reps) return;
   if (a.device_step != nullptr) {
-    const long long sc = *a.device_step + a.step_offset + 1;  // step_counter of this step
-    a.count_on = sc > a.burn_in;
-    a.swap_due = a.n_temps > 1 && a.count_on && (sc % a.swap_every == 0);
+    const SplitStepDue due = split_step_due(*a.device_step + a.step_offset + 1, a.burn_in, a.swap_every, a.n_temps);
+    a.count_on = due.count_on;
+    a.swap_due = due.swap_due;
   }
   const int D = a.dim;
   const int n_rows = (a.n_reps - first < 64) ? (int)(a.n_reps - first) : 64;
@@ -831,7 +840,7 @@ int32_t ptrwm_has_quad_variant(int32_t target_kind, int32_t proposal_kind, int32
   if (target_kind < 0 || target_kind >= PTRWM_TARGET_COUNT) return 0;
   if (proposal_kind < 0 || proposal_kind >= PTRWM_PROPOSAL_COUNT) return 0;
   const int qi = quad_index_for(dim, n_temps, target_kind);
-  return qi >= 0 && quad_variants(target_kind, false).run[proposal_kind][qi] != nullptr ? 1 : 0;
+  return qi >= 0 && quad_variants(target_kind, 0).run[proposal_kind][qi] != nullptr ? 1 : 0;
 }
 
 int32_t ptrwm_device_simds(void *stream) {
@@ -841,7 +850,7 @@ int32_t ptrwm_device_simds(void *stream) {
 
 int32_t ptrwm_auto_form_for(int32_t target_kind, int32_t proposal_kind, int32_t dim, int32_t n_temps, int64_t n_chains,
                             int32_t n_simds) {
-  if (n_temps < 1 || n_temps > PTRWM_MAX_TEMPS || n_chains < 1 || n_simds < 1) return PTRWM_E_ARG;
+  if (!temps_in_range(n_temps) || n_chains < 1 || n_simds < 1) return PTRWM_E_ARG;
   const bool th = ptrwm_has_thread_variant(target_kind, proposal_kind, dim) != 0;
   const bool qu = ptrwm_has_quad_variant(target_kind, proposal_kind, dim, n_temps) != 0;
   if (!th && !qu) return PTRWM_E_NOVARIANT;
@@ -881,7 +890,7 @@ int32_t ptrwm_has_variant(int32_t target_kind, int32_t proposal_kind, int32_t di
   if (dim < 1 || dpi < 0) return 0;
   if (target_variants(target_kind).run(proposal_kind, dpi) != nullptr) return 1;
   const int qi = quad_index_for(dim, 1, target_kind);  // above width 64 the lane-split kernel is the fused kernel
-  return qi >= 0 && quad_variants(target_kind, false).run[proposal_kind][qi] != nullptr ? 1 : 0;
+  return qi >= 0 && quad_variants(target_kind, 0).run[proposal_kind][qi] != nullptr ? 1 : 0;
 }
 
 int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
@@ -901,82 +910,152 @@ int32_t ptrwm_run_with_chain_moments(const ptrwm_target_desc *target, const ptrw
 
 }  // extern "C"
 
-static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const MomSpec &spec, void *hip_stream) {
+// ---- ptrwm_run: check, choose the kernel, fill its arguments, cut the request into launches --------------------------------
+
+// swap events whose uniforms the caller supplies (ext_swap_u) in this request
+static long long ext_swap_events(const ptrwm_run_args *args) {
+  if (args->ext_prop == nullptr || args->n_temps < 2) return 0;
+  return periodic_steps_in(args->step0, args->n_steps, args->burn_in, args->swap_every);
+}
+
+// Job 1: everything that can be refused from the arguments alone.  *empty: a valid request with nothing to do.
+static int32_t check_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                         const MomSpec &spec, bool *empty) {
   if (proposal == nullptr || args == nullptr) return PTRWM_E_NULL;
   if (int rc = check_target(target)) return rc;
-  if (args->struct_size != sizeof(ptrwm_run_args)) return PTRWM_E_STRUCT;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
   if (proposal->kind < 0 || proposal->kind >= PTRWM_PROPOSAL_COUNT) return PTRWM_E_KIND;
-  if (args->n_temps < 1 || args->n_temps > PTRWM_MAX_TEMPS) return PTRWM_E_TEMPS;
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
   if (int rc = check_moments(args, spec)) return rc;
-  const ptrwm_moments_args *const mom = spec.m;
-  if (args->n_chains < 0 || args->n_steps < 0 || args->step0 < 0 || args->burn_in < 0 || args->swap_every < 1)
+  if (args->n_chains < 0 || args->n_steps < 0 || args->step0 < 0 || args->burn_in < 0 || args->swap_every < 1 ||
+      !swap_rule_known(args) || !fused_fields_ok(args))
     return PTRWM_E_ARG;
-  if (args->swap_mode != PTRWM_SWAP_EXCHANGE && args->swap_mode != PTRWM_SWAP_REFERENCE_COPY) return PTRWM_E_ARG;
-  if (args->swap_order != PTRWM_ORDER_SEQUENTIAL && args->swap_order != PTRWM_ORDER_EVEN_ODD) return PTRWM_E_ARG;
-  if ((args->state_f64 != 0 && args->state_f64 != 1) || args->split_flags != 0 || args->device_step != nullptr) return PTRWM_E_ARG;
-  if (args->n_chains == 0 || args->n_steps == 0) return PTRWM_OK;  // empty batch: nothing to touch
+  *empty = args->n_chains == 0 || args->n_steps == 0;  // empty batch: nothing to touch
+  if (*empty) return PTRWM_OK;
   if (args->state == nullptr || args->logp == nullptr || args->beta == nullptr || proposal->temp_scale == nullptr)
     return PTRWM_E_NULL;
   if (proposal->kind == PTRWM_PROPOSAL_LAPLACE && proposal->dim_scale == nullptr) return PTRWM_E_NULL;
   const bool ext = args->ext_prop != nullptr;
-  const bool f64 = args->state_f64 == 1;  // double state / trace / ext_prop (include/ptrwm.h): lane-split form only
-  if (f64 && ext && proposal->kind != PTRWM_PROPOSAL_NORMAL) return PTRWM_E_ARG;
+  // (double state / trace / ext_prop, include/ptrwm.h state_f64: external randoms for the Normal proposal only)
+  if (args->state_f64 == 1 && ext && proposal->kind != PTRWM_PROPOSAL_NORMAL) return PTRWM_E_ARG;
   if (ext && args->ext_u == nullptr) return PTRWM_E_NULL;
   if (args->trace != nullptr && (args->trace_chains < 1 || args->trace_temps < 1 || args->trace_row0 < 0 ||
                                  args->trace_temps > args->n_temps || args->trace_chains > args->n_chains ||
                                  args->trace_every < 0))
     return PTRWM_E_ARG;
+  return PTRWM_OK;
+}
 
-  const int dpi = width_index_for_dim(target->dim, target->kind);
-  if (dpi < 0) return PTRWM_E_DIM;
-  int rc_perm[3] = {0, 1, 2};
-  int alt = specialised_form(target, rc_perm);  // the kind's specialised functor
-  if (alt == 2) {
+// what of a launch depends on the kernel form alone
+struct FormShape {
+  bool quad;  // lane-split form
+  bool wide;  // exchange groups: one wavefront holding whole ladders, or ("wide") one workgroup per ladder
+  int ladders_per_group;
+};
+static FormShape form_shape(bool quad, int n_temps) {
+  const bool wide = n_temps * (quad ? kQuad : 1) > 64;
+  return {quad, wide, quad ? quad_ladders_per_group(n_temps) : (wide ? 1 : 64 / n_temps)};
+}
+
+// Job 2: what runs.  status != PTRWM_OK: nothing can, and why.
+struct RunChoice {
+  int32_t status;
+  RunLaunchFn fn;
+  int alt;         // the kind's specialised functor (quad_variants)
+  int rc_perm[3];  // alt == 2: the target's indices of the modes -m, 0, +m
+  FormShape shape;
+  int mode;        // kRunFull / kRunStream / kRunProd
+  unsigned n_blocks;
+};
+
+// the workgroup's LDS with the moments regions behind it, as the launcher will ask for it (variants.h LaunchShape)
+static unsigned moments_lds_bytes(const FormShape &f, int n_temps, int dim, int dpi, bool f64, const MomSpec &spec) {
+  KArgs k{};  // (the launch shapes read these five fields)
+  k.n_temps = n_temps;
+  k.dim = dim;
+  k.chains_per_wave = f.ladders_per_group;
+  k.full.mom_temps = spec.m->temps;
+  k.full.mom_chain = spec.per_chain ? 1 : 0;
+  return (f.quad ? quad_launch_shape(k, canon_width(dim), f64) : thread_launch_shape(k, kWidths[dpi].dp)).lds_moments;
+}
+
+static RunChoice choose_kernel(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                               const MomSpec &spec, hipStream_t stream) {
+  RunChoice c{};
+  auto refuse = [&c](int32_t status) {
+    c.status = status;
+    return c;
+  };
+  const int kind = target->kind, dim = target->dim, T = args->n_temps, pk = proposal->kind;
+  const bool f64 = args->state_f64 == 1;  // lane-split form only
+  const int dpi = width_index_for_dim(dim, kind);
+  if (dpi < 0) return refuse(PTRWM_E_DIM);
+  const int qi = quad_index_for(dim, T, kind);
+  c.alt = specialised_form(target, c.rc_perm);
+  if (c.alt == 2) {
     // the folded tables hold no state_f64 kernels (quad_rough_carpet_sym.hip): where they lack a kernel that the
     // two-term tables have for this launch, the two-term functor runs (the same bits)
-    const int qi = quad_index_for(target->dim, args->n_temps, target->kind);
-    const QuadVariants &q2 = quad_variants(target->kind, 2), &q1 = quad_variants(target->kind, 1);
-    const bool thread_ok = target_variants(target->kind, 2).run(proposal->kind, dpi) != nullptr ||
-                           target_variants(target->kind, 1).run(proposal->kind, dpi) == nullptr;
-    const bool quad_ok = qi < 0 || (f64 ? q2.run_f64 : q2.run)[proposal->kind][qi] != nullptr ||
-                         (f64 ? q1.run_f64 : q1.run)[proposal->kind][qi] == nullptr;
-    if (!thread_ok || !quad_ok) alt = 1;
+    const QuadVariants &q2 = quad_variants(kind, 2), &q1 = quad_variants(kind, 1);
+    const bool thread_ok = target_variants(kind, 2).run(pk, dpi) != nullptr || target_variants(kind, 1).run(pk, dpi) == nullptr;
+    const bool quad_ok = qi < 0 || (f64 ? q2.run_f64 : q2.run)[pk][qi] != nullptr || (f64 ? q1.run_f64 : q1.run)[pk][qi] == nullptr;
+    if (!thread_ok || !quad_ok) c.alt = 1;
   }
-  const RunLaunchFn thread_fn = target_variants(target->kind, alt).run(proposal->kind, dpi);  // null above width 64
-  RunLaunchFn fn = thread_fn;
-  RunLaunchFn other_fn = nullptr;  // the form NOT chosen, where AUTO chose and both exist (per-chain moments: below)
-  // lane-split form? (bit-identical results: a speed decision, see g_kernel_form - except above dim 64, where it is the
-  // only form)
-  bool quad = false;
-  {
-    const int qi = quad_index_for(target->dim, args->n_temps, target->kind);
-    const QuadVariants &qv = quad_variants(target->kind, alt);
-    const RunLaunchFn qfn = qi >= 0 ? (f64 ? qv.run_f64 : qv.run)[proposal->kind][qi] : nullptr;
-    const int form = __atomic_load_n(&g_kernel_form, __ATOMIC_RELAXED);
-    if (f64) {
-      fn = qfn;  // the only form with double state registers (null: ladder too long for a 512-thread workgroup)
-      quad = true;
-    } else if (qfn != nullptr && (fn == nullptr || form != PTRWM_FORM_THREAD)) {
-      quad = fn == nullptr || form == PTRWM_FORM_QUAD ||
-             auto_prefers_lane_split(target->dim, args->n_temps, args->n_chains, device_simds((hipStream_t)hip_stream));
-      if (quad) fn = qfn;
-      if (form == PTRWM_FORM_AUTO && thread_fn != nullptr) other_fn = quad ? thread_fn : qfn;
+  // The form (bit-identical results: a speed decision, see g_kernel_form - except above dim 64, where the lane-split form
+  // is the only one, and for double states, which only it holds in registers: null = ladder too long for its workgroup)
+  const RunLaunchFn thread_fn = target_variants(kind, c.alt).run(pk, dpi);  // null above width 64
+  const QuadVariants &qv = quad_variants(kind, c.alt);
+  const RunLaunchFn quad_fn = qi >= 0 ? (f64 ? qv.run_f64 : qv.run)[pk][qi] : nullptr;
+  const int form = __atomic_load_n(&g_kernel_form, __ATOMIC_RELAXED);
+  bool quad = f64;
+  if (!f64 && quad_fn != nullptr && (thread_fn == nullptr || form != PTRWM_FORM_THREAD))
+    quad = thread_fn == nullptr || form == PTRWM_FORM_QUAD || auto_prefers_lane_split(dim, T, args->n_chains, device_simds(stream));
+  c.fn = quad ? quad_fn : thread_fn;
+  if (c.fn == nullptr) return refuse(PTRWM_E_NOVARIANT);
+  // (an argument check, made here: a caller who also asks for a missing variant has always been told of that first)
+  if (ext_swap_events(args) > 0 && args->ext_swap_u == nullptr) return refuse(PTRWM_E_NULL);
+  c.shape = form_shape(quad, T);
+  if (spec.m != nullptr) {
+    unsigned need = moments_lds_bytes(c.shape, T, dim, dpi, f64, spec);
+    // Per-chain regions grow with the ladders of a group.  Where AUTO chose the form and both exist, a workgroup that needs
+    // more than half of the CU's LDS (one workgroup resident: one wave per SIMD in the thread form) - or does not fit at
+    // all - hands over to the other form if that one needs less (the same bits).  A pinned form is taken as it is.
+    const bool both = !f64 && form == PTRWM_FORM_AUTO && thread_fn != nullptr && quad_fn != nullptr;
+    if (spec.per_chain && both && need > kMaxLdsBytes / 2u) {
+      const FormShape other = form_shape(!quad, T);
+      const unsigned other_need = moments_lds_bytes(other, T, dim, dpi, f64, spec);
+      if (other_need < need) {
+        c.fn = quad ? thread_fn : quad_fn;
+        c.shape = other;
+        need = other_need;
+      }
+    }
+    if (need > kMaxLdsBytes) return refuse(PTRWM_E_ARG);
+  }
+  // moments are accumulated by the fixture / trace twin (kernel.h FullArgs)
+  const bool full = args->ext_prop != nullptr || args->trace != nullptr || args->accept_flags != nullptr || spec.m != nullptr;
+  // the streaming form for short launches of the one-thread-per-replica kernel (see kStreamMaxSteps above)
+  bool streaming = false;
+  if (!c.shape.quad && !full && has_stream_variant(kWidths[dpi].dp, kWidths[dpi].exact) && stream_layout_ok(args, dim, c.shape.ladders_per_group)) {
+    const int mode = __atomic_load_n(&g_stream_mode, __ATOMIC_RELAXED);
+    if (mode == PTRWM_STREAM_ON) {
+      streaming = true;
+    } else if (mode == PTRWM_STREAM_AUTO && args->n_steps <= kStreamMaxSteps) {
+      // state + log-density + the two statistics every launch touches (acceptance count, squared-jump sum)
+      const long long bytes = args->n_chains * (long long)T * (4ll * dim + 20ll);
+      streaming = bytes >= kStreamMinBytes && bytes <= kStreamMaxBytes;
     }
   }
-  if (fn == nullptr) return PTRWM_E_NOVARIANT;
-  const long long se = args->swap_every;
-  // moments are accumulated by the fixture / trace twin (kernel.h FullArgs)
-  const bool full = ext || args->trace != nullptr || args->accept_flags != nullptr || mom != nullptr;
-  // swap events before step_counter sc = multiples m*se with burn_in < m*se <= sc
-  auto events_upto = [&](long long sc) -> long long {
-    const long long e = sc / se - args->burn_in / se;
-    return e > 0 ? e : 0;
-  };
-  if (ext && args->n_temps > 1 && events_upto(args->step0 + args->n_steps) > events_upto(args->step0) &&
-      args->ext_swap_u == nullptr)
-    return PTRWM_E_NULL;
+  c.mode = full ? kRunFull : (streaming ? kRunStream : kRunProd);
+  const long long n_groups = (args->n_chains + c.shape.ladders_per_group - 1) / c.shape.ladders_per_group;
+  const long long n_blocks = c.shape.wide ? n_groups : (n_groups + kWavesPerBlock - 1) / kWavesPerBlock;  // wide: one group per block
+  if (n_blocks > 0x7fffffffll) return refuse(PTRWM_E_ARG);
+  c.n_blocks = (unsigned)n_blocks;
+  return c;
+}
 
+// Job 3: the kernel arguments that every launch of the request shares
+static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                        const MomSpec &spec, const RunChoice &c) {
   KArgs k;
   k.state = args->state;
   k.logp = args->logp;
@@ -993,126 +1072,69 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   k.swap_every = args->swap_every;
   k.swap_mode = args->swap_mode;
   k.swap_order = args->swap_order;
-  // exchange groups: one wavefront holding whole ladders, or ("wide") one workgroup per ladder
-  bool wide = false;
-  auto set_form = [&](bool q) {  // what of the launch depends on the kernel form
-    quad = q;
-    wide = args->n_temps * (q ? kQuad : 1) > 64;
-    k.chains_per_wave = q ? quad_ladders_per_group(args->n_temps) : (wide ? 1 : 64 / args->n_temps);
-  };
-  set_form(quad);
+  k.chains_per_wave = c.shape.ladders_per_group;
   k.k0 = (unsigned)(args->seed & 0xffffffffull);
   k.k1 = (unsigned)(args->seed >> 32);
   k.tp = make_tparams(target);
-  if (target->kind == PTRWM_TARGET_ROUGH_CARPET && alt == 2)  // the folded form reads the modes as -m, 0, +m
-    for (int i = 0; i < 3; ++i) k.tp.p[i] = target->p[rc_perm[i]], k.tp.p[3 + i] = target->p[3 + rc_perm[i]];
+  if (target->kind == PTRWM_TARGET_ROUGH_CARPET && c.alt == 2)  // the folded form reads the modes as -m, 0, +m
+    for (int i = 0; i < 3; ++i) k.tp.p[i] = target->p[c.rc_perm[i]], k.tp.p[3 + i] = target->p[3 + c.rc_perm[i]];
   k.pp.dim_scale = proposal->dim_scale;
   k.pp.inv_dim = proposal->inv_dim;
   k.full.trace = args->trace;
   k.full.trace_logp = args->trace_logp;
   k.full.trace_chains = args->trace != nullptr ? args->trace_chains : 0;
   k.full.trace_temps = args->trace_temps;
+  k.full.trace_every = args->trace_every > 1 ? args->trace_every : 1;
   k.full.n_raw_ext = ptrwm_ext_raw_per_step(proposal->kind, target->dim);
-  k.full.mom_sum = nullptr;
-  k.full.mom_sum_sq = nullptr;
-  k.full.mom_sum_logp = nullptr;
-  k.full.mom_count = nullptr;
+  const ptrwm_moments_args *const mom = spec.m;
+  k.full.mom_sum = nullptr;  // (set per launch: a launch without an accumulated step leaves the accumulators and its LDS alone)
+  k.full.mom_sum_sq = mom != nullptr ? mom->sum_sq : nullptr;
+  k.full.mom_sum_logp = mom != nullptr ? mom->sum_logp : nullptr;
+  k.full.mom_count = mom != nullptr ? (long long *)mom->count : nullptr;
   k.full.mom_steps = 0;
   k.full.mom_temps = mom != nullptr ? mom->temps : 0;
   k.full.mom_every = mom != nullptr ? mom->every : 1;
   k.full.steps_to_mom = 0;
   k.full.mom_chain = (mom != nullptr && spec.per_chain) ? 1 : 0;
-  if (mom != nullptr) {
-    // the workgroup's LDS with the moments regions behind it, as the launcher will ask for it (variants.h LaunchShape)
-    auto lds_need = [&]() {
-      return (quad ? quad_launch_shape(k, canon_width(target->dim), f64) : thread_launch_shape(k, kWidths[dpi].dp)).lds_moments;
-    };
-    unsigned need = lds_need();
-    // Per-chain regions grow with the ladders of a group.  Where AUTO chose the form and both exist, a workgroup that needs
-    // more than half of the CU's LDS (one workgroup resident: one wave per SIMD in the thread form) - or does not fit at
-    // all - hands over to the other form if that one needs less (the same bits).  A pinned form is taken as it is.
-    if (spec.per_chain && other_fn != nullptr && need > kMaxLdsBytes / 2u) {
-      const bool chosen = quad;
-      set_form(!chosen);
-      const unsigned other = lds_need();
-      if (other < need) {
-        fn = other_fn;
-        need = other;
-      } else {
-        set_form(chosen);
-      }
-    }
-    if (need > kMaxLdsBytes) return PTRWM_E_ARG;
-  }
+  return k;
+}
 
-  // the streaming form for short launches of the one-thread-per-replica kernel (see kStreamMaxSteps above)
-  bool stream = false;
-  if (!quad && !full && has_stream_variant(kWidths[dpi].dp, kWidths[dpi].exact) && stream_layout_ok(args, target->dim, k.chains_per_wave)) {
-    const int mode = __atomic_load_n(&g_stream_mode, __ATOMIC_RELAXED);
-    if (mode == PTRWM_STREAM_ON) {
-      stream = true;
-    } else if (mode == PTRWM_STREAM_AUTO && args->n_steps <= kStreamMaxSteps) {
-      // state + log-density + the two statistics every launch touches (acceptance count, squared-jump sum)
-      const long long bytes = args->n_chains * (long long)args->n_temps * (4ll * target->dim + 20ll);
-      stream = bytes >= kStreamMinBytes && bytes <= kStreamMaxBytes;
-    }
-  }
+static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                        const MomSpec &spec, void *hip_stream) {
+  bool empty = false;
+  if (int rc = check_run(target, proposal, args, spec, &empty)) return rc;
+  if (empty) return PTRWM_OK;
+  const RunChoice c = choose_kernel(target, proposal, args, spec, (hipStream_t)hip_stream);
+  if (c.status != PTRWM_OK) return c.status;
+  KArgs k = fill_kargs(target, proposal, args, spec, c);
+  t_last_launch_kind = c.shape.quad ? PTRWM_LAUNCH_QUAD : (c.mode == kRunStream ? PTRWM_LAUNCH_STREAM : PTRWM_LAUNCH_THREAD);
+  t_last_launch_functor = c.alt;
 
-  const long long n_waves = (args->n_chains + k.chains_per_wave - 1) / k.chains_per_wave;
-  const long long n_blocks = wide ? n_waves : (n_waves + kWavesPerBlock - 1) / kWavesPerBlock;  // wide: one group per block
-  if (n_blocks > 0x7fffffffll) return PTRWM_E_ARG;
-
-  // One launch covers a bounded amount of work (32-bit in-kernel counters; no multi-second kernels on a shared
-  // GPU): at most 2^16 steps and about 2^33 chain-steps (~0.2 s at 4e10/s).  Longer requests become back-to-back
-  // launches on the same stream; step0 carries the swap schedule and the RNG position, so the split is invisible.
-  // 2^16 steps also bound how stale a launch-start decision can get: the verdict whether a replica's squared jumps may be
-  // taken from the proposal (proposals.h kJumpTrust) is re-taken at least that often - a coordinate cannot drift by more
-  // than a few hundred typical increments in between, which keeps the two definitions of the jump within ~1e-4 relative.
-  const long long kMaxUnitsPerLaunch = 1ll << 33;
-  long long kMaxStepsPerLaunch = kMaxUnitsPerLaunch / (args->n_chains * (long long)args->n_temps);
-  if (kMaxStepsPerLaunch < 1) kMaxStepsPerLaunch = 1;
-  if (kMaxStepsPerLaunch > (1 << 16)) kMaxStepsPerLaunch = 1 << 16;
-  t_last_launch_kind = quad ? PTRWM_LAUNCH_QUAD : (stream ? PTRWM_LAUNCH_STREAM : PTRWM_LAUNCH_THREAD);
-  t_last_launch_functor = alt;
-  const long long te = args->trace_every > 1 ? args->trace_every : 1;
-  k.full.trace_every = (int)te;
-  const long long reps = args->n_chains * args->n_temps;
-  const long long raw = k.full.n_raw_ext;
-  long long done = 0;
-  while (done < args->n_steps) {
-    const long long step0 = args->step0 + done;
-    const long long n = (args->n_steps - done < kMaxStepsPerLaunch) ? args->n_steps - done : kMaxStepsPerLaunch;
-    const long long ev0 = events_upto(step0);
-    k.step0 = step0;
-    k.n_steps = (int)n;
-    const long long burn_left = args->burn_in - step0;
-    k.burn_left = burn_left <= 0 ? 0 : (burn_left > n ? (int)n : (int)burn_left);
-    k.first_swap_event = ev0 + args->swap_event_offset;
-    k.steps_to_swap = (int)(se - step0 % se);
-    k.full.ext_prop = ext ? args->ext_prop + done * reps * raw * (f64 ? 2 : 1) : nullptr;  // (f64: a double array)
+  // Job 4: one launch per cut of the schedule (schedule.h); the per-step arrays advance by the steps, rows and events done
+  const bool ext = args->ext_prop != nullptr;
+  const StepRequest req = {args->step0, args->n_steps, args->burn_in, args->swap_every, args->swap_event_offset,
+                           k.full.trace_every, args->trace_row0, k.full.mom_every};
+  const long long cap = max_steps_per_launch(args->n_chains, args->n_temps);
+  const long long reps = args->n_chains * args->n_temps, raw = k.full.n_raw_ext;
+  for (long long done = 0; done < args->n_steps; done += k.n_steps) {
+    const LaunchCut cut = launch_at(req, done, cap);
+    k.step0 = cut.step0;
+    k.n_steps = cut.n;
+    k.burn_left = cut.burn_left;
+    k.first_swap_event = cut.first_swap_event;
+    k.steps_to_swap = cut.steps_to_swap;
+    k.full.ext_prop = ext ? args->ext_prop + done * reps * raw * (args->state_f64 == 1 ? 2 : 1) : nullptr;  // (f64: a double array)
     k.full.ext_u = ext ? args->ext_u + done * reps : nullptr;
-    k.full.ext_swap_u = (ext && args->ext_swap_u != nullptr)
-                            ? args->ext_swap_u + (ev0 - events_upto(args->step0)) * args->n_chains * (args->n_temps - 1)
-                            : nullptr;
+    k.full.ext_swap_u = (ext && args->ext_swap_u != nullptr) ? args->ext_swap_u + cut.events_before * args->n_chains * (args->n_temps - 1) : nullptr;
     k.full.accept_flags = args->accept_flags != nullptr ? args->accept_flags + done * reps : nullptr;
-    // traced steps are those whose step_counter is a multiple of trace_every: rows before this launch
-    k.full.trace_row0 = args->trace_row0 + (step0 / te - args->step0 / te);
-    k.full.steps_to_trace = (int)(te - step0 % te);
-    if (mom != nullptr) {
-      // accumulated steps of this launch: step_counter in (max(step0, burn_in), step0 + n], a multiple of every
-      const long long me = mom->every, lo = args->burn_in > step0 ? args->burn_in : step0;
-      const long long m = (step0 + n) / me - lo / me;
-      const bool on = m > 0;  // (a launch with none leaves the accumulators and its LDS alone)
-      k.full.mom_steps = on ? m : 0;  // (per chain: count[t] += m; pooled: += live ladders x m)
-      k.full.mom_sum = on ? mom->sum : nullptr;
-      k.full.mom_sum_sq = mom->sum_sq;
-      k.full.mom_sum_logp = mom->sum_logp;
-      k.full.mom_count = (long long *)mom->count;
-      k.full.steps_to_mom = (int)(me - step0 % me);
+    k.full.trace_row0 = cut.trace_row0;
+    k.full.steps_to_trace = cut.steps_to_trace;
+    if (spec.m != nullptr) {
+      k.full.mom_steps = cut.mom_steps;  // (per chain: count[t] += mom_steps; pooled: += live ladders x mom_steps)
+      k.full.mom_sum = cut.mom_steps > 0 ? spec.m->sum : nullptr;
+      k.full.steps_to_mom = cut.steps_to_mom;
     }
-    const hipError_t err = fn(k, (unsigned)n_blocks, full ? kRunFull : (stream ? kRunStream : kRunProd), (hipStream_t)hip_stream);
-    if (err != hipSuccess) return PTRWM_E_LAUNCH;
-    done += n;
+    if (c.fn(k, c.n_blocks, c.mode, (hipStream_t)hip_stream) != hipSuccess) return PTRWM_E_LAUNCH;
   }
   return PTRWM_OK;
 }
@@ -1122,15 +1144,13 @@ extern "C" {
 int32_t ptrwm_swap_sweep(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
                          void *stream) {
   if (args == nullptr) return PTRWM_E_NULL;
-  if (args->struct_size != sizeof(ptrwm_run_args)) return PTRWM_E_STRUCT;
-  if ((args->state_f64 != 0 && args->state_f64 != 1) || args->split_flags != 0 || args->device_step != nullptr) return PTRWM_E_ARG;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
+  if (!fused_fields_ok(args)) return PTRWM_E_ARG;
   if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
-  if (args->n_temps < 1 || args->n_temps > PTRWM_MAX_TEMPS) return PTRWM_E_TEMPS;
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
   if (args->n_chains < 0 || args->n_chains > 0x7fffffffll || args->step0 < 0 || event_index < 0 || rng_stream < 1 ||
-      rng_stream > 15)
+      rng_stream > 15 || !swap_rule_known(args))
     return PTRWM_E_ARG;
-  if (args->swap_mode != PTRWM_SWAP_EXCHANGE && args->swap_mode != PTRWM_SWAP_REFERENCE_COPY) return PTRWM_E_ARG;
-  if (args->swap_order != PTRWM_ORDER_SEQUENTIAL && args->swap_order != PTRWM_ORDER_EVEN_ODD) return PTRWM_E_ARG;
   if (args->n_chains == 0 || args->n_temps == 1) return PTRWM_OK;  // nothing to exchange
   if (args->state == nullptr || args->logp == nullptr || args->beta == nullptr) return PTRWM_E_NULL;
   return launch_sweep(args, dim, event_index, rng_stream, nullptr, nullptr, (hipStream_t)stream);
@@ -1138,16 +1158,14 @@ int32_t ptrwm_swap_sweep(const ptrwm_run_args *args, int32_t dim, int64_t event_
 
 static int32_t split_common_checks(const ptrwm_run_args *args, int32_t dim) {
   if (args == nullptr) return PTRWM_E_NULL;
-  if (args->struct_size != sizeof(ptrwm_run_args)) return PTRWM_E_STRUCT;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
   if (args->state_f64 != 0) return PTRWM_E_ARG;  // float states only
   if ((args->split_flags & ~PTRWM_SPLIT_NO_SWEEP) != 0 || (args->split_flags != 0 && args->device_step == nullptr)) return PTRWM_E_ARG;
   if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
-  if (args->n_temps < 1 || args->n_temps > PTRWM_MAX_TEMPS) return PTRWM_E_TEMPS;
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
   if (args->n_chains < 0 || args->n_chains > 0x7fffffffll || args->step0 < 0 || args->burn_in < 0 ||
-      args->swap_every < 1)
+      args->swap_every < 1 || !swap_rule_known(args))
     return PTRWM_E_ARG;
-  if (args->swap_mode != PTRWM_SWAP_EXCHANGE && args->swap_mode != PTRWM_SWAP_REFERENCE_COPY) return PTRWM_E_ARG;
-  if (args->swap_order != PTRWM_ORDER_SEQUENTIAL && args->swap_order != PTRWM_ORDER_EVEN_ODD) return PTRWM_E_ARG;
   if (args->device_step != nullptr && (args->ext_prop != nullptr || args->ext_u != nullptr || args->ext_swap_u != nullptr))
     return PTRWM_E_ARG;  // device-step mode draws from Philox only
   return PTRWM_OK;
@@ -1193,10 +1211,8 @@ int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *propo
       accept_u == nullptr || logp_proposed == nullptr)
     return PTRWM_E_NULL;
   const long long sc = args->step0 + 1;  // step_counter of this step
-  const bool count_on = sc > args->burn_in;
-  const bool swap_due = args->n_temps > 1 && count_on && (sc % args->swap_every == 0);
-  const bool ext = args->ext_prop != nullptr;
-  if (swap_due && ext && args->ext_swap_u == nullptr) return PTRWM_E_NULL;
+  const SplitStepDue due = split_step_due(sc, args->burn_in, args->swap_every, args->n_temps);
+  if (due.swap_due && args->ext_prop != nullptr && args->ext_swap_u == nullptr) return PTRWM_E_NULL;
   SplitAcceptArgs a;
   a.state = args->state;
   a.logp = args->logp;
@@ -1210,8 +1226,8 @@ int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *propo
   a.n_reps = args->n_chains * (long long)args->n_temps;
   a.n_temps = args->n_temps;
   a.dim = dim;
-  a.count_on = count_on ? 1 : 0;
-  a.swap_due = swap_due ? 1 : 0;
+  a.count_on = due.count_on ? 1 : 0;
+  a.swap_due = due.swap_due ? 1 : 0;
   a.device_step = (const long long *)args->device_step;
   a.step_offset = args->step0;
   a.burn_in = args->burn_in;
@@ -1233,9 +1249,9 @@ int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *propo
     if (args->n_temps < 2 || (args->split_flags & PTRWM_SPLIT_NO_SWEEP) != 0) return PTRWM_OK;
     return launch_sweep(args, dim, 0, (int)kStreamSwap, proposals, args->sq_jump, (hipStream_t)stream);
   }
-  if (!swap_due) return PTRWM_OK;
+  if (!due.swap_due) return PTRWM_OK;
   // the swap event of this step: event number as ptrwm_run counts them, swap uniforms from the fused kernel's stream
-  const long long ev = sc / args->swap_every - args->burn_in / args->swap_every - 1 + args->swap_event_offset;
+  const long long ev = swap_event_number(sc, args->burn_in, args->swap_every) + args->swap_event_offset;
   return launch_sweep(args, dim, ev, (int)kStreamSwap, proposals, args->sq_jump, (hipStream_t)stream);
 }
 
@@ -1249,7 +1265,7 @@ int32_t ptrwm_split_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm
 
 int32_t ptrwm_split_advance(const ptrwm_run_args *args, void *stream) {
   if (args == nullptr) return PTRWM_E_NULL;
-  if (args->struct_size != sizeof(ptrwm_run_args)) return PTRWM_E_STRUCT;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
   if (args->device_step == nullptr) return PTRWM_E_NULL;
   hipLaunchKernelGGL(split_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (long long *)args->device_step,
                      args->n_steps > 0 ? (long long)args->n_steps : 1ll);
@@ -1258,11 +1274,11 @@ int32_t ptrwm_split_advance(const ptrwm_run_args *args, void *stream) {
 
 int32_t ptrwm_init_states(const ptrwm_run_args *args, int32_t dim, const ptrwm_init_args *init, void *stream) {
   if (args == nullptr || init == nullptr) return PTRWM_E_NULL;
-  if (args->struct_size != sizeof(ptrwm_run_args) || init->struct_size != sizeof(ptrwm_init_args)) return PTRWM_E_STRUCT;
+  if (!has_abi_size(args) || init->struct_size != sizeof(ptrwm_init_args)) return PTRWM_E_STRUCT;
   if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
-  if (args->n_temps < 1 || args->n_temps > PTRWM_MAX_TEMPS) return PTRWM_E_TEMPS;
-  if (args->n_chains < 0 || args->n_chains > 0x7fffffffll || (args->state_f64 != 0 && args->state_f64 != 1) ||
-      init->attempt < 0 || init->attempt > 65535 || (init->per_temperature != 0 && init->per_temperature != 1))
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
+  if (args->n_chains < 0 || args->n_chains > 0x7fffffffll || !is_flag(args->state_f64) || init->attempt < 0 ||
+      init->attempt > 65535 || !is_flag(init->per_temperature))
     return PTRWM_E_ARG;
   if (args->n_chains == 0) return PTRWM_OK;
   if (args->state == nullptr || init->lo == nullptr || init->hi == nullptr || (init->attempt > 0 && args->logp == nullptr))
@@ -1311,7 +1327,7 @@ int32_t ptrwm_propose(const ptrwm_proposal_desc *proposal, int32_t dim, int32_t 
   if (proposal == nullptr) return PTRWM_E_NULL;
   if (proposal->kind < 0 || proposal->kind >= PTRWM_PROPOSAL_COUNT) return PTRWM_E_KIND;
   if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
-  if (n_temps < 1 || n_temps > PTRWM_MAX_TEMPS) return PTRWM_E_TEMPS;
+  if (!temps_in_range(n_temps)) return PTRWM_E_TEMPS;
   if (n < 0) return PTRWM_E_ARG;
   if (n == 0) return PTRWM_OK;
   if (out == nullptr || proposal->temp_scale == nullptr) return PTRWM_E_NULL;

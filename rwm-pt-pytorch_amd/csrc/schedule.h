@@ -1,0 +1,100 @@
+// The step schedule of a run, stated once: which step counters are past burn-in, which of them carry a swap event, a traced
+// row or an accumulated step of the moments, how many of each lie in a range of steps, and where ptrwm_run cuts a long
+// request into launches.  Plain C++ (no HIP include): the kernels and host paths of capi.hip use it, and
+// tests/schedule_test.cpp replays it step by step on the CPU.
+//
+// Steps are numbered from 0; step s has step_counter sc = s + 1 (the reference counts a step when it has happened), so a
+// call with step0 covers the step counters (step0, step0 + n_steps].  What is periodic happens at the multiples of its
+// period, counted from the start of the RUN (not of the call): that is what makes a cut, or a resumed run, invisible.
+#pragma once
+
+#ifdef __HIPCC__
+#define PTRWM_HD __host__ __device__
+#else
+#define PTRWM_HD
+#endif
+
+namespace ptrwm {
+
+// Is the step with step_counter sc past burn-in and a multiple of `period`?  The one rule of what happens every so many
+// steps once burn-in is over: a swap event (swap_every), an accumulated step of the moments (every).  A traced row
+// (trace_every) is the same rule with burn_in = 0: burn-in steps are traced too.
+PTRWM_HD inline bool periodic_step_due(long long sc, long long burn_in, long long period) {
+  return sc > burn_in && sc % period == 0;
+}
+
+// due steps with step_counter <= sc: the multiples m * period with burn_in < m * period <= sc
+PTRWM_HD inline long long periodic_steps_upto(long long sc, long long burn_in, long long period) {
+  const long long e = sc / period - burn_in / period;
+  return e > 0 ? e : 0;
+}
+
+// ... with step_counter in (step0, step0 + n]: the due steps of n steps from step0
+PTRWM_HD inline long long periodic_steps_in(long long step0, long long n, long long burn_in, long long period) {
+  return periodic_steps_upto(step0 + n, burn_in, period) - periodic_steps_upto(step0, burn_in, period);
+}
+
+// steps from step0 to the first step whose step_counter is a multiple of `period` (1 = the step at step0 itself)
+PTRWM_HD inline long long steps_to_next_multiple(long long step0, long long period) { return period - step0 % period; }
+
+// 0-based number, since the start of the run, of the swap event of the swap step sc (periodic_step_due(sc, ...) holds)
+PTRWM_HD inline long long swap_event_number(long long sc, long long burn_in, long long swap_every) {
+  return sc / swap_every - burn_in / swap_every - 1;
+}
+
+// One split step (ptrwm_split_accept): do its acceptances count, and does a swap event follow it?
+struct SplitStepDue {
+  bool count_on, swap_due;
+};
+PTRWM_HD inline SplitStepDue split_step_due(long long sc, long long burn_in, long long swap_every, int n_temps) {
+  return {sc > burn_in, n_temps > 1 && periodic_step_due(sc, burn_in, swap_every)};
+}
+
+// One launch covers a bounded amount of work (32-bit in-kernel counters; no multi-second kernels on a shared GPU): at
+// most 2^16 steps and about 2^33 chain-steps (~0.2 s at 4e10/s).  Longer requests become back-to-back launches on the
+// same stream; step0 carries the swap schedule and the RNG position, so the split is invisible.
+// 2^16 steps also bound how stale a launch-start decision can get: the verdict whether a replica's squared jumps may be
+// taken from the proposal (proposals.h kJumpTrust) is re-taken at least that often - a coordinate cannot drift by more
+// than a few hundred typical increments in between, which keeps the two definitions of the jump within ~1e-4 relative.
+inline long long max_steps_per_launch(long long n_chains, int n_temps) {
+  const long long by_work = (1ll << 33) / (n_chains * (long long)n_temps);
+  return by_work < 1 ? 1 : (by_work > (1ll << 16) ? (1ll << 16) : by_work);
+}
+
+// The launch-invariant part of a request: ptrwm_run_args' schedule fields, trace_every already >= 1, moments_every = the
+// accumulator's `every` (1 without one: mom_steps / steps_to_mom are then not looked at).
+struct StepRequest {
+  long long step0, n_steps, burn_in, swap_every, swap_event_offset, trace_every, trace_row0, moments_every;
+};
+
+// What the step kernel of one launch of a request is told (kernel.h KArgs / FullArgs: the fields of the same names)
+struct LaunchCut {
+  long long step0;             // first step of the launch
+  int n;                       // its steps (<= cap)
+  int burn_left;               // ... of which still in burn-in (step_counter <= burn_in)
+  long long first_swap_event;  // number of the launch's first swap event (swap_event_offset included)
+  long long events_before;     // swap events of the request's earlier launches: where the launch's ext_swap_u starts
+  long long trace_row0;        // row of the launch's first traced step
+  long long mom_steps;         // accumulated steps of the launch
+  int steps_to_swap, steps_to_trace, steps_to_mom;  // countdowns to the first such step (1 = the launch's first step; > n: none)
+};
+
+// The launch of `r` that starts `done` steps into it, at most `cap` steps long (1 <= cap <= 2^16: max_steps_per_launch)
+inline LaunchCut launch_at(const StepRequest &r, long long done, long long cap) {
+  LaunchCut c;
+  c.step0 = r.step0 + done;
+  const long long n = r.n_steps - done < cap ? r.n_steps - done : cap;
+  c.n = (int)n;
+  const long long burn_left = r.burn_in - c.step0;
+  c.burn_left = burn_left <= 0 ? 0 : (burn_left > n ? (int)n : (int)burn_left);
+  c.events_before = periodic_steps_in(r.step0, done, r.burn_in, r.swap_every);
+  c.first_swap_event = periodic_steps_upto(c.step0, r.burn_in, r.swap_every) + r.swap_event_offset;
+  c.trace_row0 = r.trace_row0 + periodic_steps_in(r.step0, done, 0, r.trace_every);
+  c.mom_steps = periodic_steps_in(c.step0, n, r.burn_in, r.moments_every);
+  c.steps_to_swap = (int)steps_to_next_multiple(c.step0, r.swap_every);
+  c.steps_to_trace = (int)steps_to_next_multiple(c.step0, r.trace_every);
+  c.steps_to_mom = (int)steps_to_next_multiple(c.step0, r.moments_every);
+  return c;
+}
+
+}  // namespace ptrwm

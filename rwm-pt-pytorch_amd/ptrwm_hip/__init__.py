@@ -497,6 +497,13 @@ def philox_raw(seed: int, c0: int, c1: int, c2: int, c3: int, n: int, device) ->
     return out.to(torch.int64) & 0xFFFFFFFF
 
 
+def periodic_steps_in(a: int, b: int, period: int, burn_in: int = 0) -> int:
+    """Steps with step_counter in (a, b] that are past ``burn_in`` and a multiple of ``period``: the swap events
+    (swap_every), accumulated steps (every) and, with burn_in = 0, traced rows (trace_every) of the steps a .. b - 1.
+    The library's rule (csrc/schedule.h periodic_steps_in), for sizing buffers and counting on the host."""
+    return max(0, b // period - burn_in // period) - max(0, a // period - burn_in // period)
+
+
 class RunPlan:
     """The arguments of ``ptrwm_run`` that do not change between launches of one sampler run, validated and
     marshalled once.  ``launch`` only fills in the step range, the optional trace / fixture buffers and the
@@ -704,7 +711,7 @@ class RunPlan:
                       and accept_flags is None)
         if same_trace:
             te = a.trace_every
-            if trace.shape[0] < trace_row0 + ((step0 + n_steps) // te - step0 // te):
+            if trace.shape[0] < trace_row0 + periodic_steps_in(step0, step0 + n_steps, te):
                 raise ValueError("trace must be [rows >= trace_row0 + traced steps, trace_chains, trace_temps, dim]")
             a.trace_row0 = trace_row0
         elif not (plain and self._plain):
@@ -723,7 +730,7 @@ class RunPlan:
             a.trace_every, a.trace_chains, a.trace_temps = 0, 0, 0
             if trace is not None:
                 te = max(1, int(trace_every))
-                rows = (step0 + n_steps) // te - step0 // te  # steps of this call whose step_counter is a multiple of te
+                rows = periodic_steps_in(step0, step0 + n_steps, te)
                 if trace.dim() != 4 or trace.shape[3] != D or trace.shape[0] < trace_row0 + rows:
                     raise ValueError("trace must be [rows >= trace_row0 + traced steps, trace_chains, trace_temps, dim]")
                 a.trace_every = te

@@ -160,6 +160,80 @@ def test_validation_needs_no_gpu(engine):
     sp.swap_every, sp.n_chains = 1, 0
     assert lib.ptrwm_split_accept(C.byref(sp), 30, None, None, None, None) == 0  # empty batch
     assert lib.ptrwm_split_propose(C.byref(pd2), C.byref(sp), 30, None, None, None) == 0
+    # two defects at once: the code of the check that comes first in that entry point
+    for entry, table in TWO_DEFECT_CODES.items():
+        for defects, code in table.items():
+            assert two_defect_code(engine, lib, entry, defects) == code, (entry, defects)
+            for single in defects:  # (each of the two is a defect on its own, or the pair would not pin an order)
+                if (entry, single) not in (("ptrwm_init_states", "X"), ("ptrwm_swap_sweep", "E"), ("ptrwm_split_advance", "N")):
+                    assert two_defect_code(engine, lib, entry, single) < 0, (entry, single)
+
+
+# Callers with TWO defects: which one an entry point reports is part of its behaviour (its checks run in a fixed order, and
+# not in the same order everywhere).  The defects: T = n_temps 257, F = state_f64 2, M = swap_mode 7, E = swap_every 0,
+# S = struct_size 4, N = state NULL, X = split_flags 1 (without a device_step), D = dim 105, A = the accumulator's struct_size 4.
+# The codes were read off the library before its argument checks were given shared helpers.
+TWO_DEFECT_CODES = {
+    "ptrwm_run": {"TF": -3, "ME": -5, "SN": -6, "XD": -2},
+    "ptrwm_run_with_moments": {"TF": -3, "ME": -5, "SN": -6, "XD": -2, "AE": -6},
+    "ptrwm_run_with_chain_moments": {"TF": -3, "ME": -5, "SN": -6, "XD": -2, "AE": -6},
+    "ptrwm_swap_sweep": {"TF": -5, "ME": -5, "SN": -6, "XD": -5},
+    "ptrwm_split_propose": {"TF": -5, "ME": -5, "SN": -6, "XD": -5},
+    "ptrwm_split_accept": {"TF": -5, "ME": -5, "SN": -6, "XD": -5},
+    "ptrwm_split_moments": {"TF": -5, "ME": -5, "SN": -6, "XD": -5, "AE": -5},
+    "ptrwm_split_chain_moments": {"TF": -5, "ME": -5, "SN": -6, "XD": -5, "AE": -5},
+    "ptrwm_init_states": {"TF": -3, "SN": -6, "XD": -2},
+    "ptrwm_split_advance": {"SN": -6},
+}
+
+
+def two_defect_code(engine, lib, entry, defects):
+    """`entry` called with arguments that are valid but for `defects` (the pointers point at host memory that a refused call
+    never reads)."""
+    buf = C.create_string_buffer(64)
+    ptr = C.cast(buf, C.c_void_p)
+    td, pd, ra, init = engine.TargetDesc(), engine.ProposalDesc(), engine.RunArgs(), engine.InitArgs()
+    mom = (engine.ChainMomentsArgs if "chain" in entry else engine.MomentsArgs)()
+    td.kind, td.dim = engine.TARGET_ROUGH_CARPET, 30
+    pd.kind, pd.temp_scale = engine.PROPOSAL_NORMAL, ptr
+    ra.struct_size, ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = C.sizeof(engine.RunArgs), 4, 4, 10, 1
+    ra.state = ra.logp = ra.beta = ptr
+    mom.struct_size, mom.temps, mom.every, mom.sum, mom.sum_sq = C.sizeof(mom), 1, 1, ptr, ptr
+    init.struct_size, init.lo, init.hi = C.sizeof(engine.InitArgs), ptr, ptr
+    dim = 30
+    for d in defects:
+        if d == "T":
+            ra.n_temps = 257
+        elif d == "F":
+            ra.state_f64 = 2
+        elif d == "M":
+            ra.swap_mode = 7
+        elif d == "E":
+            ra.swap_every = 0
+        elif d == "S":
+            ra.struct_size = 4
+        elif d == "N":
+            ra.state = None
+        elif d == "X":
+            ra.split_flags = 1
+        elif d == "D":
+            td.dim = dim = 105
+        elif d == "A":
+            mom.struct_size = 4
+    t, p, a, m = C.byref(td), C.byref(pd), C.byref(ra), C.byref(mom)
+    calls = {
+        "ptrwm_run": lambda: lib.ptrwm_run(t, p, a, None),
+        "ptrwm_run_with_moments": lambda: lib.ptrwm_run_with_moments(t, p, a, m, None),
+        "ptrwm_run_with_chain_moments": lambda: lib.ptrwm_run_with_chain_moments(t, p, a, m, None),
+        "ptrwm_swap_sweep": lambda: lib.ptrwm_swap_sweep(a, dim, 0, 1, None),
+        "ptrwm_split_propose": lambda: lib.ptrwm_split_propose(p, a, dim, ptr, ptr, None),
+        "ptrwm_split_accept": lambda: lib.ptrwm_split_accept(a, dim, ptr, ptr, ptr, None),
+        "ptrwm_split_moments": lambda: lib.ptrwm_split_moments(a, dim, m, None),
+        "ptrwm_split_chain_moments": lambda: lib.ptrwm_split_chain_moments(a, dim, m, None),
+        "ptrwm_init_states": lambda: lib.ptrwm_init_states(a, dim, C.byref(init), None),
+        "ptrwm_split_advance": lambda: lib.ptrwm_split_advance(a, None),
+    }
+    return calls[entry]()
 
 
 def test_product_refuses_to_run_without_its_library_or_a_gpu(engine, tmp_path):

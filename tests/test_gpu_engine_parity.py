@@ -424,6 +424,57 @@ def test_launch_split_and_resume_are_invisible(device):
     assert np.allclose(long_run["sq_jump"], a2["sq_jump"] + b2["sq_jump"], rtol=1e-12)
 
 
+@pytest.mark.parametrize("variant", ["philox-thread", "philox-quad", "external"])
+def test_the_librarys_own_cut_moves_every_per_launch_offset(device, variant):
+    """A request that ptrwm_run cuts itself (66 000 steps: launches of 65 536 and 464) with everything in play that a
+    launch is handed an offset for - burn-in ending inside the second launch, a thinned trace with log-densities, accept
+    flags, per-chain moments and (external) the caller's random arrays - equals, bit for bit, the same two launches issued
+    by the caller: the second call at step0 = 65 536, trace_row0 advanced by the first call's rows, flags and randoms
+    sliced at the cut, the same statistics and moments tensors."""
+    N, CUT, BURN, SE, TE, ME = 66_000, 65_536, 65_540, 7, 4_099, 3
+    spec = H.target_spec("funnel_d1")  # the smallest dim: the per-launch offsets are what is tested, not the target
+    Cn, T, D = 3, 2, spec.dim
+    beta = np.float32([1.0, 0.3])
+    prop = H.proposal_spec("Normal", D, beta, base_variance_scalar=1.0)
+    st0, lp0 = start_state(spec, Cn, T, np.random.default_rng(2))
+    n_events, n_rows, n_mom = N // SE - BURN // SE, N // TE, N // ME - BURN // ME
+    assert (n_events, n_rows, CUT // TE, n_mom) == (66, 16, 15, 154)
+    ext = {}
+    if variant == "external":
+        rng = np.random.default_rng(3)
+        ext = dict(ext_prop=dev_t(rng.standard_normal((N, Cn, T, E.ext_raw_per_step(E.PROPOSAL_NORMAL, D))), device),
+                   ext_u=dev_t(rng.random((N, Cn, T)), device), ext_swap_u=dev_t(rng.random((n_events, Cn, T - 1)), device))
+
+    def execute(calls):  # calls: (step0, n_steps, rows before, swap events before) of each ptrwm_run
+        out = {"state": dev_t(st0, device), "logp": dev_t(lp0, device)}
+        for k, dt in (("n_accept", torch.int64), ("sq_jump", torch.float64), ("swap_accept", torch.int64), ("last_swap_ordinal", torch.int64)):
+            out[k] = torch.zeros(Cn, T, dtype=dt, device=device)
+        plan = E.RunPlan(spec.engine(device), prop.engine(device), beta=dev_t(beta, device), burn_in=BURN, swap_every=SE, seed=91,
+                         chain_offset=4, **out)
+        out.update(trace=torch.full((n_rows, Cn, T, D), np.nan, device=device), trace_logp=torch.full((n_rows, Cn, T), np.nan, device=device),
+                   flags=torch.full((N, Cn, T), 7, dtype=torch.uint8, device=device),
+                   sum=torch.zeros(Cn, T, D, dtype=torch.float64, device=device), sum_sq=torch.zeros(Cn, T, D, dtype=torch.float64, device=device),
+                   sum_logp=torch.zeros(Cn, T, dtype=torch.float64, device=device), count=torch.zeros(T, dtype=torch.int64, device=device))
+        plan.set_chain_moments(out["sum"], out["sum_sq"], sum_logp=out["sum_logp"], count=out["count"], every=ME)
+        for s0, n, rows, events in calls:
+            rand = {k: v[events:] if k == "ext_swap_u" else v[s0:s0 + n] for k, v in ext.items()}
+            plan.launch(s0, n, trace=out["trace"], trace_logp=out["trace_logp"], trace_row0=rows, trace_every=TE,
+                        accept_flags=out["flags"][s0:s0 + n], **rand)
+        torch.cuda.synchronize()
+        return {k: v.cpu().numpy() for k, v in out.items()}
+
+    form = {"philox-thread": E.FORM_THREAD, "philox-quad": E.FORM_QUAD, "external": E.FORM_AUTO}[variant]
+    with E.kernel_form(form):
+        one = execute([(0, N, 0, 0)])
+        two = execute([(0, CUT, 0, 0), (CUT, N - CUT, CUT // TE, 0)])  # (burn-in outlasts the first launch: no event before the cut)
+    for k in one:
+        assert one[k].tobytes() == two[k].tobytes(), k
+    # ... and it is not an empty agreement: every row, flag and accumulated step of both launches was written
+    assert np.all(one["count"] == n_mom) and np.all(one["flags"] <= 1)
+    assert np.all(np.isfinite(one["trace"])) and np.all(np.isfinite(one["trace_logp"]))
+    assert one["flags"][:CUT].any() and one["flags"][CUT:].any() and one["n_accept"].sum() > 0 and one["swap_accept"].sum() > 0
+
+
 # (target, proposal, temperatures, ladders, proposal arguments, does ptrwm_run's streaming form serve this shape?)
 STREAM_CASES = [
     ("rc15_d30", "Normal", 32, 2 * 37, dict(base_variance_scalar=2.38**2 / 30), True),   # BASELINE configs[2]'s shape

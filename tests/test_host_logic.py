@@ -451,3 +451,42 @@ def test_every_tool_at_least_parses():
         else:
             assert subprocess.run(["bash", "-n", path]).returncode == 0, path
             assert head.startswith("#!/bin/bash") and "\n#" in head, path
+
+
+def test_periodic_steps_in_is_the_brute_force_count():
+    """ptrwm_hip.periodic_steps_in - the host's one statement of 'multiples of period in (a, b] past burn-in' - against
+    counting step by step, and the run's counters that are written with it against their literal forms."""
+    import types
+
+    from algorithms._engine_core import EngineRun
+
+    for burn_in in range(10):
+        for period in range(1, 6):
+            due = [sc > burn_in and sc % period == 0 for sc in range(41)]
+            for a in range(14):
+                for b in range(a, 41):
+                    assert ptrwm_hip.periodic_steps_in(a, b, period, burn_in) == sum(due[a + 1:b + 1]), (a, b, period, burn_in)
+                    if burn_in == 0:
+                        assert ptrwm_hip.periodic_steps_in(a, b, period) == sum(due[a + 1:b + 1])
+            for done in range(41):
+                for T in (1, 3):
+                    run = types.SimpleNamespace(steps_done=done, burn_in=burn_in, swap_every=period, manual_sweeps=2, n_temps=T)
+                    assert EngineRun.post_burn_steps.fget(run) == max(0, done - burn_in)
+                    assert EngineRun.swap_events(run) == (sum(due[:done + 1]) + 2 if T > 1 else 0)
+                    assert EngineRun.traced_rows(run, 7, period) == sum((done + i) % period == 0 for i in range(1, 8))
+
+
+def test_step_schedule_header_against_brute_force(tmp_path):
+    """csrc/schedule.h - the schedule every kernel and host path of csrc/capi.hip cuts ptrwm_run's launches from - compiled
+    as plain C++ under AddressSanitizer and UBSan into tests/schedule_test.cpp, a program of its own that replays every launch
+    of a grid of requests (burn-in x the three periods x step0 x n_steps x the cut) step by step."""
+    import os
+    import subprocess
+
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "schedule_test.cpp")
+    exe = str(tmp_path / "schedule_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", src, "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert "schedule ok: 2092800 launches" in out.stdout
