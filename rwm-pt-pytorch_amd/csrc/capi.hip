@@ -349,6 +349,8 @@ static TParams make_tparams(const ptrwm_target_desc *t) {
   return tp;
 }
 
+static PParams make_pparams(const ptrwm_proposal_desc *proposal) { return {proposal->dim_scale, proposal->inv_dim}; }
+
 __global__ void split_advance_kernel(long long *device_step, long long n) { *device_step += n; }
 
 __global__ void philox_raw_kernel(uint32_t *__restrict__ out, long long n, uint32_t c0, uint32_t c1, uint32_t c2,
@@ -404,17 +406,12 @@ __global__ void __launch_bounds__(256) swap_sweep_kernel(SweepArgs a) {
   const bool live = tid < T;
   const int t = live ? tid : 0;
   float my_l = a.logp[chain * T + t];
+  // event 0 of the call, on the counter words of the fused kernel's swap uniforms with this call's stream (kernel.h swap_uniform_*)
+  const unsigned long long gchain = (unsigned long long)(a.chain_offset + chain);
   float us;
-  if (a.ext_swap_u != nullptr) {
-    us = (t < T - 1) ? a.ext_swap_u[chain * (T - 1) + t] : 2.0f;
-  } else {
-    // the counter layout of the fused kernel's swap stream (kernel.h): block 0 | step_hi, step, chain, t | stream | chain_hi
-    const unsigned long long gchain = (unsigned long long)(a.chain_offset + chain);
-    const u32x4 r = philox4x32_10((uint32_t)(a.step >> 32) << 16, (uint32_t)a.step, (uint32_t)gchain,
-                                  (uint32_t)t | ((uint32_t)a.rng_stream << 8) | ((uint32_t)(gchain >> 32) << 12), a.k0,
-                                  a.k1);
-    us = u01(r.x);
-  }
+  if (a.ext_swap_u != nullptr) us = swap_uniform_ext(a.ext_swap_u, 0, 0, chain, T, t);
+  else us = swap_uniform_philox(step_word_c0hi(a.step), step_word_c1(a.step), chain_word_c2(gchain),
+                                with_stream(chain_word_c3(gchain, (uint32_t)t), (uint32_t)a.rng_stream), a.k0, a.k1);
   if (live) {
     s_l[tid] = my_l;
     s_u[tid] = us;
@@ -465,8 +462,7 @@ __global__ void __launch_bounds__(256) swap_sweep_kernel(SweepArgs a) {
     if (pair_acc) {
       if (a.swap_accept != nullptr) a.swap_accept[rep] += 1;
       if (a.last_swap_ordinal != nullptr) {
-        const long long ord =
-            (a.swap_order == PTRWM_ORDER_SEQUENTIAL) ? a.event_index * (T - 1) + t + 1 : a.event_index + 1;
+        const long long ord = swap_attempt_ordinal(a.swap_order, a.event_index, T, t);
         if (ord > a.last_swap_ordinal[rep]) a.last_swap_ordinal[rep] = ord;
       }
     }
@@ -616,13 +612,13 @@ static int32_t launch_sweep(const ptrwm_run_args *args, int32_t dim, int64_t eve
   if (chunk > dim) chunk = dim;
   a.chunk = chunk;
   const unsigned lds = (unsigned)(chunk * args->n_temps * per_elem);
-  a.k0 = (unsigned)(args->seed & 0xffffffffull);
-  a.k1 = (unsigned)(args->seed >> 32);
+  a.k0 = philox_key(args->seed).k0;
+  a.k1 = philox_key(args->seed).k1;
   a.device_step = prev != nullptr ? (const long long *)args->device_step : nullptr;  // (split steps only)
   a.burn_in = args->burn_in;
   a.swap_every = args->swap_every;
   a.event_offset = args->swap_event_offset;
-  const unsigned block = (unsigned)((args->n_temps + 63) / 64 * 64);
+  const unsigned block = (unsigned)group_threads(args->n_temps, 1);  // one ladder per workgroup, thread t = temperature t
   if (f64)
     hipLaunchKernelGGL(swap_sweep_kernel<double>, dim3((unsigned)args->n_chains), dim3(block), lds, stream, a);
   else
@@ -691,7 +687,7 @@ __global__ void __launch_bounds__(256) split_chain_moments_kernel(SplitMomentsAr
 }
 
 // Starting points (ptrwm_init_states): row (c, t) of `state` drawn uniformly from the box [lo, hi], or set to `fallback`.
-// The draw is Philox stream kStreamInit (philox.h: the counter layout; include/ptrwm.h restates it), keyed by the GLOBAL chain
+// The draw is Philox stream kStreamInit (rng_layout.h: the counter layout; include/ptrwm.h restates it), keyed by the GLOBAL chain
 // id like every other random of a run, so the starts do not depend on how chains are sharded over devices.
 struct InitStatesArgs {
   void *state;                             // float (or double, F64) [n_reps, dim]
@@ -737,11 +733,10 @@ __global__ void __launch_bounds__(64) init_states_kernel(InitStatesArgs a) {
     } else {
       const const_float_ptr lo = uniform_vec(a.lo), hi = uniform_vec(a.hi);
       const long long chain = i / a.n_temps;
-      const uint32_t t = a.per_temperature ? (uint32_t)(i - chain * a.n_temps) : 0u;
       const unsigned long long g = (unsigned long long)(a.chain_offset + chain);
-      const uint32_t c2 = (uint32_t)g, c3 = t | (kStreamInit << 8) | ((uint32_t)(g >> 32) << 12);
+      const uint32_t c2 = chain_word_c2(g), c3 = init_word_c3(g, (uint32_t)(i - chain * a.n_temps), a.per_temperature != 0);  // (stream 3: rng_layout.h)
       for (int b = 0; 4 * b < D; ++b) {
-        const u32x4 r = philox4x32_10((uint32_t)b | ((uint32_t)a.attempt << 16), 0u, c2, c3, a.k0, a.k1);
+        const u32x4 r = philox4x32_10(init_word_c0(4 * b, a.attempt), 0u, c2, c3, a.k0, a.k1);  // word k: coordinate 4 b + k
         const uint32_t w[4] = {r.x, r.y, r.z, r.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -1073,13 +1068,12 @@ static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_de
   k.swap_mode = args->swap_mode;
   k.swap_order = args->swap_order;
   k.chains_per_wave = c.shape.ladders_per_group;
-  k.k0 = (unsigned)(args->seed & 0xffffffffull);
-  k.k1 = (unsigned)(args->seed >> 32);
+  k.k0 = philox_key(args->seed).k0;
+  k.k1 = philox_key(args->seed).k1;
   k.tp = make_tparams(target);
   if (target->kind == PTRWM_TARGET_ROUGH_CARPET && c.alt == 2)  // the folded form reads the modes as -m, 0, +m
     for (int i = 0; i < 3; ++i) k.tp.p[i] = target->p[c.rc_perm[i]], k.tp.p[3 + i] = target->p[3 + c.rc_perm[i]];
-  k.pp.dim_scale = proposal->dim_scale;
-  k.pp.inv_dim = proposal->inv_dim;
+  k.pp = make_pparams(proposal);
   k.full.trace = args->trace;
   k.full.trace_logp = args->trace_logp;
   k.full.trace_chains = args->trace != nullptr ? args->trace_chains : 0;
@@ -1183,10 +1177,8 @@ int32_t ptrwm_split_propose(const ptrwm_proposal_desc *proposal, const ptrwm_run
   if (args->ext_prop != nullptr && args->ext_u == nullptr) return PTRWM_E_NULL;
   const int dpi = width_index_for_dim(dim);
   if (dpi < 0) return PTRWM_E_DIM;
-  PParams pp;
-  pp.dim_scale = proposal->dim_scale;
-  pp.inv_dim = proposal->inv_dim;
-  const unsigned k0 = (unsigned)(args->seed & 0xffffffffull), k1 = (unsigned)(args->seed >> 32);
+  const PParams pp = make_pparams(proposal);
+  const unsigned k0 = philox_key(args->seed).k0, k1 = philox_key(args->seed).k1;
   const int n_raw = ptrwm_ext_raw_per_step(proposal->kind, dim);
   hipError_t err;
 #define PTRWM_SPLIT_CALL(P)                                                                                          \
@@ -1295,8 +1287,8 @@ int32_t ptrwm_init_states(const ptrwm_run_args *args, int32_t dim, const ptrwm_i
   a.dim = dim;
   a.per_temperature = init->per_temperature;
   a.attempt = init->attempt;
-  a.k0 = (unsigned)(args->seed & 0xffffffffull);
-  a.k1 = (unsigned)(args->seed >> 32);
+  a.k0 = philox_key(args->seed).k0;
+  a.k1 = philox_key(args->seed).k1;
   const long long grid = (a.n_reps + 63) / 64;  // one wavefront per tile of 64 rows
   if (grid > 0x7fffffffll) return PTRWM_E_ARG;
   const unsigned lds = split_tile_lds_bytes(dim);  // (at most 26 640 bytes: within the default dynamic-LDS allowance)
@@ -1334,11 +1326,9 @@ int32_t ptrwm_propose(const ptrwm_proposal_desc *proposal, int32_t dim, int32_t 
   if (proposal->kind == PTRWM_PROPOSAL_LAPLACE && proposal->dim_scale == nullptr) return PTRWM_E_NULL;
   const int dpi = width_index_for_dim(dim);
   if (dpi < 0) return PTRWM_E_DIM;
-  PParams pp;
-  pp.dim_scale = proposal->dim_scale;
-  pp.inv_dim = proposal->inv_dim;
+  const PParams pp = make_pparams(proposal);
   const int n_raw = ptrwm_ext_raw_per_step(proposal->kind, dim);
-  const unsigned k0 = (unsigned)(seed & 0xffffffffull), k1 = (unsigned)(seed >> 32);
+  const unsigned k0 = philox_key(seed).k0, k1 = philox_key(seed).k1;
   hipError_t err;
   switch (proposal->kind) {
     case PTRWM_PROPOSAL_NORMAL:
@@ -1361,7 +1351,7 @@ int32_t ptrwm_philox_raw(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, u
   if (out == nullptr) return PTRWM_E_NULL;
   const unsigned grid = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(philox_raw_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, out, (long long)n, c0, c1, c2,
-                     c3, (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32));
+                     c3, philox_key(seed).k0, philox_key(seed).k1);
   return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 

@@ -215,6 +215,49 @@ __device__ __forceinline__ bool ladder_votes_plain(bool mine, int first_lane, in
   return (against & ladder) == 0ull;
 }
 
+// Wide exchange groups (the workgroup: no ballot reaches a whole ladder): an objection is the event's own stamp (1 + its
+// index in the call) in the ladder's word `word`, written together with the published values - the one barrier `sync`
+// orders both, the vote has no barrier of its own - and nothing has to be armed again: the stamp of an earlier event is
+// not this event's.  (The word is read for the last time before this event's row-exchange barrier, the next objection is
+// written after it.)  Returns the ladder's verdict.
+template <class Sync>
+__device__ __forceinline__ bool wide_ladder_votes_plain(int *word, bool mine, int stamp, Sync sync) {
+  if (!mine) *word = stamp;
+  sync();
+  return *word != stamp;
+}
+
+// This thread's pair uniform in a swap event, in its two kinds (the caller keeps the `if`: folded into one function, the
+// pair moved the register allocation of 60 production kernels, profiles/r11_swap_event_once.txt).  External: row `event`
+// of the caller's ext_swap_u[event, chain, T - 1] (the stand-alone sweep is event 0 of its call); the last temperature has
+// no pair: 2.0, which no rule accepts.  Philox: the first word of the block of the step and chain words c0hi, c1, c2 and
+// c3 = the thread's base word with the stream of the swap uniforms (rng_layout.h).
+__device__ __forceinline__ float swap_uniform_ext(const float *__restrict__ ext_swap_u, long long event, long long n_chains,
+                                                  long long chain, int T, int t) {
+  return (t < T - 1) ? ext_swap_u[(event * n_chains + chain) * (T - 1) + t] : 2.0f;
+}
+__device__ __forceinline__ float swap_uniform_philox(uint32_t c0hi, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+  const u32x4 r = philox4x32_10(c0hi, c1, c2, c3, k0, k1);
+  return u01(r.x);
+}
+
+// The sequential scan of one ladder (slots base .. base + T - 1), from the carried state (car_l, car_i) the caller starts at
+// position 0: at pair j the carried state meets the untouched one of position j + 1, and accept(j, car_l, l_k) decides -
+// from a published threshold, a threshold built in place or the literal rule (swap_decide; quad.h's one-lane scan).
+// Every thread that runs the scan computes the same values, so the outcome for position j (which slot's vector lands
+// there) is written to LDS by all of them, identically, and each thread picks up its own position after the loop: one
+// ds_write per pair instead of a compare and three selects on t == j.
+// The loops stay where they are, each with its own unroll factor, and the body is a macro: as a function - a scan taking
+// the rule as a functor, or this body taking the carried state by reference - it moved the register allocation of
+// production kernels (profiles/r11_swap_event_once.txt).  OK: the pair accepted; IK: the slot of position j + 1, LK its
+// log-density; LANDED_J: position j's outcome; CAR_L / CAR_I: the carried state.
+#define PTRWM_SWAP_SCAN_PAIR(OK, IK, LK, LANDED_J, CAR_L, CAR_I) \
+  do {                                                           \
+    (LANDED_J) = (OK) ? (IK) : (CAR_I);                          \
+    (CAR_L) = (OK) ? (CAR_L) : (LK);                             \
+    (CAR_I) = (OK) ? (CAR_I) : (IK);                             \
+  } while (0)
+
 template <class Sync>
 __device__ __forceinline__ void swap_decide(int T, int t, int base, int slot, int swap_mode, int swap_order, int par,
                                             const float *__restrict__ beta, float beta_t, float us, const float *s_l,
@@ -236,9 +279,7 @@ __device__ __forceinline__ void swap_decide(int T, int t, int base, int slot, in
           const int ik = base + j + 1;
           const float lkj = s_l[ik];
           const bool ok = car_l < s_u[base + j];
-          landed[base + j] = ok ? ik : car_i;
-          car_l = ok ? car_l : lkj;
-          car_i = ok ? car_i : ik;
+          PTRWM_SWAP_SCAN_PAIR(ok, ik, lkj, landed[base + j], car_l, car_i);
         }
       } else {
         // the literal scan: every thread of the ladder replays the sweep from the published original values (uniform
@@ -250,12 +291,7 @@ __device__ __forceinline__ void swap_decide(int T, int t, int base, int slot, in
           const float bj = beta[j], bk = beta[j + 1];
           const bool ok = swap_accept_test(u, swap_log_prob(bj, bk, car_l, lk));
           const int ik = base + j + 1;
-          // Every thread of the ladder computes the same values, so the outcome for position j (which slot's vector
-          // lands there) is written to LDS by all of them, identically, and each thread picks up its own position
-          // after the loop: one ds_write per pair instead of a compare and three selects on t == j.
-          landed[base + j] = ok ? ik : car_i;
-          car_l = ok ? car_l : lk;
-          car_i = ok ? car_i : ik;
+          PTRWM_SWAP_SCAN_PAIR(ok, ik, lk, landed[base + j], car_l, car_i);
         }
       }
       landed[base + T - 1] = car_i;
@@ -519,6 +555,25 @@ constexpr int stream_waves_per_simd(int dp) {  // what two slabs per wave leave 
 // tools/kernel_stats.py --check keeps every kernel out of - even where LDS admits no second wave)
 constexpr int stream_register_waves(int dp) { return stream_waves_per_simd(dp) < 2 ? 2 : stream_waves_per_simd(dp); }
 
+// threads of this kernel's exchange group (rng_layout.h; the streaming form serves narrow ladders only: one wave, folded)
+template <bool STREAM>
+__device__ __forceinline__ int step_group_threads(int T) { return STREAM ? 64 : group_threads(T, 1); }
+
+// Rows of the FULL twins' per-step arrays (both step kernels).  The replica's index in step i of the launch - the row of
+// accept_flags and ext_u, and of ext_prop in units of n_raw_ext elements; the row of the trace a launch that has already
+// written rows_written rows writes for (chain, t).
+__device__ __forceinline__ long long step_replica_index(int i, long long n_chains, long long chain, int T, int t) {
+  return ((long long)i * n_chains + chain) * T + t;
+}
+template <class F>  // (words: 32-bit words per element of ext_prop - 2 for the double states of the lane-split form)
+__device__ __forceinline__ const float *ext_prop_row(F f, long long srep, int words) {
+  return f->ext_prop + srep * f->n_raw_ext * words;
+}
+template <class F>
+__device__ __forceinline__ long long trace_row_index(F f, int rows_written, long long chain, int t) {
+  return ((f->trace_row0 + rows_written) * f->trace_chains + chain) * f->trace_temps + t;
+}
+
 // DP    compile-time width of the per-thread register arrays (>= dim)
 // EXACT dim == DP is known at compile time: every per-dimension predicate folds away.  Otherwise
 //       dim is a wave-uniform run-time value, re-read (opaquely) every step so the compiler tests
@@ -672,7 +727,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     const long long live_chains = (a.n_chains - chain0 < cpw) ? (a.n_chains - chain0) : cpw;
     const int stage_total = (int)live_chains * T * D0;  // floats of this group's run
     float *__restrict__ gs = a.state + chain0 * T * (long long)D0;
-    const int nthr = wide ? ((T + 63) & ~63) : 64;  // threads of the group = of the workgroup
+    const int nthr = step_group_threads<STREAM>(T);  // threads of the group = of the workgroup
     int row_head = 0;
     if constexpr (!STREAM) {
       stage_copy<true>(s_stage, gs, stage_total, tid, nthr);
@@ -723,17 +778,17 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
   }
 
   const unsigned long long gchain = (unsigned long long)(a.chain_offset + chain);
-  RngCtx rc;
-  rc.c2 = (uint32_t)gchain;
+  RngCtx rc;  // (counter words: rng_layout.h)
+  rc.c2 = chain_word_c2(gchain);
   rc.k0 = a.k0;
   rc.k1 = a.k1;
-  const uint32_t c3_base = (uint32_t)t | ((uint32_t)(gchain >> 32) << 12);
+  const uint32_t c3_base = chain_word_c3(gchain, (uint32_t)t);
 
   unsigned n_acc = 0;
   {
     // parked in LDS (StepLds): the Philox word with the temperature index, the number of accepted
     // swaps of pair (t, t+1) and the index within this launch of the last swap event in which it accepted
-    const int gt = wide ? ((T + 63) & ~63) : 64;
+    const int gt = step_group_threads<STREAM>(T);
     int *const park = reinterpret_cast<int *>(STREAM ? s_dyn + wave * kWaveFloats + L::parked(gt) : s_stage + L::parked(gt)) + tid;
     park[0] = (int)c3_base;
     park[L::kSwapCount * gt] = 0;
@@ -797,7 +852,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     if (count_on) {
       n_acc += acc ? 1u : 0u;
       const int tid_q = thread_index_now(wave);  // (the slot's address is rebuilt here, not carried across the step)
-      const int gt_q = wide ? ((T + 63) & ~63) : 64;
+      const int gt_q = wide ? group_threads(T, 1) : 64;  // (not step_group_threads: that moved the production kernels' registers here)
       double *const sq_slot = reinterpret_cast<double *>(
                                   STREAM ? s_dyn + wave * kWaveFloats + L::sq_jump(64)
                                          : s_dyn + (wide ? 0 : wave * kWaveFloats) + L::sq_jump(gt_q)) +
@@ -807,7 +862,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     if constexpr (FULL) {
       const bool trace_now = a.full.trace != nullptr && countdown_due(to_trace, a.full.trace_every);
       if (trace_now && trace_on) {
-        const long long row = ((a.full.trace_row0 + trace_rows) * a.full.trace_chains + chain) * a.full.trace_temps + t;
+        const long long row = trace_row_index(&a.full, trace_rows, chain, t);
         float *__restrict__ tr = a.full.trace + row * D;
         PTRWM_DIM_LOOP(d, DP, D, { tr[d] = x[d]; })
         if (a.full.trace_logp != nullptr) a.full.trace_logp[row] = lp;
@@ -816,7 +871,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       // the state after the whole step
       if (a.full.mom_sum != nullptr && countdown_due(to_mom, a.full.mom_every) && count_on && live && t < a.full.mom_temps) {
         MomentsAcc m(&a.full, cpw, D);
-        m.reg = L::moments_region(s_dyn, wide, wide ? ((T + 63) & ~63) : 64, wave, m.doubles());
+        m.reg = L::moments_region(s_dyn, wide, step_group_threads<STREAM>(T), wave, m.doubles());
         const MomentsAcc::Row r = m.row(cw, t);
         PTRWM_DIM_LOOP(d, DP, D, {
           const double v = (double)x[d];
@@ -849,9 +904,9 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     int D;
     for (;; ++i, ++s) {
       count_on = i >= a.burn_left;
-      rc.c0hi = (uint32_t)(s >> 32) << 16;
-      rc.c1 = (uint32_t)s;
-      rc.c3 = c3_base | (kStreamMH << 8);
+      rc.c0hi = step_word_c0hi(s);
+      rc.c1 = step_word_c1(s);
+      rc.c3 = with_stream(c3_base, kStreamMH);
       // (at the register cap the chain word is made opaque per step: its product with the Philox multiplier is otherwise
       // hoisted out of the step loop as a 64-bit pair, which THERE is spilled and fetched back from scratch at the top of
       // every step - one v_mad_u64_u32 per step instead.  Only there: every kernel with registers to spare keeps the hoisted
@@ -862,9 +917,9 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       const float *ext_raw = nullptr;
       float ext_u = 0.0f;
       if constexpr (FULL) {
-        srep = ((long long)i * a.n_chains + chain) * T + t;
+        srep = step_replica_index(i, a.n_chains, chain, T, t);
         if (ext) {
-          ext_raw = a.full.ext_prop + srep * a.full.n_raw_ext;
+          ext_raw = ext_prop_row(&a.full, srep, 1);
           ext_u = a.full.ext_u[srep];
         }
       }
@@ -899,40 +954,32 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       // register (or a scratch slot) across the MH part of the step.
       const int tid_s = thread_index_now(wave);
       const int slot = wide ? tid_s : (tid_s & 63);  // this thread's slot in s_l / s_u and its row in s_stage
-      const int group_threads = wide ? ((T + 63) & ~63) : 64;
+      const int group_threads = step_group_threads<STREAM>(T);
       float *const rows = STREAM ? s_dyn + wave * kWaveFloats + cur * L::kSlabFloats
                                  : s_dyn + (wide ? 0 : (tid_s >> 6) * kWaveFloats);
       float *const s_l = STREAM ? s_dyn + wave * kWaveFloats + L::s_l(64) : rows + L::s_l(group_threads);
       float *const s_u = s_l + L::kSu * group_threads;
       int *const park = reinterpret_cast<int *>(s_l + L::kParked * group_threads) + slot;
       const uint32_t c3_s = (uint32_t)park[0];
-      const int t = (int)(c3_s & 0xffu);  // the temperature index, as the Philox counter holds it
+      const int t = temperature_of(c3_s);  // the temperature index, as the Philox counter holds it
       const int base = live ? slot - t : 0;            // slot of temperature 0 of this thread's ladder
       // src = slot whose post-MH vector ends up at this thread's temperature
       int src = slot;
       float my_l = lp_mh;
       bool pair_acc = false;  // did pair (t, t+1) accept (recorded on the thread of temperature t)
       float us;
-      if (ext) {
-        us = (t < T - 1) ? a.full.ext_swap_u[((long long)swap_in_call * a.n_chains + chain) * (T - 1) + t] : 2.0f;
-      } else {
-        const u32x4 r = philox4x32_10(rc.c0hi, rc.c1, rc.c2, c3_s | (kStreamSwap << 8), rc.k0, rc.k1);
-        us = u01(r.x);
-      }
+      if (ext) us = swap_uniform_ext(a.full.ext_swap_u, swap_in_call, a.n_chains, chain, T, t);
+      else us = swap_uniform_philox(rc.c0hi, rc.c1, rc.c2, with_stream(c3_s, kStreamSwap), rc.k0, rc.k1);
       // publish this thread's log-density and swap uniform; the sweep reads them back with broadcast ds_reads
       s_l[slot] = my_l;
       s_u[slot] = us;
       // may this ladder's sequential sweep take the threshold form in THIS event?  (swap_decide: a verdict of the ladder)
       const bool pair_plain = swap_pair_plain(T, t, STREAM ? db_s : sub_rn(beta_t, a.beta[t < T - 1 ? t + 1 : t]), my_l, us);
-      // (narrow groups: a ballot over the ladder's lanes.  Wide: an objection is the event's stamp in the ladder's word
-      // behind the parked words, written together with the published values - the one barrier orders both - and read
-      // for the last time before this event's row-exchange barrier, after which the next event may stamp it again)
+      // (narrow groups: a ballot over the ladder's lanes.  Wide: the ladder's word behind the parked words,
+      // wide_ladder_votes_plain)
       bool swap_plain;
       if (wide) {
-        int *const objection = reinterpret_cast<int *>(s_l + L::kVote * group_threads);
-        if (!pair_plain) *objection = swap_in_call + 1;
-        sync_group();
-        swap_plain = *objection != swap_in_call + 1;
+        swap_plain = wide_ladder_votes_plain(reinterpret_cast<int *>(s_l + L::kVote * group_threads), pair_plain, swap_in_call + 1, sync_group);
       } else {
         swap_plain = ladder_votes_plain(pair_plain, base, T);
         sync_group();
@@ -1000,7 +1047,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
         if (d < D2) row[d] = x[d];
     }
     sync_group();
-    const int nthr = wide2 ? ((T2 + 63) & ~63) : 64;
+    const int nthr = group_threads(T2, 1);
     if constexpr (FULL) {
       // every add of the launch is behind the barrier above: the group's partial sums go to HBM, once
       const kargs_full_ptr fa = &ae->full;
@@ -1027,11 +1074,11 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     const int tid_o = thread_index_now(wave);
     const int T_o = fresh_dim<false>(T);
     const long long rep = c0_out * T_o + (T_o > 64 ? tid_o : (tid_o & 63));  // live: replica index in group == tid
-    const int gt_o = T_o > 64 ? ((T_o + 63) & ~63) : 64;
+    const int gt_o = group_threads(T_o, 1);
     const int *const park = reinterpret_cast<const int *>(STREAM ? s_dyn + wave * kWaveFloats + L::parked(64)
                                                                  : s_dyn + (T_o > 64 ? 0 : (tid_o >> 6) * kWaveFloats) + L::parked(gt_o)) +
                             (T_o > 64 ? tid_o : (tid_o & 63));
-    const int t = park[0] & 0xff;
+    const int t = temperature_of((uint32_t)park[0]);
     const unsigned n_swap_acc = (unsigned)park[L::kSwapCount * gt_o];
     const int last_event = park[L::kLastEvent * gt_o];
     const int tid_g = T_o > 64 ? tid_o : (tid_o & 63);
@@ -1047,8 +1094,10 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       pend_sq = sq_old + sq;
       pend_ord_on = ae->last_swap_ordinal != nullptr && last_event >= 0;
       const long long ev = ae->first_swap_event + last_event;
-      pend_ord = (ae->swap_order == PTRWM_ORDER_SEQUENTIAL) ? ev * (T_o - 1) + t + 1 : ev + 1;
+      pend_ord = swap_attempt_ordinal(ae->swap_order, ev, T_o, t);
     } else {
+    // (the classic results store is written out here and in quad.h: as one function it moved the register allocation of
+    // both forms' production kernels, profiles/r11_swap_event_once.txt)
     ae->logp[rep] = lp;
     // statistics: read-modify-write only where this launch has something to add (a launch without a swap event - nine in
     // ten at one step per launch - then leaves the swap counters' cache lines alone)
@@ -1056,10 +1105,8 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     if (ae->sq_jump != nullptr && sq != 0.0) ae->sq_jump[rep] += sq;
     if (ae->swap_accept != nullptr && n_swap_acc != 0u) count_add(&ae->swap_accept[rep], (long long)n_swap_acc);
     if (ae->last_swap_ordinal != nullptr && last_event >= 0) {
-      // 1-based attempt ordinal counted from the start of the run.  Sequential order: T-1 attempts
-      // per event; even/odd events have a varying pair count, so the event number is recorded.
       const long long ev = ae->first_swap_event + last_event;
-      const long long ord = (ae->swap_order == PTRWM_ORDER_SEQUENTIAL) ? ev * (T_o - 1) + t + 1 : ev + 1;
+      const long long ord = swap_attempt_ordinal(ae->swap_order, ev, T_o, t);
       if (ord > ae->last_swap_ordinal[rep]) ae->last_swap_ordinal[rep] = ord;
     }
     }
@@ -1105,10 +1152,10 @@ __global__ void __launch_bounds__(kBlockThreads, standalone_min_waves(DP)) ptrwm
 #pragma unroll
   for (int d = 0; d < DP; ++d) x[d] = 0.0f;
   RngCtx rc;
-  rc.c0hi = (uint32_t)((unsigned long long)row >> 32) << 16;
-  rc.c1 = (uint32_t)row;  // "step" = row, chain 0
-  rc.c2 = 0;
-  rc.c3 = (uint32_t)t | (kStreamMH << 8);
+  rc.c0hi = step_word_c0hi((unsigned long long)row);
+  rc.c1 = step_word_c1((unsigned long long)row);  // "step" = row, chain 0
+  rc.c2 = chain_word_c2(0ull);
+  rc.c3 = with_stream(chain_word_c3(0ull, (uint32_t)t), kStreamMH);
   rc.k0 = k0;
   rc.k1 = k1;
   const float *er = ext_raw != nullptr ? ext_raw + i * n_raw_ext : nullptr;
@@ -1159,10 +1206,10 @@ __global__ void __launch_bounds__(64, standalone_min_waves(DP)) ptrwm_split_prop
   }
   const unsigned long long gchain = (unsigned long long)(chain_offset + chain);
   RngCtx rc;
-  rc.c0hi = (uint32_t)(step >> 32) << 16;
-  rc.c1 = (uint32_t)step;
-  rc.c2 = (uint32_t)gchain;
-  rc.c3 = (uint32_t)t | ((uint32_t)(gchain >> 32) << 12) | (kStreamMH << 8);
+  rc.c0hi = step_word_c0hi(step);
+  rc.c1 = step_word_c1(step);
+  rc.c2 = chain_word_c2(gchain);
+  rc.c3 = with_stream(chain_word_c3(gchain, (uint32_t)t), kStreamMH);
   rc.k0 = k0;
   rc.k1 = k1;
   const float *er = ext_raw != nullptr ? ext_raw + i * n_raw_ext : nullptr;

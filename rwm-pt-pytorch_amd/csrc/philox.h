@@ -5,22 +5,13 @@
 // at 65 536 chains x 32 temperatures that is not storable, so each
 // (chain, temperature, step) derives its own Philox block instead.
 //
-// Counter layout (shared with oracle/ptrwm_oracle.c, which restates it):
-//   c0 = block index within the step | (step >> 32) << 16
-//   c1 = step (low 32 bits, 0-based)
-//   c2 = global chain id (low 32 bits)
-//   c3 = temperature index | stream << 8 | (global chain id >> 32) << 12
-//   key = (seed low, seed high)
-// stream 0 = MH proposal + accept draws, stream 1 = swap uniforms, stream 2 = stand-alone swap sweeps (the binding's
-// default rng_stream for ptrwm_swap_sweep).
-// stream 3 = starting points (ptrwm_init_states, capi.hip).  They are drawn before step 0, so the step words are free:
-//   c0 = (coordinate / 4) | attempt << 16      one block per four coordinates, word d % 4 is coordinate d's
-//   c1 = 0
-//   c2 = global chain id (low 32 bits)
-//   c3 = (per_temperature ? temperature index : 0) | 3 << 8 | (global chain id >> 32) << 12
+// The counter layout - which words of the counter hold the step, the chain, the temperature and the stream - and the
+// helpers that build them: rng_layout.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "rng_layout.h"
 
 namespace ptrwm {
 
@@ -32,10 +23,6 @@ constexpr uint32_t kPhiloxM0 = 0xD2511F53u;
 constexpr uint32_t kPhiloxM1 = 0xCD9E8D57u;
 constexpr uint32_t kPhiloxW0 = 0x9E3779B9u;
 constexpr uint32_t kPhiloxW1 = 0xBB67AE85u;
-
-constexpr uint32_t kStreamMH = 0u;
-constexpr uint32_t kStreamSwap = 1u;
-constexpr uint32_t kStreamInit = 3u;
 
 // 32x32 -> 64 multiply by a round constant: one v_mad_u64_u32 (both halves, ~7 cycles per wave at 4 waves/SIMD).
 // Splitting it into v_mul_hi_u32 + v_mul_lo_u32 was measured SLOWER (v_mul_lo_u32 is quarter rate: 2.4 + 8.5

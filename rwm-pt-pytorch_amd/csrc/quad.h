@@ -761,11 +761,11 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
   }
 
   const unsigned long long gchain = (unsigned long long)(a.chain_offset + chain);
-  RngCtx rc;
-  rc.c2 = (uint32_t)gchain;
+  RngCtx rc;  // (counter words: rng_layout.h)
+  rc.c2 = chain_word_c2(gchain);
   rc.k0 = a.k0;
   rc.k1 = a.k1;
-  const uint32_t c3_base = (uint32_t)t | ((uint32_t)(gchain >> 32) << 12);
+  const uint32_t c3_base = chain_word_c3(gchain, (uint32_t)t);
 
   unsigned n_acc = 0, n_swap_acc = 0;
   int last_event = -1;
@@ -789,17 +789,17 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
     if (multiple) to_swap = a.swap_every;
     const bool swap_due = multiple && count_on && (T > 1);
 
-    rc.c0hi = (uint32_t)(s >> 32) << 16;
-    rc.c1 = (uint32_t)s;
-    rc.c3 = c3_base | (kStreamMH << 8);
+    rc.c0hi = step_word_c0hi(s);
+    rc.c1 = step_word_c1(s);
+    rc.c3 = with_stream(c3_base, kStreamMH);
 
     long long srep = 0;
     const float *ext_rep = nullptr;
     float ext_u = 0.0f;
     if constexpr (FULL) {
-      srep = ((long long)i * a.n_chains + chain) * T + t;
+      srep = step_replica_index(i, a.n_chains, chain, T, t);  // (kernel.h)
       if (ext) {
-        ext_rep = a.full.ext_prop + srep * a.full.n_raw_ext * SW;
+        ext_rep = ext_prop_row(&a.full, srep, SW);
         ext_u = a.full.ext_u[srep];
       }
     }
@@ -889,34 +889,24 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
       int src = slot;
       float my_l = lp_mh;
       bool pair_acc = false;
-      float us;
-      if (ext) {
-        us = (t < T - 1) ? a.full.ext_swap_u[((long long)swap_in_call * a.n_chains + chain) * (T - 1) + t] : 2.0f;
-      } else {
-        const u32x4 r = philox4x32_10(rc.c0hi, rc.c1, rc.c2, c3_base | (kStreamSwap << 8), rc.k0, rc.k1);
-        us = u01(r.x);
-      }
+      float us;  // (kernel.h)
+      if (ext) us = swap_uniform_ext(a.full.ext_swap_u, swap_in_call, a.n_chains, chain, T, t);
+      else us = swap_uniform_philox(rc.c0hi, rc.c1, rc.c2, with_stream(c3_base, kStreamSwap), rc.k0, rc.k1);
       // (the previous event's reads of s_l / the outcome slots are separated from these writes by its two row-exchange
       // synchronisations)
       s_l[slot_raw] = my_l;  // the four lanes of a quad write the same value
       s_u[slot_raw] = us;
       // may this ladder's sequential sweep take the threshold form in THIS event?  A verdict of the ladder alone, from the
       // values it enters the event with (kernel.h swap_pair_plain): narrow groups vote over the ladder's 4 T lanes of the
-      // wavefront; a workgroup holding several whole ladders votes through one flag per ladder behind the outcome slots
-      // (`base` is the ladder's first slot, unique to it)
+      // wavefront; a workgroup holding several whole ladders votes through one word per ladder behind the outcome slots
+      // (`base` is the ladder's first slot, unique to it; kernel.h wide_ladder_votes_plain)
       const bool pair_plain = swap_pair_plain(T, t, sub_rn(beta_t, a.beta[t < T - 1 ? t + 1 : t]), my_l, us);
       bool swap_plain;
       if (!wide) {
         swap_plain = ladder_votes_plain(pair_plain, 4 * base, 4 * T);
         sync_group();
       } else {
-        // An objection is the event's own stamp (1 + its index in the call) in the ladder's word, written together with
-        // the published values - the one barrier below orders both, the vote has no barrier of its own - and nothing has
-        // to be armed again: the stamp of an earlier event is not this event's.  (The word is read for the last time
-        // before this event's row-exchange barrier, the next objection is written after it.)
-        if (!pair_plain) s_landed[kToObjection * nslots + base] = swap_in_call + 1;
-        sync_group();
-        swap_plain = s_landed[kToObjection * nslots + base] != swap_in_call + 1;
+        swap_plain = wide_ladder_votes_plain(&s_landed[kToObjection * nslots + base], pair_plain, swap_in_call + 1, sync_group);
       }
       if (wide && a.swap_order == PTRWM_ORDER_SEQUENTIAL && a.swap_mode == PTRWM_SWAP_EXCHANGE) {
         // A wide ladder spans several wavefronts; the sequential sweep (kernel.h swap_decide: a scan over the ladder's
@@ -937,9 +927,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
               const float lk = s_l[b0 + j + 1];
               const float thr = fmaf(-hw_ln(s_u[b0 + j]), __builtin_amdgcn_rcpf(sub_rn(a.beta[j], a.beta[j + 1])), lk);
               const bool ok = car_l < thr;
-              s_landed[b0 + j] = ok ? b0 + j + 1 : car_i;
-              car_l = ok ? car_l : lk;
-              car_i = ok ? car_i : b0 + j + 1;
+              PTRWM_SWAP_SCAN_PAIR(ok, b0 + j + 1, lk, s_landed[b0 + j], car_l, car_i);  // (kernel.h)
             }
           } else {
 #pragma unroll 2
@@ -947,9 +935,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
               const float lk = s_l[b0 + j + 1];
               const float u = s_u[b0 + j];
               const bool ok = swap_accept_test(u, swap_log_prob(a.beta[j], a.beta[j + 1], car_l, lk));
-              s_landed[b0 + j] = ok ? b0 + j + 1 : car_i;
-              car_l = ok ? car_l : lk;
-              car_i = ok ? car_i : b0 + j + 1;
+              PTRWM_SWAP_SCAN_PAIR(ok, b0 + j + 1, lk, s_landed[b0 + j], car_l, car_i);
             }
           }
           s_landed[b0 + T - 1] = car_i;
@@ -1003,7 +989,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
     if constexpr (FULL) {
       const bool trace_now = a.full.trace != nullptr && countdown_due(to_trace, a.full.trace_every);
       if (trace_now && trace_on) {
-        const long long row = ((a.full.trace_row0 + trace_rows) * a.full.trace_chains + chain) * a.full.trace_temps + t;
+        const long long row = trace_row_index(&a.full, trace_rows, chain, t);  // (kernel.h)
         state_t *__restrict__ tr = reinterpret_cast<state_t *>(a.full.trace) + row * D + l.d0;
 #pragma unroll
         for (int j = 0; j < W; ++j)
@@ -1055,14 +1041,14 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
     }
     stage_copy<false>(rows_f, gs, stage_total, tid, gthreads);
   }
-  if (live && l.q == 0) {
+  if (live && l.q == 0) {  // (the thread form's epilogue, kernel.h)
     ae->logp[rep] = lp;
     if (ae->n_accept != nullptr && n_acc != 0u) count_add(&ae->n_accept[rep], (long long)n_acc);  // (kernel.h: only where there is a delta)
     if (ae->sq_jump != nullptr && sq != 0.0) ae->sq_jump[rep] += sq;
     if (ae->swap_accept != nullptr && n_swap_acc != 0u) count_add(&ae->swap_accept[rep], (long long)n_swap_acc);
     if (ae->last_swap_ordinal != nullptr && last_event >= 0) {
       const long long ev = ae->first_swap_event + last_event;
-      const long long ord = (ae->swap_order == PTRWM_ORDER_SEQUENTIAL) ? ev * (T - 1) + t + 1 : ev + 1;
+      const long long ord = swap_attempt_ordinal(ae->swap_order, ev, T, t);
       if (ord > ae->last_swap_ordinal[rep]) ae->last_swap_ordinal[rep] = ord;
     }
   }

@@ -132,7 +132,7 @@ inline LaunchShape with_moments(unsigned block, unsigned lds, bool wide, const K
 // thread form.  Narrow ladders: four independent one-wave groups per workgroup; wide (n_temps > 64): the waves the ladder needs
 inline LaunchShape thread_launch_shape(const KArgs &a, int dp) {
   const bool wide = a.n_temps > 64;
-  const unsigned block = wide ? (unsigned)((a.n_temps + 63) & ~63) : (unsigned)kBlockThreads;
+  const unsigned block = wide ? (unsigned)group_threads(a.n_temps, 1) : (unsigned)kBlockThreads;
   return with_moments(block, StepLdsWords::bytes((int)block, dp, false, wide), wide, a);
 }
 using StepKernelFn = void (*)(const KArgs);
@@ -240,25 +240,12 @@ PTRWM_QUAD_WIDTHS_EXTRA(PTRWM_X_QOK)
 // 256-thread workgroup.  Longer ladders: the group is the workgroup; it holds as many whole ladders as make the best use
 // of its lanes within 256 threads (T = 17: three ladders in 204 of 256 lanes instead of one in 68 of 128), one ladder
 // in 4 T threads rounded up to whole waves when even one does not fit.
+static_assert(kPackThreads == kBlockThreads, "rng_layout.h packs the ladders of a wide lane-split group into one workgroup");
 inline int quad_ladders_per_group(int n_temps) {
   const int need = 4 * n_temps;
-  if (need <= 64) return 64 / need;
-  int best_k = 1;
-  double best_use = 0.0;
-  for (int k = 1; k * need <= kBlockThreads; ++k) {
-    const int b = (k * need + 63) & ~63;
-    const double use = (double)(k * need) / b;
-    if (use > best_use + 1e-9) {
-      best_use = use;
-      best_k = k;
-    }
-  }
-  return best_k;
+  return need <= 64 ? 64 / need : packed_ladders_per_group(need);
 }
-inline int quad_block_threads(int n_temps) {
-  const int need = 4 * n_temps;
-  return need <= 64 ? kBlockThreads : ((quad_ladders_per_group(n_temps) * need + 63) & ~63);
-}
+inline int quad_block_threads(int n_temps) { return 4 * n_temps <= 64 ? kBlockThreads : group_threads(n_temps, 4); }
 
 // the kernel with this dim compiled in if there is one, else the generic kernel of the dim's class, in the smallest
 // workgroup class that holds the ladder; -1 if none

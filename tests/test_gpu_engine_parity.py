@@ -395,6 +395,62 @@ def test_philox_mode_vs_oracle(device, tkey, pkind, T, Cn, pkw, form):
                                   swap_mode=E.SWAP_MODES[mode], swap_order=E.SWAP_ORDERS[order], segment=PHILOX_SEGMENT)
 
 
+def _split_steps(device, spec, prop, st0, lp0, beta, step0, n_steps, **plan_kw):
+    """ptrwm_run's steps [step0, step0 + n_steps) one split step at a time, the library's own log-density in between
+    (the drive of test_split_step_reproduces_the_fused_kernel, Philox randoms): numpy results as helpers.gpu_run's."""
+    Cn, T, D = st0.shape
+    st, lp = dev_t(st0, device), dev_t(lp0, device).reshape(Cn, T).contiguous()
+    stats = {k: torch.zeros(Cn, T, dtype=(torch.float64 if k == "sq_jump" else torch.int64), device=device)
+             for k in ("n_accept", "sq_jump", "swap_accept", "last_swap_ordinal")}
+    plan = E.RunPlan(None, prop.engine(device), state=st, logp=lp, beta=dev_t(beta, device), **plan_kw, **stats)
+    tgt = spec.engine(device)
+    for s in range(step0, step0 + n_steps):
+        props = plan.split_propose(s)
+        plan.split_accept(s, E.logdensity(tgt, props.view(-1, D)).view(Cn, T))
+    torch.cuda.synchronize()
+    out = {k: v.cpu().numpy() for k, v in stats.items()}
+    out["state"], out["logp"] = st.cpu().numpy(), lp.cpu().numpy()
+    return out
+
+
+def test_step_and_chain_counters_cross_their_high_words_inside_a_launch(device):
+    """The Philox counter holds the step index and the global chain id as two words each (csrc/rng_layout.h), built in six
+    kernels.  Here the step's low word wraps and its high word turns on INSIDE one launch (step0 = 2^32 - 6, 12 steps,
+    burn-in over two steps into it, a swap event on either side of the boundary) while half of the 16 chains lie on each
+    side of chain id 2^32: the thread kernel, its streaming twin, the lane-split kernel and the split-step kernels
+    (proposal, Metropolis, sweep) give the same bits - states, log-densities and all four statistics - and those follow
+    the oracle's restatement of the layout decision for decision."""
+    tkey, pkind, T, _, pkw = next(s for s in SWEEP if s[0] == "beta_d5")  # dim 5 compiled in: a streaming twin exists
+    T, Cn, N, se = 4, 16, 12, 3  # 16 ladders of 4: one whole wave group, what the streaming form serves
+    step0, chain_offset = 2**32 - 6, 2**32 - 8
+    spec = H.target_spec(tkey)
+    beta = (0.05 ** (np.arange(T) / (T - 1))).astype(np.float32)
+    prop = H.proposal_spec(pkind, spec.dim, beta, **pkw)
+    st, lp = start_state(spec, Cn, T, np.random.default_rng(17))
+    sched = dict(burn_in=step0 + 2, swap_every=se, seed=0xC0FFEE1234, chain_offset=chain_offset,
+                 swap_mode=E.SWAP_MODES["exchange"], swap_order=E.SWAP_ORDERS["sequential"])
+    kw = dict(state=st, logp=lp, beta=beta, step0=step0, n_steps=N, **sched)
+    assert E.has_stream_variant(spec.kind, prop.kind, spec.dim) and E.has_quad_variant(spec.kind, prop.kind, spec.dim, T)
+    runs = {}
+    with E.kernel_form(E.FORM_THREAD):
+        with E.stream_mode(E.STREAM_OFF):
+            runs["thread"] = gpu_run(spec, prop, device, **kw)
+            assert E.last_launch_kind() == E.LAUNCH_THREAD
+        with E.stream_mode(E.STREAM_ON):
+            runs["streaming"] = gpu_run(spec, prop, device, **kw)
+            assert E.last_launch_kind() == E.LAUNCH_STREAM
+    with E.kernel_form(E.FORM_QUAD):
+        runs["lane-split"] = gpu_run(spec, prop, device, **kw)
+        assert E.last_launch_kind() == E.LAUNCH_QUAD
+    runs["split steps"] = _split_steps(device, spec, prop, st, lp, beta, step0, N, **sched)
+    for name, r in runs.items():
+        for k in ("state", "logp", "n_accept", "sq_jump", "swap_accept", "last_swap_ordinal"):
+            assert r[k].tobytes() == runs["thread"][k].tobytes(), (name, k)
+    assert runs["thread"]["n_accept"].sum() > 0 and runs["thread"]["swap_accept"].sum() > 0
+    with E.kernel_form(E.FORM_THREAD), E.stream_mode(E.STREAM_OFF):
+        H.check_parity_philox(gpu_runner(spec, prop, device), spec, prop, state=st, logp=lp, beta=beta, step0=step0, n_steps=N, **sched)
+
+
 def test_launch_split_and_resume_are_invisible(device):
     """n steps in one call == the same steps in several calls (step0 carries the schedule and the RNG position)."""
     spec = H.target_spec("rc15_d30")

@@ -490,3 +490,20 @@ def test_step_schedule_header_against_brute_force(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "schedule ok: 2092800 launches" in out.stdout
+
+
+def test_rng_layout_header_against_literal_restatements(tmp_path):
+    """csrc/rng_layout.h - the Philox key and counter words of every draw, the swap-attempt ordinal and the threads of an
+    exchange group, as every kernel and host path of csrc/ builds them - compiled as plain C++ under AddressSanitizer and
+    UBSan into tests/rng_layout_test.cpp, a program of its own that checks each helper against a literal restatement over a
+    grid crossing the 32-bit boundaries of the step index and the chain id."""
+    import os
+    import subprocess
+
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "rng_layout_test.cpp")
+    exe = str(tmp_path / "rng_layout_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", src, "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert "rng layout ok: " in out.stdout
