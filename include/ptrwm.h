@@ -381,6 +381,61 @@ int32_t ptrwm_run_with_chain_moments(const ptrwm_target_desc *target, const ptrw
 int32_t ptrwm_split_chain_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm_chain_moments_args *chain_moments,
                                   void *stream);
 
+/* ---- replica flow through the ladder: round trips and up-fraction without a trace ----------------------------------------
+ * swap_accept says how often neighbouring temperatures trade; it does not say whether anything travels the ladder.  Replica
+ * flow does (Katzgraber et al. 2006): every position (c, t) carries a FLOW WORD that moves with its row through every swap
+ * event - bits 0..15 a walker id, bits 16..17 a direction: 0 none, 1 up (the last end it touched was the cold one, t = 0),
+ * 2 down (the hot one, t = n_temps - 1).  The caller starts a run with walker[c, t] = t (direction none) and zeroed counters.
+ * At every swap event of ladder c, with src[t] the position whose post-Metropolis row the event puts at position t:
+ *   1. new[t] = old[src[t]] for every t.  PTRWM_SWAP_EXCHANGE: a permutation, T distinct walkers for ever.
+ *      PTRWM_SWAP_REFERENCE_COPY: a copy, as the rows are copied - ids repeat and vanish; an id then names the LINEAGE of the
+ *      vector at a position (which starting position it descends from), and round_trips counts by lineage;
+ *   2. ends: at t = 0 a word whose direction is down has completed a round trip (cold -> hot -> cold):
+ *      round_trips[c, id] += 1 (an id >= n_temps, which only a walker array the caller did not initialise can hold, is
+ *      counted nowhere), and its direction becomes up; at t = n_temps - 1 its direction becomes down;
+ *   3. visits: for every t, direction up: n_up[c, t] += 1; down: n_down[c, t] += 1; none: nothing.
+ * f(t) = n_up / (n_up + n_down) is the fraction of visits to temperature t by replicas coming from the cold end: 1 at t = 0,
+ * 0 at the hot end, falling roughly linearly over a well-placed ladder; a plateau or a cliff shows where replicas turn back.
+ * Determinism: everything is integer, each element has one writer per event and events are ordered by the stream - the
+ * results are exact and do not depend on where a run is cut into launches, on the kernel form (pinned or AUTO's choice),
+ * on how chains are sharded over devices (chain_offset), or on whether the events come from ptrwm_run, from split steps or
+ * from stand-alone sweeps.  No other output of a run changes: state, logp and every counter are bit-identical to the same
+ * run without flow.
+ * How: the fixture / trace twin of the step kernel (never the streaming form) parks the word of every position in LDS when a
+ * launch begins, exchanges it next to the rows in every swap event (round_trips is updated there, by the thread of
+ * temperature 0), and stores the words back and adds the launch's visit counts when the launch ends.
+ * Limits: n_temps >= 2; 16 bytes of LDS per replica on top of what the kernel and its moments regions hold (thread form:
+ * 16 per thread; lane-split form: 4 per thread), at most 160 KiB per workgroup together - a shape that does not fit returns
+ * PTRWM_E_ARG before anything is enqueued; the arrays are ordinary device memory of the current device. */
+typedef struct ptrwm_flow_args {
+  uint32_t struct_size; /* sizeof(ptrwm_flow_args) */
+  int32_t reserved;     /* 0 */
+  int32_t *walker;      /* [n_chains, n_temps] device, in/out, required: flow words */
+  int64_t *round_trips; /* [n_chains, n_temps] device, +=, indexed by walker id; or NULL */
+  int64_t *n_up;        /* [n_chains, n_temps] device, +=, indexed by temperature; or NULL */
+  int64_t *n_down;      /* [n_chains, n_temps] device, +=, indexed by temperature; or NULL */
+} ptrwm_flow_args;
+
+/* ptrwm_run with any of its diagnostics: pooled moments OR per-chain moments (at most one of the two non-NULL, else
+ * PTRWM_E_ARG), and replica flow.  flow == NULL: exactly ptrwm_run / ptrwm_run_with_moments / ptrwm_run_with_chain_moments.
+ * Checked before anything is enqueued, after the accumulator's checks: PTRWM_E_STRUCT for a wrong flow->struct_size;
+ * PTRWM_E_NULL for a NULL walker; PTRWM_E_ARG for n_temps < 2, reserved != 0, or flow regions that do not fit the kernel's LDS
+ * together with the moments regions (above). */
+int32_t ptrwm_run_with_diagnostics(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                                   const ptrwm_run_args *args, const ptrwm_moments_args *moments,
+                                   const ptrwm_chain_moments_args *chain_moments, const ptrwm_flow_args *flow, void *stream);
+
+/* ptrwm_swap_sweep (below), and the flow update of that event.  flow == NULL: exactly ptrwm_swap_sweep.  The flow checks
+ * (as above; no LDS limit) come after ptrwm_swap_sweep's own argument checks and before its empty-batch return. */
+int32_t ptrwm_swap_sweep_with_flow(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
+                                   const ptrwm_flow_args *flow, void *stream);
+
+/* ptrwm_split_accept (below), and the flow update of the step's swap event, inside the swap kernel it enqueues: in
+ * device-step mode the call can sit in a captured block; a step without an event (the kernel returns at once, or is not
+ * enqueued: PTRWM_SPLIT_NO_SWEEP) leaves flow untouched.  flow == NULL: exactly ptrwm_split_accept. */
+int32_t ptrwm_split_accept_with_flow(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
+                                     const float *logp_proposed, const ptrwm_flow_args *flow, void *stream);
+
 /* One stand-alone swap event over the current states: what the reference's
  * ParallelTemperingRWM_GPU_Optimized._attempt_all_swaps() does when called on its own
  * (pt_rwm_gpu_optimized.py:594-633; tests/debug_pt_performance.py:156).  Exactly the swap part of a ptrwm_run step:

@@ -19,6 +19,12 @@ kept apart per replica (ptrwm_chain_moments_args; deterministic sums):
     sum_logp float64 [*L, moments_temps]              sum of the log-density
     count    int64   [moments_temps]                  pooled: (replica, step) pairs added; per replica: accumulated steps
 
+and, with flow=True, the replica-flow arrays (`_flow`, a dict; include/ptrwm.h ptrwm_flow_args), updated at every swap event:
+
+    walker       int32   [n_replicas, n_temps]        flow word of every position: walker id | direction << 16
+    round_trips  int64   [n_replicas, n_temps]        completed cold -> hot -> cold trips, by walker id
+    n_up, n_down int64   [n_replicas, n_temps]        visits by replicas that last touched the cold / the hot end
+
 `n_replicas` is the axis the reference does not have: independent copies of the whole chain /
 ladder, one Philox subsequence each (global replica id = chain_offset + local index), so a run is
 invariant to how replicas are sharded over GPUs.
@@ -125,7 +131,7 @@ class EngineRun:
                  swap_mode: str, swap_order: str, seed: Optional[int], chain_offset: int = 0,
                  dtype: torch.dtype = torch.float32, moments_temps: int = 0, moments_every: int = 1,
                  moments_per_chain: bool = False, init_box=None, init_per_temperature: bool = False,
-                 init_attempts: int = 8):
+                 init_attempts: int = 8, flow: bool = False):
         if swap_mode not in ptrwm_hip.SWAP_MODES:
             raise ValueError(f"swap_mode must be one of {sorted(ptrwm_hip.SWAP_MODES)}, got {swap_mode!r}")
         if swap_order not in ptrwm_hip.SWAP_ORDERS:
@@ -133,6 +139,8 @@ class EngineRun:
         if n_replicas < 1:
             raise ValueError("number of replicas must be >= 1")
         n_temps = len(beta_ladder)
+        if flow and n_temps < 2:
+            raise ValueError("flow=True tracks replicas through a ladder: it needs at least two temperatures")
         if not 1 <= n_temps <= ptrwm_hip.MAX_TEMPS:
             raise ValueError(f"the fused kernel keeps one ladder inside one workgroup: 1..{ptrwm_hip.MAX_TEMPS} "
                              f"temperatures, got {n_temps}")
@@ -237,6 +245,13 @@ class EngineRun:
             bind = self._plan.set_chain_moments if self.moments_per_chain else self._plan.set_moments
             bind(self._mom["sum"], self._mom["sum_sq"], sum_logp=self._mom["sum_logp"], count=self._mom["count"],
                  every=self.moments_every)
+        # replica flow through the ladder, exchanged next to the rows in every swap event (off: None)
+        self._flow = None
+        if flow:
+            self._flow = {"walker": torch.empty(shape, device=device, dtype=torch.int32),
+                          **{k: torch.empty(shape, device=device, dtype=torch.int64) for k in ("round_trips", "n_up", "n_down")}}
+            self.reset_flow()
+            self._plan.set_flow(self._flow["walker"], self._flow["round_trips"], self._flow["n_up"], self._flow["n_down"])
         if box is not None:
             self._draw_starts(box, x0.to(torch.float32).contiguous(), bool(init_per_temperature), attempts)
 
@@ -448,6 +463,21 @@ class EngineRun:
         """Zero the moment accumulators (the chains keep their states)."""
         for t in (self._mom or {}).values():
             t.zero_()
+
+    def flow(self) -> Optional[dict]:
+        """Replica flow of this shard (device tensors, no synchronisation), or None when flow is off: walker (int32 flow
+        words), round_trips (by walker id), n_up / n_down (by temperature), all [n_replicas, n_temps], and events - the swap
+        events so far that the arrays cover: since the start of the run or the last reset_flow(), stand-alone sweeps included."""
+        return {**self._flow, "events": self.swap_events() - self._flow_events0} if self._flow is not None else None
+
+    def reset_flow(self) -> None:
+        """Every walker back on its starting position (id = temperature index, no direction), counters zeroed, and the event
+        count of flow() restarted: n_up[:, 0] == events and the round-trip rate hold for the arrays as they are."""
+        self._flow_events0 = self.swap_events()
+        if self._flow is not None:
+            self._flow["walker"].copy_(torch.arange(self.n_temps, device=self.device, dtype=torch.int32).expand(self.n_replicas, -1))
+            for k in ("round_trips", "n_up", "n_down"):
+                self._flow[k].zero_()
 
     def chain_moments(self) -> Optional[dict]:
         """The raw per-chain moment sums of this shard (device tensors, no synchronisation), or None when

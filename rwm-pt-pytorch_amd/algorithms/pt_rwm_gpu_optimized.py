@@ -15,7 +15,9 @@ refresh on accepted swaps only.  Made explicit instead of silently inherited (SU
   swap_order "sequential" (default; the reference's j = 0..T-2 sweep) or "even_odd"
 
 Extensions: `num_replicas` independent ladders advanced together (default 1); any of the three
-proposal families via `proposal_distribution` (the reference PT class is Gaussian-only).
+proposal families via `proposal_distribution` (the reference PT class is Gaussian-only);
+`flow=True` tracks every replica through the ladder inside the swap events (include/ptrwm.h
+ptrwm_flow_args): `round_trips()`, `round_trip_rate()`, `up_fraction()`, `walker_positions()`.
 """
 from __future__ import annotations
 
@@ -31,6 +33,7 @@ from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
 from ._engine_core import EngineRun, PosteriorMoments, check_class_starts, moments_temps, resolve_device
+from .sharding import flow_round_trip_rate, flow_up_fraction
 
 
 def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
@@ -56,8 +59,9 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
                  swap_mode: str = "exchange", swap_order: str = "sequential", seed: Optional[int] = None,
                  chain_offset: int = 0, trace: str = "all", thin: int = 1, moments: Optional[str] = None,
                  moments_every: int = 1, moments_per_chain: bool = False, initial_states=None, init_box=None,
-                 init_per_temperature: bool = False, init_attempts: int = 8):
+                 init_per_temperature: bool = False, init_attempts: int = 8, flow: bool = False):
         super().__init__(dim, var, target_dist, symmetric)
+        self._flow_on = bool(flow)
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         self._moments_mode, self._moments_every = moments, int(moments_every)
         if moments_per_chain and moments is None:
@@ -106,6 +110,8 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
                 warnings.warn("No specific ladder construction method chosen. Using geometric spacing as default.")
 
         self.num_chains = len(self.beta_ladder)  # = number of temperatures, as in the reference
+        if self._flow_on and self.num_chains < 2:
+            raise ValueError("flow=True tracks replicas through a ladder: it needs at least two temperatures")
         # Double states need the lane-split kernel with double state registers (ladders of <= 128 temperatures) and a target
         # with a fused kernel (split steps carry float32 states).  What it cannot serve runs in float32 and says so - the
         # reference's scripts pass --use_double_precision to every target (experiment_pt_GPU.py:236) and must keep running.
@@ -246,7 +252,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             burn_in=self.burn_in, swap_every=self.swap_every,
             swap_mode=self._swap_mode, swap_order=self._swap_order, seed=self._seed, chain_offset=self._chain_offset,
             dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
-            moments_every=self._moments_every, moments_per_chain=self._moments_per_chain)
+            moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, flow=self._flow_on)
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
         self.current_log_densities = self._run.logp[0] if self.num_replicas == 1 else self._run.logp
@@ -386,6 +392,44 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
         den = self._stat_denominator()
         return self._sq_beta_jumps() / den if den else 0.0
 
+    # ---- replica flow through the ladder (flow=True; Katzgraber et al. 2006) --------------------------------------
+    def _flow_arrays(self) -> dict:
+        """The run's flow arrays (EngineRun.flow()); before the first step, or after reset(): the starting arrays."""
+        if not self._flow_on:
+            raise RuntimeError("replica flow is off: construct the sampler with flow=True")
+        if self._run is None:
+            R, T = self.num_replicas, self.num_chains
+            z = torch.zeros(R, T, device=self.device, dtype=torch.int64)
+            return {"walker": torch.arange(T, device=self.device, dtype=torch.int32).expand(R, -1).contiguous(),
+                    "round_trips": z, "n_up": z.clone(), "n_down": z.clone(), "events": 0}
+        return self._run.flow()
+
+    def round_trips(self) -> torch.Tensor:
+        """Completed cold -> hot -> cold round trips of every walker: int64 [num_replicas, T] by walker id (the temperature
+        index it started at; under swap_mode="reference_copy" ids are lineages, include/ptrwm.h)."""
+        return self._flow_arrays()["round_trips"]
+
+    def round_trip_rate(self) -> float:
+        """Round trips per walker and swap event: total trips / (replicas x T x events); 0 before the first event."""
+        f = self._flow_arrays()
+        return flow_round_trip_rate(int(f["round_trips"].sum().item()), self.num_replicas, self.num_chains, f["events"])
+
+    def up_fraction(self) -> torch.Tensor:
+        """f(t) = n_up / (n_up + n_down) pooled over the replicas: of the visits to temperature t by walkers that have
+        touched an end, the fraction that last touched the cold one.  float64 [T] on the device, 1 at t = 0 and 0 at the
+        hot end once an event has happened, NaN where nothing has visited yet."""
+        f = self._flow_arrays()
+        return flow_up_fraction(f["n_up"].sum(0), f["n_down"].sum(0))
+
+    def walker_positions(self) -> torch.Tensor:
+        """The walker id at every position: int32 [num_replicas, T]."""
+        return self._flow_arrays()["walker"] & 0xFFFF
+
+    def _flow_diagnostics(self) -> dict:
+        if not self._flow_on:
+            return {}
+        return {"round_trips_total": int(self.round_trips().sum().item()), "up_fraction": self.up_fraction().cpu()}
+
     def mh_acceptance_rates(self) -> torch.Tensor:
         """Per-temperature MH acceptance rate (an extra: the reference PT class tracks none)."""
         self._ensure_started()
@@ -410,8 +454,9 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
 
     def _attempt_all_swaps(self):
         """One swap sweep over the current states, outside the step schedule (reference :594-633; called on its own
-        by tests/debug_pt_performance.py:156).  Counted in num_swap_attempts / num_swap_acceptances; the stored
-        chain is not extended (the reference appends states in step(), not here)."""
+        by tests/debug_pt_performance.py:156).  Counted in num_swap_attempts / num_swap_acceptances - and, with flow=True,
+        in the flow arrays: the event moves the flow words as it moves the rows; the stored chain is not extended (the
+        reference appends states in step(), not here)."""
         self._ensure_started()
         self._run.swap_sweep()
         self._chain_cache = None
@@ -439,6 +484,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             "kernel_fusion": "proposal, log-density, accept, update, swaps and statistics in one HIP kernel",
             "memory_allocated_mb": torch.cuda.memory_allocated() / 1e6 if self.device.type == "cuda" else 0,
             **self._moments_diagnostics(),
+            **self._flow_diagnostics(),
         }
 
     def performance_summary(self):

@@ -124,3 +124,35 @@ def allreduce_chain_summary(chain_moments: dict, group: Optional[dist.ProcessGro
     pairs = [rhat_ess_from_chain_summary(m, sm[t], sq[t], sv[t], cs["draws"][t]) for t in range(temps)]
     return {"rhat": torch.stack([p[0] for p in pairs]), "ess": torch.stack([p[1] for p in pairs]), "n_chains": m,
             "draws": cs["draws"]}
+
+
+# ---- replica flow (EngineRun.flow(); include/ptrwm.h ptrwm_flow_args) --------------------------------------------------------
+def flow_up_fraction(n_up: torch.Tensor, n_down: torch.Tensor) -> torch.Tensor:
+    """f(t) = n_up / (n_up + n_down) per temperature from visit counts already summed over the replicas ([T], any integer or
+    float dtype): float64 [T], NaN where no walker that has touched an end has visited yet."""
+    up, down = n_up.double(), n_down.double()
+    return up / (up + down)  # (0 / 0 = NaN)
+
+
+def flow_round_trip_rate(trips: int, n_replicas: int, n_temps: int, events: int) -> float:
+    """Round trips per walker and swap event: trips / (replicas x temperatures x events); 0.0 before the first event."""
+    den = n_replicas * n_temps * events
+    return float(trips) / den if den > 0 else 0.0
+
+
+def allreduce_flow(flow: dict, group: Optional[dist.ProcessGroup] = None) -> dict:
+    """Whole-job up-fraction and round-trip rate from every rank's flow arrays (EngineRun.flow()): ONE SUM all-reduce of an
+    int64 vector - n_up and n_down summed over the local replicas ([T] each), the local trip total and the local replica
+    count - separate from the summary's (pack_summary keeps its layout).  `events` is the same on every shard of a run.
+    Returns up_fraction (float64 [T], a new tensor on the shards' device), round_trip_rate, round_trips_total, n_up / n_down
+    ([T] int64, whole job), n_replicas and events."""
+    up, down, trips = flow["n_up"], flow["n_down"], flow["round_trips"]
+    n_rep, n_temps = up.shape
+    vec = torch.cat([up.sum(0).to(torch.int64), down.sum(0).to(torch.int64), trips.sum().to(torch.int64).reshape(1),
+                     torch.tensor([n_rep], dtype=torch.int64, device=up.device)])
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=group)
+    g_up, g_down = vec[:n_temps], vec[n_temps:2 * n_temps]
+    total, reps, events = int(vec[2 * n_temps].item()), int(vec[2 * n_temps + 1].item()), int(flow["events"])
+    return {"up_fraction": flow_up_fraction(g_up, g_down), "round_trip_rate": flow_round_trip_rate(total, reps, n_temps, events),
+            "round_trips_total": total, "n_up": g_up, "n_down": g_down, "n_replicas": reps, "events": events}

@@ -380,6 +380,9 @@ struct SweepArgs {
   // device-step mode (include/ptrwm.h device_step): the step index, whether an event is due and its number come from here
   const long long *device_step;
   long long burn_in, swap_every, event_offset;
+  // replica flow (include/ptrwm.h ptrwm_flow_args, flow.h; NULL flow_walker = off)
+  int *flow_walker;
+  long long *flow_round_trips, *flow_up, *flow_down;
 };
 constexpr int kSweepLdsBytes = 32768;  // at most: rows (and, in a split step, the pre-step rows) of one column chunk
 
@@ -425,6 +428,22 @@ __global__ void __launch_bounds__(256) swap_sweep_kernel(SweepArgs a) {
               my_l, src, pair_acc, [] { __syncthreads(); }, plain);
   if (live) s_src[tid] = src;
   __syncthreads();
+  if (a.flow_walker != nullptr) {  // (grid-uniform)
+    // replica flow, all of it behind swap_decide (flow.h): the word travels as the row does.  Every thread fetches the word
+    // of position `src` from HBM; the barrier keeps the stores below behind every fetch of the ladder.  Thread 0 is the
+    // ladder's one writer of round_trips.
+    int *const wk = a.flow_walker + chain * T;
+    const int32_t w_src = live ? wk[src] : 0;
+    __syncthreads();
+    if (live) {
+      bool trip;
+      const int32_t fw = flow_ends(w_src, t, T, trip);
+      wk[t] = fw;
+      if (trip && flow_id(fw) < T && a.flow_round_trips != nullptr) a.flow_round_trips[chain * T + flow_id(fw)] += 1;
+      if (a.flow_up != nullptr && flow_visit_up(fw) != 0u) a.flow_up[chain * T + t] += 1;
+      if (a.flow_down != nullptr && flow_visit_down(fw) != 0u) a.flow_down[chain * T + t] += 1;
+    }
+  }
   state_t *gs = reinterpret_cast<state_t *>(a.state) + chain * T * (long long)D;
   const float *prev = a.prev != nullptr ? a.prev + chain * T * (long long)D : nullptr;
   // |final - prev|^2 of this thread's replica in the canonical four-range order of the fused kernel (philox.h)
@@ -587,8 +606,12 @@ static hipError_t launch_propose(int wi, float *out, long long n, int D, int T, 
 
 // One swap event over the current states (ptrwm_swap_sweep, and the swap step of ptrwm_split_accept).
 static int32_t launch_sweep(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
-                            const float *prev, double *sq_jump, hipStream_t stream) {
+                            const float *prev, double *sq_jump, const ptrwm_flow_args *flow, hipStream_t stream) {
   SweepArgs a;
+  a.flow_walker = flow != nullptr ? flow->walker : nullptr;
+  a.flow_round_trips = flow != nullptr ? (long long *)flow->round_trips : nullptr;
+  a.flow_up = flow != nullptr ? (long long *)flow->n_up : nullptr;
+  a.flow_down = flow != nullptr ? (long long *)flow->n_down : nullptr;
   a.state = args->state;
   a.logp = args->logp;
   a.beta = args->beta;
@@ -788,8 +811,21 @@ static int32_t check_moments(const ptrwm_run_args *args, const MomSpec &mom) {
   return PTRWM_OK;
 }
 
+// the flow checks shared by the three entry points that take ptrwm_flow_args (args already checked); none: ok
+static int32_t check_flow(const ptrwm_run_args *args, const ptrwm_flow_args *flow) {
+  if (flow == nullptr) return PTRWM_OK;
+  if (flow->struct_size != sizeof(ptrwm_flow_args)) return PTRWM_E_STRUCT;
+  if (flow->walker == nullptr) return PTRWM_E_NULL;
+  if (args->n_temps < 2 || flow->reserved != 0) return PTRWM_E_ARG;
+  return PTRWM_OK;
+}
+
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const MomSpec &spec, void *hip_stream);
+                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream);
+static int32_t swap_sweep_impl(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
+                               const ptrwm_flow_args *flow, void *stream);
+static int32_t split_accept_impl(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
+                                 const float *logp_proposed, const ptrwm_flow_args *flow, void *stream);
 static int32_t split_moments_impl(const ptrwm_run_args *args, int32_t dim, const MomSpec &spec, void *stream);
 
 extern "C" {
@@ -890,17 +926,24 @@ int32_t ptrwm_has_variant(int32_t target_kind, int32_t proposal_kind, int32_t di
 
 int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                   void *hip_stream) {
-  return run_impl(target, proposal, args, MomSpec(), hip_stream);
+  return run_impl(target, proposal, args, MomSpec(), nullptr, hip_stream);
 }
 
 int32_t ptrwm_run_with_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
                                const ptrwm_run_args *args, const ptrwm_moments_args *moments, void *stream) {
-  return run_impl(target, proposal, args, moments, stream);
+  return run_impl(target, proposal, args, moments, nullptr, stream);
 }
 
 int32_t ptrwm_run_with_chain_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
                                      const ptrwm_run_args *args, const ptrwm_chain_moments_args *chain_moments, void *stream) {
-  return run_impl(target, proposal, args, chain_moments, stream);
+  return run_impl(target, proposal, args, chain_moments, nullptr, stream);
+}
+
+int32_t ptrwm_run_with_diagnostics(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                                   const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
+                                   const ptrwm_flow_args *flow, void *stream) {
+  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // one accumulator, pooled or per chain
+  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream);
 }
 
 }  // extern "C"
@@ -915,13 +958,14 @@ static long long ext_swap_events(const ptrwm_run_args *args) {
 
 // Job 1: everything that can be refused from the arguments alone.  *empty: a valid request with nothing to do.
 static int32_t check_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                         const MomSpec &spec, bool *empty) {
+                         const MomSpec &spec, const ptrwm_flow_args *flow, bool *empty) {
   if (proposal == nullptr || args == nullptr) return PTRWM_E_NULL;
   if (int rc = check_target(target)) return rc;
   if (!has_abi_size(args)) return PTRWM_E_STRUCT;
   if (proposal->kind < 0 || proposal->kind >= PTRWM_PROPOSAL_COUNT) return PTRWM_E_KIND;
   if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
   if (int rc = check_moments(args, spec)) return rc;
+  if (int rc = check_flow(args, flow)) return rc;
   if (args->n_chains < 0 || args->n_steps < 0 || args->step0 < 0 || args->burn_in < 0 || args->swap_every < 1 ||
       !swap_rule_known(args) || !fused_fields_ok(args))
     return PTRWM_E_ARG;
@@ -963,19 +1007,20 @@ struct RunChoice {
   unsigned n_blocks;
 };
 
-// the workgroup's LDS with the moments regions behind it, as the launcher will ask for it (variants.h LaunchShape)
-static unsigned moments_lds_bytes(const FormShape &f, int n_temps, int dim, int dpi, bool f64, const MomSpec &spec) {
+// the workgroup's LDS with the moments regions (if any) and the flow regions (if any) behind it, as the launcher will ask for
+// it at most (variants.h LaunchShape)
+static unsigned moments_lds_bytes(const FormShape &f, int n_temps, int dim, int dpi, bool f64, const MomSpec &spec, bool flow) {
   KArgs k{};  // (the launch shapes read these five fields)
   k.n_temps = n_temps;
   k.dim = dim;
   k.chains_per_wave = f.ladders_per_group;
-  k.full.mom_temps = spec.m->temps;
+  k.full.mom_temps = spec.m != nullptr ? spec.m->temps : 0;
   k.full.mom_chain = spec.per_chain ? 1 : 0;
-  return (f.quad ? quad_launch_shape(k, canon_width(dim), f64) : thread_launch_shape(k, kWidths[dpi].dp)).lds_moments;
+  return (f.quad ? quad_launch_shape(k, canon_width(dim), f64) : thread_launch_shape(k, kWidths[dpi].dp)).full_bytes(spec.m != nullptr, flow);
 }
 
 static RunChoice choose_kernel(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                               const MomSpec &spec, hipStream_t stream) {
+                               const MomSpec &spec, bool flow, hipStream_t stream) {
   RunChoice c{};
   auto refuse = [&c](int32_t status) {
     c.status = status;
@@ -1009,15 +1054,15 @@ static RunChoice choose_kernel(const ptrwm_target_desc *target, const ptrwm_prop
   // (an argument check, made here: a caller who also asks for a missing variant has always been told of that first)
   if (ext_swap_events(args) > 0 && args->ext_swap_u == nullptr) return refuse(PTRWM_E_NULL);
   c.shape = form_shape(quad, T);
-  if (spec.m != nullptr) {
-    unsigned need = moments_lds_bytes(c.shape, T, dim, dpi, f64, spec);
+  if (spec.m != nullptr || flow) {
+    unsigned need = moments_lds_bytes(c.shape, T, dim, dpi, f64, spec, flow);
     // Per-chain regions grow with the ladders of a group.  Where AUTO chose the form and both exist, a workgroup that needs
     // more than half of the CU's LDS (one workgroup resident: one wave per SIMD in the thread form) - or does not fit at
     // all - hands over to the other form if that one needs less (the same bits).  A pinned form is taken as it is.
     const bool both = !f64 && form == PTRWM_FORM_AUTO && thread_fn != nullptr && quad_fn != nullptr;
     if (spec.per_chain && both && need > kMaxLdsBytes / 2u) {
       const FormShape other = form_shape(!quad, T);
-      const unsigned other_need = moments_lds_bytes(other, T, dim, dpi, f64, spec);
+      const unsigned other_need = moments_lds_bytes(other, T, dim, dpi, f64, spec, flow);
       if (other_need < need) {
         c.fn = quad ? thread_fn : quad_fn;
         c.shape = other;
@@ -1026,8 +1071,8 @@ static RunChoice choose_kernel(const ptrwm_target_desc *target, const ptrwm_prop
     }
     if (need > kMaxLdsBytes) return refuse(PTRWM_E_ARG);
   }
-  // moments are accumulated by the fixture / trace twin (kernel.h FullArgs)
-  const bool full = args->ext_prop != nullptr || args->trace != nullptr || args->accept_flags != nullptr || spec.m != nullptr;
+  // moments are accumulated, and flow words exchanged, by the fixture / trace twin (kernel.h FullArgs)
+  const bool full = args->ext_prop != nullptr || args->trace != nullptr || args->accept_flags != nullptr || spec.m != nullptr || flow;
   // the streaming form for short launches of the one-thread-per-replica kernel (see kStreamMaxSteps above)
   bool streaming = false;
   if (!c.shape.quad && !full && has_stream_variant(kWidths[dpi].dp, kWidths[dpi].exact) && stream_layout_ok(args, dim, c.shape.ladders_per_group)) {
@@ -1050,7 +1095,7 @@ static RunChoice choose_kernel(const ptrwm_target_desc *target, const ptrwm_prop
 
 // Job 3: the kernel arguments that every launch of the request shares
 static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const MomSpec &spec, const RunChoice &c) {
+                        const MomSpec &spec, const ptrwm_flow_args *flow, const RunChoice &c) {
   KArgs k;
   k.state = args->state;
   k.logp = args->logp;
@@ -1077,30 +1122,34 @@ static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_de
   k.full.trace = args->trace;
   k.full.trace_logp = args->trace_logp;
   k.full.trace_chains = args->trace != nullptr ? args->trace_chains : 0;
-  k.full.trace_temps = args->trace_temps;
+  k.full.trace_temps = args->trace != nullptr ? (unsigned)args->trace_temps : 0u;  // (checked: 1..n_temps with a trace)
   k.full.trace_every = args->trace_every > 1 ? args->trace_every : 1;
-  k.full.n_raw_ext = ptrwm_ext_raw_per_step(proposal->kind, target->dim);
+  k.full_flow_lds = 0;  // (set by the launcher for a launch with flow, variants.h launch_twins)
   const ptrwm_moments_args *const mom = spec.m;
   k.full.mom_sum = nullptr;  // (set per launch: a launch without an accumulated step leaves the accumulators and its LDS alone)
   k.full.mom_sum_sq = mom != nullptr ? mom->sum_sq : nullptr;
   k.full.mom_sum_logp = mom != nullptr ? mom->sum_logp : nullptr;
   k.full.mom_count = mom != nullptr ? (long long *)mom->count : nullptr;
-  k.full.mom_steps = 0;
+  k.full_mom_steps = 0;
   k.full.mom_temps = mom != nullptr ? mom->temps : 0;
   k.full.mom_every = mom != nullptr ? mom->every : 1;
-  k.full.steps_to_mom = 0;
+  k.full.steps_to_mom = kNoStepInLaunch;
   k.full.mom_chain = (mom != nullptr && spec.per_chain) ? 1 : 0;
+  k.full.flow_walker = flow != nullptr ? flow->walker : nullptr;
+  k.full.flow_round_trips = flow != nullptr ? (long long *)flow->round_trips : nullptr;
+  k.full.flow_up = flow != nullptr ? (long long *)flow->n_up : nullptr;
+  k.full.flow_down = flow != nullptr ? (long long *)flow->n_down : nullptr;
   return k;
 }
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const MomSpec &spec, void *hip_stream) {
+                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream) {
   bool empty = false;
-  if (int rc = check_run(target, proposal, args, spec, &empty)) return rc;
+  if (int rc = check_run(target, proposal, args, spec, flow, &empty)) return rc;
   if (empty) return PTRWM_OK;
-  const RunChoice c = choose_kernel(target, proposal, args, spec, (hipStream_t)hip_stream);
+  const RunChoice c = choose_kernel(target, proposal, args, spec, flow != nullptr, (hipStream_t)hip_stream);
   if (c.status != PTRWM_OK) return c.status;
-  KArgs k = fill_kargs(target, proposal, args, spec, c);
+  KArgs k = fill_kargs(target, proposal, args, spec, flow, c);
   t_last_launch_kind = c.shape.quad ? PTRWM_LAUNCH_QUAD : (c.mode == kRunStream ? PTRWM_LAUNCH_STREAM : PTRWM_LAUNCH_THREAD);
   t_last_launch_functor = c.alt;
 
@@ -1109,7 +1158,10 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   const StepRequest req = {args->step0, args->n_steps, args->burn_in, args->swap_every, args->swap_event_offset,
                            k.full.trace_every, args->trace_row0, k.full.mom_every};
   const long long cap = max_steps_per_launch(args->n_chains, args->n_temps);
-  const long long reps = args->n_chains * args->n_temps, raw = k.full.n_raw_ext;
+  const long long reps = args->n_chains * args->n_temps, raw = ext_raw_per_step(proposal->kind, target->dim);
+  // (a launch's trace pointers stand at the row of its first traced step; a row: trace_chains x trace_temps replicas)
+  const long long trace_row = args->trace != nullptr ? args->trace_chains * (long long)args->trace_temps : 0;
+  const auto countdown = [](int steps) { return (unsigned)(steps < kNoStepInLaunch ? steps : kNoStepInLaunch); };  // (a launch: <= 2^16 steps)
   for (long long done = 0; done < args->n_steps; done += k.n_steps) {
     const LaunchCut cut = launch_at(req, done, cap);
     k.step0 = cut.step0;
@@ -1121,12 +1173,13 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
     k.full.ext_u = ext ? args->ext_u + done * reps : nullptr;
     k.full.ext_swap_u = (ext && args->ext_swap_u != nullptr) ? args->ext_swap_u + cut.events_before * args->n_chains * (args->n_temps - 1) : nullptr;
     k.full.accept_flags = args->accept_flags != nullptr ? args->accept_flags + done * reps : nullptr;
-    k.full.trace_row0 = cut.trace_row0;
-    k.full.steps_to_trace = cut.steps_to_trace;
+    k.full.trace = args->trace != nullptr ? args->trace + cut.trace_row0 * trace_row * target->dim * (args->state_f64 == 1 ? 2 : 1) : nullptr;
+    k.full.trace_logp = args->trace_logp != nullptr ? args->trace_logp + cut.trace_row0 * trace_row : nullptr;
+    k.full.steps_to_trace = countdown(cut.steps_to_trace);
     if (spec.m != nullptr) {
-      k.full.mom_steps = cut.mom_steps;  // (per chain: count[t] += mom_steps; pooled: += live ladders x mom_steps)
+      k.full_mom_steps = (unsigned)cut.mom_steps;  // (per chain: count[t] += mom_steps; pooled: += live ladders x mom_steps)
       k.full.mom_sum = cut.mom_steps > 0 ? spec.m->sum : nullptr;
-      k.full.steps_to_mom = cut.steps_to_mom;
+      k.full.steps_to_mom = countdown(cut.steps_to_mom);
     }
     if (c.fn(k, c.n_blocks, c.mode, (hipStream_t)hip_stream) != hipSuccess) return PTRWM_E_LAUNCH;
   }
@@ -1137,6 +1190,28 @@ extern "C" {
 
 int32_t ptrwm_swap_sweep(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
                          void *stream) {
+  return swap_sweep_impl(args, dim, event_index, rng_stream, nullptr, stream);
+}
+
+int32_t ptrwm_swap_sweep_with_flow(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
+                                   const ptrwm_flow_args *flow, void *stream) {
+  return swap_sweep_impl(args, dim, event_index, rng_stream, flow, stream);
+}
+
+int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
+                           const float *logp_proposed, void *stream) {
+  return split_accept_impl(args, dim, proposals, accept_u, logp_proposed, nullptr, stream);
+}
+
+int32_t ptrwm_split_accept_with_flow(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
+                                     const float *logp_proposed, const ptrwm_flow_args *flow, void *stream) {
+  return split_accept_impl(args, dim, proposals, accept_u, logp_proposed, flow, stream);
+}
+
+}  // extern "C"
+
+static int32_t swap_sweep_impl(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
+                               const ptrwm_flow_args *flow, void *stream) {
   if (args == nullptr) return PTRWM_E_NULL;
   if (!has_abi_size(args)) return PTRWM_E_STRUCT;
   if (!fused_fields_ok(args)) return PTRWM_E_ARG;
@@ -1145,10 +1220,13 @@ int32_t ptrwm_swap_sweep(const ptrwm_run_args *args, int32_t dim, int64_t event_
   if (args->n_chains < 0 || args->n_chains > 0x7fffffffll || args->step0 < 0 || event_index < 0 || rng_stream < 1 ||
       rng_stream > 15 || !swap_rule_known(args))
     return PTRWM_E_ARG;
+  if (int rc = check_flow(args, flow)) return rc;
   if (args->n_chains == 0 || args->n_temps == 1) return PTRWM_OK;  // nothing to exchange
   if (args->state == nullptr || args->logp == nullptr || args->beta == nullptr) return PTRWM_E_NULL;
-  return launch_sweep(args, dim, event_index, rng_stream, nullptr, nullptr, (hipStream_t)stream);
+  return launch_sweep(args, dim, event_index, rng_stream, nullptr, nullptr, flow, (hipStream_t)stream);
 }
+
+extern "C" {
 
 static int32_t split_common_checks(const ptrwm_run_args *args, int32_t dim) {
   if (args == nullptr) return PTRWM_E_NULL;
@@ -1195,9 +1273,12 @@ int32_t ptrwm_split_propose(const ptrwm_proposal_desc *proposal, const ptrwm_run
   return err == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 
-int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
-                           const float *logp_proposed, void *stream) {
+}  // extern "C"
+
+static int32_t split_accept_impl(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
+                                 const float *logp_proposed, const ptrwm_flow_args *flow, void *stream) {
   if (int rc = split_common_checks(args, dim)) return rc;
+  if (int rc = check_flow(args, flow)) return rc;
   if (args->n_chains == 0) return PTRWM_OK;
   if (args->state == nullptr || args->logp == nullptr || args->beta == nullptr || proposals == nullptr ||
       accept_u == nullptr || logp_proposed == nullptr)
@@ -1239,13 +1320,15 @@ int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *propo
     // device-step mode: the sweep is enqueued with every step and decides on the device whether its event is due - unless
     // the caller vouches that this step has none (PTRWM_SPLIT_NO_SWEEP)
     if (args->n_temps < 2 || (args->split_flags & PTRWM_SPLIT_NO_SWEEP) != 0) return PTRWM_OK;
-    return launch_sweep(args, dim, 0, (int)kStreamSwap, proposals, args->sq_jump, (hipStream_t)stream);
+    return launch_sweep(args, dim, 0, (int)kStreamSwap, proposals, args->sq_jump, flow, (hipStream_t)stream);
   }
   if (!due.swap_due) return PTRWM_OK;
   // the swap event of this step: event number as ptrwm_run counts them, swap uniforms from the fused kernel's stream
   const long long ev = swap_event_number(sc, args->burn_in, args->swap_every) + args->swap_event_offset;
-  return launch_sweep(args, dim, ev, (int)kStreamSwap, proposals, args->sq_jump, (hipStream_t)stream);
+  return launch_sweep(args, dim, ev, (int)kStreamSwap, proposals, args->sq_jump, flow, (hipStream_t)stream);
 }
+
+extern "C" {
 
 int32_t ptrwm_split_chain_moments(const ptrwm_run_args *args, int32_t dim, const ptrwm_chain_moments_args *cm, void *stream) {
   return split_moments_impl(args, dim, cm, stream);

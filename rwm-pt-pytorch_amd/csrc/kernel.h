@@ -14,6 +14,9 @@
 // Either way a ladder lives inside one workgroup and swaps go through LDS (broadcast reads of the ladder's
 // log-densities, row exchange through the staging rows), never HBM.
 #pragma once
+#include <cstddef>
+
+#include "flow.h"
 #include "philox.h"
 #include "proposals.h"
 #include "targets.h"
@@ -30,6 +33,8 @@ constexpr int kWavesPerBlock = kBlockThreads / 64;
 // a workgroup is kBlockThreads / 64 one-wave groups, kWaveFloats apart) or the workgroup (wide: one ladder, n_temps > 64).
 //   classic, per group:  [rows: gt x DP][s_l][s_u][landed][c3][swap count][last event][squared-jump sums: gt doubles]
 //                        behind ALL groups: [wide only: the ladder's vote word][FULL twin with moments: the regions]
+//                        [FULL twin with flow: a flow region per group: the flow word of even events, of odd events, the
+//                        launch's up visits, its down visits - gt ints each (flow.h)]
 //   streaming, per wave: [slab 0: 64 x DP][slab 1][s_l .. squared-jump sums, gt = 64][zone 0][zone 1]
 //                        zone: [64 log-densities][64 squared-jump sums (double)][64 acceptance counts (64-bit)]
 // rows: up to DP floats per thread, packed (row stride = dim) for the coalesced state copy and a swap's row exchange; the
@@ -46,6 +51,10 @@ struct StepLdsWords {  // what does not depend on the register width
   static constexpr int kStreamSlabs = 2;
   static constexpr int kStreamStatPerThread = 5;  // floats per thread and landing zone: a float, a double, a 64-bit integer
   static constexpr unsigned kVoteBytes = 16u;
+  static constexpr unsigned kFlowLdsUnit = 8u;  // the flow regions start at a multiple of this (behind floats x whole waves, doubles)
+  static constexpr int kFlowIntsPerThread = 4;  // flow region (FULL twin with flow): two word buffers, up visits, down visits
+  static constexpr int kFlowUp = 2, kFlowDown = 3;  // from the region's start, in units of gt (the word buffers: 0 and 1)
+  static constexpr unsigned flow_bytes(int threads) { return (unsigned)(threads * kFlowIntsPerThread) * 4u; }  // of a workgroup: one region per group
   static constexpr int floats_per_thread(int dp, bool stream) { return (stream ? kStreamSlabs * (dp + kStreamStatPerThread) : dp) + kExtraPerThread; }
   // what a launch of `threads` threads asks for (the moments regions of a FULL twin come on top)
   static constexpr unsigned bytes(int threads, int dp, bool stream, bool wide) { return (unsigned)(threads * floats_per_thread(dp, stream)) * 4u + (wide ? kVoteBytes : 0u); }
@@ -68,6 +77,12 @@ struct StepLds : StepLdsWords {
   static constexpr int moments(bool wide, int gt) { return wide ? gt * (DP + kExtraPerThread) + (int)(kVoteBytes / 4u) : kBlockThreads * (DP + kExtraPerThread); }
   __device__ __forceinline__ static double *moments_region(float *s_dyn, bool wide, int gt, int wave, int stride) {
     return reinterpret_cast<double *>(s_dyn + moments(wide, gt)) + (wide ? 0 : wave * stride);
+  }
+  // the flow regions (FULL twin), behind the moments regions of this launch: one per wave (narrow), one for a wide ladder.
+  // Where they begin is the launch's LDS size without them - the host knows it (variants.h LaunchShape) and says so in
+  // KArgs::full_flow_lds, in units of kFlowLdsUnit bytes: nothing of the moments' shape is rebuilt at a swap event
+  __device__ __forceinline__ static int *flow_region(float *s_dyn, bool wide, int wave, unsigned flow_lds) {
+    return reinterpret_cast<int *>(s_dyn) + (int)flow_lds * (int)(kFlowLdsUnit / 4u) + (wide ? 0 : wave * (64 * kFlowIntsPerThread));
   }
   static constexpr unsigned bytes(int threads, bool wide) { return StepLdsWords::bytes(threads, DP, STREAM, wide); }
 };
@@ -95,34 +110,50 @@ constexpr bool aligned(bool ok = true) {
 }
 static_assert(aligned<2>() && aligned<3>() && aligned<5>() && aligned<9>() && aligned<29>() && aligned<30>() && aligned<50>() && aligned<64>(), "alignment");
 static_assert(C::bytes(256, false) == 38912u && S::bytes(256, false) == 79872u && C::bytes(256, true) == 38928u, "LDS bytes, as before the layout had a name");
+static_assert(0 < C::kFlowUp && C::kFlowUp < C::kFlowDown && C::kFlowDown < C::kFlowIntsPerThread && C::flow_bytes(256) == 4096u &&
+                  C::flow_bytes(kBlockThreads) == (unsigned)kWavesPerBlock * 64u * C::kFlowIntsPerThread * 4u,
+              "flow region: two word buffers, up visits, down visits, one region per group; nothing of it in a launch without flow");
 }  // namespace lds_check
 
 // Arguments only the fixture / trace variant of the kernel (FULL = true) reads.  Keeping them out
 // of the production variant keeps its wave-uniform state inside the 100-odd SGPRs of a wave.
+// The struct keeps its SIZE (static_assert behind KArgs): the hidden arguments of every step kernel - production and streaming
+// ones too, which read the grid's and the workgroup's extent there - follow the explicit ones, so a KArgs that grows moves
+// them and with them an s_load offset in kernels this struct has nothing to do with.  What is small is therefore packed: the
+// countdowns and the count of a launch (at most 2^16 steps: kNoStepInLaunch stands for "none in this launch"), the two
+// temperature counts, the flag; two more live in the four bytes KArgs had to spare (KArgs::full_mom_steps, full_flow_lds).  The
+// raw random numbers per proposal of ext_prop are not passed at all: ext_raw_per_step(kind, dim), below.
+constexpr int kNoStepInLaunch = (1 << 16) + 1;
 struct FullArgs {
   const float *__restrict__ ext_prop;
   const float *__restrict__ ext_u;
   const float *__restrict__ ext_swap_u;
-  float *__restrict__ trace;
+  float *__restrict__ trace;       // (both: at the row of this launch's first traced step - the host adds the rows before it)
   float *__restrict__ trace_logp;
   unsigned char *__restrict__ accept_flags;
-  long long trace_chains, trace_row0;
-  int trace_temps, n_raw_ext;
-  int trace_every;     // thinning period (>= 1)
-  int steps_to_trace;  // steps until the first traced step of this launch (1 = the first step)
+  long long trace_chains;
+  int trace_every;  // thinning period (>= 1)
+  int mom_every;
+  unsigned steps_to_trace : 17;  // steps until the first traced step of this launch (1 = the first step; kNoStepInLaunch: none)
+  unsigned trace_temps : 9;
+  unsigned steps_to_mom : 17;    // steps until the first step whose step_counter % mom_every == 0 (likewise)
+  unsigned mom_temps : 9;
+  // 1: per-chain accumulators (include/ptrwm.h ptrwm_chain_moments_args): mom_sum / mom_sum_sq are [n_chains, mom_temps, dim],
+  // mom_sum_logp [n_chains, mom_temps]; the group's region has a row per (ladder of the group, temperature), is LOADED from
+  // them in the prologue and stored back with plain stores (one group owns each element); mom_count[t] += mom_steps
+  unsigned mom_chain : 1;
   // moments accumulator (include/ptrwm.h ptrwm_moments_args; NULL mom_sum = off): fp64 partial sums in a region of the
   // dynamic LDS per exchange group, added to at every accumulated step and flushed to HBM once at the end of the launch
   double *__restrict__ mom_sum;       // [mom_temps, dim]
   double *__restrict__ mom_sum_sq;    // [mom_temps, dim]
   double *__restrict__ mom_sum_logp;  // [mom_temps] or NULL
-  long long *__restrict__ mom_count;  // [mom_temps] or NULL
-  long long mom_steps;                // accumulated steps in this launch: count[t] += live ladders x mom_steps
-  int mom_temps, mom_every;
-  int steps_to_mom;                   // steps until the first step whose step_counter % mom_every == 0 (1 = the first step)
-  // 1: per-chain accumulators (include/ptrwm.h ptrwm_chain_moments_args): mom_sum / mom_sum_sq are [n_chains, mom_temps, dim],
-  // mom_sum_logp [n_chains, mom_temps]; the group's region has a row per (ladder of the group, temperature), is LOADED from
-  // them in the prologue and stored back with plain stores (one group owns each element); mom_count[t] += mom_steps
-  int mom_chain;
+  long long *__restrict__ mom_count;  // [mom_temps] or NULL (KArgs::full_mom_steps: count[t] += live ladders x that)
+  // replica flow (include/ptrwm.h ptrwm_flow_args, flow.h; NULL flow_walker = off): the flow word of every position is parked
+  // in the group's flow region for the launch, travels with the rows in every swap event, and is stored back in the epilogue
+  int *__restrict__ flow_walker;             // [n_chains, n_temps] flow words, in / out
+  long long *__restrict__ flow_round_trips;  // [n_chains, n_temps] by walker id, += at event time by the thread of temperature 0; or NULL
+  long long *__restrict__ flow_up;           // [n_chains, n_temps] visits by temperature, += in the epilogue; or NULL
+  long long *__restrict__ flow_down;
 };
 
 typedef const __attribute__((address_space(4))) FullArgs *kargs_full_ptr;
@@ -143,10 +174,20 @@ struct KArgs {
   int n_temps, dim, swap_every, swap_mode, swap_order, chains_per_wave;
   int steps_to_swap;  // steps until the next step whose step_counter is a multiple of swap_every (1 = the first step)
   unsigned k0, k1;
+  // (of FullArgs, in the four bytes in front of the 8-byte aligned TParams: the accumulated steps of this launch, and where
+  // this launch's flow regions begin in the dynamic LDS, in units of StepLdsWords::kFlowLdsUnit bytes - set by the launcher)
+  unsigned full_mom_steps : 17;
+  unsigned full_flow_lds : 15;
   TParams tp;
   PParams pp;
   FullArgs full;
 };
+static_assert(sizeof(FullArgs) == 136 && sizeof(KArgs) == 392 && offsetof(KArgs, tp) == 144, "the kernel arguments keep their size: see FullArgs");
+// what the packed fields must hold: temperature counts up to PTRWM_MAX_TEMPS (9 bits), countdowns and counts of a launch of at
+// most 2^16 steps up to kNoStepInLaunch (17 bits; schedule.h max_steps_per_launch), an LDS offset up to a CU's 160 KiB (15 bits)
+static_assert(PTRWM_MAX_TEMPS < (1 << 9) && kNoStepInLaunch < (1 << 17) && 160u * 1024u / StepLdsWords::kFlowLdsUnit < (1u << 15), "FullArgs bitfield widths");
+// raw random numbers one proposal reads from ext_prop (include/ptrwm.h ptrwm_ext_raw_per_step): the radius word of UniformRadius
+__host__ __device__ constexpr int ext_raw_per_step(int proposal_kind, int dim) { return dim + (proposal_kind == PTRWM_PROPOSAL_UNIFORM_RADIUS ? 1 : 0); }
 
 // log swap probability exactly as fused_swap_probability_calculation evaluates it
 // (algorithms/pt_rwm_gpu_optimized.py:37-48): four products summed left to right.
@@ -475,7 +516,7 @@ struct MomentsAcc {
   // steps per chain.  Pooled: one no-return global_atomic_add_f64 per non-zero partial sum (device memory: include/ptrwm.h)
   // and count[t] += live ladders x steps.
   template <class F>
-  __device__ __forceinline__ void end(F f, long long live_ladders, long long chain0, int tid, int nthr) const {
+  __device__ __forceinline__ void end(F f, long long mom_steps, long long live_ladders, long long chain0, int tid, int nthr) const {
     long long *const count = f->mom_count;
     if (per_chain) {
       chain_copy<false>(f, (int)live_ladders, chain0, tid, nthr);
@@ -489,7 +530,7 @@ struct MomentsAcc {
         if (v != 0.0) unsafeAtomicAdd(i < td ? sum + i : (i < 2 * td ? sum_sq + (i - td) : sum_logp + (i - 2 * td)), v);
       }
     }
-    const long long add = (per_chain ? 1 : live_ladders) * f->mom_steps;
+    const long long add = (per_chain ? 1 : live_ladders) * mom_steps;
     if (count != nullptr)
       for (int i = tid; i < temps; i += nthr) count_add(&count[i], add);
   }
@@ -560,18 +601,18 @@ template <bool STREAM>
 __device__ __forceinline__ int step_group_threads(int T) { return STREAM ? 64 : group_threads(T, 1); }
 
 // Rows of the FULL twins' per-step arrays (both step kernels).  The replica's index in step i of the launch - the row of
-// accept_flags and ext_u, and of ext_prop in units of n_raw_ext elements; the row of the trace a launch that has already
+// accept_flags and ext_u, and of ext_prop in units of n_raw_ext elements; the row of the trace (from its first) a launch that has already
 // written rows_written rows writes for (chain, t).
 __device__ __forceinline__ long long step_replica_index(int i, long long n_chains, long long chain, int T, int t) {
   return ((long long)i * n_chains + chain) * T + t;
 }
 template <class F>  // (words: 32-bit words per element of ext_prop - 2 for the double states of the lane-split form)
-__device__ __forceinline__ const float *ext_prop_row(F f, long long srep, int words) {
-  return f->ext_prop + srep * f->n_raw_ext * words;
+__device__ __forceinline__ const float *ext_prop_row(F f, int n_raw_ext, long long srep, int words) {
+  return f->ext_prop + srep * n_raw_ext * words;
 }
 template <class F>
 __device__ __forceinline__ long long trace_row_index(F f, int rows_written, long long chain, int t) {
-  return ((f->trace_row0 + rows_written) * f->trace_chains + chain) * f->trace_temps + t;
+  return ((long long)rows_written * f->trace_chains + chain) * (long long)f->trace_temps + t;
 }
 
 // DP    compile-time width of the per-thread register arrays (>= dim)
@@ -739,6 +780,12 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
           m.reg = L::moments_region(s_dyn, wide, nthr, wave, m.doubles());
           m.begin(&a.full, (int)live_chains, chain0, tid, nthr);
         }
+        if (a.full.flow_walker != nullptr) {  // the word of this position in the buffer of even events, no visits yet
+          int *const fl = L::flow_region(s_dyn, wide, wave, a.full_flow_lds) + tid;
+          fl[0] = live ? a.full.flow_walker[rep] : 0;
+          fl[L::kFlowUp * nthr] = 0;
+          fl[L::kFlowDown * nthr] = 0;
+        }
       }
     }
     // (streaming form: the run is landing in slab `cur` by LDS-DMA.  The compiler does not order LDS reads behind it:
@@ -800,10 +847,10 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
 
   const bool ext = FULL && a.full.ext_prop != nullptr;
   const bool trace_on =
-      FULL && live && a.full.trace != nullptr && (chain < a.full.trace_chains) && (t < a.full.trace_temps);
+      FULL && live && a.full.trace != nullptr && (chain < a.full.trace_chains) && (t < (int)a.full.trace_temps);
   int to_swap = a.steps_to_swap;
-  int to_trace = FULL ? a.full.steps_to_trace : 0;
-  [[maybe_unused]] int to_mom = FULL ? a.full.steps_to_mom : 0;
+  int to_trace = FULL ? (int)a.full.steps_to_trace : 0;
+  [[maybe_unused]] int to_mom = FULL ? (int)a.full.steps_to_mom : 0;
   int trace_rows = 0;    // rows of the trace written by this launch
   int swap_in_call = 0;  // swap events already done in this launch
   const int ev_par0 = (int)(a.first_swap_event & 1);
@@ -869,7 +916,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       }
       trace_rows += trace_now ? 1 : 0;
       // the state after the whole step
-      if (a.full.mom_sum != nullptr && countdown_due(to_mom, a.full.mom_every) && count_on && live && t < a.full.mom_temps) {
+      if (a.full.mom_sum != nullptr && countdown_due(to_mom, a.full.mom_every) && count_on && live && t < (int)a.full.mom_temps) {
         MomentsAcc m(&a.full, cpw, D);
         m.reg = L::moments_region(s_dyn, wide, step_group_threads<STREAM>(T), wave, m.doubles());
         const MomentsAcc::Row r = m.row(cw, t);
@@ -919,7 +966,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       if constexpr (FULL) {
         srep = step_replica_index(i, a.n_chains, chain, T, t);
         if (ext) {
-          ext_raw = ext_prop_row(&a.full, srep, 1);
+          ext_raw = ext_prop_row(&a.full, ext_raw_per_step(Proposal::kKind, D0), srep, 1);
           ext_u = a.full.ext_u[srep];
         }
       }
@@ -1007,6 +1054,28 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
           if ((d & 7) == 7) sched_fence_soft();
         })
         j2 = tree4_add(j2p);
+        if constexpr (FULL) {
+          // replica flow (flow.h): the word travels as the row does - fetched from slot `src` behind the barrier above, which
+          // also orders it behind that slot's write of the previous event, and written to the OTHER buffer: slot `slot` of this
+          // event's buffer may still be read by the thread it lands at.  The next write to this event's buffer is two events
+          // away, behind the barriers of the next one.
+          if (a.full.flow_walker != nullptr && live) {
+            int *const fl = L::flow_region(s_dyn, wide, wave, a.full_flow_lds);
+            const int buf = swap_in_call & 1;
+            bool trip;
+            const int32_t fw = flow_ends(fl[buf * group_threads + src], t, T, trip);
+            fl[(buf ^ 1) * group_threads + slot] = fw;
+            if (trip && flow_id(fw) < T && a.full.flow_round_trips != nullptr) {  // (t = 0: the ladder's one writer; an id the caller never set counts nowhere)
+              // (the row's address from an opaque copy of the chain index: it is loop-invariant, and hoisted out of the step
+              // loop it was a register pair kept - at the 128-VGPR cap: in scratch - for the whole launch)
+              long long ch = chain;
+              PTRWM_VALUE_BARRIER("+v"(ch));
+              a.full.flow_round_trips[ch * T + flow_id(fw)] += 1;
+            }
+            fl[L::kFlowUp * group_threads + slot] += (int)flow_visit_up(fw);
+            fl[L::kFlowDown * group_threads + slot] += (int)flow_visit_down(fw);
+          }
+        }
       }
       lp = my_l;
       ++swap_in_call;
@@ -1054,7 +1123,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       if (fa->mom_sum != nullptr) {
         MomentsAcc m(fa, cpw2, D2);
         m.reg = L::moments_region(s_dyn, wide2, nthr, wave, m.doubles());
-        m.end(fa, live_chains, c0, tid2, nthr);
+        m.end(fa, (long long)ae->full_mom_steps, live_chains, c0, tid2, nthr);
       }
     }
     if constexpr (STREAM) {
@@ -1108,6 +1177,17 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       const long long ev = ae->first_swap_event + last_event;
       const long long ord = swap_attempt_ordinal(ae->swap_order, ev, T_o, t);
       if (ord > ae->last_swap_ordinal[rep]) ae->last_swap_ordinal[rep] = ord;
+    }
+    if constexpr (FULL) {
+      // replica flow: the word this position holds now (the buffer the next event would read) and the launch's visits
+      const kargs_full_ptr fa = &ae->full;
+      if (fa->flow_walker != nullptr) {
+        const int *const fl = L::flow_region(s_dyn, T_o > 64, wave, ae->full_flow_lds) + tid_g;
+        fa->flow_walker[rep] = fl[(swap_in_call & 1) * gt_o];
+        const int n_up = fl[L::kFlowUp * gt_o], n_down = fl[L::kFlowDown * gt_o];
+        if (fa->flow_up != nullptr && n_up != 0) count_add(&fa->flow_up[rep], (long long)n_up);
+        if (fa->flow_down != nullptr && n_down != 0) count_add(&fa->flow_down[rep], (long long)n_down);
+      }
     }
     }
   }

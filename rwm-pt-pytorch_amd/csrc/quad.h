@@ -586,11 +586,15 @@ struct QNealFunnel {
 // StepLds).  Offsets in floats; gthreads = threads of the exchange group (64: one-wave groups kWaveFloats apart; or the
 // workgroup), nslots = gthreads / 4.  Per group: [rows: nslots x 4 W state elements (float; F64: double)][s_l][s_u][outcome]
 // [objection], nslots words each (log-density, swap uniform, outcome of a swap sweep; the swap-form objection of the ladder
-// whose first slot it is: one word per thread; a second one is allocated, unused); behind ALL groups the FULL twin's moments regions.
+// whose first slot it is: one word per thread; a second one is allocated, unused); behind ALL groups the FULL twin's moments regions,
+// and behind those its flow regions, one per group: [flow word of even events][of odd events][up visits][down visits], nslots ints
+// each (flow.h; kernel.h StepLds has the same region per thread).
 struct QuadLdsWords {  // what does not depend on the lane width
   static constexpr int kExtraPerThread = 2;
   static constexpr int floats_per_thread(int w, bool f64) { return w * (f64 ? 2 : 1) + kExtraPerThread; }
   static constexpr unsigned bytes(int threads, int w, bool f64) { return (unsigned)(threads * floats_per_thread(w, f64)) * 4u; }
+  static constexpr int kFlowIntsPerSlot = StepLdsWords::kFlowIntsPerThread, kFlowUp = StepLdsWords::kFlowUp, kFlowDown = StepLdsWords::kFlowDown;
+  static constexpr unsigned flow_bytes(int threads) { return (unsigned)(threads / 4 * kFlowIntsPerSlot) * 4u; }  // of a workgroup: a slot per four threads
 };
 template <int W, bool F64 = false>
 struct QuadLds : QuadLdsWords {
@@ -603,6 +607,10 @@ struct QuadLds : QuadLdsWords {
   __device__ __forceinline__ static double *moments_region(float *s_dyn, bool wide, int wave, int stride) {
     return reinterpret_cast<double *>(s_dyn + moments((int)blockDim.x)) + (wide ? 0 : wave * stride);
   }
+  // the flow regions (FULL twin), behind the moments regions of this launch: from KArgs::full_flow_lds (kernel.h StepLds)
+  __device__ __forceinline__ static int *flow_region(float *s_dyn, bool wide, int wave, unsigned flow_lds) {
+    return reinterpret_cast<int *>(s_dyn) + (int)flow_lds * (int)(StepLdsWords::kFlowLdsUnit / 4u) + (wide ? 0 : wave * (16 * kFlowIntsPerSlot));
+  }
   static constexpr unsigned bytes(int threads) { return QuadLdsWords::bytes(threads, W, F64); }
 };
 static_assert(QuadLds<8>::s_l(16) == 16 * 32 && QuadLds<8>::s_l(16) + (QuadLds<8>::kObjection + 1) * 16 <= QuadLds<8>::kWaveFloats && QuadLds<8, true>::s_l(16) == 16 * 64 &&
@@ -612,6 +620,7 @@ static_assert(QuadLds<8>::s_l(16) == 16 * 32 && QuadLds<8>::s_l(16) + (QuadLds<8
 static_assert(QuadLds<8>::kWaveFloats % 4 == 0 && QuadLds<8, true>::kWaveFloats % 4 == 0 && QuadLds<28>::kWaveFloats % 4 == 0 && QuadLds<8>::moments(64) % 2 == 0 &&
                   QuadLds<20>::moments(64) % 2 == 0, "wave strides 16-byte aligned (16-byte row copies), moments regions (doubles) 8-byte aligned");
 static_assert(QuadLds<8>::bytes(256) == 10240u && QuadLds<8, true>::bytes(256) == 18432u, "LDS bytes, as before the layout had a name");
+static_assert(QuadLdsWords::flow_bytes(256) == 1024u && QuadLdsWords::flow_bytes(512) == 2048u, "flow region: four ints per slot, one region per group");
 // Widest workgroup = one ladder.  Every variant is compiled for workgroups of up to 512 threads (ladders of <= 128
 // temperatures: up to 256 VGPRs).  (Until round 4 the W >= 20 classes also existed for 1024 threads: 128 VGPRs, 40 of
 // them spilled inside the step loop - retired, variants.h.)
@@ -735,6 +744,12 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
         m.reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), m.doubles());
         m.begin(&a.full, (int)live_chains, chain0, tid, gthreads);
       }
+      if (a.full.flow_walker != nullptr && l.q == 0) {  // (kernel.h) this slot's word in the buffer of even events, no visits yet
+        int *const fl = L::flow_region(s_dyn, wide, (int)(threadIdx.x >> 6), a.full_flow_lds) + slot_raw;
+        fl[0] = live ? a.full.flow_walker[rep] : 0;
+        fl[L::kFlowUp * nslots] = 0;
+        fl[L::kFlowDown * nslots] = 0;
+      }
     }
     sync_group();
     const state_t *seg = reinterpret_cast<const state_t *>(rows_f + stage_head(gs)) + slot * D + l.d0;
@@ -773,10 +788,10 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
 
   const bool ext = FULL && a.full.ext_prop != nullptr;
   const bool trace_on =
-      FULL && live && a.full.trace != nullptr && (chain < a.full.trace_chains) && (t < a.full.trace_temps);
+      FULL && live && a.full.trace != nullptr && (chain < a.full.trace_chains) && (t < (int)a.full.trace_temps);
   int to_swap = a.steps_to_swap;
-  int to_trace = FULL ? a.full.steps_to_trace : 0;
-  [[maybe_unused]] int to_mom = FULL ? a.full.steps_to_mom : 0;
+  int to_trace = FULL ? (int)a.full.steps_to_trace : 0;
+  [[maybe_unused]] int to_mom = FULL ? (int)a.full.steps_to_mom : 0;
   int trace_rows = 0;
   int swap_in_call = 0;
   const int ev_par0 = (int)(a.first_swap_event & 1);
@@ -799,7 +814,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
     if constexpr (FULL) {
       srep = step_replica_index(i, a.n_chains, chain, T, t);  // (kernel.h)
       if (ext) {
-        ext_rep = ext_prop_row(&a.full, srep, SW);
+        ext_rep = ext_prop_row(&a.full, ext_raw_per_step(Proposal::kKind, D), srep, SW);
         ext_u = a.full.ext_u[srep];
       }
     }
@@ -977,6 +992,24 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
           }
         }
         j2 = quad_tree_add(j2l);
+        if constexpr (FULL) {
+          // replica flow (flow.h; kernel.h has the barrier argument): the first lane of the quad fetches the word of slot
+          // `src` behind the barrier above and writes it to the other buffer
+          if (a.full.flow_walker != nullptr && live && l.q == 0) {
+            int *const fl = L::flow_region(s_dyn, wide, (int)(threadIdx.x >> 6), a.full_flow_lds);
+            const int buf = swap_in_call & 1;
+            bool trip;
+            const int32_t fw = flow_ends(fl[buf * nslots + src], t, T, trip);
+            fl[(buf ^ 1) * nslots + slot] = fw;
+            if (trip && flow_id(fw) < T && a.full.flow_round_trips != nullptr) {  // (t = 0: the ladder's one writer)
+              long long ch = chain;  // (kernel.h: an opaque copy, so that the row's address is built here and not kept across the steps)
+              PTRWM_VALUE_BARRIER("+v"(ch));
+              a.full.flow_round_trips[ch * T + flow_id(fw)] += 1;
+            }
+            fl[L::kFlowUp * nslots + slot] += (int)flow_visit_up(fw);
+            fl[L::kFlowDown * nslots + slot] += (int)flow_visit_down(fw);
+          }
+        }
       }
       lp = my_l;
       ++swap_in_call;
@@ -998,7 +1031,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
       }
       trace_rows += trace_now ? 1 : 0;
       // the state after the whole step: every lane adds its own range of the row, the first lane the log-density
-      if (a.full.mom_sum != nullptr && countdown_due(to_mom, a.full.mom_every) && count_on && live && t < a.full.mom_temps) {
+      if (a.full.mom_sum != nullptr && countdown_due(to_mom, a.full.mom_every) && count_on && live && t < (int)a.full.mom_temps) {
         MomentsAcc m(&a.full, cpw, D);
         m.reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), m.doubles());
         const MomentsAcc::Row r = m.row(cw, t);
@@ -1036,7 +1069,7 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
       if (fa->mom_sum != nullptr) {
         MomentsAcc m(fa, cpw, D);
         m.reg = L::moments_region(s_dyn, wide, (int)(threadIdx.x >> 6), m.doubles());
-        m.end(fa, live_chains, chain0, tid, gthreads);
+        m.end(fa, (long long)ae->full_mom_steps, live_chains, chain0, tid, gthreads);
       }
     }
     stage_copy<false>(rows_f, gs, stage_total, tid, gthreads);
@@ -1050,6 +1083,16 @@ __global__ void __launch_bounds__(MAXT, quad_min_waves(W, F64, FULL)) ptrwm_quad
       const long long ev = ae->first_swap_event + last_event;
       const long long ord = swap_attempt_ordinal(ae->swap_order, ev, T, t);
       if (ord > ae->last_swap_ordinal[rep]) ae->last_swap_ordinal[rep] = ord;
+    }
+    if constexpr (FULL) {  // replica flow (kernel.h): the word this position holds now, the launch's visits
+      const kargs_full_ptr fa = &ae->full;
+      if (fa->flow_walker != nullptr) {
+        const int *const fl = L::flow_region(s_dyn, wide, (int)(threadIdx.x >> 6), ae->full_flow_lds) + slot;
+        fa->flow_walker[rep] = fl[(swap_in_call & 1) * nslots];
+        const int n_up = fl[L::kFlowUp * nslots], n_down = fl[L::kFlowDown * nslots];
+        if (fa->flow_up != nullptr && n_up != 0) count_add(&fa->flow_up[rep], (long long)n_up);
+        if (fa->flow_down != nullptr && n_down != 0) count_add(&fa->flow_down[rep], (long long)n_down);
+      }
     }
   }
 }

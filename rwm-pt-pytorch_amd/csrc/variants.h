@@ -120,37 +120,49 @@ inline int device_cus() {
 // LDS of a CU (MI355X: 160 KiB), the most one workgroup may declare
 constexpr unsigned kMaxLdsBytes = 160u * 1024u;
 // What a step-kernel launch asks for: threads of a workgroup, its dynamic LDS bytes (kernel.h StepLds, quad.h QuadLds), and
-// those bytes with the FULL twin's moments regions behind them (one per wave of a narrow workgroup, one for a wide ladder).
+// those bytes with the FULL twin's moments regions behind them (one per wave of a narrow workgroup, one for a wide ladder),
+// and the bytes of its flow regions, which come behind either in a launch with flow (kernel.h StepLds, quad.h QuadLds).
 // ONE function per kernel form: the launcher launches with it, the C ABI refuses with it what does not fit (capi.hip).
 struct LaunchShape {
-  unsigned block, lds, lds_moments;
+  unsigned block, lds, lds_moments, flow;
+  // what a launch of the FULL twin asks for
+  unsigned full_bytes(bool moments, bool with_flow) const { return (moments ? lds_moments : lds) + (with_flow ? flow : 0u); }
 };
-inline LaunchShape with_moments(unsigned block, unsigned lds, bool wide, const KArgs &a) {
+inline LaunchShape with_moments(unsigned block, unsigned lds, bool wide, unsigned flow, const KArgs &a) {
   const int rows = moments_rows(a.full.mom_chain != 0, a.chains_per_wave, a.full.mom_temps);  // (per chain: a row per ladder of the group)
-  return {block, lds, lds + (wide ? 1u : block / 64u) * moments_region_doubles(rows, a.dim) * 8u};
+  return {block, lds, lds + (wide ? 1u : block / 64u) * moments_region_doubles(rows, a.dim) * 8u, flow};
 }
 // thread form.  Narrow ladders: four independent one-wave groups per workgroup; wide (n_temps > 64): the waves the ladder needs
 inline LaunchShape thread_launch_shape(const KArgs &a, int dp) {
   const bool wide = a.n_temps > 64;
   const unsigned block = wide ? (unsigned)group_threads(a.n_temps, 1) : (unsigned)kBlockThreads;
-  return with_moments(block, StepLdsWords::bytes((int)block, dp, false, wide), wide, a);
+  return with_moments(block, StepLdsWords::bytes((int)block, dp, false, wide), wide, StepLdsWords::flow_bytes((int)block), a);
 }
 using StepKernelFn = void (*)(const KArgs);
 // The common end of a launcher: the production kernel or its FULL twin with `sh` (with the moments regions when the launch
 // accumulates moments).  Above the default dynamic-LDS allowance the pair's is raised to `cap` bytes first (the most this
-// variant ever asks for), the twin's alone to a CU's whole LDS for moments.  raised / raised_m: the caller's per-instantiation statics.
+// variant ever asks for), the twin's alone to a CU's whole LDS for moments and flow.  raised / raised_m: the caller's per-instantiation statics.
 inline hipError_t launch_twins(StepKernelFn kfull, StepKernelFn kprod, const KArgs &a, unsigned grid, const LaunchShape &sh, bool full,
                                unsigned cap, unsigned long long &raised, unsigned long long &raised_m, hipStream_t stream) {
   if (sh.lds > 48u * 1024u) {
     const hipError_t e = raise_dynamic_lds((const void *)kfull, (const void *)kprod, (int)cap, raised);
     if (e != hipSuccess) return e;
   }
-  const bool moments = full && a.full.mom_sum != nullptr;
-  if (moments && sh.lds_moments > 48u * 1024u) {
+  const bool moments = full && a.full.mom_sum != nullptr, flow = full && a.full.flow_walker != nullptr;
+  const unsigned ask = sh.full_bytes(moments, flow);
+  if ((moments || flow) && ask > 48u * 1024u) {
     const hipError_t e = raise_dynamic_lds((const void *)kfull, (const void *)kfull, (int)kMaxLdsBytes, raised_m);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(full ? kfull : kprod, dim3(grid), dim3(sh.block), moments ? sh.lds_moments : sh.lds, stream, a);
+  if (flow) {  // where the flow regions begin: behind everything else this launch holds (kernel.h StepLds::flow_region)
+    KArgs b = a;
+    b.full_flow_lds = sh.full_bytes(moments, false) / StepLdsWords::kFlowLdsUnit;
+    static_assert(StepLdsWords::bytes(64, 1, false, false) % StepLdsWords::kFlowLdsUnit == 0 && StepLdsWords::kVoteBytes % StepLdsWords::kFlowLdsUnit == 0 &&
+                      QuadLdsWords::bytes(64, 1, false) % StepLdsWords::kFlowLdsUnit == 0, "whole units: floats x whole waves, the vote word, doubles");
+    hipLaunchKernelGGL(kfull, dim3(grid), dim3(sh.block), ask, stream, b);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(full ? kfull : kprod, dim3(grid), dim3(sh.block), ask, stream, a);
   return hipGetLastError();
 }
 
@@ -276,7 +288,7 @@ struct QuadVariants {
 // lane-split form.  Narrow ladders (4 T <= 64): four independent one-wave groups per workgroup; wide: the workgroup is the group
 inline LaunchShape quad_launch_shape(const KArgs &a, int w, bool f64) {
   const unsigned block = (unsigned)quad_block_threads(a.n_temps);
-  return with_moments(block, QuadLdsWords::bytes((int)block, w, f64), 4 * a.n_temps > 64, a);
+  return with_moments(block, QuadLdsWords::bytes((int)block, w, f64), 4 * a.n_temps > 64, QuadLdsWords::flow_bytes((int)block), a);
 }
 
 template <class Target, class Proposal, int W, int DEXACT, int MAXT, bool F64 = false>

@@ -140,6 +140,18 @@ class ChainMomentsArgs(C.Structure):
     _fields_ = _MOMENTS_FIELDS
 
 
+class FlowArgs(C.Structure):
+    """ptrwm_flow_args: the flow words of every position and the round-trip / visit counters (include/ptrwm.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("reserved", C.c_int32),
+        ("walker", C.c_void_p),
+        ("round_trips", C.c_void_p),
+        ("n_up", C.c_void_p),
+        ("n_down", C.c_void_p),
+    ]
+
+
 class InitArgs(C.Structure):
     """ptrwm_init_args: starting points drawn from a box, or set to a fallback point (include/ptrwm.h)."""
     _fields_ = [
@@ -179,6 +191,14 @@ SYMBOLS = {
         C.c_int32,
         [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(ChainMomentsArgs), C.c_void_p]),
     "ptrwm_split_chain_moments": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(ChainMomentsArgs), C.c_void_p]),
+    "ptrwm_run_with_diagnostics": (
+        C.c_int32,
+        [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.POINTER(ChainMomentsArgs),
+         C.POINTER(FlowArgs), C.c_void_p]),
+    "ptrwm_swap_sweep_with_flow": (
+        C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_int64, C.c_int32, C.POINTER(FlowArgs), C.c_void_p]),
+    "ptrwm_split_accept_with_flow": (
+        C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FlowArgs), C.c_void_p]),
     "ptrwm_swap_sweep": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_int64, C.c_int32, C.c_void_p]),
     "ptrwm_split_propose": (
         C.c_int32, [C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -580,6 +600,7 @@ class RunPlan:
         self._last_trace = (None, None, None)  # (trace, trace_logp, trace_every) marshalled into _a by the last launch
         self._guard = on_device(self.device)  # (after the checks above: they reject CPU tensors first)
         self._mom = None  # the accumulator, pooled or per chain: (kind of _MOMENT_KINDS, struct, byref, tensors)
+        self._flow = None  # replica flow: (struct, byref, tensors)
 
     # kind of accumulator -> (words of its messages, struct, entry point of launch(), entry point of split_moments())
     _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
@@ -641,6 +662,29 @@ class RunPlan:
         A plan holds ONE accumulator, pooled or per chain: this replaces whichever was set.
         ``set_chain_moments(None)`` switches per-chain moments off."""
         self._bind_moments("chain", (self.shape[0],), sum, sum_sq, sum_logp, count, every)
+
+    def set_flow(self, walker: Optional[torch.Tensor], round_trips: Optional[torch.Tensor] = None,
+                 n_up: Optional[torch.Tensor] = None, n_down: Optional[torch.Tensor] = None) -> None:
+        """Track replica flow (include/ptrwm.h ptrwm_flow_args) in every following ``launch``, ``split_accept`` and
+        ``swap_sweep``: ``walker`` [n_chains, n_temps] int32 flow words (the caller starts them at ``arange(n_temps)`` per
+        ladder), ``round_trips`` (by walker id), ``n_up`` and ``n_down`` (by temperature) [n_chains, n_temps] int64, each
+        optional, all on the run's device and added to (+=).  ``set_flow(None)`` switches flow off."""
+        if walker is None:
+            self._flow = None
+            return
+        Cn, T, _ = self.shape
+        if T < 2:
+            raise ValueError("replica flow needs a ladder of at least two temperatures")
+        for name, t in (("walker", walker), ("round_trips", round_trips), ("n_up", n_up), ("n_down", n_down)):
+            if t is not None and (tuple(t.shape) != (Cn, T) or t.device != self.device):
+                raise ValueError(f"flow {name} must be a [{Cn}, {T}] tensor on {self.device}")
+        f = FlowArgs()
+        f.struct_size = C.sizeof(FlowArgs)
+        f.walker = _require_device(walker, "flow walker", torch.int32)
+        f.round_trips = _opt(round_trips, "flow round_trips", torch.int64)
+        f.n_up = _opt(n_up, "flow n_up", torch.int64)
+        f.n_down = _opt(n_down, "flow n_down", torch.int64)
+        self._flow = (f, C.byref(f), (walker, round_trips, n_up, n_down))
 
     def init_states(self, lo: torch.Tensor, hi: torch.Tensor, *, attempt: int = 0, per_temperature: bool = False,
                     fallback: Optional[torch.Tensor] = None) -> None:
@@ -745,8 +789,15 @@ class RunPlan:
                 self._last_trace = (trace, trace_logp, trace_every)
         # ptrwm_run, or the accumulator's entry point with its struct in front of the stream
         name, mom = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
-        with self._guard:
-            rc = getattr(self._lib, name)(self._refs[2], self._refs[3], self._refs[4], *mom, _stream(self.device))
+        if self._flow is not None:  # flow bound: the entry point that takes every diagnostic
+            name = "ptrwm_run_with_diagnostics"
+            pooled = self._mom[2] if self._mom is not None and self._mom[0] == "pooled" else None
+            chain = self._mom[2] if self._mom is not None and self._mom[0] == "chain" else None
+            with self._guard:
+                rc = self._lib.ptrwm_run_with_diagnostics(self._refs[2], self._refs[3], self._refs[4], pooled, chain, self._flow[1], _stream(self.device))
+        else:
+            with self._guard:
+                rc = getattr(self._lib, name)(self._refs[2], self._refs[3], self._refs[4], *mom, _stream(self.device))
         if rc != 0:
             raise PTRWMError(rc, name)
 
@@ -829,15 +880,18 @@ class RunPlan:
         a.ext_swap_u = _opt(ext_swap_u, "ext_swap_u", torch.float32)
         a.accept_flags = _opt(accept_flags, "accept_flags", torch.uint8)
         self._plain = False
+        lp = _require_device(logp_proposed, "logp_proposed", torch.float32)
         try:
-            with self._guard:
-                rc = self._lib.ptrwm_split_accept(self._refs[4], D, props.data_ptr(), acc_u.data_ptr(),
-                                                  _require_device(logp_proposed, "logp_proposed", torch.float32),
-                                                  _stream(self.device))
+            if self._flow is not None:  # the flow update happens inside the swap kernel this enqueues
+                with self._guard:
+                    rc = self._lib.ptrwm_split_accept_with_flow(self._refs[4], D, props.data_ptr(), acc_u.data_ptr(), lp, self._flow[1], _stream(self.device))
+            else:
+                with self._guard:
+                    rc = self._lib.ptrwm_split_accept(self._refs[4], D, props.data_ptr(), acc_u.data_ptr(), lp, _stream(self.device))
         finally:
             a.split_flags = 0  # (every other entry point requires 0)
         if rc != 0:
-            raise PTRWMError(rc, "ptrwm_split_accept")
+            raise PTRWMError(rc, "ptrwm_split_accept_with_flow" if self._flow is not None else "ptrwm_split_accept")
 
     def swap_sweep(self, rng_step: int, event_index: int, rng_stream: int = 2,
                    ext_swap_u: Optional[torch.Tensor] = None) -> None:
@@ -854,10 +908,14 @@ class RunPlan:
         self._last_trace = (None, None, None)
         a.ext_swap_u = _opt(ext_swap_u, "ext_swap_u", torch.float32)
         self._plain = False  # per-launch fields of _a were touched: the next launch() rewrites them
-        with self._guard:
-            rc = self._lib.ptrwm_swap_sweep(self._refs[4], D, event_index, rng_stream, _stream(self.device))
+        if self._flow is not None:
+            with self._guard:
+                rc = self._lib.ptrwm_swap_sweep_with_flow(self._refs[4], D, event_index, rng_stream, self._flow[1], _stream(self.device))
+        else:
+            with self._guard:
+                rc = self._lib.ptrwm_swap_sweep(self._refs[4], D, event_index, rng_stream, _stream(self.device))
         if rc != 0:
-            raise PTRWMError(rc, "ptrwm_swap_sweep")
+            raise PTRWMError(rc, "ptrwm_swap_sweep_with_flow" if self._flow is not None else "ptrwm_swap_sweep")
 
 
 def run(

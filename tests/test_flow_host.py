@@ -1,0 +1,207 @@
+"""Replica flow (include/ptrwm.h ptrwm_flow_args, csrc/flow.h) without a GPU: the rule's header against a literal
+restatement, the struct's C layout, every validation code of the three entry points that returns before a HIP call, and the
+arithmetic of the class accessors and of the shards' all-reduce on hand-made tensors."""
+import ctypes as C
+import math
+import os
+import subprocess
+
+import pytest
+import torch
+
+import ptrwm_hip as E
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+
+
+def test_flow_header_against_a_literal_restatement(tmp_path):
+    """csrc/flow.h compiled as plain C++ under AddressSanitizer and UBSan into tests/flow_test.cpp, a program of its own:
+    random accept patterns for T in {2, 3, 5, 8, 64, 70, 256}, both modes and both orders; flow words moved through src[t] as
+    the kernels move them against explicit id / direction arrays and sequential transpositions or copies, after every event."""
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "flow_test.cpp")
+    exe = str(tmp_path / "flow_test")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", src, "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    assert "flow ok: 62400 events, 7 ladder lengths x 2 modes x 2 orders x 3 acceptance rates" in out.stdout
+
+
+def test_flow_struct_layout_matches_the_c_header(tmp_path):
+    fields = [f[0] for f in E.FlowArgs._fields_]
+    assert fields == ["struct_size", "reserved", "walker", "round_trips", "n_up", "n_down"]
+    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){",
+             'printf("size %zu\\n", sizeof(ptrwm_flow_args));']
+    lines += [f'printf("{f} %zu\\n", offsetof(ptrwm_flow_args, {f}));' for f in fields]
+    lines.append('printf("abi %d\\n", PTRWM_ABI_VERSION);')
+    lines.append("return 0;}")
+    src = tmp_path / "probe.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "probe"
+    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
+    got = dict(ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())
+    assert C.sizeof(E.FlowArgs) == int(got["size"])
+    for f in fields:
+        assert getattr(E.FlowArgs, f).offset == int(got[f]), f
+    assert int(got["abi"]) == E.ABI_VERSION == 3  # additive: the version stays
+
+
+def _valid(n_temps=4):
+    """Arguments every entry point accepts up to its first HIP call (the pointers point at host memory a refused call never
+    reads)."""
+    buf = C.create_string_buffer(64)
+    ptr = C.cast(buf, C.c_void_p)
+    td, pd, ra, fl = E.TargetDesc(), E.ProposalDesc(), E.RunArgs(), E.FlowArgs()
+    td.kind, td.dim = E.TARGET_ROUGH_CARPET, 30
+    pd.kind, pd.temp_scale = E.PROPOSAL_NORMAL, ptr
+    ra.struct_size, ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = C.sizeof(E.RunArgs), n_temps, 4, 10, 1
+    ra.state = ra.logp = ra.beta = ptr
+    fl.struct_size, fl.walker = C.sizeof(E.FlowArgs), ptr
+    mom, cmom = E.MomentsArgs(), E.ChainMomentsArgs()
+    for m in (mom, cmom):
+        m.struct_size, m.temps, m.every, m.sum, m.sum_sq = C.sizeof(m), 1, 1, ptr, ptr
+    return {"buf": buf, "ptr": ptr, "td": td, "pd": pd, "ra": ra, "fl": fl, "mom": mom, "cmom": cmom}
+
+
+def test_flow_validation_needs_no_gpu():
+    lib = E.load_library()
+
+    def run(v, mom=None, cmom=None, flow="fl"):
+        return lib.ptrwm_run_with_diagnostics(C.byref(v["td"]), C.byref(v["pd"]), C.byref(v["ra"]),
+                                              C.byref(v[mom]) if mom else None, C.byref(v[cmom]) if cmom else None,
+                                              C.byref(v[flow]) if flow else None, None)
+
+    def sweep(v, flow="fl", dim=30):
+        return lib.ptrwm_swap_sweep_with_flow(C.byref(v["ra"]), dim, 0, 1, C.byref(v[flow]) if flow else None, None)
+
+    def accept(v, flow="fl", dim=30):
+        p = v["ptr"]
+        return lib.ptrwm_split_accept_with_flow(C.byref(v["ra"]), dim, p, p, p, C.byref(v[flow]) if flow else None, None)
+
+    for call in (run, sweep, accept):
+        v = _valid()
+        v["fl"].struct_size = 4
+        assert call(v) == -6, call.__name__  # PTRWM_E_STRUCT
+        v = _valid()
+        v["fl"].walker = None
+        assert call(v) == -1, call.__name__  # PTRWM_E_NULL
+        v = _valid()
+        v["fl"].reserved = 1
+        assert call(v) == -5, call.__name__  # PTRWM_E_ARG
+        v = _valid(n_temps=1)
+        assert call(v) == -5, call.__name__  # a ladder of one temperature has no flow
+        # the struct size is looked at first, then the walker, then the arguments
+        v = _valid(n_temps=1)
+        v["fl"].struct_size, v["fl"].walker = 4, None
+        assert call(v) == -6
+        v = _valid(n_temps=1)
+        v["fl"].walker = None
+        assert call(v) == -1
+        # the entry point's own checks come first: the argument block's size, the ladder's length
+        v = _valid()
+        v["ra"].struct_size, v["fl"].struct_size = 4, 4
+        assert call(v) == -6
+        v = _valid(n_temps=257)
+        v["fl"].walker = None
+        assert call(v) == -3
+        # ptrwm_run looks at its diagnostics before its remaining arguments (as it does for the moments), the other two after
+        v = _valid()
+        v["ra"].swap_mode, v["fl"].walker = 7, None
+        assert call(v) == (-1 if call is run else -5)
+        # an empty batch with valid flow: nothing to do; with a bad flow block: still refused
+        v = _valid()
+        v["ra"].n_chains = 0
+        assert call(v) == 0
+        v["fl"].reserved = 2
+        assert call(v) == -5
+    # ptrwm_run_with_diagnostics: at most one accumulator; its checks come before flow's
+    v = _valid()
+    assert run(v, mom="mom", cmom="cmom") == -5
+    assert run(v, mom="mom", cmom="cmom", flow=None) == -5
+    v["mom"].struct_size, v["fl"].walker = 4, None
+    assert run(v, mom="mom") == -6
+    v = _valid()
+    v["cmom"].temps, v["fl"].struct_size = 9, 4
+    assert run(v, cmom="cmom") == -5
+    v = _valid(n_temps=257)
+    assert run(v) == -3 and sweep(v) == -3 and accept(v) == -3
+    v = _valid()
+    assert sweep(v, dim=105) == -2 and accept(v, dim=105) == -2
+    v["td"].dim = 105
+    assert run(v) == -2
+    # flow == NULL: the existing entry points' codes (tests/test_capi_library.py TWO_DEFECT_CODES)
+    v = _valid()
+    v["ra"].n_temps, v["ra"].state_f64 = 257, 2
+    assert run(v, flow=None) == -3 and sweep(v, flow=None) == -5 and accept(v, flow=None) == -5
+    v = _valid()
+    v["ra"].state = None
+    assert run(v, flow=None) == -1 and sweep(v, flow=None) == -1 and accept(v, flow=None) == -1
+    # the LDS budget, refused before anything is enqueued: per-chain moments of every temperature that fill the workgroup's
+    # 160 KiB to the last byte (include/ptrwm.h: RWM-like shape, here 2 temperatures x 32 ladders per wave, dim 30) leave no
+    # room for the flow regions; the same request without flow passes this check and goes on to the launch, which a machine
+    # without a GPU cannot make (PTRWM_E_LAUNCH or, with one, success - never PTRWM_E_ARG)
+    prev = E.set_kernel_form(E.FORM_THREAD)
+    try:
+        v = _valid(n_temps=2)
+        v["ra"].n_chains = 0  # (validated, nothing enqueued)
+        v["cmom"].temps = 2
+        assert run(v, cmom="cmom") == 0
+        v["ra"].n_chains = 64
+        # thread form: 38 912 bytes + 4 waves x 32 ladders x 2 temps x 61 doubles x 8 = 38 912 + 124 928 = 163 840 = 160 KiB
+        assert run(v, cmom="cmom") == -5  # + 4 096 bytes of flow regions: does not fit
+        # the controls - that this -5 is the budget and nothing else - are requests that PASS every check and go on to the
+        # launch.  Their pointers are fakes, so they are made only where no launch can happen: without a device the first HIP
+        # call fails and the entry point says PTRWM_E_LAUNCH, which it can only say once every argument check lies behind it
+        if not torch.cuda.is_available():
+            assert run(v, cmom="cmom", flow=None) == -7  # the same request without flow: exactly 160 KiB, fits
+            v["cmom"].temps = 1
+            assert run(v, cmom="cmom") == -7  # with flow, one moments temperature less: 38 912 + 62 464 + 4 096 bytes, fits
+    finally:
+        E.set_kernel_form(prev)
+
+
+def test_up_fraction_round_trip_rate_and_allreduce_on_hand_made_tensors():
+    from algorithms.sharding import allreduce_flow, flow_round_trip_rate, flow_up_fraction
+
+    n_up = torch.tensor([[5, 3, 0, 0], [5, 1, 2, 0]])
+    n_down = torch.tensor([[0, 1, 0, 5], [0, 3, 0, 5]])
+    f = flow_up_fraction(n_up.sum(0), n_down.sum(0))
+    assert f.dtype == torch.float64 and f.shape == (4,)
+    assert f[0] == 1.0 and f[3] == 0.0 and f[1] == 0.5 and f[2] == 1.0
+    f = flow_up_fraction(torch.tensor([5, 0]), torch.tensor([0, 0]))
+    assert f[0] == 1.0 and math.isnan(f[1])  # nothing has visited: NaN, not 0
+    assert flow_round_trip_rate(6, 2, 4, 5) == 6 / 40
+    assert flow_round_trip_rate(0, 2, 4, 0) == 0.0
+    trips = torch.tensor([[1, 0, 2, 0], [0, 3, 0, 0]])
+    out = allreduce_flow({"walker": torch.zeros(2, 4, dtype=torch.int32), "round_trips": trips, "n_up": n_up, "n_down": n_down,
+                          "events": 5})  # single process, no process group: the job is this shard
+    assert out["round_trips_total"] == 6 and out["n_replicas"] == 2 and out["events"] == 5
+    assert out["round_trip_rate"] == 6 / (2 * 4 * 5)
+    assert out["n_up"].tolist() == [10, 4, 2, 0] and out["n_down"].tolist() == [0, 4, 0, 10]
+    assert out["up_fraction"].tolist() == [1.0, 0.5, 1.0, 0.0]
+
+
+def test_class_flow_checks_need_no_gpu():
+    """What the class and the run refuse before a device is asked for."""
+    import numpy as np
+
+    from algorithms import ParallelTemperingRWM_GPU_Optimized
+    from algorithms._engine_core import EngineRun
+    from target_distributions import RoughCarpetDistributionTorch
+
+    tgt = RoughCarpetDistributionTorch(3, device="cpu")
+    with pytest.raises(ValueError, match="two temperatures"):
+        ParallelTemperingRWM_GPU_Optimized(3, 1.0, tgt, beta_ladder=[1.0], device="cpu", flow=True)
+    alg = ParallelTemperingRWM_GPU_Optimized(3, 1.0, tgt, beta_ladder=[1.0, 0.5, 0.1], device="cpu", flow=True, num_replicas=2)
+    assert alg.walker_positions().tolist() == [[0, 1, 2], [0, 1, 2]] and alg.walker_positions().dtype == torch.int32
+    assert alg.round_trips().shape == (2, 3) and alg.round_trips().dtype == torch.int64 and alg.round_trip_rate() == 0.0
+    assert torch.isnan(alg.up_fraction()).all() and alg.up_fraction().dtype == torch.float64
+    off = ParallelTemperingRWM_GPU_Optimized(3, 1.0, tgt, beta_ladder=[1.0, 0.5], device="cpu")
+    with pytest.raises(RuntimeError, match="flow=True"):
+        off.round_trips()
+    assert "round_trips_total" not in off.get_diagnostic_info()
+    with pytest.raises(ValueError, match="two temperatures"):
+        EngineRun(target_dist=tgt, proposal=None, beta_ladder=[1.0], dim=3, device=torch.device("cpu"), n_replicas=1,
+                  initial_state=np.zeros(3, np.float32), burn_in=0, swap_every=1, swap_mode="exchange", swap_order="sequential",
+                  seed=1, flow=True)
