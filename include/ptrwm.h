@@ -436,6 +436,62 @@ int32_t ptrwm_swap_sweep_with_flow(const ptrwm_run_args *args, int32_t dim, int6
 int32_t ptrwm_split_accept_with_flow(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
                                      const float *logp_proposed, const ptrwm_flow_args *flow, void *stream);
 
+/* ---- pooled marginal histograms: mode weights and quantiles without a trace -------------------------------------------------
+ * Mean and variance cannot tell a population stuck in one mode from one that splits its mass over three.  A histogram
+ * accumulator covers the first `temps` temperatures.  For each such temperature t, every coordinate d and every local chain, at
+ * every step whose step_counter > burn_in and step_counter % every == 0:
+ *   counts[t, d, bin(x_d)] += 1,   count[t] += 1
+ * where x is the replica's state after the whole step (MH move and that step's swap event) - the values a trace with
+ * trace_every = every records at that step.  The bin rule (csrc/hist.h), with n_bins equal bins over [lo[d], hi[d]) and the
+ * caller's scale[d] = n_bins / (hi[d] - lo[d]) as a float:
+ *   u = (x_d - lo[d]) * scale[d]      in float, each operation rounded on its own (a double state is rounded to float first)
+ *   bin = 0            if !(u >= 0)   underflow; a NaN coordinate lands HERE too
+ *   bin = n_bins + 1   if u >= n_bins overflow, +inf included
+ *   bin = 1 + (int)u   otherwise
+ * Everything is integer and only ever added to (+=): results are exact, do not depend on the order of the additions, and
+ * launches, calls and shards compose.  ptrwm_swap_sweep events are not steps and add nothing.
+ * How: NOT in the step kernels.  A small stand-alone snapshot kernel reads `state` between launches: ptrwm_run_with_histogram
+ * ends a launch at every due step and enqueues the snapshot kernel behind it on the same stream.  A workgroup takes a tile of
+ * 256 chains and up to 256 of the temps * dim columns; it counts in 32-bit LDS counters (32 KiB) and flushes each non-zero
+ * counter with one 64-bit atomic.  With n_bins > 126 fewer than 64 columns of counters would fit the LDS and the kernel
+ * adds to `counts` with global atomics directly.  The accumulators must be ordinary device memory of the current device. */
+#define PTRWM_HIST_MAX_BINS 1024
+typedef struct ptrwm_hist_args {
+  uint32_t struct_size; /* sizeof(ptrwm_hist_args) */
+  int32_t temps;        /* 1..n_temps: the first `temps` temperatures */
+  int32_t every;        /* >= 1: a snapshot at every step past burn-in whose step_counter is a multiple */
+  int32_t n_bins;       /* 1..PTRWM_HIST_MAX_BINS */
+  const float *lo;      /* device [dim] */
+  const float *scale;   /* device [dim]: n_bins / (hi - lo), as float */
+  int64_t *counts;      /* device [temps, dim, n_bins + 2], +=; bin 0 underflow, bin n_bins + 1 overflow */
+  int64_t *count;       /* device [temps], +=, or NULL: (chain, step) pairs added per temperature */
+} ptrwm_hist_args;
+
+/* One snapshot: the state as it stands after step args->step0 (device-step mode: *device_step + step0 - read on the device,
+ * so the call can sit inside a captured block of split steps, after ptrwm_split_accept); a step that is not due adds
+ * nothing.  Reads from `args`: n_temps, n_chains, state, state_f64, burn_in, step0, device_step.
+ * Checked, in this order, before anything is enqueued: PTRWM_E_NULL for a NULL args / hist; PTRWM_E_STRUCT for a wrong
+ * struct_size of args; PTRWM_E_DIM / PTRWM_E_TEMPS as everywhere; PTRWM_E_ARG for state_f64 outside 0..1 or a negative
+ * n_chains, step0 or burn_in; then the block's own checks as below; an empty batch returns PTRWM_OK; PTRWM_E_NULL for a NULL
+ * state. */
+int32_t ptrwm_histogram(const ptrwm_run_args *args, int32_t dim, const ptrwm_hist_args *hist, void *stream);
+
+/* ptrwm_run_with_diagnostics, plus histograms.  hist == NULL: exactly ptrwm_run_with_diagnostics.
+ * A launch of the request additionally ends at every step whose step_counter is past burn_in and a multiple of hist->every,
+ * and the snapshot kernel is enqueued right after it on `stream`; a request without such a step performs exactly the launches
+ * it performs without `hist`.  No step kernel is told about the histogram: a run with histograms and nothing else runs the
+ * production kernel.  Everything else of the run is bit-identical with and without `hist` - state, logp, every counter,
+ * moments, flow, traces - with the one exception that holds for any change of where a run is cut into launches
+ * (ptrwm_run_args.sq_jump above): the sq_jump sum of a replica that crosses the trust bound in the middle of a launch can
+ * differ in its last bits.  External randoms are allowed (the cuts advance ext_* by the steps done).
+ * Checked before anything is enqueued, after the accumulators' and flow's checks: PTRWM_E_STRUCT for a wrong
+ * hist->struct_size; PTRWM_E_ARG for temps outside 1..n_temps, every < 1 or n_bins outside 1..PTRWM_HIST_MAX_BINS;
+ * PTRWM_E_NULL for a NULL lo, scale or counts.  An empty batch returns PTRWM_OK. */
+int32_t ptrwm_run_with_histogram(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                                 const ptrwm_run_args *args, const ptrwm_moments_args *moments,
+                                 const ptrwm_chain_moments_args *chain_moments, const ptrwm_flow_args *flow,
+                                 const ptrwm_hist_args *hist, void *stream);
+
 /* One stand-alone swap event over the current states: what the reference's
  * ParallelTemperingRWM_GPU_Optimized._attempt_all_swaps() does when called on its own
  * (pt_rwm_gpu_optimized.py:594-633; tests/debug_pt_performance.py:156).  Exactly the swap part of a ptrwm_run step:

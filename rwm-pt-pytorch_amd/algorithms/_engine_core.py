@@ -25,6 +25,13 @@ and, with flow=True, the replica-flow arrays (`_flow`, a dict; include/ptrwm.h p
     round_trips  int64   [n_replicas, n_temps]        completed cold -> hot -> cold trips, by walker id
     n_up, n_down int64   [n_replicas, n_temps]        visits by replicas that last touched the cold / the hot end
 
+and, with hist_temps > 0, the pooled marginal histograms (`_hist`, a dict; include/ptrwm.h ptrwm_hist_args), added to by a
+snapshot kernel between launches at every hist_every-th step past burn-in:
+
+    counts       int64   [hist_temps, dim, hist_bins + 2]   bin 0 underflow (and NaN), bin hist_bins + 1 overflow
+    count        int64   [hist_temps]                       (replica, step) pairs added per temperature
+    lo, scale    float32 [dim]                              the bin rule's constants (csrc/hist.h)
+
 `n_replicas` is the axis the reference does not have: independent copies of the whole chain /
 ladder, one Philox subsequence each (global replica id = chain_offset + local index), so a run is
 invariant to how replicas are sharded over GPUs.
@@ -87,6 +94,58 @@ def check_init_box(init_box, dim: int) -> Optional[tuple]:
     return out[0], out[1]
 
 
+def check_hist_range(hist_range, dim: int) -> tuple:
+    """`hist_range` = (lo, hi), each bound a scalar or a [dim] vector, as two float32 [dim] arrays.  ValueError unless both are
+    finite and lo < hi element-wise AFTER rounding to float32 (the bin rule divides by their float32 difference).  Host-only."""
+    try:
+        lo, hi = hist_range
+    except (TypeError, ValueError):
+        raise ValueError("hist_range must be a pair (lo, hi)") from None
+    out = []
+    for name, b in (("lo", lo), ("hi", hi)):
+        b = np.asarray(b.detach().cpu() if torch.is_tensor(b) else b, dtype=np.float64)
+        if b.shape not in ((), (dim,)):
+            raise ValueError(f"hist_range: {name} must be a scalar or a [{dim}] vector, got shape {list(b.shape)}")
+        if not np.all(np.isfinite(b)):
+            raise ValueError(f"hist_range: {name} must be finite")
+        out.append(np.ascontiguousarray(np.broadcast_to(b, (dim,)).astype(np.float32)))
+    if not np.all(np.isfinite(out[0])) or not np.all(np.isfinite(out[1])) or not np.all(out[0] < out[1]):
+        raise ValueError("hist_range: lo < hi must hold in every coordinate")
+    return out[0], out[1]
+
+
+def hist_scale(lo: np.ndarray, hi: np.ndarray, n_bins: int) -> np.ndarray:
+    """scale[d] of the bin rule (csrc/hist.h): float32(n_bins) / (float32(hi) - float32(lo)), every operation in float32."""
+    return (np.float32(n_bins) / (hi.astype(np.float32) - lo.astype(np.float32))).astype(np.float32)
+
+
+def hist_edges(lo: np.ndarray, hi: np.ndarray, n_bins: int) -> torch.Tensor:
+    """The n_bins + 1 edges of every coordinate, float64 [dim, n_bins + 1] (CPU): lo + i (hi - lo) / n_bins of the float32 bounds."""
+    lo64, hi64 = lo.astype(np.float64), hi.astype(np.float64)
+    i = np.arange(n_bins + 1, dtype=np.float64)
+    e = lo64[:, None] + i[None, :] * ((hi64 - lo64) / n_bins)[:, None]
+    e[:, -1] = hi64
+    return torch.from_numpy(e)
+
+
+def check_hist_args(hist_temps, hist_every, hist_bins, hist_range, n_temps: int, dim: int):
+    """EngineRun's histogram arguments (no GPU needed): None when off, else (lo, hi) as float32 arrays."""
+    for name, v in (("hist_temps", hist_temps), ("hist_every", hist_every), ("hist_bins", hist_bins)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not 0 <= hist_temps <= n_temps:
+        raise ValueError(f"hist_temps must be in 0..{n_temps}, got {hist_temps}")
+    if not hist_temps:
+        return None
+    if hist_every < 1:
+        raise ValueError(f"hist_every must be >= 1, got {hist_every}")
+    if not 1 <= hist_bins <= ptrwm_hip.HIST_MAX_BINS:
+        raise ValueError(f"hist_bins must be in 1..{ptrwm_hip.HIST_MAX_BINS}, got {hist_bins}")
+    if hist_range is None:
+        raise ValueError("histograms need hist_range=(lo, hi): the range the bins cover (there are no adaptive ranges)")
+    return check_hist_range(hist_range, dim)
+
+
 def check_init_attempts(init_attempts) -> int:
     if isinstance(init_attempts, bool) or not isinstance(init_attempts, (int, np.integer)) or not 1 <= init_attempts <= 65535:
         raise ValueError(f"init_attempts must be an integer in 1..65535, got {init_attempts!r}")
@@ -131,7 +190,8 @@ class EngineRun:
                  swap_mode: str, swap_order: str, seed: Optional[int], chain_offset: int = 0,
                  dtype: torch.dtype = torch.float32, moments_temps: int = 0, moments_every: int = 1,
                  moments_per_chain: bool = False, init_box=None, init_per_temperature: bool = False,
-                 init_attempts: int = 8, flow: bool = False):
+                 init_attempts: int = 8, flow: bool = False, hist_temps: int = 0, hist_every: int = 1, hist_bins: int = 64,
+                 hist_range=None):
         if swap_mode not in ptrwm_hip.SWAP_MODES:
             raise ValueError(f"swap_mode must be one of {sorted(ptrwm_hip.SWAP_MODES)}, got {swap_mode!r}")
         if swap_order not in ptrwm_hip.SWAP_ORDERS:
@@ -146,6 +206,7 @@ class EngineRun:
                              f"temperatures, got {n_temps}")
         if not 1 <= dim <= ptrwm_hip.MAX_DIM:
             raise ValueError(f"dim must be in 1..{ptrwm_hip.MAX_DIM} for the fused kernel, got {dim}")
+        hist_box = check_hist_args(hist_temps, hist_every, hist_bins, hist_range, n_temps, dim)
         # the starts (host-side checks, before the device is asked for: bad arguments fail the same way without a GPU)
         axes = start_shape(initial_state, dim, n_replicas, n_temps)
         box = check_init_box(init_box, dim)
@@ -252,6 +313,17 @@ class EngineRun:
                           **{k: torch.empty(shape, device=device, dtype=torch.int64) for k in ("round_trips", "n_up", "n_down")}}
             self.reset_flow()
             self._plan.set_flow(self._flow["walker"], self._flow["round_trips"], self._flow["n_up"], self._flow["n_down"])
+        # pooled marginal histograms, counted by a snapshot kernel between launches (off: None)
+        self.hist_temps, self.hist_every, self.hist_bins = int(hist_temps), int(hist_every), int(hist_bins)
+        self._hist = None
+        if hist_box is not None:
+            lo, hi = hist_box
+            self._hist = {"counts": torch.zeros(self.hist_temps, dim, self.hist_bins + 2, device=device, dtype=torch.int64),
+                          "count": torch.zeros(self.hist_temps, device=device, dtype=torch.int64),
+                          "lo": torch.from_numpy(lo).to(device), "scale": torch.from_numpy(hist_scale(lo, hi, self.hist_bins)).to(device)}
+            self._hist_edges = hist_edges(lo, hi, self.hist_bins)
+            self._plan.set_histogram(self._hist["counts"], self._hist["lo"], self._hist["scale"], n_bins=self.hist_bins,
+                                     temps=self.hist_temps, every=self.hist_every, count=self._hist["count"])
         if box is not None:
             self._draw_starts(box, x0.to(torch.float32).contiguous(), bool(init_per_temperature), attempts)
 
@@ -325,6 +397,7 @@ class EngineRun:
         lp_new = self._density(props.view(-1, D)).view(C, T)
         self._plan.split_accept(offset, lp_new, swap_event_offset=self.manual_sweeps, no_sweep=no_sweep)
         self._plan.split_moments(offset)  # (decides on the device whether this step counts; no-op without moments)
+        self._plan.split_histogram(offset)  # (likewise; no-op without a histogram)
         if advance:
             self._plan.split_advance(advance)
 
@@ -412,6 +485,7 @@ class EngineRun:
             lp_new = self._density(props.view(-1, D)).view(C, T)
             self._plan.split_accept(s, lp_new, swap_event_offset=self.manual_sweeps)
             self._plan.split_moments(s)
+            self._plan.split_histogram(s)
             self.steps_done += 1
             if trace is not None and ptrwm_hip.periodic_steps_in(s, s + 1, trace_every):
                 tc, tt = trace.shape[1], trace.shape[2]
@@ -463,6 +537,19 @@ class EngineRun:
         """Zero the moment accumulators (the chains keep their states)."""
         for t in (self._mom or {}).values():
             t.zero_()
+
+    def histogram(self) -> Optional[dict]:
+        """The pooled marginal histograms of this shard, or None when they are off: counts [hist_temps, dim, hist_bins + 2]
+        and count [hist_temps] (int64 device tensors, no synchronisation) and edges [dim, hist_bins + 1] (float64, CPU)."""
+        if self._hist is None:
+            return None
+        return {"counts": self._hist["counts"], "count": self._hist["count"], "edges": self._hist_edges}
+
+    def reset_histogram(self) -> None:
+        """Zero the histogram counters (the chains keep their states)."""
+        if self._hist is not None:
+            self._hist["counts"].zero_()
+            self._hist["count"].zero_()
 
     def flow(self) -> Optional[dict]:
         """Replica flow of this shard (device tensors, no synchronisation), or None when flow is off: walker (int32 flow
@@ -646,3 +733,175 @@ class PosteriorMoments:
             "posterior_variance": (m["sum_sq"] / n[:, None] - mean * mean).cpu(),
             "mean_log_density": (m["sum_logp"] / n).cpu(),
         }
+
+
+# ---- pooled marginal histograms of the drop-in classes -------------------------------------------------------------
+HIST_MODES = (None, "cold", "all")
+
+
+def hist_temps(mode, n_temps: int) -> int:
+    """Temperatures a `hist=` mode covers (0: off)."""
+    if mode not in HIST_MODES:
+        raise ValueError(f"hist must be None, 'cold' or 'all', got {mode!r}")
+    return {None: 0, "cold": 1, "all": n_temps}[mode]
+
+
+def _hist_cpu(counts, edges) -> tuple:
+    counts = torch.as_tensor(counts).detach().cpu().to(torch.int64)
+    edges = torch.as_tensor(edges).detach().cpu().to(torch.float64)
+    if counts.dim() != 2 or edges.shape != (counts.shape[0], counts.shape[1] - 1) or counts.shape[1] < 3:
+        raise ValueError("counts must be [dim, bins + 2] and edges [dim, bins + 1]")
+    return counts, edges
+
+
+def hist_density(counts, edges) -> torch.Tensor:
+    """counts [dim, bins + 2] / (total x bin width) over the bins proper: float64 [dim, bins].  The total includes the two end
+    bins, so the density integrates to the in-range fraction; NaN where nothing has been counted."""
+    counts, edges = _hist_cpu(counts, edges)
+    total = counts.sum(1).double()
+    total[total == 0] = float("nan")
+    return counts[:, 1:-1].double() / total[:, None] / (edges[:, 1:] - edges[:, :-1])
+
+
+def hist_quantiles(counts, edges, q) -> torch.Tensor:
+    """Quantiles per coordinate, float64 [len(q), dim]: with target = q x total (end bins included), the first non-empty bin
+    whose cumulative count reaches the target, and linear interpolation inside it; NaN where that is the underflow or the
+    overflow bin, and where nothing has been counted."""
+    counts, edges = _hist_cpu(counts, edges)
+    qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if qs.ndim != 1 or not np.all((qs >= 0.0) & (qs <= 1.0)):
+        raise ValueError("quantiles: q must be numbers in [0, 1]")
+    dim, nb = counts.shape[0], counts.shape[1] - 2
+    cum = torch.cumsum(counts, 1).double()
+    total = cum[:, -1]
+    out = torch.full((len(qs), dim), float("nan"), dtype=torch.float64)
+    for i, qv in enumerate(qs):
+        for d in range(dim):
+            if total[d] == 0:
+                continue
+            target = qv * float(total[d])
+            hit = torch.nonzero((cum[d] >= target) & (cum[d] > 0))
+            j = int(hit[0])
+            if j == 0 or j == nb + 1:
+                continue
+            below = float(cum[d, j - 1])
+            out[i, d] = edges[d, j - 1] + (target - below) / float(counts[d, j]) * (edges[d, j] - edges[d, j - 1])
+    return out
+
+
+def _hist_edge_index(edges: torch.Tensor, v, what: str) -> list:
+    """Per coordinate, the index of the edge `v` names (a scalar or a [dim] vector; -inf: -1, below the underflow bin;
+    +inf: bins + 1, above the overflow bin).  ValueError, naming the nearest edges, where it names none."""
+    dim, ne = edges.shape
+    vs = np.broadcast_to(np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float64), (dim,))
+    idx = []
+    for d in range(dim):
+        x = float(vs[d])
+        if np.isnan(x):
+            raise ValueError(f"mass_between: {what} is NaN")
+        if np.isinf(x):
+            idx.append(-1 if x < 0 else ne)
+            continue
+        e = edges[d].numpy()
+        j = int(np.argmin(np.abs(e - x)))
+        width = (e[-1] - e[0]) / (ne - 1)
+        if abs(e[j] - x) > 1e-6 * width:
+            lo_j = max(0, min(ne - 2, int(np.searchsorted(e, x)) - 1))
+            raise ValueError(f"mass_between: {what} = {x!r} is not a bin edge of coordinate {d}; the nearest edges are "
+                             f"{float(e[lo_j])!r} and {float(e[lo_j + 1])!r} (the histogram does not interpolate)")
+        idx.append(j)
+    return idx
+
+
+def hist_mass_between(counts, edges, a, b) -> torch.Tensor:
+    """Fraction of the total (end bins included) counted in [a, b): float64 [dim].  `a` and `b` must be bin edges (within 1e-6
+    of a bin width), or -inf / +inf to take the underflow / overflow bin in; then the answer is a ratio of exact counts.
+    NaN where nothing has been counted."""
+    counts, edges = _hist_cpu(counts, edges)
+    ia, ib = _hist_edge_index(edges, a, "a"), _hist_edge_index(edges, b, "b")
+    total = counts.sum(1).double()
+    total[total == 0] = float("nan")
+    out = torch.zeros(counts.shape[0], dtype=torch.float64)
+    for d in range(counts.shape[0]):
+        if ib[d] < ia[d]:
+            raise ValueError("mass_between: a <= b must hold")
+        # edge i is the left end of bin 1 + i; -1 / bins + 1 take the end bins in
+        out[d] = counts[d, 1 + ia[d]:1 + ib[d]].sum().double()
+    return out / total
+
+
+def hist_mode_weights(counts, edges, boundaries) -> torch.Tensor:
+    """mass_between over (-inf, b_0), [b_0, b_1), ..., [b_last, +inf): float64 [len(boundaries) + 1, dim]; underflow and
+    overflow are folded into the end intervals, so the weights of a coordinate add up to 1."""
+    bs = [-np.inf] + [float(x) for x in np.atleast_1d(np.asarray(boundaries, dtype=np.float64))] + [np.inf]
+    if any(not bs[i] < bs[i + 1] for i in range(len(bs) - 1)):
+        raise ValueError("mode_weights: boundaries must be finite and strictly increasing")
+    return torch.stack([hist_mass_between(counts, edges, bs[i], bs[i + 1]) for i in range(len(bs) - 1)])
+
+
+class MarginalHistograms:
+    """Estimates from the pooled marginal histograms (include/ptrwm.h ptrwm_hist_args): the marginal distribution of every
+    coordinate over every replica of the run.  The host class sets `_hist_mode` / `_hist_every` / `_hist_bins` /
+    `_hist_range` and owns `_run` (an EngineRun).  Every read synchronises; results are CPU tensors."""
+
+    def _check_hist_ctor(self, dim: int, hist, hist_range, hist_bins, hist_every) -> None:
+        """The constructor's histogram arguments, checked before anything is built (no GPU needed)."""
+        if hist_temps(hist, 1):
+            check_hist_args(1, hist_every, hist_bins, hist_range, 1, dim)
+        self._hist_mode, self._hist_every, self._hist_bins, self._hist_range = hist, hist_every, hist_bins, hist_range
+
+    def _hist_kwargs(self, n_temps: int) -> dict:
+        """EngineRun's histogram arguments."""
+        if self._hist_mode is None:
+            return {}
+        return {"hist_temps": hist_temps(self._hist_mode, n_temps), "hist_every": self._hist_every, "hist_bins": self._hist_bins,
+                "hist_range": self._hist_range}
+
+    def _hist_data(self, temperature: int) -> tuple:
+        if getattr(self, "_hist_mode", None) is None:
+            raise RuntimeError("histograms are off: construct the sampler with hist='cold' or 'all' and hist_range=(lo, hi)")
+        run = getattr(self, "_run", None)
+        n_temps = len(getattr(self, "beta_ladder", [1.0]))
+        temps = hist_temps(self._hist_mode, n_temps)
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, np.integer)) or not 0 <= temperature < temps:
+            raise ValueError(f"temperature must be in 0..{temps - 1} (the histograms cover the first {temps}), got {temperature!r}")
+        if run is None or run.histogram() is None:  # nothing run yet, or reset(): empty counters
+            lo, hi = check_hist_range(self._hist_range, self.dim)
+            return torch.zeros(self.dim, self._hist_bins + 2, dtype=torch.int64), hist_edges(lo, hi, self._hist_bins)
+        h = run.histogram()
+        return h["counts"][int(temperature)].cpu(), h["edges"]
+
+    def marginal_histogram(self, temperature: int = 0) -> tuple:
+        """(counts [dim, bins + 2] int64, edges [dim, bins + 1] float64) of `temperature`, pooled over every replica and every
+        snapshot: counts[:, 0] below the range (and NaN), counts[:, -1] at or above it."""
+        return self._hist_data(temperature)
+
+    def marginal_density(self, temperature: int = 0) -> torch.Tensor:
+        """counts normalised by the total and the bin width: float64 [dim, bins].  Out-of-range mass is left out of the density
+        but not out of the total, so a coordinate's density integrates to its in-range fraction."""
+        return hist_density(*self._hist_data(temperature))
+
+    def quantiles(self, q, temperature: int = 0) -> torch.Tensor:
+        """Marginal quantiles, float64 [len(q), dim]: linear interpolation inside the bin where the cumulative count crosses q;
+        NaN where it crosses in the underflow or overflow bin."""
+        return hist_quantiles(*self._hist_data(temperature), q)
+
+    def mass_between(self, a, b, temperature: int = 0) -> torch.Tensor:
+        """Fraction of the mass in [a, b) per coordinate: float64 [dim].  Exact: `a` and `b` must be bin edges (or -inf /
+        +inf); anything else raises ValueError naming the nearest edges."""
+        return hist_mass_between(*self._hist_data(temperature), a, b)
+
+    def mode_weights(self, boundaries, temperature: int = 0) -> torch.Tensor:
+        """mass_between over the consecutive intervals the (bin-edge) boundaries cut the line into, underflow and overflow
+        folded into the end intervals: float64 [len(boundaries) + 1, dim]."""
+        return hist_mode_weights(*self._hist_data(temperature), boundaries)
+
+    def _hist_diagnostics(self) -> dict:
+        if getattr(self, "_hist_mode", None) is None:
+            return {}
+        run = getattr(self, "_run", None)
+        if run is None or run.histogram() is None:
+            return {"hist_out_of_range": float("nan")}
+        c = run.histogram()["counts"]
+        total = int(c.sum().item())
+        return {"hist_out_of_range": (int(c[..., 0].sum().item()) + int(c[..., -1].sum().item())) / total if total else float("nan")}

@@ -32,7 +32,7 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import EngineRun, PosteriorMoments, check_class_starts, moments_temps, resolve_device
+from ._engine_core import EngineRun, MarginalHistograms, PosteriorMoments, check_class_starts, moments_temps, resolve_device
 from .sharding import flow_round_trip_rate, flow_up_fraction
 
 
@@ -46,7 +46,7 @@ def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
     return [float(beta_min ** (t / (n_temps - 1))) for t in range(n_temps)]
 
 
-class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
+class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, MHAlgorithm):
     def __init__(self, dim: int, var: float, target_dist=None, symmetric: bool = True, beta_ladder: list = None,
                  iterative_temp_spacing: bool = False, geom_temp_spacing: bool = False,
                  swap_acceptance_rate: float = 0.234, beta_min_iterative: float = 0.01, N_samples_swap_est: int = 3000,
@@ -59,8 +59,12 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
                  swap_mode: str = "exchange", swap_order: str = "sequential", seed: Optional[int] = None,
                  chain_offset: int = 0, trace: str = "all", thin: int = 1, moments: Optional[str] = None,
                  moments_every: int = 1, moments_per_chain: bool = False, initial_states=None, init_box=None,
-                 init_per_temperature: bool = False, init_attempts: int = 8, flow: bool = False):
+                 init_per_temperature: bool = False, init_attempts: int = 8, flow: bool = False,
+                 hist: Optional[str] = None, hist_range=None, hist_bins: int = 64, hist_every: int = 1):
         super().__init__(dim, var, target_dist, symmetric)
+        # pooled marginal histograms over every replica (include/ptrwm.h ptrwm_hist_args): hist='cold' or 'all' temperatures,
+        # hist_range=(lo, hi) the range of the hist_bins bins, a snapshot every hist_every-th step past burn-in
+        self._check_hist_ctor(dim, hist, hist_range, hist_bins, hist_every)
         self._flow_on = bool(flow)
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         self._moments_mode, self._moments_every = moments, int(moments_every)
@@ -252,7 +256,8 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             burn_in=self.burn_in, swap_every=self.swap_every,
             swap_mode=self._swap_mode, swap_order=self._swap_order, seed=self._seed, chain_offset=self._chain_offset,
             dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
-            moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, flow=self._flow_on)
+            moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, flow=self._flow_on,
+            **self._hist_kwargs(len(self.beta_ladder)))
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
         self.current_log_densities = self._run.logp[0] if self.num_replicas == 1 else self._run.logp
@@ -485,6 +490,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             "memory_allocated_mb": torch.cuda.memory_allocated() / 1e6 if self.device.type == "cuda" else 0,
             **self._moments_diagnostics(),
             **self._flow_diagnostics(),
+            **self._hist_diagnostics(),
         }
 
     def performance_summary(self):

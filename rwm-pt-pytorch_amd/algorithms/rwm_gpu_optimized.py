@@ -22,7 +22,7 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import EngineRun, PosteriorMoments, check_class_starts, moments_temps, resolve_device
+from ._engine_core import EngineRun, MarginalHistograms, PosteriorMoments, check_class_starts, moments_temps, resolve_device
 
 
 def ultra_fused_mcmc_step_basic(current_state, current_log_density, increment, random_val, beta, log_density_proposed):
@@ -52,14 +52,18 @@ def _rebuild_proposal(p: ProposalDistribution, dim, beta, device, dtype, rng):
     )
 
 
-class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
+class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, MHAlgorithm):
     def __init__(self, dim: int, var: float = None, target_dist=None, symmetric: bool = True, beta: float = 1.0,
                  burn_in: int = 0, device: str = None, pre_allocate_steps: int = None, use_efficient_rng: bool = True,
                  compile_mode: str = None, proposal_distribution: ProposalDistribution = None, *,
                  num_chains: int = 1, seed: Optional[int] = None, chain_offset: int = 0, thin: int = 1,
                  moments: Optional[str] = None, moments_every: int = 1, moments_per_chain: bool = False,
-                 initial_states=None, init_box=None, init_attempts: int = 8):
+                 initial_states=None, init_box=None, init_attempts: int = 8, hist: Optional[str] = None, hist_range=None,
+                 hist_bins: int = 64, hist_every: int = 1):
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
+        # pooled marginal histograms over every chain (include/ptrwm.h ptrwm_hist_args): hist='cold' (= 'all' here: one
+        # temperature), hist_range=(lo, hi) the range of the hist_bins bins, a snapshot every hist_every-th step past burn-in
+        self._check_hist_ctor(dim, hist, hist_range, hist_bins, hist_every)
         # where the chains start (EngineRun's docstring): by default all from the reference's one point; `initial_states`
         # [num_chains, dim] (or [dim] / [num_chains, 1, dim]) gives every chain its own - a warm restart is
         # initial_states=previous.current_states; `init_box` = (lo, hi) draws over-dispersed starts in the library, redrawing
@@ -173,7 +177,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             burn_in=self.burn_in, swap_every=1, swap_mode="exchange", swap_order="sequential", seed=self._seed,
             chain_offset=self._chain_offset, moments_temps=moments_temps(self._moments_mode, 1, self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, init_box=self._init_box,
-            init_attempts=self._init_attempts,
+            init_attempts=self._init_attempts, **self._hist_kwargs(1),
         )
         self.current_state = self._run.state[0, 0]  # views: always the live values
         self.current_states = self._run.state[:, 0]
@@ -264,6 +268,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MHAlgorithm):
             "memory_efficiency": "state in registers for the whole launch; HBM touched at launch start/end",
             "random_generation": "Philox4x32-10 in-kernel (no precomputed random tensors)",
             **self._moments_diagnostics(),
+            **self._hist_diagnostics(),
         }
 
     def performance_comparison_summary(self):

@@ -156,3 +156,22 @@ def allreduce_flow(flow: dict, group: Optional[dist.ProcessGroup] = None) -> dic
     total, reps, events = int(vec[2 * n_temps].item()), int(vec[2 * n_temps + 1].item()), int(flow["events"])
     return {"up_fraction": flow_up_fraction(g_up, g_down), "round_trip_rate": flow_round_trip_rate(total, reps, n_temps, events),
             "round_trips_total": total, "n_up": g_up, "n_down": g_down, "n_replicas": reps, "events": events}
+
+
+def allreduce_histogram(sampler, group: Optional[dist.ProcessGroup] = None) -> dict:
+    """Whole-job pooled marginal histograms from every rank's shard: ONE int64 SUM all-reduce of `counts` and `count` packed
+    into one vector (integers: exact, whatever the order).  `sampler`: a sampler constructed with hist=, its EngineRun, or the
+    dict EngineRun.histogram() returns.  Returns new tensors {"counts", "count"} on the shards' device plus "edges"; the
+    shard's own arrays are not modified."""
+    h = sampler
+    if not isinstance(h, dict):
+        run = getattr(sampler, "_run", sampler)
+        h = run.histogram() if run is not None and hasattr(run, "histogram") else None
+        if h is None:
+            raise RuntimeError("allreduce_histogram: histograms are off, or nothing has run yet")
+    counts, count = h["counts"], h["count"]
+    vec = torch.cat([counts.reshape(-1).to(torch.int64), count.reshape(-1).to(torch.int64)])
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=group)
+    n = counts.numel()
+    return {"counts": vec[:n].view(counts.shape), "count": vec[n:].view(count.shape), "edges": h.get("edges")}

@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "../../include/ptrwm.h"
+#include "hist.h"
 #include "schedule.h"
 #include "variants.h"
 
@@ -709,6 +710,64 @@ __global__ void __launch_bounds__(256) split_chain_moments_kernel(SplitMomentsAr
   if (i < a.temps && a.count != nullptr) a.count[i] += 1;
 }
 
+// Pooled marginal histograms (ptrwm_histogram, and the snapshots of ptrwm_run_with_histogram): one snapshot of `state`,
+// shaped as split_moments_kernel - a workgroup takes a tile of kHistChains chains (blockIdx.x) and a group of `cols` of the
+// first temps * dim elements of every chain's run (blockIdx.y); consecutive threads read consecutive elements of a chain, and
+// where a group has fewer than 256 columns the workgroup's threads take 256 / cols chains at a time.  Counters: 32-bit, in
+// LDS, n_bins + 2 per column of the group, added to with ds_add_u32 (columns are shared between the chains in flight) and
+// flushed once per workgroup, one no-return 64-bit atomic per NON-ZERO counter (count_add).  kHistLdsCounters = 32 KiB of
+// LDS: up to five workgroups per CU.  `direct` (n_bins + 2 > kHistLdsCounters / kHistMinCols: fewer than a wavefront's worth
+// of columns would fit): no LDS, every sample is one global atomic.
+constexpr int kHistChains = 256;
+constexpr int kHistLdsCounters = 8192;
+constexpr int kHistMinCols = 64;
+struct HistSnapArgs {
+  const void *state;  // float or double [n_chains, n_temps, dim]
+  const float *lo, *scale;
+  long long *counts, *count;
+  long long n_chains, step, burn_in, every;
+  const long long *device_step;
+  int n_temps, dim, temps, n_bins, cols, direct;
+};
+
+template <class state_t>
+__global__ void __launch_bounds__(256) hist_snapshot_kernel(HistSnapArgs a) {
+  // is the step just performed a due one?  (grid-uniform, as SplitMomentsArgs::step_counts)
+  if (!periodic_step_due((a.device_step != nullptr ? *a.device_step + a.step : a.step) + 1, a.burn_in, a.every)) return;
+  __shared__ unsigned s_cnt[kHistLdsCounters];
+  const int tid = (int)threadIdx.x, nbp = a.n_bins + 2, td = a.temps * a.dim;
+  const int k0 = (int)blockIdx.y * a.cols;
+  const int cols = td - k0 < a.cols ? td - k0 : a.cols;  // (1..256; cols * nbp <= kHistLdsCounters unless direct)
+  const long long c0 = (long long)blockIdx.x * kHistChains;
+  const long long c1 = (a.n_chains - c0 < kHistChains) ? a.n_chains : c0 + kHistChains;
+  const bool direct = a.direct != 0;
+  if (!direct) {
+    for (int i = tid; i < cols * nbp; i += 256) s_cnt[i] = 0u;
+    __syncthreads();
+  }
+  const int per = 256 / cols, sub = tid / cols, kk = tid - sub * cols;  // chains in flight; this thread's; its column
+  if (sub < per) {
+    const int k = k0 + kk;
+    const float lo = a.lo[k % a.dim], sc = a.scale[k % a.dim];
+    const long long run = (long long)a.n_temps * a.dim;
+    const state_t *__restrict__ p = reinterpret_cast<const state_t *>(a.state) + k;
+    for (long long c = c0 + sub; c < c1; c += per) {
+      const int b = hist_bin(static_cast<float>(p[c * run]), lo, sc, a.n_bins);
+      if (direct) count_add(&a.counts[(long long)k * nbp + b], 1ll);
+      else atomicAdd(&s_cnt[kk * nbp + b], 1u);
+    }
+  }
+  if (!direct) {
+    __syncthreads();
+    for (int i = tid; i < cols * nbp; i += 256) {
+      const unsigned v = s_cnt[i];
+      if (v != 0u) count_add(&a.counts[(long long)k0 * nbp + i], (long long)v);
+    }
+  }
+  if (blockIdx.y == 0 && a.count != nullptr)
+    for (int t = tid; t < a.temps; t += 256) count_add(&a.count[t], c1 - c0);
+}
+
 // Starting points (ptrwm_init_states): row (c, t) of `state` drawn uniformly from the box [lo, hi], or set to `fallback`.
 // The draw is Philox stream kStreamInit (rng_layout.h: the counter layout; include/ptrwm.h restates it), keyed by the GLOBAL chain
 // id like every other random of a run, so the starts do not depend on how chains are sharded over devices.
@@ -820,8 +879,52 @@ static int32_t check_flow(const ptrwm_run_args *args, const ptrwm_flow_args *flo
   return PTRWM_OK;
 }
 
+// the histogram checks shared by ptrwm_run_with_histogram and ptrwm_histogram (args already checked); none: ok
+static int32_t check_hist(const ptrwm_run_args *args, const ptrwm_hist_args *h) {
+  if (h == nullptr) return PTRWM_OK;
+  if (h->struct_size != sizeof(ptrwm_hist_args)) return PTRWM_E_STRUCT;
+  if (h->temps < 1 || h->temps > args->n_temps || h->every < 1 || h->n_bins < 1 || h->n_bins > PTRWM_HIST_MAX_BINS) return PTRWM_E_ARG;
+  if (h->lo == nullptr || h->scale == nullptr || h->counts == nullptr) return PTRWM_E_NULL;
+  return PTRWM_OK;
+}
+static_assert(PTRWM_HIST_MAX_BINS == kHistMaxBins, "hist.h and include/ptrwm.h: one bin limit");
+
+// One snapshot of the state after step `step` (device_step != NULL: *device_step + step); everything checked
+static int32_t launch_hist(const ptrwm_run_args *args, int32_t dim, const ptrwm_hist_args *h, long long step,
+                           const long long *device_step, hipStream_t stream) {
+  HistSnapArgs a;
+  a.state = args->state;
+  a.lo = h->lo;
+  a.scale = h->scale;
+  a.counts = (long long *)h->counts;
+  a.count = (long long *)h->count;
+  a.n_chains = args->n_chains;
+  a.step = step;
+  a.burn_in = args->burn_in;
+  a.every = h->every;
+  a.device_step = device_step;
+  a.n_temps = args->n_temps;
+  a.dim = dim;
+  a.temps = h->temps;
+  a.n_bins = h->n_bins;
+  const int nbp = h->n_bins + 2, td = h->temps * dim;
+  a.direct = nbp > kHistLdsCounters / kHistMinCols ? 1 : 0;
+  int cols = a.direct ? 256 : kHistLdsCounters / nbp;  // (>= kHistMinCols)
+  if (cols > 256) cols = 256;
+  if (cols > td) cols = td;
+  a.cols = cols;
+  const long long gx = (args->n_chains + kHistChains - 1) / kHistChains;
+  if (gx > 0x7fffffffll) return PTRWM_E_ARG;
+  const dim3 grid((unsigned)gx, (unsigned)((td + cols - 1) / cols));  // (y <= 256 * 104 / 64)
+  if (args->state_f64 == 1)
+    hipLaunchKernelGGL(hist_snapshot_kernel<double>, grid, dim3(256), 0, stream, a);
+  else
+    hipLaunchKernelGGL(hist_snapshot_kernel<float>, grid, dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}
+
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream);
+                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist = nullptr);
 static int32_t swap_sweep_impl(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
                                const ptrwm_flow_args *flow, void *stream);
 static int32_t split_accept_impl(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
@@ -946,6 +1049,27 @@ int32_t ptrwm_run_with_diagnostics(const ptrwm_target_desc *target, const ptrwm_
   return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream);
 }
 
+int32_t ptrwm_run_with_histogram(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                                 const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
+                                 const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, void *stream) {
+  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // (as ptrwm_run_with_diagnostics)
+  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist);
+}
+
+int32_t ptrwm_histogram(const ptrwm_run_args *args, int32_t dim, const ptrwm_hist_args *hist, void *stream) {
+  if (args == nullptr || hist == nullptr) return PTRWM_E_NULL;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
+  if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
+  if (!is_flag(args->state_f64) || args->n_chains < 0 || args->step0 < 0 || args->burn_in < 0) return PTRWM_E_ARG;
+  if (int rc = check_hist(args, hist)) return rc;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->state == nullptr) return PTRWM_E_NULL;
+  if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, hist->every))
+    return PTRWM_OK;  // (known on the host: no snapshot is due)
+  return launch_hist(args, dim, hist, args->step0, (const long long *)args->device_step, (hipStream_t)stream);
+}
+
 }  // extern "C"
 
 // ---- ptrwm_run: check, choose the kernel, fill its arguments, cut the request into launches --------------------------------
@@ -958,7 +1082,7 @@ static long long ext_swap_events(const ptrwm_run_args *args) {
 
 // Job 1: everything that can be refused from the arguments alone.  *empty: a valid request with nothing to do.
 static int32_t check_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                         const MomSpec &spec, const ptrwm_flow_args *flow, bool *empty) {
+                         const MomSpec &spec, const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, bool *empty) {
   if (proposal == nullptr || args == nullptr) return PTRWM_E_NULL;
   if (int rc = check_target(target)) return rc;
   if (!has_abi_size(args)) return PTRWM_E_STRUCT;
@@ -966,6 +1090,7 @@ static int32_t check_run(const ptrwm_target_desc *target, const ptrwm_proposal_d
   if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
   if (int rc = check_moments(args, spec)) return rc;
   if (int rc = check_flow(args, flow)) return rc;
+  if (int rc = check_hist(args, hist)) return rc;
   if (args->n_chains < 0 || args->n_steps < 0 || args->step0 < 0 || args->burn_in < 0 || args->swap_every < 1 ||
       !swap_rule_known(args) || !fused_fields_ok(args))
     return PTRWM_E_ARG;
@@ -1143,9 +1268,9 @@ static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_de
 }
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream) {
+                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist) {
   bool empty = false;
-  if (int rc = check_run(target, proposal, args, spec, flow, &empty)) return rc;
+  if (int rc = check_run(target, proposal, args, spec, flow, hist, &empty)) return rc;
   if (empty) return PTRWM_OK;
   const RunChoice c = choose_kernel(target, proposal, args, spec, flow != nullptr, (hipStream_t)hip_stream);
   if (c.status != PTRWM_OK) return c.status;
@@ -1163,7 +1288,9 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   const long long trace_row = args->trace != nullptr ? args->trace_chains * (long long)args->trace_temps : 0;
   const auto countdown = [](int steps) { return (unsigned)(steps < kNoStepInLaunch ? steps : kNoStepInLaunch); };  // (a launch: <= 2^16 steps)
   for (long long done = 0; done < args->n_steps; done += k.n_steps) {
-    const LaunchCut cut = launch_at(req, done, cap);
+    // (histograms: a launch also ends at every due snapshot step - the snapshot kernel reads the state between launches)
+    const long long to_snap = hist != nullptr ? steps_to_next_due(args->step0 + done, args->burn_in, hist->every) : cap;
+    const LaunchCut cut = launch_at(req, done, to_snap < cap ? to_snap : cap);
     k.step0 = cut.step0;
     k.n_steps = cut.n;
     k.burn_left = cut.burn_left;
@@ -1182,6 +1309,8 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
       k.full.steps_to_mom = countdown(cut.steps_to_mom);
     }
     if (c.fn(k, c.n_blocks, c.mode, (hipStream_t)hip_stream) != hipSuccess) return PTRWM_E_LAUNCH;
+    if (hist != nullptr && periodic_step_due(cut.step0 + cut.n, args->burn_in, hist->every))
+      if (int rc = launch_hist(args, target->dim, hist, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
   }
   return PTRWM_OK;
 }

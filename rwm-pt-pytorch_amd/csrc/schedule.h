@@ -37,6 +37,15 @@ PTRWM_HD inline long long periodic_steps_in(long long step0, long long n, long l
 // steps from step0 to the first step whose step_counter is a multiple of `period` (1 = the step at step0 itself)
 PTRWM_HD inline long long steps_to_next_multiple(long long step0, long long period) { return period - step0 % period; }
 
+// steps from step0 to the next DUE step of a period, burn-in honoured (1 = the step at step0 itself): the distance to the
+// first multiple of `period` above both step0 and burn_in.  A launch of that many steps from step0 ends exactly on a due
+// step and holds no other; ptrwm_run_with_histogram min-s it into the cap of launch_at, so a snapshot kernel can read the
+// state between two launches.
+PTRWM_HD inline long long steps_to_next_due(long long step0, long long burn_in, long long period) {
+  const long long base = step0 > burn_in ? step0 : burn_in;
+  return (base / period + 1) * period - step0;
+}
+
 // 0-based number, since the start of the run, of the swap event of the swap step sc (periodic_step_due(sc, ...) holds)
 PTRWM_HD inline long long swap_event_number(long long sc, long long burn_in, long long swap_every) {
   return sc / swap_every - burn_in / swap_every - 1;

@@ -152,6 +152,23 @@ class FlowArgs(C.Structure):
     ]
 
 
+class HistArgs(C.Structure):
+    """ptrwm_hist_args: pooled marginal histograms of the first ``temps`` temperatures (include/ptrwm.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("temps", C.c_int32),
+        ("every", C.c_int32),
+        ("n_bins", C.c_int32),
+        ("lo", C.c_void_p),
+        ("scale", C.c_void_p),
+        ("counts", C.c_void_p),
+        ("count", C.c_void_p),
+    ]
+
+
+HIST_MAX_BINS = 1024
+
+
 class InitArgs(C.Structure):
     """ptrwm_init_args: starting points drawn from a box, or set to a fallback point (include/ptrwm.h)."""
     _fields_ = [
@@ -195,6 +212,11 @@ SYMBOLS = {
         C.c_int32,
         [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.POINTER(ChainMomentsArgs),
          C.POINTER(FlowArgs), C.c_void_p]),
+    "ptrwm_run_with_histogram": (
+        C.c_int32,
+        [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.POINTER(ChainMomentsArgs),
+         C.POINTER(FlowArgs), C.POINTER(HistArgs), C.c_void_p]),
+    "ptrwm_histogram": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(HistArgs), C.c_void_p]),
     "ptrwm_swap_sweep_with_flow": (
         C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_int64, C.c_int32, C.POINTER(FlowArgs), C.c_void_p]),
     "ptrwm_split_accept_with_flow": (
@@ -601,6 +623,7 @@ class RunPlan:
         self._guard = on_device(self.device)  # (after the checks above: they reject CPU tensors first)
         self._mom = None  # the accumulator, pooled or per chain: (kind of _MOMENT_KINDS, struct, byref, tensors)
         self._flow = None  # replica flow: (struct, byref, tensors)
+        self._hist = None  # pooled marginal histograms: (struct, byref, tensors)
 
     # kind of accumulator -> (words of its messages, struct, entry point of launch(), entry point of split_moments())
     _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
@@ -685,6 +708,56 @@ class RunPlan:
         f.n_up = _opt(n_up, "flow n_up", torch.int64)
         f.n_down = _opt(n_down, "flow n_down", torch.int64)
         self._flow = (f, C.byref(f), (walker, round_trips, n_up, n_down))
+
+    def set_histogram(self, counts: Optional[torch.Tensor], lo: Optional[torch.Tensor] = None,
+                      scale: Optional[torch.Tensor] = None, *, n_bins: int = 0, temps: int = 0, every: int = 1,
+                      count: Optional[torch.Tensor] = None) -> None:
+        """Accumulate pooled marginal histograms (include/ptrwm.h ptrwm_hist_args) in every following ``launch`` and
+        ``split_histogram``: ``counts`` [temps, dim, n_bins + 2] int64 (bin 0 underflow, bin n_bins + 1 overflow), ``lo`` and
+        ``scale`` = n_bins / (hi - lo) [dim] float32, ``count`` [temps] int64 (optional), all on the run's device; counts and
+        count are added to (+=).  ``launch`` then ends a kernel launch at every due step and enqueues the snapshot kernel
+        behind it.  ``set_histogram(None)`` switches histograms off."""
+        if counts is None:
+            self._hist = None
+            return
+        T, D = self.shape[1:]
+        n_bins, temps, every = int(n_bins), int(temps), int(every)
+        if not 1 <= n_bins <= HIST_MAX_BINS:
+            raise ValueError(f"histogram n_bins must be in 1..{HIST_MAX_BINS}, got {n_bins}")
+        if not 1 <= temps <= T:
+            raise ValueError(f"histogram temps must be in 1..{T}, got {temps}")
+        if every < 1:
+            raise ValueError("histogram every must be >= 1")
+        if tuple(counts.shape) != (temps, D, n_bins + 2):
+            raise ValueError(f"histogram counts must be [{temps}, {D}, {n_bins + 2}]")
+        if count is not None and tuple(count.shape) != (temps,):
+            raise ValueError(f"histogram count must be [{temps}]")
+        for name, t in (("lo", lo), ("scale", scale)):
+            if t is None or tuple(t.shape) != (D,):
+                raise ValueError(f"histogram {name} must be a [{D}] float32 tensor")
+        for name, t in (("counts", counts), ("lo", lo), ("scale", scale), ("count", count)):
+            if t is not None and t.device != self.device:
+                raise ValueError(f"histogram {name} is on {t.device}, state on {self.device}")
+        h = HistArgs()
+        h.struct_size = C.sizeof(HistArgs)
+        h.temps, h.every, h.n_bins = temps, every, n_bins
+        h.lo = _require_device(lo, "histogram lo", torch.float32)
+        h.scale = _require_device(scale, "histogram scale", torch.float32)
+        h.counts = _require_device(counts, "histogram counts", torch.int64)
+        h.count = _opt(count, "histogram count", torch.int64)
+        self._hist = (h, C.byref(h), (counts, lo, scale, count))
+
+    def split_histogram(self, step: int) -> None:
+        """Histogram snapshot of the state after the split step ``step`` just performed (ptrwm_histogram; device-step mode:
+        counter + step - decided on the device, so the call can sit in a captured block).  Enqueue after ``split_accept``.
+        No-op without a histogram."""
+        if self._hist is None:
+            return
+        self._a.step0 = step
+        with self._guard:
+            rc = self._lib.ptrwm_histogram(self._refs[4], self.shape[2], self._hist[1], _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_histogram")
 
     def init_states(self, lo: torch.Tensor, hi: torch.Tensor, *, attempt: int = 0, per_temperature: bool = False,
                     fallback: Optional[torch.Tensor] = None) -> None:
@@ -789,12 +862,17 @@ class RunPlan:
                 self._last_trace = (trace, trace_logp, trace_every)
         # ptrwm_run, or the accumulator's entry point with its struct in front of the stream
         name, mom = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
-        if self._flow is not None:  # flow bound: the entry point that takes every diagnostic
-            name = "ptrwm_run_with_diagnostics"
+        if self._flow is not None or self._hist is not None:  # flow or histograms bound: the entry points that take every diagnostic
+            name = "ptrwm_run_with_diagnostics" if self._hist is None else "ptrwm_run_with_histogram"
             pooled = self._mom[2] if self._mom is not None and self._mom[0] == "pooled" else None
             chain = self._mom[2] if self._mom is not None and self._mom[0] == "chain" else None
-            with self._guard:
-                rc = self._lib.ptrwm_run_with_diagnostics(self._refs[2], self._refs[3], self._refs[4], pooled, chain, self._flow[1], _stream(self.device))
+            flow = self._flow[1] if self._flow is not None else None
+            if self._hist is None:
+                with self._guard:
+                    rc = self._lib.ptrwm_run_with_diagnostics(self._refs[2], self._refs[3], self._refs[4], pooled, chain, flow, _stream(self.device))
+            else:
+                with self._guard:
+                    rc = self._lib.ptrwm_run_with_histogram(self._refs[2], self._refs[3], self._refs[4], pooled, chain, flow, self._hist[1], _stream(self.device))
         else:
             with self._guard:
                 rc = getattr(self._lib, name)(self._refs[2], self._refs[3], self._refs[4], *mom, _stream(self.device))
