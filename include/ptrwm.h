@@ -452,9 +452,10 @@ int32_t ptrwm_split_accept_with_flow(const ptrwm_run_args *args, int32_t dim, fl
  * launches, calls and shards compose.  ptrwm_swap_sweep events are not steps and add nothing.
  * How: NOT in the step kernels.  A small stand-alone snapshot kernel reads `state` between launches: ptrwm_run_with_histogram
  * ends a launch at every due step and enqueues the snapshot kernel behind it on the same stream.  A workgroup takes a tile of
- * 256 chains and up to 256 of the temps * dim columns; it counts in 32-bit LDS counters (32 KiB) and flushes each non-zero
- * counter with one 64-bit atomic.  With n_bins > 126 fewer than 64 columns of counters would fit the LDS and the kernel
- * adds to `counts` with global atomics directly.  The accumulators must be ordinary device memory of the current device. */
+ * chains and a group of the temps * dim columns (csrc/hist.h hist_geometry states the sizes); it counts in 32-bit LDS counters
+ * and flushes each non-zero counter with one 64-bit atomic.  Where too few columns of counters would fit the LDS - many
+ * bins - the kernel adds to `counts` with global atomics directly.  The accumulators must be ordinary device memory of the
+ * current device. */
 #define PTRWM_HIST_MAX_BINS 1024
 typedef struct ptrwm_hist_args {
   uint32_t struct_size; /* sizeof(ptrwm_hist_args) */

@@ -717,10 +717,8 @@ __global__ void __launch_bounds__(256) split_chain_moments_kernel(SplitMomentsAr
 // LDS, n_bins + 2 per column of the group, added to with ds_add_u32 (columns are shared between the chains in flight) and
 // flushed once per workgroup, one no-return 64-bit atomic per NON-ZERO counter (count_add).  kHistLdsCounters = 32 KiB of
 // LDS: up to five workgroups per CU.  `direct` (n_bins + 2 > kHistLdsCounters / kHistMinCols: fewer than a wavefront's worth
-// of columns would fit): no LDS, every sample is one global atomic.
-constexpr int kHistChains = 256;
-constexpr int kHistLdsCounters = 8192;
-constexpr int kHistMinCols = 64;
+// of columns would fit): no LDS, every sample is one global atomic.  The constants and the host's choice of `cols` and
+// `direct` are hist.h's (hist_geometry).
 struct HistSnapArgs {
   const void *state;  // float or double [n_chains, n_temps, dim]
   const float *lo, *scale;
@@ -907,15 +905,12 @@ static int32_t launch_hist(const ptrwm_run_args *args, int32_t dim, const ptrwm_
   a.dim = dim;
   a.temps = h->temps;
   a.n_bins = h->n_bins;
-  const int nbp = h->n_bins + 2, td = h->temps * dim;
-  a.direct = nbp > kHistLdsCounters / kHistMinCols ? 1 : 0;
-  int cols = a.direct ? 256 : kHistLdsCounters / nbp;  // (>= kHistMinCols)
-  if (cols > 256) cols = 256;
-  if (cols > td) cols = td;
-  a.cols = cols;
+  const HistGeometry g = hist_geometry(h->n_bins, h->temps * dim);
+  a.direct = g.direct;
+  a.cols = g.cols;
   const long long gx = (args->n_chains + kHistChains - 1) / kHistChains;
   if (gx > 0x7fffffffll) return PTRWM_E_ARG;
-  const dim3 grid((unsigned)gx, (unsigned)((td + cols - 1) / cols));  // (y <= 256 * 104 / 64)
+  const dim3 grid((unsigned)gx, (unsigned)g.groups);  // (y <= 256 * 104 / 64)
   if (args->state_f64 == 1)
     hipLaunchKernelGGL(hist_snapshot_kernel<double>, grid, dim3(256), 0, stream, a);
   else

@@ -1,6 +1,7 @@
 // The bin rule of the pooled marginal histograms, stated once: which of the n_bins + 2 counters of a coordinate a value
-// lands in.  Plain C++ (no HIP include): the snapshot kernel of capi.hip calls it, tests/hist_test.cpp checks it on the CPU
-// against a double-precision restatement, and NumPy can replay it bit for bit (np.float32 arithmetic, astype(np.int64)).
+// lands in - and, below it, the geometry of the snapshot kernel's grid (hist_geometry).  Plain C++ (no HIP include): the
+// snapshot kernel of capi.hip calls the rule, tests/hist_test.cpp checks it on the CPU against a double-precision
+// restatement, and NumPy can replay it bit for bit (np.float32 arithmetic, astype(np.int64)).
 //
 // A coordinate d has n_bins equal bins over [lo[d], hi[d]) and two end bins; its counters are
 //   bin 0             underflow: x < lo[d] - and NaN, see below
@@ -39,6 +40,34 @@ PTRWM_HD inline int hist_bin(float x, float lo, float scale, int n_bins) {
   if (!(u >= 0.0f)) return 0;
   if (u >= (float)n_bins) return n_bins + 1;
   return 1 + (int)u;
+}
+
+// The geometry of one snapshot (capi.hip hist_snapshot_kernel), stated once: how the td = temps * dim covered columns of a
+// chain's run are tiled into groups (blockIdx.y) of `cols` columns, chains into tiles of kHistChains (blockIdx.x).  A
+// workgroup has 256 threads, so a group has at most 256 columns; the LDS strategy keeps n_bins + 2 32-bit counters per column
+// of its group in kHistLdsCounters counters (32 KiB: up to five workgroups per CU), as many columns as fit; `direct` - no LDS,
+// every sample a global atomic - when fewer than kHistMinCols columns (a wavefront's worth) would fit.  The last group holds
+// td - (groups - 1) * cols columns.  Host code: launch_hist calls it, tests/hist_test.cpp checks it for every n_bins and td
+// the C ABI accepts.
+constexpr int kHistChains = 256;
+constexpr int kHistLdsCounters = 8192;
+constexpr int kHistMinCols = 64;
+constexpr int kHistMaxCols = 256;  // the workgroup's threads
+
+struct HistGeometry {
+  int direct, cols, groups;
+};
+
+inline HistGeometry hist_geometry(int n_bins, int td) {
+  const int nbp = n_bins + 2;
+  HistGeometry g;
+  g.direct = nbp > kHistLdsCounters / kHistMinCols ? 1 : 0;
+  int cols = g.direct ? kHistMaxCols : kHistLdsCounters / nbp;  // (>= kHistMinCols)
+  if (cols > kHistMaxCols) cols = kHistMaxCols;
+  if (cols > td) cols = td;
+  g.cols = cols;
+  g.groups = (td + cols - 1) / cols;
+  return g;
 }
 
 }  // namespace ptrwm

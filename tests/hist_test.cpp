@@ -4,10 +4,16 @@
 //     that holds lo, hi, their neighbours, +-inf, NaN and denormals, for n_bins in {1, 2, 7, 64, 1024};
 //  2. steps_to_next_due, and the cuts ptrwm_run_with_histogram makes with it (min-ed into launch_at's cap), replayed step by
 //     step: every launch ends on a due step or at the cap or at the request's end, holds no due step before its last, the
-//     launches cover the request, none exceeds the cap.
+//     launches cover the request, none exceeds the cap;
+//  3. hist_geometry - how the snapshot kernel's grid tiles the td = temps * dim covered columns - for every n_bins the C ABI
+//     accepts (1..1024) and every td it can be asked for (1..256 * 104): the group fits the workgroup and the LDS counters,
+//     the groups cover the columns exactly, and `direct` is taken exactly where fewer than kHistMinCols columns would fit.
+// With the argument "geometry" it reads pairs "n_bins td" from stdin and prints "direct cols groups last_cols" for each
+// (tests/test_hist_host.py: the geometry that each GPU case of tests/test_gpu_hist.py is named for).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <vector>
 
@@ -155,9 +161,41 @@ static void test_cuts() {
   CHECK(launches > 1000, "the grid must make launches");
 }
 
-int main() {
+static void test_geometry() {
+  const int max_td = 256 * 104;  // PTRWM_MAX_TEMPS * PTRWM_MAX_DIM of include/ptrwm.h
+  long long n_direct = 0, n_lds = 0, n_multi = 0, n_narrow_last = 0;
+  for (int nb = 1; nb <= kHistMaxBins; ++nb)
+    for (int td = 1; td <= max_td; ++td) {
+      const HistGeometry g = hist_geometry(nb, td);
+      const bool direct = g.direct != 0;
+      CHECK(g.cols >= 1 && g.cols <= 256, "%d bins, td %d: cols %d", nb, td, g.cols);
+      CHECK(g.cols <= td, "%d bins, td %d: cols %d above td", nb, td, g.cols);
+      CHECK(direct || g.cols * (nb + 2) <= kHistLdsCounters, "%d bins, td %d: %d columns do not fit the LDS counters", nb, td, g.cols);
+      CHECK(direct || g.cols >= (kHistMinCols < td ? kHistMinCols : td), "%d bins, td %d: an LDS group of %d columns", nb, td, g.cols);
+      CHECK((long long)(g.groups - 1) * g.cols < td && td <= (long long)g.groups * g.cols, "%d bins, td %d: %d groups of %d", nb, td, g.groups, g.cols);
+      CHECK(direct == (nb + 2 > kHistLdsCounters / kHistMinCols), "%d bins: direct %d", nb, g.direct);
+      (direct ? n_direct : n_lds) += 1;
+      n_multi += g.groups > 1;
+      n_narrow_last += g.groups > 1 && td % g.cols != 0;
+    }
+  CHECK(n_direct > 0 && n_lds > 0 && n_multi > 0 && n_narrow_last > 0, "the grid must reach both strategies and several groups");
+  CHECK(kHistChains == 256 && kHistMaxCols == 256, "the kernel's workgroup is 256 threads: tile and widest group");
+}
+
+static int print_geometry() {
+  int nb, td;
+  while (std::scanf("%d %d", &nb, &td) == 2) {
+    const HistGeometry g = hist_geometry(nb, td);
+    std::printf("%d %d %d %d\n", g.direct, g.cols, g.groups, td - (g.groups - 1) * g.cols);
+  }
+  return 0;
+}
+
+int main(int argc, char **argv) {
+  if (argc > 1 && std::strcmp(argv[1], "geometry") == 0) return print_geometry();
   test_bin_rule();
   test_cuts();
+  test_geometry();
   std::printf("hist ok: %lld checks\n", g_checks);
   return 0;
 }

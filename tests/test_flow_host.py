@@ -4,10 +4,13 @@ arithmetic of the class accessors and of the shards' all-reduce on hand-made ten
 import ctypes as C
 import math
 import os
+import socket
 import subprocess
 
 import pytest
 import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
 
 import ptrwm_hip as E
 
@@ -180,6 +183,63 @@ def test_up_fraction_round_trip_rate_and_allreduce_on_hand_made_tensors():
     assert out["round_trip_rate"] == 6 / (2 * 4 * 5)
     assert out["n_up"].tolist() == [10, 4, 2, 0] and out["n_down"].tolist() == [0, 4, 0, 10]
     assert out["up_fraction"].tolist() == [1.0, 0.5, 1.0, 0.0]
+
+
+FLOW_TEMPS, FLOW_EVENTS = 4, 7
+
+
+def _flow_shard(rank):
+    """Hand-made flow arrays of a shard of 3 (rank 0) or 5 (rank 1) replicas of an 8-replica run."""
+    n = (3, 5)[rank]
+    g = torch.Generator().manual_seed(40 + rank)
+    return {"walker": torch.arange(FLOW_TEMPS, dtype=torch.int32).repeat(n, 1),
+            "round_trips": torch.randint(0, 6, (n, FLOW_TEMPS), generator=g, dtype=torch.int64),
+            "n_up": torch.randint(0, 50, (n, FLOW_TEMPS), generator=g, dtype=torch.int64),
+            "n_down": torch.randint(0, 50, (n, FLOW_TEMPS), generator=g, dtype=torch.int64), "events": FLOW_EVENTS}
+
+
+def _flow_worker(rank, world, port, q):
+    from algorithms.sharding import allreduce_flow
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    shard = _flow_shard(rank)
+    kept = {k: v.clone() for k, v in shard.items() if torch.is_tensor(v)}
+    total = allreduce_flow(shard)
+    assert all(torch.equal(shard[k], v) for k, v in kept.items())  # inputs untouched
+    q.put((rank, {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in total.items()}))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_allreduce_flow_over_two_ranks_is_the_flow_of_the_whole():
+    """gloo, two spawned ranks holding 3 and 5 replicas, CPU tensors: both ranks return the arrays of the 8-replica whole, and
+    the up-fraction and round-trip rate computed from those."""
+    from algorithms.sharding import flow_round_trip_rate, flow_up_fraction
+
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_flow_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = [q.get(timeout=180) for _ in procs]
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    a, b = _flow_shard(0), _flow_shard(1)
+    whole = {k: torch.cat([a[k], b[k]]) for k in ("round_trips", "n_up", "n_down")}
+    assert whole["n_up"].shape == (8, FLOW_TEMPS)
+    up, down, trips = whole["n_up"].sum(0), whole["n_down"].sum(0), int(whole["round_trips"].sum())
+    assert trips > 0 and not torch.equal(a["n_up"].sum(0), b["n_up"].sum(0))
+    assert sorted(r for r, _ in got) == [0, 1]
+    for _, total in got:
+        assert total["n_up"].tolist() == up.tolist() and total["n_down"].tolist() == down.tolist()
+        assert total["round_trips_total"] == trips and total["n_replicas"] == 8 and total["events"] == FLOW_EVENTS
+        assert total["up_fraction"].tolist() == flow_up_fraction(up, down).tolist()
+        assert total["round_trip_rate"] == flow_round_trip_rate(trips, 8, FLOW_TEMPS, FLOW_EVENTS) == trips / (8 * FLOW_TEMPS * FLOW_EVENTS)
 
 
 def test_class_flow_checks_need_no_gpu():

@@ -20,7 +20,7 @@ import ptrwm_hip as E
 gpu = pytest.mark.gpu
 
 SEED = 20241019
-HIST_TILE = 256  # chains per workgroup of the snapshot kernel (include/ptrwm.h, the histogram section)
+HIST_TILE = 256  # chains per workgroup of the snapshot kernel (csrc/hist.h kHistChains)
 LO, HI = -0.8, 0.9
 
 
@@ -128,7 +128,9 @@ SHAPES = [("rwm70", 5, 1, 70, 7, 1, False),                  # more than a wave;
           ("dim70", 70, 1, 5, 1024, 1, False),                # lane-split step kernel only
           ("bins126", 5, 2, 9, 126, 2, False),                # the last bin count the LDS strategy takes ...
           ("bins127", 5, 2, 9, 127, 2, False),                # ... and the first that goes direct
-          ("f64", 3, 4, 3, 64, 4, True)]                      # double states
+          ("f64", 3, 4, 3, 64, 4, True),                      # double states
+          ("pt32x30_all", 30, 32, 70, 64, 32, False),         # the README shape: 960 columns in 8 groups of the snapshot kernel
+          ("quad_d70_t8", 70, 8, 9, 64, 8, False)]            # lane-split only; 560 columns in 5 groups
 
 
 def test_every_shape_has_a_step_kernel():
@@ -199,6 +201,79 @@ def test_standalone_snapshot_of_a_hand_written_state(device):
             assert np.array_equal(st_np, state.astype(st_np.dtype), equal_nan=True)  # a snapshot only reads
 
 
+# The snapshot kernel beyond one group of columns (csrc/hist.h hist_geometry: td = temps * dim columns in `groups` groups of
+# `cols`, the last of `last`).  tests/test_hist_host.py holds every row against hist_geometry itself, so that no case falls back
+# to a single group if a constant of hist.h changes.
+#                  id                dim  T   temps bins chains direct cols groups last  f64 as well
+GEOMETRY_CASES = [("readme_8_groups", 30, 32, 32, 64, 300, False, 124, 8, 92, True),   # boundaries inside a temperature; a partial second chain tile
+                  ("lds_min_cols", 13, 10, 10, 126, 257, False, 64, 3, 2, False),      # a last group of 2 columns: 128 chains in flight; a tile of one chain
+                  ("lds_cols_cap", 7, 40, 40, 16, 70, False, 256, 2, 24, False),       # last group of 24: threads 240..255 idle
+                  ("cold_5_of_12", 30, 12, 5, 64, 70, False, 124, 2, 26, False),       # temps < n_temps: chain stride 360 against td 150
+                  ("direct_2_groups", 30, 10, 10, 127, 300, True, 256, 2, 44, True),
+                  ("direct_max_bins", 104, 3, 3, 1024, 5, True, 256, 2, 56, False),    # the bin limit and the largest dim
+                  ("widest_state", 104, 256, 256, 126, 3, False, 64, 416, 64, False)]  # td 26 624: the widest state the ABI accepts
+GEOMETRY_RUNS = [(c, False) for c in GEOMETRY_CASES] + [(c, True) for c in GEOMETRY_CASES if c[-1]]
+
+
+def hand_made_state(dim, T, temps, Cn, lo, cols, groups):
+    """x[c, t, d] = mu[t, d] + sigma z in float64, mu a ramp over the column index t * dim + d across the histogram's range: no
+    two columns hold the same distribution, so a column binned with another column's bounds, flushed to another column's
+    counters, skipped or counted twice changes the counts.  +inf, -inf, NaN and lo[d] itself are planted in the second and in
+    the last group of columns (under, over and bin 1 are then certain there).  Returns the state and the planted (chain, column)s."""
+    rng = np.random.default_rng(dim * 1000 + T * 10 + Cn)
+    mu = np.linspace(LO + 0.2, HI - 0.2, T * dim).reshape(T, dim)
+    x = mu[None] + 0.45 * rng.standard_normal((Cn, T, dim))
+    td, planted = temps * dim, []
+    for g in sorted({1, groups - 1}):
+        k0 = g * cols
+        gcols = min(cols, td - k0)
+        slots = [((3 * i + 1) % Cn, k0 + (5 * i) % gcols) for i in range(4)]
+        assert len(set(slots)) == 4
+        for (c, k), v in zip(slots, (np.inf, -np.inf, np.nan, None)):
+            x[c, k // dim, k % dim] = lo[k % dim] if v is None else v
+        planted += slots
+    return x, planted
+
+
+@gpu
+@pytest.mark.parametrize("case,f64", GEOMETRY_RUNS, ids=[c[0] + ("_f64" if f else "") for c, f in GEOMETRY_RUNS])
+def test_standalone_snapshot_at_every_multi_group_geometry(device, case, f64):
+    """ptrwm_histogram on a hand-made state, no step kernel in the way, at the geometries of GEOMETRY_CASES: counts and count
+    equal the NumPy replay, a second snapshot doubles them."""
+    _, dim, T, temps, nb, Cn, _, cols, groups, last, _ = case
+    td = temps * dim
+    assert groups > 1 and (groups - 1) * cols + last == td
+    lo = np.full(dim, LO, np.float32) + np.arange(dim, dtype=np.float32) * np.float32(0.01)  # (a range per coordinate, as Run)
+    scale = (np.float32(nb) / (np.full(dim, HI, np.float32) - lo)).astype(np.float32)
+    x, planted = hand_made_state(dim, T, temps, Cn, lo, cols, groups)
+    st = torch.tensor(x, device=device, dtype=torch.float64 if f64 else torch.float32)
+    plan = E.RunPlan(None, H.proposal_spec("Normal", dim, np.ones(T, np.float32), base_variance_scalar=1.0).engine(device), state=st,
+                     logp=torch.zeros(Cn, T, device=device), beta=torch.ones(T, device=device), burn_in=0)
+    counts = torch.zeros(temps, dim, nb + 2, dtype=torch.int64, device=device)
+    count = torch.zeros(temps, dtype=torch.int64, device=device)
+    plan.set_histogram(counts, torch.tensor(lo, device=device), torch.tensor(scale, device=device), n_bins=nb, temps=temps, every=1,
+                       count=count)
+    x_np = st.cpu().numpy()
+    want, want_n = replay(x_np[None, :, :temps], lo, scale, nb)
+    for times in (1, 2):  # += : the second snapshot doubles the counts
+        plan.split_histogram(times - 1)
+        torch.cuda.synchronize()
+        got, got_n = counts.cpu().numpy(), count.cpu().numpy()
+        assert np.array_equal(got_n, times * want_n), f"count after {times} snapshot(s)"
+        bad = np.argwhere((got != times * want).any(-1))
+        assert bad.size == 0, f"after {times} snapshot(s), {len(bad)} of {td} columns differ; the first (t, d): {bad[:5].tolist()}"
+        assert (got.sum(-1) == got_n[:, None]).all()
+    assert want_n.tolist() == [Cn] * temps
+    # the planted values are where the replay says, and the last group's columns reach both end bins and the bins between
+    flat = want.reshape(td, nb + 2)
+    for c, k in planted:
+        v = x_np[c, k // dim, k % dim]
+        assert flat[k, nb + 1 if v == np.inf else (1 if v == lo[k % dim] else 0)] >= 1
+    tail = flat[td - last:]
+    assert tail[:, 0].sum() > 0 and tail[:, -1].sum() > 0 and tail[:, 1:-1].sum() > 0
+    assert np.array_equal(st.cpu().numpy(), x_np, equal_nan=True)  # a snapshot only reads
+
+
 @gpu
 def test_counts_do_not_depend_on_how_the_caller_cuts_the_run(device):
     """One request of 60 steps against the same run as 3 and as 60 launches, and against step0 continued from an earlier call."""
@@ -219,6 +294,38 @@ def test_counts_do_not_depend_on_how_the_caller_cuts_the_run(device):
     off = Run(device, dim, T, Cn, burn=7, se=3).launches([N])
     assert_rest_equal(none.rest_np(), off.rest_np(), "no due step")  # (the same launches: sq_jump bit-equal too)
     assert_rest_equal(one.rest_np(), off.rest_np(), "histograms on and off", sq_jump_exact=False)
+
+
+@gpu
+def test_histograms_under_the_streaming_form(device):
+    """A snapshot ends a launch, and the streaming form of the step kernel (kernel.h STREAM) keeps state in flight across the
+    groups of one launch: 12 one-step launches with a snapshot behind each, streaming against classic - every output equal - and
+    both against the NumPy replay of a traced twin."""
+    from test_gpu_engine_parity import STREAM_CASES
+
+    tkey, pkind, T, Cn, _, streams = STREAM_CASES[0]
+    assert (tkey, pkind, streams) == ("rc15_d30", "Normal", True)  # the shape: dim 30, 32 temperatures, 2 x 37 ladders
+    dim, N, burn, nb = 30, 12, 3, 32
+    assert E.has_stream_variant(diag_spec(dim).kind, E.PROPOSAL_NORMAL, dim)
+    kw = dict(burn=burn, se=2, n_bins=nb, temps=T, every=1)
+    runs = {}
+    with E.kernel_form(E.FORM_THREAD):
+        for mode in (E.STREAM_ON, E.STREAM_OFF):
+            with E.stream_mode(mode):
+                runs[mode] = Run(device, dim, T, Cn, **kw).launches([1] * N)
+                assert E.last_launch_kind() == (E.LAUNCH_STREAM if mode == E.STREAM_ON else E.LAUNCH_THREAD)
+        traced = Run(device, dim, T, Cn, **kw)
+        trace = torch.zeros(N, Cn, T, dim, device=device)
+        traced.launches([1] * N, trace=trace)
+    on, off = runs[E.STREAM_ON], runs[E.STREAM_OFF]
+    assert np.array_equal(on.hist_np()[0], off.hist_np()[0]) and np.array_equal(on.hist_np()[1], off.hist_np()[1])
+    assert_rest_equal(on.rest_np(), off.rest_np(), "streaming and classic")  # (the same launches: sq_jump bit-equal too)
+    want, want_n = replay(trace.cpu().numpy()[due_rows(0, N, burn, 1)], traced.lo, traced.scale, nb)
+    assert want_n.tolist() == [Cn * 9] * T  # step counters 4, 5, ..., 12
+    assert np.array_equal(on.hist_np()[0], want) and np.array_equal(on.hist_np()[1], want_n)
+    assert want[..., 0].sum() > 0 and want[..., -1].sum() > 0 and want[..., 1:-1].sum() > 0
+    assert_rest_equal(on.rest_np(), traced.rest_np(), "streaming and the traced twin", sq_jump_exact=False)
+    assert on.rest_np()["n_accept"].sum() > 0 and on.rest_np()["swap_accept"].sum() > 0
 
 
 @gpu

@@ -4,11 +4,14 @@ NumPy replay of the rule that the GPU tests rely on, and the arithmetic of the c
 import ctypes as C
 import math
 import os
+import socket
 import subprocess
 
 import numpy as np
 import pytest
 import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
 
 import ptrwm_hip as E
 
@@ -16,17 +19,57 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "ptrwm.h")
 
 
-def test_bin_rule_and_cuts_against_brute_force(tmp_path):
-    """csrc/hist.h and the new helper of csrc/schedule.h compiled as plain C++ under AddressSanitizer and UBSan into
-    tests/hist_test.cpp, a program of its own: the rule against a double-precision restatement (lo, hi, their neighbours,
-    +-inf, NaN, denormals; 1, 2, 7, 64 and 1024 bins), and the cuts of ptrwm_run_with_histogram replayed step by step."""
+def _build_hist_test(tmp_path):
+    """tests/hist_test.cpp, a program of its own, compiled as plain C++ under AddressSanitizer and UBSan."""
     src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hist_test.cpp")
     exe = str(tmp_path / "hist_test")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
                            "-fno-sanitize-recover=all", src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    return exe
+
+
+def test_bin_rule_and_cuts_against_brute_force(tmp_path):
+    """csrc/hist.h and the histogram helper of csrc/schedule.h in tests/hist_test.cpp: the rule against a double-precision
+    restatement (lo, hi, their neighbours, +-inf, NaN, denormals; 1, 2, 7, 64 and 1024 bins), the cuts of
+    ptrwm_run_with_histogram replayed step by step, and hist_geometry - the snapshot kernel's tiling of the covered columns -
+    for every n_bins in 1..1024 and every temps * dim in 1..26 624."""
+    out = subprocess.run([_build_hist_test(tmp_path)], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "hist ok:" in out.stdout
+
+
+def test_gpu_geometry_cases_force_the_geometry_they_are_named_for(tmp_path):
+    """The table of tests/test_gpu_hist.py through hist_geometry itself (the program's "geometry" mode): every case has more
+    than one group of columns and the strategy, group width, group count and last group its row states - so a change of a
+    constant of csrc/hist.h cannot quietly turn the GPU cases back into single-group ones - and, case by case, the property
+    it is there for."""
+    from test_gpu_hist import GEOMETRY_CASES
+
+    exe = _build_hist_test(tmp_path)
+    lines = "".join(f"{c[4]} {c[3] * c[1]}\n" for c in GEOMETRY_CASES)
+    out = subprocess.run([exe, "geometry"], input=lines, capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    got = [tuple(int(v) for v in ln.split()) for ln in out.stdout.splitlines()]
+    assert len(got) == len(GEOMETRY_CASES) == 7
+    geo = {}
+    for (name, dim, T, temps, _, Cn, direct, cols, groups, last, _), g in zip(GEOMETRY_CASES, got):
+        assert g == (int(direct), cols, groups, last), (name, g)
+        assert groups > 1 and 1 <= temps <= T and Cn >= 1, name
+        geo[name] = dict(dim=dim, T=T, temps=temps, Cn=Cn, direct=direct, cols=cols, groups=groups, last=last)
+    g = geo["readme_8_groups"]  # group boundaries inside a temperature's run; two chain tiles, the second partial
+    assert not g["direct"] and g["groups"] == 8 and g["cols"] % g["dim"] != 0 and g["last"] < g["cols"] and 256 < g["Cn"] < 512
+    g = geo["lds_min_cols"]  # the narrowest LDS group; a last group of 2 columns; the second chain tile holds one chain
+    assert not g["direct"] and g["cols"] == 64 and g["groups"] == 3 and g["last"] == 2 and g["Cn"] == 257
+    g = geo["lds_cols_cap"]  # the widest group; the last one does not divide the workgroup: idle threads
+    assert not g["direct"] and g["cols"] == 256 and g["last"] < g["cols"] and 256 % g["last"] != 0
+    g = geo["cold_5_of_12"]  # the chain stride is not the number of covered columns
+    assert g["temps"] < g["T"] and g["cols"] % g["dim"] != 0 and g["last"] < g["cols"]
+    g = geo["direct_2_groups"]
+    assert g["direct"] and g["groups"] == 2 and g["last"] < g["cols"] and g["cols"] % g["dim"] != 0
+    g = geo["direct_max_bins"]
+    assert g["direct"] and g["dim"] == 104 and g["last"] < g["cols"] and GEOMETRY_CASES[5][4] == E.HIST_MAX_BINS
+    g = geo["widest_state"]
+    assert not g["direct"] and g["dim"] * g["temps"] == 104 * 256 and g["groups"] == 416
 
 
 def numpy_bins(x, lo, scale, n_bins):
@@ -313,3 +356,53 @@ def test_class_hist_checks_need_no_gpu():
     h = {"counts": torch.arange(12, dtype=torch.int64).view(1, 2, 6), "count": torch.tensor([7]), "edges": None}
     out = allreduce_histogram(h)
     assert torch.equal(out["counts"], h["counts"]) and out["counts"] is not h["counts"] and out["count"].tolist() == [7]
+
+
+HIST_SHAPE = (2, 3, 6)  # temps, dim, n_bins + 2
+
+
+def _hist_shard(rank):
+    g = torch.Generator().manual_seed(70 + rank)
+    counts = torch.randint(0, 1 << 20, HIST_SHAPE, generator=g, dtype=torch.int64)
+    counts[1, 2, 3] = (1 << 31) + 5 + rank  # above 2^31: a narrowing conversion anywhere in the packing would show
+    count = counts[:, 0, :].sum(-1)
+    edges = torch.linspace(-2.0, 2.0, HIST_SHAPE[2] - 1, dtype=torch.float64).repeat(HIST_SHAPE[1], 1)
+    return {"counts": counts, "count": count, "edges": edges}
+
+
+def _hist_worker(rank, world, port, q):
+    from algorithms.sharding import allreduce_histogram
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    shard = _hist_shard(rank)
+    kept = {k: v.clone() for k, v in shard.items()}
+    total = allreduce_histogram(shard)
+    assert all(torch.equal(shard[k], v) for k, v in kept.items())  # inputs untouched
+    assert total["counts"].dtype == torch.int64 and total["count"].dtype == torch.int64
+    q.put((rank, {k: v.numpy() for k, v in total.items()}))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_allreduce_histogram_over_two_ranks_is_the_sum_of_the_shards():
+    """gloo, two spawned ranks, CPU tensors: counts and count add up exactly on both ranks, the edges pass through."""
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_hist_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    got = [q.get(timeout=180) for _ in procs]
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    a, b = _hist_shard(0), _hist_shard(1)
+    assert int((a["counts"] + b["counts"])[1, 2, 3]) == (1 << 32) + 11 and int((a["count"] + b["count"]).min()) > 0
+    assert sorted(r for r, _ in got) == [0, 1]
+    for _, total in got:
+        assert total["counts"].shape == HIST_SHAPE and np.array_equal(total["counts"], (a["counts"] + b["counts"]).numpy())
+        assert np.array_equal(total["count"], (a["count"] + b["count"]).numpy())
+        assert np.array_equal(total["edges"], a["edges"].numpy())
