@@ -15,6 +15,7 @@
 // log-densities, row exchange through the staging rows), never HBM.
 #pragma once
 #include <cstddef>
+#include <type_traits>
 
 #include "flow.h"
 #include "philox.h"
@@ -44,6 +45,8 @@ constexpr int kWavesPerBlock = kBlockThreads / 64;
 // five VGPRs spilled to scratch otherwise, 42 MB of HBM traffic per launch): the Philox word with the temperature index,
 // the accepted swaps of pair (t, t+1), the last event it accepted in, the sum of squared jumps (a double, ds_add_f64 -
 // profiles/r04_scratch_ab.txt).  Vote word: a wide ladder's objection to the threshold form of a swap event.
+// Between the prologue, the swap events and the epilogue the rows and the first swap-scratch words of the kernels of
+// philox_heads_in_lds hold the parked heads of the thread's Philox blocks: StepLds::heads.
 struct StepLdsWords {  // what does not depend on the register width
   static constexpr int kSwapWords = 3;                                  // s_l, s_u, landed
   static constexpr int kParkedInts = 3;                                 // c3, swap count, last event
@@ -85,6 +88,17 @@ struct StepLds : StepLdsWords {
     return reinterpret_cast<int *>(s_dyn) + (int)flow_lds * (int)(kFlowLdsUnit / 4u) + (wide ? 0 : wave * (64 * kFlowIntsPerThread));
   }
   static constexpr unsigned bytes(int threads, bool wide) { return StepLdsWords::bytes(threads, DP, STREAM, wide); }
+  // The parked Philox heads (philox_head.h; the kernels of philox_heads_in_lds, below): per WAVE normal_blocks(DP) blocks of
+  // 64 slots of 16 bytes, block-major (proposals.h PhiloxHeadSlot), from heads(wide, wave) floats behind s_dyn.  They lie
+  // OVER the rows and - width 30: 8 x 64 x 4 = 2048 words against 64 x 30 of rows - over the first words of the swap scratch
+  // behind them: all dead between the prologue, the swap events and the epilogue, i.e. in nine steps of ten.  Never over the
+  // parked words.  Narrow: a wave's heads lie in its own group's region, program order keeps them apart from the rows.
+  // Wide: wave w's lie w * kHeadWaveWords into the one group's region, over rows and scratch words that OTHER waves read and
+  // write in a swap event - the group's barrier stands between a step's last head read and the event's first store, and
+  // between the event's last row read and the store of the heads.
+  static constexpr int kHeadWaveWords = normal_blocks(DP) * kHeadBlockSlots * kHeadSlotWords;
+  static constexpr bool kHeadsFit = !STREAM && kHeadWaveWords <= 64 * (DP + kSwapWords) && kWaveFloats % kHeadSlotWords == 0;
+  static constexpr int heads(bool wide, int wave) { return wave * (wide ? kHeadWaveWords : kWaveFloats); }
 };
 namespace lds_check {
 using C = StepLds<30>;
@@ -110,6 +124,10 @@ constexpr bool aligned(bool ok = true) {
 }
 static_assert(aligned<2>() && aligned<3>() && aligned<5>() && aligned<9>() && aligned<29>() && aligned<30>() && aligned<50>() && aligned<64>(), "alignment");
 static_assert(C::bytes(256, false) == 38912u && S::bytes(256, false) == 79872u && C::bytes(256, true) == 38928u, "LDS bytes, as before the layout had a name");
+static_assert(C::kHeadsFit && C::kHeadWaveWords == 2048 && C::heads(false, 3) + C::kHeadWaveWords <= 3 * C::kWaveFloats + C::parked(64) &&
+                  C::heads(true, 3) + C::kHeadWaveWords <= C::parked(256) && C::heads(true, 1) + C::kHeadWaveWords <= C::parked(128) &&
+                  !StepLds<8>::kHeadsFit && !S::kHeadsFit,
+              "parked heads: 16-byte slots over the rows and the swap scratch of the wave's group, below the parked words; width 8 has no room");
 static_assert(0 < C::kFlowUp && C::kFlowUp < C::kFlowDown && C::kFlowDown < C::kFlowIntsPerThread && C::flow_bytes(256) == 4096u &&
                   C::flow_bytes(kBlockThreads) == (unsigned)kWavesPerBlock * 64u * C::kFlowIntsPerThread * 4u,
               "flow region: two word buffers, up visits, down visits, one region per group; nothing of it in a launch without flow");
@@ -586,6 +604,15 @@ constexpr int min_waves_per_simd(int dp) {
 // for HybridRosenbrock): what is loop-invariant there is recomputed rather than kept (ptrwm_step_kernel, the chain word)
 constexpr bool step_loop_at_register_cap(int dp, bool stream) { return !stream && min_waves_per_simd(dp) >= 4 && dp > 24; }
 
+// Which step kernels park the step-invariant heads of their Philox blocks in LDS (philox_head.h, StepLds::heads) and enter
+// every block at round 2: the production thread-form kernel of the compiled-in width 30 with the Normal proposal - the
+// headline shape, whose step loop is bound by VALU issue while LDS idles.  The heads live in LDS, never in registers: held
+// in VGPRs (24 of them) that kernel spills 16, and at five waves per SIMD 45.  FULL twins, the streaming form and the
+// lane-split kernels keep the plain block; so does every other width and proposal until it is measured.
+constexpr bool philox_heads_in_lds(int dp, bool exact, bool full, bool stream, int proposal_kind) {
+  return !full && !stream && exact && dp == 30 && proposal_kind == PTRWM_PROPOSAL_NORMAL;
+}
+
 // The streaming form (STREAM, below) keeps two slabs of rows per wave in LDS: fewer waves per SIMD fit (and each gets the
 // registers of that residency).
 constexpr int stream_waves_per_simd(int dp) {  // what two slabs per wave leave room for in 160 KB of LDS per CU, at most 4
@@ -825,11 +852,33 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
   }
 
   const unsigned long long gchain = (unsigned long long)(a.chain_offset + chain);
-  RngCtx rc;  // (counter words: rng_layout.h)
+  constexpr bool kHeads = philox_heads_in_lds(DP, EXACT, FULL, STREAM, Proposal::kKind);
+  static_assert(!kHeads || L::kHeadsFit, "the parked heads need room over the rows and the swap scratch");
+  typename std::conditional<kHeads, RngCtxHeads, RngCtx>::type rc;  // (counter words: rng_layout.h)
   rc.c2 = chain_word_c2(gchain);
   rc.k0 = a.k0;
   rc.k1 = a.k1;
   const uint32_t c3_base = chain_word_c3(gchain, (uint32_t)t);
+  // This thread's slot of block 0 of the parked heads, rebuilt from the hardware wherever it is needed (thread_index_now),
+  // and the store of all its heads for the counter word c0hi: in the prologue and behind every swap event's row exchange,
+  // each time behind the group's barrier (StepLds::heads).  c0hi holds for the launch: schedule.h cuts at 2^32 steps.
+  [[maybe_unused]] auto head_slot0 = [&]() __attribute__((always_inline)) {
+    return reinterpret_cast<PhiloxHeadSlot *>(s_dyn + L::heads(wide, wave)) + (thread_index_now(wave) & 63);
+  };
+  [[maybe_unused]] auto store_heads = [&](uint32_t c0hi, uint32_t c3) __attribute__((always_inline)) {
+    PhiloxHeadSlot *const slot0 = head_slot0();
+    uint32_t chain_hi, chain_lo;
+    philox_mul(kPhiloxM1, rc.c2, chain_hi, chain_lo);
+#pragma unroll
+    for (int c = 0; c < normal_blocks(DP); ++c) {
+      const PhiloxHead h = philox_head(c0hi | (uint32_t)c, chain_lo, c3, rc.k0, rc.k1);
+      slot0[c * kHeadBlockSlots] = PhiloxHeadSlot{h.pk, h.qk, h.ql, 0u};
+    }
+  };
+  if constexpr (kHeads) {
+    sync_group();  // every row of the group has been read
+    store_heads(step_word_c0hi((unsigned long long)a.step0), with_stream(c3_base, kStreamMH));
+  }
 
   unsigned n_acc = 0;
   {
@@ -958,7 +1007,9 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       // hoisted out of the step loop as a 64-bit pair, which THERE is spilled and fetched back from scratch at the top of
       // every step - one v_mad_u64_u32 per step instead.  Only there: every kernel with registers to spare keeps the hoisted
       // product and runs 2-5 % faster for it - dims 24 / 48 / 50 in profiles/r04_scratch_ab.txt, table 6)
-      if constexpr (step_loop_at_register_cap(DP, STREAM)) asm volatile("" : "+v"(rc.c2));
+      // (with the heads parked that product is in the loop no more: only its high half is, one register)
+      if constexpr (step_loop_at_register_cap(DP, STREAM) && !kHeads) asm volatile("" : "+v"(rc.c2));
+      if constexpr (kHeads) rc.heads = head_slot0();  // (the address is rebuilt per step, not carried: finish_step)
 
       long long srep = 0;
       const float *ext_raw = nullptr;
@@ -1017,6 +1068,8 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       float us;
       if (ext) us = swap_uniform_ext(a.full.ext_swap_u, swap_in_call, a.n_chains, chain, T, t);
       else us = swap_uniform_philox(rc.c0hi, rc.c1, rc.c2, with_stream(c3_s, kStreamSwap), rc.k0, rc.k1);
+      // (parked heads lie under the scratch words and the rows: every thread of the group has read this step's)
+      if constexpr (kHeads) sync_group();
       // publish this thread's log-density and swap uniform; the sweep reads them back with broadcast ds_reads
       s_l[slot] = my_l;
       s_u[slot] = us;
@@ -1054,6 +1107,10 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
           if ((d & 7) == 7) sched_fence_soft();
         })
         j2 = tree4_add(j2p);
+        if constexpr (kHeads) {
+          sync_group();  // every row of the group has been fetched: the heads go back over them
+          store_heads(rc.c0hi, with_stream(c3_s, kStreamMH));
+        }
         if constexpr (FULL) {
           // replica flow (flow.h): the word travels as the row does - fetched from slot `src` behind the barrier above, which
           // also orders it behind that slot's write of the previous event, and written to the OTHER buffer: slot `slot` of this

@@ -11,18 +11,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "philox_head.h"  // u32x4, the round constants; the head / tail split of a block (the production step kernel)
 #include "rng_layout.h"
 
 namespace ptrwm {
-
-struct u32x4 {
-  uint32_t x, y, z, w;
-};
-
-constexpr uint32_t kPhiloxM0 = 0xD2511F53u;
-constexpr uint32_t kPhiloxM1 = 0xCD9E8D57u;
-constexpr uint32_t kPhiloxW0 = 0x9E3779B9u;
-constexpr uint32_t kPhiloxW1 = 0xBB67AE85u;
 
 // 32x32 -> 64 multiply by a round constant: one v_mad_u64_u32 (both halves, ~7 cycles per wave at 4 waves/SIMD).
 // Splitting it into v_mul_hi_u32 + v_mul_lo_u32 was measured SLOWER (v_mul_lo_u32 is quarter rate: 2.4 + 8.5
@@ -106,10 +98,7 @@ __device__ __forceinline__ const_float_ptr uniform_vec_again(const_float_ptr p) 
 
 // top 24 bits -> [0, 1): same lattice as torch.rand(float32)
 __device__ __forceinline__ float u01(uint32_t r) { return (float)(r >> 8) * 0x1p-24f; }
-// top 24 bits -> (0, 1]
-__device__ __forceinline__ float u01_open0(uint32_t r) {
-  return ((float)(r >> 8) + 1.0f) * 0x1p-24f;
-}
+// top 24 bits -> (0, 1]: u01_open0, philox_head.h
 
 constexpr float kLn2 = 0.69314718055994530942f;
 constexpr float kLog2e = 1.44269504088896340736f;

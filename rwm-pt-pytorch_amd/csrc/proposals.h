@@ -18,7 +18,24 @@
 namespace ptrwm {
 
 struct RngCtx {
+  static constexpr bool kHeads = false;
   uint32_t c0hi, c1, c2, c3, k0, k1;
+};
+
+// Blocks of one step of the Normal proposal: up to the one holding word 2*ceil(DP/2), the accept uniform
+constexpr int normal_blocks(int dp) { return (2 * ((dp + 1) / 2)) / 4 + 1; }
+
+// The counter words of a kernel that parks the step-invariant heads of its blocks in LDS (philox_head.h; kernel.h
+// StepLds::heads says where and philox_heads_in_lds for which kernels): `heads` is this thread's slot of block 0, block c's
+// slot lies c * kHeadBlockSlots slots on.  A slot is 16 bytes - PK, QK, QL and a spare word - so that one aligned ds_read
+// per block serves a thread and the 64 slots of a wave are conflict-free.  (may_alias: the slots lie over the rows and
+// the swap scratch, which are floats.)
+typedef uint32_t PhiloxHeadSlot __attribute__((ext_vector_type(4), may_alias));
+constexpr int kHeadSlotWords = 4;
+constexpr int kHeadBlockSlots = 64;
+struct RngCtxHeads : RngCtx {
+  static constexpr bool kHeads = true;
+  const PhiloxHeadSlot *heads;
 };
 
 // What a proposal functor says about the squared length of the increment it just made (the Metropolis step's squared jump
@@ -102,13 +119,32 @@ __device__ __forceinline__ void philox_normals(float (&z)[DP], int D, const RngC
 // the pair's square root, with c_t = -2 ln 2 tscale^2 folded once per step - summed per canonical range (a pair never
 // straddles two ranges: W is even); the last dimension of an odd dim contributes (rad sin)^2.  One add per pair instead of
 // a subtraction and an fma per dimension; within 1e-6 relative of |y - x|^2 (the rounding of x + inc and of sin^2 + cos^2).
-template <int DP>
+// With the heads parked (Rng::kHeads) a step computes its own product X once and enters every block at round 2
+// (philox_tail); the slot of block c + 1 is read before the rounds of block c.
+template <int DP, class Rng>
 __device__ __forceinline__ float philox_normal_step(float (&y)[DP], const float (&x)[DP], int D, float tscale,
-                                                    const RngCtx &rc, float &jump_total) {
+                                                    const Rng &rc, float &jump_total) {
   constexpr int W = canon_width(DP);
   float jump[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   const float c_t = mul_rn(mul_rn(-2.0f * kLn2, tscale), tscale);
-  constexpr int NB = (2 * ((DP + 1) / 2)) / 4 + 1;  // blocks up to the one holding word 2*ceil(DP/2)
+  constexpr int NB = normal_blocks(DP);
+  [[maybe_unused]] uint32_t x_hi = 0u, x_lo = 0u;
+  [[maybe_unused]] PhiloxHeadSlot next_head;
+  if constexpr (Rng::kHeads) {
+    uint32_t chain_hi, chain_lo;
+    philox_mul(kPhiloxM1, rc.c2, chain_hi, chain_lo);
+    philox_step_product(chain_hi, rc.c1, rc.k0, x_hi, x_lo);
+    next_head = rc.heads[0];
+  }
+  auto block = [&](int c) __attribute__((always_inline)) -> u32x4 {
+    if constexpr (Rng::kHeads) {
+      const PhiloxHeadSlot h = next_head;
+      if (c + 1 < NB) next_head = rc.heads[(c + 1) * kHeadBlockSlots];
+      return philox_tail(PhiloxHead{h.x, h.y, h.z}, rc.c0hi | (uint32_t)c, x_hi, x_lo, rc.k0, rc.k1);
+    } else {
+      return philox4x32_10(rc.c0hi | (uint32_t)c, rc.c1, rc.c2, rc.c3, rc.k0, rc.k1);
+    }
+  };
 #ifdef PTRWM_INJECT_ACCEPT_WORD_SLIP
   // FAULT INJECTION (tools/inject_slip_check.sh only, never in a shipped build): the accept uniform is taken one pair
   // early - the radius word of the last Box-Muller pair - so the Philox-mode parity tests can be shown to fail on it
@@ -121,7 +157,7 @@ __device__ __forceinline__ float philox_normal_step(float (&y)[DP], const float 
   for (int c = 0; c < NB; ++c) {
     if (4 * c + 4 <= DP && 4 * c + 4 <= D) {
       // a block entirely below dim: no per-pair tests (run-time dim: one scalar branch per block, see PTRWM_DIM_LOOP)
-      const u32x4 r = philox4x32_10(rc.c0hi | (uint32_t)c, rc.c1, rc.c2, rc.c3, rc.k0, rc.k1);
+      const u32x4 r = block(c);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int d = (4 * c + 2 * h + 1 < DP) ? 4 * c + 2 * h : 0;
@@ -135,7 +171,7 @@ __device__ __forceinline__ float philox_normal_step(float (&y)[DP], const float 
       }
       sched_fence();
     } else if (4 * c <= w_a) {
-      const u32x4 r = philox4x32_10(rc.c0hi | (uint32_t)c, rc.c1, rc.c2, rc.c3, rc.k0, rc.k1);
+      const u32x4 r = block(c);
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int d = 4 * c + 2 * h;
@@ -172,8 +208,9 @@ struct NormalProposal {
   static constexpr bool kKnowsJump = true;
   // the size of a typical per-dimension increment (for jump_trusted)
   __device__ __forceinline__ static float increment_scale(float tscale, const PParams &) { return tscale; }
+  template <class Rng>
   __device__ __forceinline__ static float propose(float (&y)[DP], const float (&x)[DP], int D,
-                                                  float tscale, const PParams &, const RngCtx &rc,
+                                                  float tscale, const PParams &, const Rng &rc,
                                                   const float *ext_raw, float ext_u, float &jump, int &jump_kind) {
     float u_acc = ext_u;
     if (ext_raw != nullptr) {

@@ -88,10 +88,18 @@ struct LaunchCut {
   int steps_to_swap, steps_to_trace, steps_to_mom;  // countdowns to the first such step (1 = the launch's first step; > n: none)
 };
 
-// The launch of `r` that starts `done` steps into it, at most `cap` steps long (1 <= cap <= 2^16: max_steps_per_launch)
+// steps from step0 (>= 0) up to the next multiple of 2^32: as far as the high word of the step index - a part of every Philox
+// counter (rng_layout.h step_word_c0hi) - holds.  No launch goes further: what a step kernel derives from that word at
+// the start of a launch (kernel.h: the parked heads of its Philox blocks) then holds for the whole launch.
+inline long long steps_to_step_word_wrap(long long step0) { return (1ll << 32) - (step0 & 0xffffffffll); }
+
+// The launch of `r` that starts `done` steps into it, at most `cap` steps long (1 <= cap <= 2^16: max_steps_per_launch) and
+// ending where the step index's high word changes, if that comes first
 inline LaunchCut launch_at(const StepRequest &r, long long done, long long cap) {
   LaunchCut c;
   c.step0 = r.step0 + done;
+  const long long to_wrap = steps_to_step_word_wrap(c.step0);
+  if (to_wrap < cap) cap = to_wrap;
   const long long n = r.n_steps - done < cap ? r.n_steps - done : cap;
   c.n = (int)n;
   const long long burn_left = r.burn_in - c.step0;
