@@ -20,6 +20,7 @@
 #include "flow.h"
 #include "philox.h"
 #include "proposals.h"
+#include "swap_walk.h"
 #include "targets.h"
 
 namespace ptrwm {
@@ -317,13 +318,16 @@ __device__ __forceinline__ float swap_uniform_philox(uint32_t c0hi, uint32_t c1,
     (CAR_I) = (OK) ? (CAR_I) : (IK);                             \
   } while (0)
 
-template <class Sync>
+// SCAN = false: a caller whose sequential exchange sweeps never come here (the streaming step kernels that walk: narrow ladders
+// only, swap_walk_decide below) compiles the scan out.
+template <bool SCAN = true, class Sync>
 __device__ __forceinline__ void swap_decide(int T, int t, int base, int slot, int swap_mode, int swap_order, int par,
                                             const float *__restrict__ beta, float beta_t, float us, const float *s_l,
                                             float *s_u, int *landed, float &my_l, int &src, bool &pair_acc, Sync sync,
                                             bool plain) {
   if (swap_order == PTRWM_ORDER_SEQUENTIAL) {
     if (swap_mode == PTRWM_SWAP_EXCHANGE) {
+      if constexpr (!SCAN) return;
       const bool has_k = t < T - 1;
       const float db = has_k ? sub_rn(beta_t, beta[t + 1]) : 1.0f;
       float car_l = s_l[base];
@@ -392,6 +396,62 @@ __device__ __forceinline__ void swap_decide(int T, int t, int base, int slot, in
       pair_acc = ok && lower;
     }
   }
+}
+
+// The sequential exchange sweep of an exchange group that is ONE wavefront (T <= 64: the step kernel's narrow groups), by
+// lane masks and a scalar walk (swap_walk.h) instead of the scan above, which every lane of a ladder replays: 64 lanes then
+// compute the same T - 1 decisions - a compare, three selects and a ds_write per pair on the vector unit that bounds the
+// kernel - while the scalar unit idles.  Here lane k answers, per pair j, ONE question about its own published log-density
+// my_l: would it be accepted at pair j of its ladder, were it the carried state?  The ballot of the answers is a wave-uniform
+// word, the walk over the words runs on the scalar unit for all ladders of the wavefront at once, and every lane reads its
+// outcome from the walk's `rejected` word once.  Same compares on the same values as the scan: same decisions, bit for bit.
+// In / out as swap_decide; every lane of the wavefront calls it (idle lanes shadow position 0 of ladder 0, as there).
+// plain (the ladder's verdict, swap_decide): the threshold form - own pair's threshold published in place of its uniform,
+// the question is my_l < thr_j.  A ladder that must take the literal rule asks swap_accept_test(u_j, swap_log_prob(b_j,
+// b_j+1, my_l, l_j+1)) instead - also a function of (carrier, j) alone.  The rule is chosen per LADDER: a wavefront with a
+// literal ladder anywhere runs the loop in which every lane selects its own ladder's answer (cold: corner cases only), and a
+// plain ladder's answers there are the compares of the fast loop.
+// LEAN (the fixture twins, whose speed nobody measures): the one general loop only - the library's size budget
+// (tools/kernel_stats.py --size) has no room for a fast loop in every twin.
+template <bool LEAN, class Sync>
+__device__ __forceinline__ void swap_walk_decide(int T, int t, int base, int slot, const float *__restrict__ beta, float db,
+                                                 float us, const float *s_l, float *s_u, float &my_l, int &src, bool &pair_acc,
+                                                 Sync sync, bool plain) {
+  const bool has_k = t < T - 1;
+  if (plain) {
+    // own pair's threshold in place of its uniform (swap_decide)
+    const float lk = s_l[has_k ? slot + 1 : slot];
+    s_u[slot] = fmaf(-hw_ln(us), __builtin_amdgcn_rcpf(db), lk);  // (the last position's: b_t - b_t = 0, read by no pair)
+  }
+  sync();
+  const uint64_t seg0 = __builtin_amdgcn_ballot_w64(slot == base);  // (an idle lane's base is 0; lane 0 is never idle)
+  const float *const pair = s_u + base;  // pair j of this lane's ladder: one address, j an immediate offset
+  const bool all_plain = __builtin_amdgcn_ballot_w64(!plain) == 0ull;
+  SwapWalk w = swap_walk_begin(seg0);
+  int j = 0;
+  if constexpr (!LEAN) {
+    // the fast loop: one ds_read2 and two compares per trip on the vector unit, the rest scalar.  (Two pairs per trip written
+    // out: a ballot is a convergent operation, and the compiler unrolls no loop of a run-time trip count around one.)
+    if (all_plain)
+      for (; j + 2 <= T - 1; j += 2) {
+        swap_walk_step(w, seg0, j, __builtin_amdgcn_ballot_w64(my_l < pair[j]));
+        swap_walk_step(w, seg0, j + 1, __builtin_amdgcn_ballot_w64(my_l < pair[j + 1]));
+      }
+  }
+  // the general loop: the fast loop's odd last pair; the whole sweep of a wavefront with a literal ladder, or of a LEAN kernel
+#pragma unroll 1
+  for (; j < T - 1; ++j) {
+    const float v = pair[j];  // the pair's threshold (plain ladders) or its uniform
+    bool ok = my_l < v;
+    if (!all_plain) {
+      PTRWM_COLD_PATH();
+      const bool literal = swap_accept_test(v, swap_log_prob(beta[j], beta[j + 1], my_l, s_l[base + j + 1]));
+      ok = plain ? ok : literal;
+    }
+    swap_walk_step(w, seg0, j, __builtin_amdgcn_ballot_w64(ok));
+  }
+  src = swap_walk_source(w.rejected, seg0, base + t, has_k, pair_acc);
+  my_l = s_l[src];  // log-densities travel with the states: s_l still holds the originals
 }
 
 // Staging between a group's contiguous run of `total` floats in HBM (`g`, any 4-byte alignment) and its LDS slab, 16 bytes
@@ -622,6 +682,15 @@ constexpr int stream_waves_per_simd(int dp) {  // what two slabs per wave leave 
 // (the register budget it is compiled for: never that of ONE wave per SIMD - 512 registers invite AGPR copies, the regime
 // tools/kernel_stats.py --check keeps every kernel out of - even where LDS admits no second wave)
 constexpr int stream_register_waves(int dp) { return stream_waves_per_simd(dp) < 2 ? 2 : stream_waves_per_simd(dp); }
+
+// Which step kernels decide the sequential exchange sweep of their one-wavefront groups by the walk (swap_walk_decide): the
+// widths up to 44, compiled for three or four waves per SIMD.  The wider ones already keep 40 to 150 scalars spilled in VGPR
+// lanes, and the six scalar registers the walk holds across its loop cost them more than the scan's selects: with the walk
+// the width-50 kernel of BASELINE configs[4] spilled 44 SGPRs instead of 40 and ran 0.8 % SLOWER (503.4 against 499.4 ms per
+// launch, three alternating runs each, no overlap), and the streaming twin of Hypercube<50> with the UniformRadius proposal
+// went one above the spilled-SGPR ratchet of tools/kernel_stats.py (129, ceiling 128; 117 with the scan).  They keep the
+// scan, and their machine code (profiles/r16_swap_walk.txt).
+constexpr bool swap_walk_in_kernel(int dp) { return dp <= 44; }
 
 // threads of this kernel's exchange group (rng_layout.h; the streaming form serves narrow ladders only: one wave, folded)
 template <bool STREAM>
@@ -1074,7 +1143,8 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       s_l[slot] = my_l;
       s_u[slot] = us;
       // may this ladder's sequential sweep take the threshold form in THIS event?  (swap_decide: a verdict of the ladder)
-      const bool pair_plain = swap_pair_plain(T, t, STREAM ? db_s : sub_rn(beta_t, a.beta[t < T - 1 ? t + 1 : t]), my_l, us);
+      const float db_pair = STREAM ? db_s : sub_rn(beta_t, a.beta[t < T - 1 ? t + 1 : t]);  // b_t - b_{t+1}; the last position: 0
+      const bool pair_plain = swap_pair_plain(T, t, db_pair, my_l, us);
       // (narrow groups: a ballot over the ladder's lanes.  Wide: the ladder's word behind the parked words,
       // wide_ladder_votes_plain)
       bool swap_plain;
@@ -1084,8 +1154,12 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
         swap_plain = ladder_votes_plain(pair_plain, base, T);
         sync_group();
       }
-      swap_decide(T, t, base, slot, a.swap_mode, a.swap_order, (ev_par0 + swap_in_call) & 1, a.beta, beta_t, us, s_l, s_u,
-                  reinterpret_cast<int *>(s_u + (L::kLanded - L::kSu) * group_threads), my_l, src, pair_acc, sync_group, swap_plain);
+      // (one-wavefront groups decide the sequential exchange sweep by lane masks and a scalar walk; wide ladders keep the scan)
+      if (swap_walk_in_kernel(DP) && !wide && a.swap_order == PTRWM_ORDER_SEQUENTIAL && a.swap_mode == PTRWM_SWAP_EXCHANGE)
+        swap_walk_decide<FULL>(T, t, base, slot, a.beta, db_pair, us, s_l, s_u, my_l, src, pair_acc, sync_group, swap_plain);
+      else
+        swap_decide<!(STREAM && swap_walk_in_kernel(DP))>(T, t, base, slot, a.swap_mode, a.swap_order, (ev_par0 + swap_in_call) & 1, a.beta, beta_t, us, s_l, s_u,
+                    reinterpret_cast<int *>(s_u + (L::kLanded - L::kSu) * group_threads), my_l, src, pair_acc, sync_group, swap_plain);
       if (pair_acc) {
         park[L::kSwapCount * group_threads] += 1;
         park[L::kLastEvent * group_threads] = swap_in_call;

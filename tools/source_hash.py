@@ -13,7 +13,7 @@ import os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "rwm-pt-pytorch_amd", "csrc")
 # (capi.hip and form_table.inc are not part of it: the dispatch rule and the table are what the hash is compared WITH)
-FILES = ["kernel.h", "quad.h", "flow.h", "philox.h", "philox_head.h", "rng_layout.h", "proposals.h", "targets.h", "variants.h", "Makefile"]
+FILES = ["kernel.h", "quad.h", "flow.h", "philox.h", "philox_head.h", "rng_layout.h", "swap_walk.h", "proposals.h", "targets.h", "variants.h", "Makefile"]
 
 
 def source_hash() -> str:
