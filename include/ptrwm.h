@@ -493,6 +493,68 @@ int32_t ptrwm_run_with_histogram(const ptrwm_target_desc *target, const ptrwm_pr
                                  const ptrwm_chain_moments_args *chain_moments, const ptrwm_flow_args *flow,
                                  const ptrwm_hist_args *hist, void *stream);
 
+/* ---- warm-up tuning of the proposal scale, per temperature, on the device ------------------------------------------------------
+ * temp_scale[t] = sqrt(var / beta_t) is exact for Gaussians only; elsewhere the hot rungs of a ladder sit far from the
+ * acceptance rate a random-walk Metropolis kernel works best at.  During burn-in the library can tune every temperature's
+ * scale towards a target acceptance rate, pooled over every replica (csrc/adapt.h states the rule once).
+ * Windows: with W = every, window k is the steps [k W, (k + 1) W).  The K = until / W windows that end at or before `until`
+ * (<= burn_in) adapt; steps [K W, burn_in) are ordinary burn-in under the final scale; past burn-in nothing adapts, so the
+ * chain that is sampled is a fixed-kernel Markov chain.  After window k, for every temperature t:
+ *   rate  = pooled[t] / pooled[n_temps]       acceptances / chain-steps of the window (pooled[n_temps] = 0: scale left alone)
+ *   s_new = (float) clamp((double) s_old * exp(gain_k * (rate - target)), min_scale, max_scale),   gain_k = gain / (k + 1)^decay
+ * in double (gain_k on the host).  Suggested: target 0.234, gain 3, decay 0.5.
+ * How: NOT in the step kernels.  Every launch reads temp_scale from device memory when it starts, so a kernel enqueued between
+ * two launches rewrites the scales in stream order.  A launch inside an adapting window ends with the window at the latest; it
+ * is the production kernel, told to count acceptances from its first step into `window_accept` (which accumulates: a window
+ * may span launches and calls), with no squared-jump sum and no swap step - exactly what a burn-in step does to state and
+ * logp, which are bit-identical to the same steps run as ordinary burn-in under the same scales (the Philox words depend on
+ * seed, step and chain only).  n_accept, sq_jump, the swap counters, moments, flow and histograms see post-burn-in steps only,
+ * as always; traces and accept_flags behave as in any burn-in.  After the launch that ends window k the reduce kernel
+ * (window_accept summed over chains into pooled, the scratch left zero) and, unless defer_update, the update kernel
+ * (temp_scale, the histories; pooled left zero) are enqueued.  Everything between scratch and scale is integer or one
+ * deterministic double expression, and the window comes from step0: a run cut into calls anywhere gives the same bits, and a
+ * request at or past `until` adapts nothing.
+ * Shards: with defer_update = 1 a request ends at window ends (one that would step past the end of the adapting window its
+ * step0 lies in returns PTRWM_E_ARG before anything is enqueued); the caller all-reduces (SUM) `pooled` over the shards and
+ * calls ptrwm_adapt_update on each: every shard applies the same update to the same integers, so a sharded run equals the
+ * unsharded one bit for bit.
+ * Split steps: a warm-up step is ptrwm_split_propose / ptrwm_split_accept with burn_in = 0, swap_every = INT32_MAX,
+ * n_accept = window_accept and sq_jump = NULL in ptrwm_run_args; ptrwm_adapt_reduce, then ptrwm_adapt_update, after the last
+ * step of every adapting window. */
+typedef struct ptrwm_adapt_args {
+  uint32_t struct_size;    /* sizeof(ptrwm_adapt_args) */
+  int32_t every;           /* W >= 1: the window length */
+  int64_t until;           /* 0..burn_in: windows that end at or before this step adapt */
+  float target;            /* in (0, 1): the acceptance rate aimed at */
+  float gain, decay;       /* gain_k = gain / (k + 1)^decay; gain > 0 and finite, decay in 0..1 */
+  float min_scale, max_scale; /* 0 < min_scale <= max_scale, finite: every scale is clamped to this range */
+  int32_t defer_update;    /* 0: update after every window.  1: the caller does (ptrwm_adapt_update), see "Shards" */
+  float *temp_scale;       /* [n_temps] device, in/out; must be the memory proposal->temp_scale points to */
+  int64_t *window_accept;  /* [n_chains, n_temps] device scratch, zero before the run, zero again after every window */
+  int64_t *pooled;         /* [n_temps + 1] device, zero before the run */
+  float *scale_history;    /* [K + 1, n_temps] device or NULL: row 0 the starting scales, row k + 1 those after window k */
+  int64_t *accept_history; /* [K, n_temps] device or NULL: pooled[t] of window k */
+} ptrwm_adapt_args;
+
+/* ptrwm_run_with_histogram, plus adaptation.  adapt == NULL: exactly ptrwm_run_with_histogram.
+ * Checked before anything is enqueued, after the existing checks: PTRWM_E_STRUCT for a wrong adapt->struct_size; PTRWM_E_NULL
+ * for a NULL temp_scale, window_accept or pooled; PTRWM_E_ARG for every < 1, until outside 0..burn_in, target not in (0, 1),
+ * gain not positive and finite, decay outside 0..1, min_scale / max_scale not 0 < min <= max and finite,
+ * temp_scale != proposal->temp_scale, defer_update outside 0..1, or (defer_update = 1) a request that steps past a pending
+ * window end.  External randoms are allowed, as with histograms. */
+int32_t ptrwm_run_with_adaptation(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                                  const ptrwm_run_args *args, const ptrwm_moments_args *moments,
+                                  const ptrwm_chain_moments_args *chain_moments, const ptrwm_flow_args *flow,
+                                  const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt, void *stream);
+
+/* The end of a window, stand-alone (split steps; shards): adapt->window_accept [args->n_chains, args->n_temps] summed over
+ * chains into adapt->pooled[t], args->n_chains * adapt->every added to pooled[n_temps], the scratch left zero.  Reads n_temps
+ * and n_chains from `args`.  PTRWM_E_NULL / PTRWM_E_STRUCT / PTRWM_E_TEMPS / PTRWM_E_ARG as above; an empty batch: PTRWM_OK. */
+int32_t ptrwm_adapt_reduce(const ptrwm_run_args *args, const ptrwm_adapt_args *adapt, void *stream);
+/* The update of window `window` (0 <= window < K = until / every, else PTRWM_E_ARG) from adapt->pooled: temp_scale and the
+ * histories written, pooled[0 .. n_temps] left zero.  One small workgroup. */
+int32_t ptrwm_adapt_update(const ptrwm_adapt_args *adapt, int32_t n_temps, int64_t window, void *stream);
+
 /* One stand-alone swap event over the current states: what the reference's
  * ParallelTemperingRWM_GPU_Optimized._attempt_all_swaps() does when called on its own
  * (pt_rwm_gpu_optimized.py:594-633; tests/debug_pt_performance.py:156).  Exactly the swap part of a ptrwm_run step:

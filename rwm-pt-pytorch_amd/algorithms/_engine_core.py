@@ -32,6 +32,14 @@ snapshot kernel between launches at every hist_every-th step past burn-in:
     count        int64   [hist_temps]                       (replica, step) pairs added per temperature
     lo, scale    float32 [dim]                              the bin rule's constants (csrc/hist.h)
 
+and, with adapt_scale=True, the arrays of the warm-up tuning of the proposal scale (`_adapt`, a dict; include/ptrwm.h
+ptrwm_adapt_args), used by two small kernels between launches at the end of every adaptation window of burn-in:
+
+    window_accept  int64   [n_replicas, n_temps]      acceptances of the current window (scratch, zero between windows)
+    pooled         int64   [n_temps + 1]              their sum over replicas, and the window's chain-steps (zero between windows)
+    scale_history  float32 [K + 1, n_temps]           the scales before the first and after every window (NaN: not run yet)
+    accept_history int64   [K, n_temps]               pooled acceptances of every window
+
 `n_replicas` is the axis the reference does not have: independent copies of the whole chain /
 ladder, one Philox subsequence each (global replica id = chain_offset + local index), so a run is
 invariant to how replicas are sharded over GPUs.
@@ -146,6 +154,52 @@ def check_hist_args(hist_temps, hist_every, hist_bins, hist_range, n_temps: int,
     return check_hist_range(hist_range, dim)
 
 
+def check_adapt_args(adapt_scale, burn_in: int, adapt_every=50, adapt_until=None, adapt_target=0.234, adapt_gain=3.0,
+                     adapt_decay=0.5, adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None) -> Optional[dict]:
+    """The warm-up tuning arguments of EngineRun and the sampler classes (no GPU needed): None when off, else a dict with
+    every / until / target / gain / decay / bounds / sync and windows = until // every.  ValueError for anything the library
+    would refuse (include/ptrwm.h ptrwm_adapt_args); a warning when no window fits into burn-in."""
+    if not isinstance(adapt_scale, (bool, np.bool_)):
+        raise ValueError(f"adapt_scale must be True or False, got {adapt_scale!r}")
+    if not adapt_scale:
+        return None
+    burn_in = int(burn_in)
+    if isinstance(adapt_every, bool) or not isinstance(adapt_every, (int, np.integer)) or adapt_every < 1:
+        raise ValueError(f"adapt_every must be an integer >= 1, got {adapt_every!r}")
+    if adapt_until is None:
+        adapt_until = burn_in
+    if isinstance(adapt_until, bool) or not isinstance(adapt_until, (int, np.integer)) or not 0 <= adapt_until <= burn_in:
+        raise ValueError(f"adapt_until must be an integer in 0..burn_in = {burn_in}, got {adapt_until!r}")
+
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+        return float(v)
+
+    target, gain, decay = number("adapt_target", adapt_target), number("adapt_gain", adapt_gain), number("adapt_decay", adapt_decay)
+    if not 0.0 < target < 1.0:
+        raise ValueError(f"adapt_target must lie in (0, 1), got {adapt_target!r}")
+    if not gain > 0.0:
+        raise ValueError(f"adapt_gain must be positive, got {adapt_gain!r}")
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f"adapt_decay must lie in 0..1, got {adapt_decay!r}")
+    try:
+        lo, hi = adapt_scale_bounds
+    except (TypeError, ValueError):
+        raise ValueError("adapt_scale_bounds must be a pair (lo, hi) of factors on the initial scales") from None
+    lo, hi = number("adapt_scale_bounds lo", lo), number("adapt_scale_bounds hi", hi)
+    if not 0.0 < lo <= hi:
+        raise ValueError(f"adapt_scale_bounds must satisfy 0 < lo <= hi, got {adapt_scale_bounds!r}")
+    if adapt_sync is not None and not callable(adapt_sync):
+        raise ValueError("adapt_sync must be None or a callable applied to the pooled [n_temps + 1] int64 tensor")
+    windows = int(adapt_until) // int(adapt_every)
+    if windows == 0:
+        warnings.warn(f"adapt_scale=True but no window of adapt_every = {adapt_every} steps ends within the first "
+                      f"{adapt_until} burn-in steps: nothing will adapt")
+    return {"every": int(adapt_every), "until": int(adapt_until), "target": target, "gain": gain, "decay": decay,
+            "bounds": (lo, hi), "sync": adapt_sync, "windows": windows}
+
+
 def check_init_attempts(init_attempts) -> int:
     if isinstance(init_attempts, bool) or not isinstance(init_attempts, (int, np.integer)) or not 1 <= init_attempts <= 65535:
         raise ValueError(f"init_attempts must be an integer in 1..65535, got {init_attempts!r}")
@@ -191,7 +245,11 @@ class EngineRun:
                  dtype: torch.dtype = torch.float32, moments_temps: int = 0, moments_every: int = 1,
                  moments_per_chain: bool = False, init_box=None, init_per_temperature: bool = False,
                  init_attempts: int = 8, flow: bool = False, hist_temps: int = 0, hist_every: int = 1, hist_bins: int = 64,
-                 hist_range=None):
+                 hist_range=None, adapt_scale: bool = False, adapt_every: int = 50, adapt_until: Optional[int] = None,
+                 adapt_target: float = 0.234, adapt_gain: float = 3.0, adapt_decay: float = 0.5,
+                 adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None):
+        adapt = check_adapt_args(adapt_scale, max(0, int(burn_in)), adapt_every, adapt_until, adapt_target, adapt_gain,
+                                 adapt_decay, adapt_scale_bounds, adapt_sync)
         if swap_mode not in ptrwm_hip.SWAP_MODES:
             raise ValueError(f"swap_mode must be one of {sorted(ptrwm_hip.SWAP_MODES)}, got {swap_mode!r}")
         if swap_order not in ptrwm_hip.SWAP_ORDERS:
@@ -237,6 +295,10 @@ class EngineRun:
                                             or ptrwm_hip.has_quad_variant(self.target.kind, proposal.kind, dim, n_temps)):
             raise ValueError(f"no fused kernel for dim {dim} with a ladder of {n_temps} temperatures: above dim 64 a ladder "
                              "holds at most 128 temperatures (one 512-thread workgroup of the lane-split kernel)")
+        if adapt is not None:
+            # the run rewrites its scales in place: a copy of its own (engine_proposal() may hand out a view of the proposal
+            # object's tensors, which a reset() must find as they were)
+            proposal = ptrwm_hip.Proposal(proposal.kind, proposal.temp_scale.clone(), proposal.dim_scale, proposal.inv_dim)
         self.proposal = proposal
         self.dim, self.n_temps, self.n_replicas = dim, n_temps, n_replicas
         self.device = device
@@ -324,6 +386,28 @@ class EngineRun:
             self._hist_edges = hist_edges(lo, hi, self.hist_bins)
             self._plan.set_histogram(self._hist["counts"], self._hist["lo"], self._hist["scale"], n_bins=self.hist_bins,
                                      temps=self.hist_temps, every=self.hist_every, count=self._hist["count"])
+        # warm-up tuning of the proposal scale, per temperature, by two small kernels between launches (off: None)
+        self.init_scales = self.proposal.temp_scale.clone()
+        self._adapt = None
+        if adapt is not None:
+            K, W = adapt["windows"], adapt["every"]
+            # the bounds are factors on the initial scales; the library clamps every temperature to one range
+            tiny, huge = float(np.finfo(np.float32).tiny), float(np.finfo(np.float32).max)
+            lo = min(max(adapt["bounds"][0] * float(self.init_scales.min().item()), tiny), huge)
+            hi = min(max(adapt["bounds"][1] * float(self.init_scales.max().item()), lo), huge)
+            self._adapt = {**adapt, "min_scale": lo, "max_scale": hi, "end": K * W,
+                           "window_accept": torch.zeros(shape, device=device, dtype=torch.int64),
+                           "pooled": torch.zeros(n_temps + 1, device=device, dtype=torch.int64),
+                           "scale_history": torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
+                           "accept_history": torch.zeros(K, n_temps, device=device, dtype=torch.int64),
+                           # chain-steps behind every row of accept_history (with adapt_sync: of every shard, recorded)
+                           "count_history": torch.full((K,), 0 if adapt["sync"] is not None else n_replicas * W,
+                                                       device=device, dtype=torch.int64)}
+            self._adapt["scale_history"][0] = self.init_scales
+            self._plan.set_adaptation(self._adapt["window_accept"], self._adapt["pooled"], every=W, until=adapt["until"],
+                                      target=adapt["target"], gain=adapt["gain"], decay=adapt["decay"], min_scale=lo,
+                                      max_scale=hi, defer_update=adapt["sync"] is not None,
+                                      scale_history=self._adapt["scale_history"], accept_history=self._adapt["accept_history"])
         if box is not None:
             self._draw_starts(box, x0.to(torch.float32).contiguous(), bool(init_per_temperature), attempts)
 
@@ -374,12 +458,81 @@ class EngineRun:
         if self.density_fn is not None:
             self._advance_split(n_steps, trace, trace_logp, trace_row0, max(1, int(trace_every)))
             return
+        if self._adapt is not None and self._adapt["sync"] is not None and self.steps_done < self._adapt["end"]:
+            # adapt_sync: one launch per window (the library refuses to step past a pending update), the caller's
+            # all-reduce of `pooled` and the update in between; ordinary launches from the end of warm-up
+            W, end = self._adapt["every"], self._adapt["end"]
+            while n_steps > 0:
+                s = self.steps_done
+                n = min(n_steps, W - s % W) if s < end else n_steps
+                self._launch(n, trace, trace_logp, trace_row0, trace_every)
+                if trace is not None:
+                    trace_row0 += ptrwm_hip.periodic_steps_in(s, s + n, max(1, int(trace_every)))
+                if s < end and (s + n) % W == 0:
+                    self._adapt_window_end((s + n) // W - 1, reduce=False)
+                n_steps -= n
+            return
+        self._launch(n_steps, trace, trace_logp, trace_row0, trace_every)
+
+    def _launch(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> None:
         if trace is None and trace_logp is None:
             self._plan.launch(self.steps_done, n_steps, swap_event_offset=self.manual_sweeps)
         else:
             self._plan.launch(self.steps_done, n_steps, trace=trace, trace_logp=trace_logp, trace_row0=trace_row0,
                               trace_every=trace_every, swap_event_offset=self.manual_sweeps)
         self.steps_done += n_steps
+
+    def _adapt_window_end(self, window: int, reduce: bool) -> None:
+        """What follows the last step of adapting window `window` where the library does not do it itself (split steps; with
+        adapt_sync the update): the reduce kernel, the caller's all-reduce of `pooled`, the update kernel."""
+        ad = self._adapt
+        if reduce:
+            self._plan.adapt_reduce()
+        if ad["sync"] is not None:
+            ad["sync"](ad["pooled"])
+            ad["count_history"][window] = ad["pooled"][self.n_temps]
+        self._plan.adapt_update(window)
+
+    # ---- warm-up tuning: read-outs -------------------------------------------------------------------------------
+    def proposal_scales(self) -> torch.Tensor:
+        """The current per-temperature proposal scales: float32 [n_temps] on the device (a copy)."""
+        return self.proposal.temp_scale.clone()
+
+    def adaptation_history(self) -> Optional[dict]:
+        """None when adaptation is off, else "scales" float32 [K + 1, n_temps] (row 0 the initial scales, row k + 1 those after
+        window k) and "acceptance" float64 [K, n_temps] (the pooled acceptance rate of window k, from the integer history);
+        rows of windows that have not run yet are NaN.  Device tensors."""
+        if self._adapt is None:
+            return None
+        ad = self._adapt
+        return {"scales": ad["scale_history"].clone(),
+                "acceptance": ad["accept_history"].double() / ad["count_history"].double()[:, None],
+                "accepted": ad["accept_history"].clone()}
+
+    def _advance_split_warmup(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> int:
+        """n_steps eager split steps inside adapting windows by the recipe of include/ptrwm.h (acceptances counted into the
+        window scratch, no swap event), the reduce and update kernels at window ends; returns the rows traced."""
+        C, T, D = self.n_replicas, self.n_temps, self.dim
+        W, row = self._adapt["every"], trace_row0
+        self._plan.split_warmup(True)
+        try:
+            for _ in range(n_steps):
+                s = self.steps_done
+                props = self._plan.split_propose(s)
+                lp_new = self._density(props.view(-1, D)).view(C, T)
+                self._plan.split_accept(s, lp_new, swap_event_offset=self.manual_sweeps)
+                self.steps_done += 1
+                if trace is not None and ptrwm_hip.periodic_steps_in(s, s + 1, trace_every):
+                    tc, tt = trace.shape[1], trace.shape[2]
+                    trace[row] = self.state[:tc, :tt]
+                    if trace_logp is not None:
+                        trace_logp[row] = self.logp[:tc, :tt]
+                    row += 1
+                if (s + 1) % W == 0:
+                    self._adapt_window_end((s + 1) // W - 1, reduce=True)
+        finally:
+            self._plan.split_warmup(False)
+        return row - trace_row0
 
     # ---- split steps through a captured HIP graph ------------------------------------------------------------
     # A split step is four launches of this library (proposal, Metropolis rule, swap event, step counter) around the
@@ -475,6 +628,12 @@ class EngineRun:
 
     def _advance_split(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> None:
         """n_steps split steps; traced steps (step_counter a multiple of trace_every) are copied with torch."""
+        if self._adapt is not None and self.steps_done < self._adapt["end"]:
+            k = min(n_steps, self._adapt["end"] - self.steps_done)
+            trace_row0 += self._advance_split_warmup(k, trace, trace_logp, trace_row0, trace_every)
+            n_steps -= k
+            if n_steps == 0:
+                return
         if trace is None and n_steps >= 2 and self.use_graph and self._advance_split_graph(n_steps):
             return
         C, T, D = self.n_replicas, self.n_temps, self.dim
@@ -905,3 +1064,48 @@ class MarginalHistograms:
         c = run.histogram()["counts"]
         total = int(c.sum().item())
         return {"hist_out_of_range": (int(c[..., 0].sum().item()) + int(c[..., -1].sum().item())) / total if total else float("nan")}
+
+
+# ---- warm-up tuning of the proposal scale in the drop-in classes ----------------------------------------------------------
+class ScaleAdaptation:
+    """Readers of the per-temperature proposal scales and of their warm-up tuning (include/ptrwm.h ptrwm_adapt_args).  The
+    host class calls `_check_adapt_ctor` in its constructor, passes `_adapt_kwargs()` to EngineRun, owns `_run` and defines
+    `_initial_proposal()` (the engine proposal a fresh run starts from).  Every read synchronises."""
+
+    def _check_adapt_ctor(self, burn_in: int, adapt_scale, **kw) -> None:
+        """The constructor's adaptation arguments, checked before anything is built (no GPU needed)."""
+        self._adapt_args = check_adapt_args(adapt_scale, max(0, int(burn_in)), **kw)
+        self._adapt_kw = {"adapt_scale": bool(adapt_scale), **kw} if self._adapt_args is not None else {}
+
+    def _adapt_kwargs(self) -> dict:
+        """EngineRun's adaptation arguments."""
+        return dict(self._adapt_kw)
+
+    def _init_scales(self) -> torch.Tensor:
+        run = getattr(self, "_run", None)
+        return (run.init_scales if run is not None else self._initial_proposal().temp_scale).clone()
+
+    def proposal_scales(self) -> torch.Tensor:
+        """The current proposal scale of every temperature: float32 [T] on the device (the initial scales before the first
+        step and after reset(); the tuned ones once warm-up has run)."""
+        run = getattr(self, "_run", None)
+        return run.proposal_scales() if run is not None else self._init_scales()
+
+    def adaptation_history(self) -> dict:
+        """{"scales": float32 [K + 1, T], "acceptance": float64 [K, T]} of the K = adapt_until // adapt_every adaptation
+        windows: row 0 of scales the initial scales, row k + 1 those after window k; acceptance the pooled acceptance rate of
+        window k (from the integer counts).  Rows of windows that have not run yet are NaN.  Device tensors."""
+        if getattr(self, "_adapt_args", None) is None:
+            raise RuntimeError("adaptation is off: construct the sampler with adapt_scale=True")
+        run = getattr(self, "_run", None)
+        if run is not None:
+            h = run.adaptation_history()
+            return {"scales": h["scales"], "acceptance": h["acceptance"]}
+        init = self._init_scales()
+        K, T = self._adapt_args["windows"], init.numel()
+        scales = torch.full((K + 1, T), float("nan"), device=init.device, dtype=torch.float32)
+        scales[0] = init
+        return {"scales": scales, "acceptance": torch.full((K, T), float("nan"), device=init.device, dtype=torch.float64)}
+
+    def _adapt_diagnostics(self) -> dict:
+        return {"adapted_scales": self.proposal_scales().cpu().tolist(), "init_scales": self._init_scales().cpu().tolist()}

@@ -32,7 +32,8 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import EngineRun, MarginalHistograms, PosteriorMoments, check_class_starts, moments_temps, resolve_device
+from ._engine_core import (EngineRun, MarginalHistograms, PosteriorMoments, ScaleAdaptation, check_class_starts, moments_temps,
+                           resolve_device)
 from .sharding import flow_round_trip_rate, flow_up_fraction
 
 
@@ -46,7 +47,7 @@ def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
     return [float(beta_min ** (t / (n_temps - 1))) for t in range(n_temps)]
 
 
-class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, MHAlgorithm):
+class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, ScaleAdaptation, MHAlgorithm):
     def __init__(self, dim: int, var: float, target_dist=None, symmetric: bool = True, beta_ladder: list = None,
                  iterative_temp_spacing: bool = False, geom_temp_spacing: bool = False,
                  swap_acceptance_rate: float = 0.234, beta_min_iterative: float = 0.01, N_samples_swap_est: int = 3000,
@@ -60,8 +61,18 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, M
                  chain_offset: int = 0, trace: str = "all", thin: int = 1, moments: Optional[str] = None,
                  moments_every: int = 1, moments_per_chain: bool = False, initial_states=None, init_box=None,
                  init_per_temperature: bool = False, init_attempts: int = 8, flow: bool = False,
-                 hist: Optional[str] = None, hist_range=None, hist_bins: int = 64, hist_every: int = 1):
+                 hist: Optional[str] = None, hist_range=None, hist_bins: int = 64, hist_every: int = 1,
+                 adapt_scale: bool = False, adapt_every: int = 50, adapt_until: Optional[int] = None,
+                 adapt_target: float = 0.234, adapt_gain: float = 3.0, adapt_decay: float = 0.5,
+                 adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None):
         super().__init__(dim, var, target_dist, symmetric)
+        # warm-up tuning of the proposal scale per temperature (include/ptrwm.h ptrwm_adapt_args): adapt_scale=True tunes towards
+        # adapt_target in windows of adapt_every steps up to adapt_until (default: all of burn-in); adapt_scale_bounds are factors
+        # on the initial scales; adapt_sync, a callable applied to the pooled [T + 1] counts at every window end, makes shards
+        # of one run adapt together (algorithms.sharding.adaptation_sync)
+        self._check_adapt_ctor(burn_in, adapt_scale, adapt_every=adapt_every, adapt_until=adapt_until, adapt_target=adapt_target,
+                               adapt_gain=adapt_gain, adapt_decay=adapt_decay, adapt_scale_bounds=adapt_scale_bounds,
+                               adapt_sync=adapt_sync)
         # pooled marginal histograms over every replica (include/ptrwm.h ptrwm_hist_args): hist='cold' or 'all' temperatures,
         # hist_range=(lo, hi) the range of the hist_bins bins, a snapshot every hist_every-th step past burn-in
         self._check_hist_ctor(dim, hist, hist_range, hist_bins, hist_every)
@@ -257,7 +268,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, M
             swap_mode=self._swap_mode, swap_order=self._swap_order, seed=self._seed, chain_offset=self._chain_offset,
             dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, flow=self._flow_on,
-            **self._hist_kwargs(len(self.beta_ladder)))
+            **self._hist_kwargs(len(self.beta_ladder)), **self._adapt_kwargs())
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
         self.current_log_densities = self._run.logp[0] if self.num_replicas == 1 else self._run.logp
@@ -266,6 +277,9 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, M
             self._trace[0, 0] = self._run.state[0, :nt]
             self._trace_logp[0, 0] = self._run.logp[0, :nt]
             self._rows_used = 1
+
+    def _initial_proposal(self):
+        return self.proposal_dist.engine_proposal(self.beta_ladder)
 
     def _advance(self, n_steps: int):
         self._ensure_started()
@@ -491,6 +505,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, M
             **self._moments_diagnostics(),
             **self._flow_diagnostics(),
             **self._hist_diagnostics(),
+            **self._adapt_diagnostics(),
         }
 
     def performance_summary(self):

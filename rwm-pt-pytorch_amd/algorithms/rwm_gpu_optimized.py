@@ -22,7 +22,8 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import EngineRun, MarginalHistograms, PosteriorMoments, check_class_starts, moments_temps, resolve_device
+from ._engine_core import (EngineRun, MarginalHistograms, PosteriorMoments, ScaleAdaptation, check_class_starts, moments_temps,
+                           resolve_device)
 
 
 def ultra_fused_mcmc_step_basic(current_state, current_log_density, increment, random_val, beta, log_density_proposed):
@@ -52,15 +53,25 @@ def _rebuild_proposal(p: ProposalDistribution, dim, beta, device, dtype, rng):
     )
 
 
-class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, MHAlgorithm):
+class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, ScaleAdaptation, MHAlgorithm):
     def __init__(self, dim: int, var: float = None, target_dist=None, symmetric: bool = True, beta: float = 1.0,
                  burn_in: int = 0, device: str = None, pre_allocate_steps: int = None, use_efficient_rng: bool = True,
                  compile_mode: str = None, proposal_distribution: ProposalDistribution = None, *,
                  num_chains: int = 1, seed: Optional[int] = None, chain_offset: int = 0, thin: int = 1,
                  moments: Optional[str] = None, moments_every: int = 1, moments_per_chain: bool = False,
                  initial_states=None, init_box=None, init_attempts: int = 8, hist: Optional[str] = None, hist_range=None,
-                 hist_bins: int = 64, hist_every: int = 1):
+                 hist_bins: int = 64, hist_every: int = 1, adapt_scale: bool = False, adapt_every: int = 50,
+                 adapt_until: Optional[int] = None,
+                 adapt_target: float = 0.234, adapt_gain: float = 3.0, adapt_decay: float = 0.5,
+                 adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None):
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
+        # warm-up tuning of the proposal scale per temperature (include/ptrwm.h ptrwm_adapt_args): adapt_scale=True tunes towards
+        # adapt_target in windows of adapt_every steps up to adapt_until (default: all of burn-in); adapt_scale_bounds are factors
+        # on the initial scales; adapt_sync, a callable applied to the pooled [T + 1] counts at every window end, makes shards
+        # of one run adapt together (algorithms.sharding.adaptation_sync)
+        self._check_adapt_ctor(burn_in, adapt_scale, adapt_every=adapt_every, adapt_until=adapt_until, adapt_target=adapt_target,
+                               adapt_gain=adapt_gain, adapt_decay=adapt_decay, adapt_scale_bounds=adapt_scale_bounds,
+                               adapt_sync=adapt_sync)
         # pooled marginal histograms over every chain (include/ptrwm.h ptrwm_hist_args): hist='cold' (= 'all' here: one
         # temperature), hist_range=(lo, hi) the range of the hist_bins bins, a snapshot every hist_every-th step past burn-in
         self._check_hist_ctor(dim, hist, hist_range, hist_bins, hist_every)
@@ -177,7 +188,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, MHAlgorit
             burn_in=self.burn_in, swap_every=1, swap_mode="exchange", swap_order="sequential", seed=self._seed,
             chain_offset=self._chain_offset, moments_temps=moments_temps(self._moments_mode, 1, self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, init_box=self._init_box,
-            init_attempts=self._init_attempts, **self._hist_kwargs(1),
+            init_attempts=self._init_attempts, **self._hist_kwargs(1), **self._adapt_kwargs(),
         )
         self.current_state = self._run.state[0, 0]  # views: always the live values
         self.current_states = self._run.state[:, 0]
@@ -188,6 +199,9 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, MHAlgorit
             self.pre_allocated_chain[0] = self.current_state
             self.pre_allocated_log_densities[0] = self.log_target_density_current
             self.chain_index = 1
+
+    def _initial_proposal(self):
+        return self.proposal_dist.engine_proposal()
 
     def _advance(self, n_steps: int):
         """n_steps fused MH steps; chain 0's states go to the pre-allocated chain or the Python list."""
@@ -269,6 +283,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, MHAlgorit
             "random_generation": "Philox4x32-10 in-kernel (no precomputed random tensors)",
             **self._moments_diagnostics(),
             **self._hist_diagnostics(),
+            **self._adapt_diagnostics(),
         }
 
     def performance_comparison_summary(self):

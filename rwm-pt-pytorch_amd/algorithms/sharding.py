@@ -175,3 +175,17 @@ def allreduce_histogram(sampler, group: Optional[dist.ProcessGroup] = None) -> d
         dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=group)
     n = counts.numel()
     return {"counts": vec[:n].view(counts.shape), "count": vec[n:].view(count.shape), "edges": h.get("edges")}
+
+
+# ---- warm-up tuning of the proposal scale (include/ptrwm.h ptrwm_adapt_args) ---------------------------------------------------
+def adaptation_sync(group: Optional[dist.ProcessGroup] = None):
+    """The `adapt_sync=` callable of a sharded run: all-reduces (SUM) the pooled [n_temps + 1] int64 counts of a window in place,
+    over `group`.  Every rank then applies the same update to the same integers, so a sharded run adapts - and samples - exactly
+    as the unsharded one.  Without an initialised process group the counts are left as they are (one shard)."""
+
+    def sync(pooled: torch.Tensor) -> torch.Tensor:
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(pooled, op=dist.ReduceOp.SUM, group=group)
+        return pooled
+
+    return sync

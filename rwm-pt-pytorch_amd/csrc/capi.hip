@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "../../include/ptrwm.h"
+#include "adapt.h"
 #include "hist.h"
 #include "schedule.h"
 #include "variants.h"
@@ -766,6 +767,109 @@ __global__ void __launch_bounds__(256) hist_snapshot_kernel(HistSnapArgs a) {
     for (int t = tid; t < a.temps; t += 256) count_add(&a.count[t], c1 - c0);
 }
 
+// ---- warm-up tuning of the proposal scale (adapt.h; include/ptrwm.h ptrwm_adapt_args) ---------------------------------------
+// Two small kernels between launches, as the histogram's snapshot: the step kernels are told nothing.  A launch inside an
+// adapting window adds its acceptances to window_accept [n_chains, n_temps]; at the window's end adapt_reduce_kernel sums
+// that scratch over chains into pooled[t], adds the window's chain-steps to pooled[n_temps] and leaves the scratch zero;
+// adapt_update_kernel then applies adapt.h's rule to temp_scale, which the next launch reads when it starts.
+//
+// Reduce: a workgroup takes a tile of whole chains, about kAdaptTileElems elements - one contiguous run of the scratch that
+// starts at a chain, so element e of the tile belongs to temperature e % n_temps whatever n_temps is.  The run is read and
+// zeroed in 16-byte vectors (two counters; an element in front of the first 16-byte boundary and one behind the last vector
+// are taken on their own).  A thread keeps the sum of a temperature in a register for as long as its elements stay on it
+// (its stride is 512 elements: for ever where n_temps divides 512) and adds it to the workgroup's 64-bit LDS counter of
+// that temperature when they move on; one 64-bit global atomic per non-zero (workgroup, temperature) flushes.  All integer:
+// exact, whatever the order.
+constexpr int kAdaptTileElems = 4096;
+struct AdaptReduceArgs {
+  long long *window_accept;  // [n_chains, n_temps]
+  long long *pooled;         // [n_temps + 1]
+  long long n_chains, every;
+  int n_temps, tile_chains;  // tile_chains = max(1, kAdaptTileElems / n_temps)
+};
+inline int adapt_tile_chains(int n_temps) { return kAdaptTileElems / n_temps > 1 ? kAdaptTileElems / n_temps : 1; }
+
+__global__ void __launch_bounds__(256) adapt_reduce_kernel(AdaptReduceArgs a) {
+  typedef long long ll2 __attribute__((ext_vector_type(2)));
+  __shared__ unsigned long long s_sum[PTRWM_MAX_TEMPS];
+  const int tid = (int)threadIdx.x, T = a.n_temps;
+  for (int t = tid; t < T; t += 256) s_sum[t] = 0ull;
+  __syncthreads();
+  const long long c0 = (long long)blockIdx.x * a.tile_chains;
+  const long long c1 = (a.n_chains - c0 < a.tile_chains) ? a.n_chains : c0 + a.tile_chains;
+  const int n = (int)((c1 - c0) * T);  // the tile's elements (1 .. tile_chains * n_temps <= kAdaptTileElems)
+  long long *const p = a.window_accept + c0 * T;
+  const int head = (reinterpret_cast<uintptr_t>(p) & 15u) != 0 ? 1 : 0;  // (counters are 8-byte aligned)
+  const int n_vec = (n - head) / 2;
+  const auto add = [&](int t, long long v) {
+    if (v != 0) atomicAdd(&s_sum[t], (unsigned long long)v);
+  };
+  ll2 *const pv = reinterpret_cast<ll2 *>(p + head);
+  int cur0 = 0, cur1 = 0;
+  long long acc0 = 0, acc1 = 0;
+  for (int v = tid; v < n_vec; v += 256) {
+    const ll2 x = pv[v];
+    pv[v] = ll2{0ll, 0ll};
+    const int t0 = (head + 2 * v) % T;
+    const int t1 = t0 + 1 == T ? 0 : t0 + 1;
+    if (t0 != cur0) add(cur0, acc0), cur0 = t0, acc0 = 0;
+    if (t1 != cur1) add(cur1, acc1), cur1 = t1, acc1 = 0;
+    acc0 += x.x;
+    acc1 += x.y;
+  }
+  add(cur0, acc0);
+  add(cur1, acc1);
+  if (tid == 0 && head != 0) {  // the element in front of the vectors: the tile's first, temperature 0
+    add(0, p[0]);
+    p[0] = 0;
+  }
+  const int tail = head + 2 * n_vec;  // the element behind them, if any
+  if (tid == 64 && tail < n) {
+    add(tail % T, p[tail]);
+    p[tail] = 0;
+  }
+  __syncthreads();
+  for (int t = tid; t < T; t += 256) {
+    const unsigned long long v = s_sum[t];
+    if (v != 0ull) count_add(&a.pooled[t], (long long)v);
+  }
+  if (tid == 0) count_add(&a.pooled[T], (c1 - c0) * a.every);
+}
+
+// Update: one workgroup, thread t < n_temps.  Every thread reads what it needs of `pooled` before any of it is zeroed.
+struct AdaptUpdateArgs {
+  float *temp_scale;          // [n_temps] in/out
+  long long *pooled;          // [n_temps + 1], zeroed
+  float *scale_history;       // [K + 1, n_temps] or NULL
+  long long *accept_history;  // [K, n_temps] or NULL
+  long long window;           // k (0 <= k < K: checked on the host)
+  double gain_k, target;
+  float min_scale, max_scale;
+  int n_temps;
+};
+
+__global__ void __launch_bounds__(256) adapt_update_kernel(AdaptUpdateArgs a) {
+  const int t = (int)threadIdx.x, T = a.n_temps;
+  long long accepted = 0, counted = 0;
+  if (t < T) {
+    accepted = a.pooled[t];
+    counted = a.pooled[T];
+  }
+  __syncthreads();
+  if (t < T) {
+    const float s_old = a.temp_scale[t];
+    const float s_new = adapt_update(s_old, accepted, counted, a.gain_k, a.target, a.min_scale, a.max_scale);
+    a.temp_scale[t] = s_new;
+    if (a.scale_history != nullptr) {
+      if (a.window == 0) a.scale_history[t] = s_old;
+      a.scale_history[(a.window + 1) * T + t] = s_new;
+    }
+    if (a.accept_history != nullptr) a.accept_history[a.window * T + t] = accepted;
+    a.pooled[t] = 0;
+  }
+  if (t == 0) a.pooled[T] = 0;
+}
+
 // Starting points (ptrwm_init_states): row (c, t) of `state` drawn uniformly from the box [lo, hi], or set to `fallback`.
 // The draw is Philox stream kStreamInit (rng_layout.h: the counter layout; include/ptrwm.h restates it), keyed by the GLOBAL chain
 // id like every other random of a run, so the starts do not depend on how chains are sharded over devices.
@@ -918,8 +1022,57 @@ static int32_t launch_hist(const ptrwm_run_args *args, int32_t dim, const ptrwm_
   return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 
+// the adaptation checks shared by ptrwm_run_with_adaptation, ptrwm_adapt_reduce and ptrwm_adapt_update (none: ok); what
+// needs the run (until <= burn_in, temp_scale == proposal->temp_scale) is checked by ptrwm_run_with_adaptation itself
+static int32_t check_adapt(const ptrwm_adapt_args *ad) {
+  if (ad == nullptr) return PTRWM_OK;
+  if (ad->struct_size != sizeof(ptrwm_adapt_args)) return PTRWM_E_STRUCT;
+  if (ad->temp_scale == nullptr || ad->window_accept == nullptr || ad->pooled == nullptr) return PTRWM_E_NULL;
+  if (ad->every < 1 || ad->until < 0) return PTRWM_E_ARG;
+  if (!(ad->target > 0.0f && ad->target < 1.0f)) return PTRWM_E_ARG;
+  if (!(ad->gain > 0.0f) || !std::isfinite(ad->gain)) return PTRWM_E_ARG;
+  if (!(ad->decay >= 0.0f && ad->decay <= 1.0f)) return PTRWM_E_ARG;
+  if (!(ad->min_scale > 0.0f && ad->min_scale <= ad->max_scale) || !std::isfinite(ad->max_scale)) return PTRWM_E_ARG;
+  if (!is_flag(ad->defer_update)) return PTRWM_E_ARG;
+  return PTRWM_OK;
+}
+
+// the window scratch of n_chains x n_temps summed into pooled and zeroed; everything checked, n_chains >= 1
+static int32_t launch_adapt_reduce(const ptrwm_adapt_args *ad, long long n_chains, int n_temps, hipStream_t stream) {
+  AdaptReduceArgs a;
+  a.window_accept = (long long *)ad->window_accept;
+  a.pooled = (long long *)ad->pooled;
+  a.n_chains = n_chains;
+  a.every = ad->every;
+  a.n_temps = n_temps;
+  a.tile_chains = adapt_tile_chains(n_temps);
+  const long long blocks = (n_chains + a.tile_chains - 1) / a.tile_chains;
+  if (blocks > 0x7fffffffll) return PTRWM_E_ARG;
+  hipLaunchKernelGGL(adapt_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}
+
+// the update of window k (0 <= k < K); everything checked
+static int32_t launch_adapt_update(const ptrwm_adapt_args *ad, int n_temps, long long window, hipStream_t stream) {
+  AdaptUpdateArgs a;
+  a.temp_scale = ad->temp_scale;
+  a.pooled = (long long *)ad->pooled;
+  a.scale_history = ad->scale_history;
+  a.accept_history = (long long *)ad->accept_history;
+  a.window = window;
+  a.gain_k = adapt_gain((double)ad->gain, (double)ad->decay, window);
+  a.target = (double)ad->target;
+  a.min_scale = ad->min_scale;
+  a.max_scale = ad->max_scale;
+  a.n_temps = n_temps;
+  hipLaunchKernelGGL(adapt_update_kernel, dim3(1), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}
+static_assert(PTRWM_MAX_TEMPS <= 256, "adapt_update_kernel: one thread per temperature in one 256-thread workgroup");
+
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist = nullptr);
+                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist = nullptr,
+                        const ptrwm_adapt_args *adapt = nullptr);
 static int32_t swap_sweep_impl(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
                                const ptrwm_flow_args *flow, void *stream);
 static int32_t split_accept_impl(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
@@ -1051,6 +1204,32 @@ int32_t ptrwm_run_with_histogram(const ptrwm_target_desc *target, const ptrwm_pr
   return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist);
 }
 
+int32_t ptrwm_run_with_adaptation(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                                  const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
+                                  const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt,
+                                  void *stream) {
+  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // (as ptrwm_run_with_diagnostics)
+  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist, adapt);
+}
+
+int32_t ptrwm_adapt_reduce(const ptrwm_run_args *args, const ptrwm_adapt_args *adapt, void *stream) {
+  if (args == nullptr || adapt == nullptr) return PTRWM_E_NULL;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
+  if (args->n_chains < 0) return PTRWM_E_ARG;
+  if (int rc = check_adapt(adapt)) return rc;
+  if (args->n_chains == 0) return PTRWM_OK;
+  return launch_adapt_reduce(adapt, args->n_chains, args->n_temps, (hipStream_t)stream);
+}
+
+int32_t ptrwm_adapt_update(const ptrwm_adapt_args *adapt, int32_t n_temps, int64_t window, void *stream) {
+  if (adapt == nullptr) return PTRWM_E_NULL;
+  if (!temps_in_range(n_temps)) return PTRWM_E_TEMPS;
+  if (int rc = check_adapt(adapt)) return rc;
+  if (window < 0 || window >= adapt_window_count(adapt->every, adapt->until)) return PTRWM_E_ARG;  // (the histories have K rows)
+  return launch_adapt_update(adapt, n_temps, window, (hipStream_t)stream);
+}
+
 int32_t ptrwm_histogram(const ptrwm_run_args *args, int32_t dim, const ptrwm_hist_args *hist, void *stream) {
   if (args == nullptr || hist == nullptr) return PTRWM_E_NULL;
   if (!has_abi_size(args)) return PTRWM_E_STRUCT;
@@ -1140,7 +1319,7 @@ static unsigned moments_lds_bytes(const FormShape &f, int n_temps, int dim, int 
 }
 
 static RunChoice choose_kernel(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                               const MomSpec &spec, bool flow, hipStream_t stream) {
+                               const MomSpec &spec, bool flow, hipStream_t stream, bool allow_stream = true) {
   RunChoice c{};
   auto refuse = [&c](int32_t status) {
     c.status = status;
@@ -1195,7 +1374,7 @@ static RunChoice choose_kernel(const ptrwm_target_desc *target, const ptrwm_prop
   const bool full = args->ext_prop != nullptr || args->trace != nullptr || args->accept_flags != nullptr || spec.m != nullptr || flow;
   // the streaming form for short launches of the one-thread-per-replica kernel (see kStreamMaxSteps above)
   bool streaming = false;
-  if (!c.shape.quad && !full && has_stream_variant(kWidths[dpi].dp, kWidths[dpi].exact) && stream_layout_ok(args, dim, c.shape.ladders_per_group)) {
+  if (allow_stream && !c.shape.quad && !full && has_stream_variant(kWidths[dpi].dp, kWidths[dpi].exact) && stream_layout_ok(args, dim, c.shape.ladders_per_group)) {
     const int mode = __atomic_load_n(&g_stream_mode, __ATOMIC_RELAXED);
     if (mode == PTRWM_STREAM_ON) {
       streaming = true;
@@ -1263,11 +1442,23 @@ static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_de
 }
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist) {
+                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist,
+                        const ptrwm_adapt_args *adapt) {
   bool empty = false;
   if (int rc = check_run(target, proposal, args, spec, flow, hist, &empty)) return rc;
+  // adaptation (adapt.h): its own checks after the existing ones, all before anything is enqueued
+  if (int rc = check_adapt(adapt)) return rc;
+  if (adapt != nullptr) {
+    if (adapt->until > args->burn_in || adapt->temp_scale != proposal->temp_scale) return PTRWM_E_ARG;
+    // defer_update: the caller applies the update between requests, so none may step past a window end that awaits it
+    if (adapt->defer_update == 1 && !adapt_request_within_window(args->step0, args->n_steps, adapt->every, adapt->until))
+      return PTRWM_E_ARG;
+  }
   if (empty) return PTRWM_OK;
-  const RunChoice c = choose_kernel(target, proposal, args, spec, flow != nullptr, (hipStream_t)hip_stream);
+  // (a request that touches an adapting window keeps to the classic kernels: the streaming form prefetches the counters
+  // it adds to, and a warm-up launch has no squared-jump sum)
+  const bool adapts = adapt != nullptr && adapt_step_adapts(args->step0, adapt->every, adapt->until);
+  const RunChoice c = choose_kernel(target, proposal, args, spec, flow != nullptr, (hipStream_t)hip_stream, !adapts);
   if (c.status != PTRWM_OK) return c.status;
   KArgs k = fill_kargs(target, proposal, args, spec, flow, c);
   t_last_launch_kind = c.shape.quad ? PTRWM_LAUNCH_QUAD : (c.mode == kRunStream ? PTRWM_LAUNCH_STREAM : PTRWM_LAUNCH_THREAD);
@@ -1285,12 +1476,20 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   for (long long done = 0; done < args->n_steps; done += k.n_steps) {
     // (histograms: a launch also ends at every due snapshot step - the snapshot kernel reads the state between launches)
     const long long to_snap = hist != nullptr ? steps_to_next_due(args->step0 + done, args->burn_in, hist->every) : cap;
-    const LaunchCut cut = launch_at(req, done, to_snap < cap ? to_snap : cap);
+    // (adaptation: a launch inside an adapting window ends with the window at the latest - the reduce and update kernels
+    // run between two launches - and is the production kernel told to count from its first step, into the window scratch,
+    // and that no multiple of swap_every lies in it: count_on holds and swap_due never does, kernel.h)
+    const AdaptCut ac = adapt != nullptr ? adapt_cut_at(args->step0 + done, adapt->every, adapt->until) : AdaptCut{false, 0, 0};
+    long long lim = to_snap < cap ? to_snap : cap;
+    if (ac.adapting && ac.to_end < lim) lim = ac.to_end;
+    const LaunchCut cut = launch_at(req, done, lim);
     k.step0 = cut.step0;
     k.n_steps = cut.n;
-    k.burn_left = cut.burn_left;
+    k.burn_left = ac.adapting ? 0 : cut.burn_left;
     k.first_swap_event = cut.first_swap_event;
-    k.steps_to_swap = cut.steps_to_swap;
+    k.steps_to_swap = ac.adapting ? kNoStepInLaunch : cut.steps_to_swap;
+    k.n_accept = ac.adapting ? (long long *)adapt->window_accept : (long long *)args->n_accept;
+    k.sq_jump = ac.adapting ? nullptr : args->sq_jump;
     k.full.ext_prop = ext ? args->ext_prop + done * reps * raw * (args->state_f64 == 1 ? 2 : 1) : nullptr;  // (f64: a double array)
     k.full.ext_u = ext ? args->ext_u + done * reps : nullptr;
     k.full.ext_swap_u = (ext && args->ext_swap_u != nullptr) ? args->ext_swap_u + cut.events_before * args->n_chains * (args->n_temps - 1) : nullptr;
@@ -1306,6 +1505,11 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
     if (c.fn(k, c.n_blocks, c.mode, (hipStream_t)hip_stream) != hipSuccess) return PTRWM_E_LAUNCH;
     if (hist != nullptr && periodic_step_due(cut.step0 + cut.n, args->burn_in, hist->every))
       if (int rc = launch_hist(args, target->dim, hist, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
+    if (ac.adapting && adapt_launch_ends_window(cut.step0, cut.n, adapt->every)) {
+      if (int rc = launch_adapt_reduce(adapt, args->n_chains, args->n_temps, (hipStream_t)hip_stream)) return rc;
+      if (adapt->defer_update == 0)
+        if (int rc = launch_adapt_update(adapt, args->n_temps, ac.window, (hipStream_t)hip_stream)) return rc;
+    }
   }
   return PTRWM_OK;
 }

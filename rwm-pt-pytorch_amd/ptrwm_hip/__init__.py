@@ -169,6 +169,26 @@ class HistArgs(C.Structure):
 HIST_MAX_BINS = 1024
 
 
+class AdaptArgs(C.Structure):
+    """ptrwm_adapt_args: warm-up tuning of the per-temperature proposal scale (include/ptrwm.h, csrc/adapt.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("every", C.c_int32),
+        ("until", C.c_int64),
+        ("target", C.c_float),
+        ("gain", C.c_float),
+        ("decay", C.c_float),
+        ("min_scale", C.c_float),
+        ("max_scale", C.c_float),
+        ("defer_update", C.c_int32),
+        ("temp_scale", C.c_void_p),
+        ("window_accept", C.c_void_p),
+        ("pooled", C.c_void_p),
+        ("scale_history", C.c_void_p),
+        ("accept_history", C.c_void_p),
+    ]
+
+
 class InitArgs(C.Structure):
     """ptrwm_init_args: starting points drawn from a box, or set to a fallback point (include/ptrwm.h)."""
     _fields_ = [
@@ -217,6 +237,12 @@ SYMBOLS = {
         [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.POINTER(ChainMomentsArgs),
          C.POINTER(FlowArgs), C.POINTER(HistArgs), C.c_void_p]),
     "ptrwm_histogram": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(HistArgs), C.c_void_p]),
+    "ptrwm_run_with_adaptation": (
+        C.c_int32,
+        [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.POINTER(ChainMomentsArgs),
+         C.POINTER(FlowArgs), C.POINTER(HistArgs), C.POINTER(AdaptArgs), C.c_void_p]),
+    "ptrwm_adapt_reduce": (C.c_int32, [C.POINTER(RunArgs), C.POINTER(AdaptArgs), C.c_void_p]),
+    "ptrwm_adapt_update": (C.c_int32, [C.POINTER(AdaptArgs), C.c_int32, C.c_int64, C.c_void_p]),
     "ptrwm_swap_sweep_with_flow": (
         C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_int64, C.c_int32, C.POINTER(FlowArgs), C.c_void_p]),
     "ptrwm_split_accept_with_flow": (
@@ -624,6 +650,7 @@ class RunPlan:
         self._mom = None  # the accumulator, pooled or per chain: (kind of _MOMENT_KINDS, struct, byref, tensors)
         self._flow = None  # replica flow: (struct, byref, tensors)
         self._hist = None  # pooled marginal histograms: (struct, byref, tensors)
+        self._adapt = None  # warm-up tuning of the proposal scale: (struct, byref, tensors)
 
     # kind of accumulator -> (words of its messages, struct, entry point of launch(), entry point of split_moments())
     _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
@@ -747,6 +774,80 @@ class RunPlan:
         h.count = _opt(count, "histogram count", torch.int64)
         self._hist = (h, C.byref(h), (counts, lo, scale, count))
 
+    def set_adaptation(self, window_accept: Optional[torch.Tensor], pooled: Optional[torch.Tensor] = None, *, every: int = 50,
+                       until: int = 0, target: float = 0.234, gain: float = 3.0, decay: float = 0.5,
+                       min_scale: float = 1e-30, max_scale: float = 1e30, defer_update: bool = False,
+                       scale_history: Optional[torch.Tensor] = None, accept_history: Optional[torch.Tensor] = None) -> None:
+        """Tune the proposal scale of every temperature during burn-in (include/ptrwm.h ptrwm_adapt_args) in every following
+        ``launch``: the plan's own ``proposal.temp_scale`` is rewritten in place after every window of ``every`` steps that
+        ends at or before ``until`` (<= burn_in).  ``window_accept`` [n_chains, n_temps] int64 and ``pooled`` [n_temps + 1]
+        int64 are scratch, zero before the run; ``scale_history`` [K + 1, n_temps] float32 and ``accept_history``
+        [K, n_temps] int64 (K = until // every) are optional records.  ``defer_update``: ``launch`` stops at window ends and
+        the caller all-reduces ``pooled`` and calls ``adapt_update``.  ``set_adaptation(None)`` switches it off."""
+        if window_accept is None:
+            self._adapt = None
+            return
+        Cn, T, _ = self.shape
+        every, until = int(every), int(until)
+        if every < 1:
+            raise ValueError("adaptation every must be >= 1")
+        if not 0 <= until <= self._a.burn_in:
+            raise ValueError(f"adaptation until must be in 0..burn_in = {self._a.burn_in}, got {until}")
+        K = until // every
+        scale = self._keep[1].temp_scale
+        for name, t, shape in (("window_accept", window_accept, (Cn, T)), ("pooled", pooled, (T + 1,)),
+                               ("scale_history", scale_history, (K + 1, T)), ("accept_history", accept_history, (K, T))):
+            if t is None and name in ("scale_history", "accept_history"):
+                continue
+            if t is None or tuple(t.shape) != shape or t.device != self.device:
+                raise ValueError(f"adaptation {name} must be a {list(shape)} tensor on {self.device}")
+        ad = AdaptArgs()
+        ad.struct_size = C.sizeof(AdaptArgs)
+        ad.every, ad.until = every, until
+        ad.target, ad.gain, ad.decay = float(target), float(gain), float(decay)
+        ad.min_scale, ad.max_scale = float(min_scale), float(max_scale)
+        ad.defer_update = 1 if defer_update else 0
+        ad.temp_scale = _require_device(scale, "proposal.temp_scale", torch.float32)
+        ad.window_accept = _require_device(window_accept, "adaptation window_accept", torch.int64)
+        ad.pooled = _require_device(pooled, "adaptation pooled", torch.int64)
+        ad.scale_history = _opt(scale_history, "adaptation scale_history", torch.float32)
+        ad.accept_history = _opt(accept_history, "adaptation accept_history", torch.int64)
+        self._adapt = (ad, C.byref(ad), (scale, window_accept, pooled, scale_history, accept_history))
+
+    def adapt_reduce(self) -> None:
+        """The end of an adapting window, stand-alone (ptrwm_adapt_reduce): ``window_accept`` summed over chains into
+        ``pooled``, the scratch left zero.  ``launch`` does this itself; split steps and tests call it."""
+        if self._adapt is None:
+            raise RuntimeError("adapt_reduce: no adaptation set (set_adaptation)")
+        with self._guard:
+            rc = self._lib.ptrwm_adapt_reduce(self._refs[4], self._adapt[1], _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_adapt_reduce")
+
+    def adapt_update(self, window: int) -> None:
+        """The scale update of window ``window`` from ``pooled`` (ptrwm_adapt_update); ``pooled`` is left zero."""
+        if self._adapt is None:
+            raise RuntimeError("adapt_update: no adaptation set (set_adaptation)")
+        with self._guard:
+            rc = self._lib.ptrwm_adapt_update(self._adapt[1], self.shape[1], int(window), _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_adapt_update")
+
+    def split_warmup(self, on: bool) -> None:
+        """Split steps inside an adapting window (include/ptrwm.h, the split-step recipe): while on, split_accept counts every
+        step's acceptances into the adaptation's ``window_accept``, adds no squared jump and performs no swap event
+        (burn_in = 0, swap_every = INT32_MAX, sq_jump = NULL); off restores the plan's own arguments."""
+        a = self._a
+        if on:
+            if self._adapt is None:
+                raise RuntimeError("split_warmup: no adaptation set (set_adaptation)")
+            if getattr(self, "_warm_saved", None) is None:
+                self._warm_saved = (a.burn_in, a.swap_every, a.n_accept, a.sq_jump)
+            a.burn_in, a.swap_every, a.n_accept, a.sq_jump = 0, 2**31 - 1, self._adapt[0].window_accept, None
+        elif getattr(self, "_warm_saved", None) is not None:
+            a.burn_in, a.swap_every, a.n_accept, a.sq_jump = self._warm_saved
+            self._warm_saved = None
+
     def split_histogram(self, step: int) -> None:
         """Histogram snapshot of the state after the split step ``step`` just performed (ptrwm_histogram; device-step mode:
         counter + step - decided on the device, so the call can sit in a captured block).  Enqueue after ``split_accept``.
@@ -862,7 +963,15 @@ class RunPlan:
                 self._last_trace = (trace, trace_logp, trace_every)
         # ptrwm_run, or the accumulator's entry point with its struct in front of the stream
         name, mom = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
-        if self._flow is not None or self._hist is not None:  # flow or histograms bound: the entry points that take every diagnostic
+        if self._adapt is not None:  # adaptation bound: the entry point that takes everything
+            name = "ptrwm_run_with_adaptation"
+            pooled = self._mom[2] if self._mom is not None and self._mom[0] == "pooled" else None
+            chain = self._mom[2] if self._mom is not None and self._mom[0] == "chain" else None
+            flow = self._flow[1] if self._flow is not None else None
+            hist = self._hist[1] if self._hist is not None else None
+            with self._guard:
+                rc = self._lib.ptrwm_run_with_adaptation(self._refs[2], self._refs[3], self._refs[4], pooled, chain, flow, hist, self._adapt[1], _stream(self.device))
+        elif self._flow is not None or self._hist is not None:  # flow or histograms bound: the entry points that take every diagnostic
             name = "ptrwm_run_with_diagnostics" if self._hist is None else "ptrwm_run_with_histogram"
             pooled = self._mom[2] if self._mom is not None and self._mom[0] == "pooled" else None
             chain = self._mom[2] if self._mom is not None and self._mom[0] == "chain" else None
