@@ -100,6 +100,15 @@ struct StepLds : StepLdsWords {
   static constexpr int kHeadWaveWords = normal_blocks(DP) * kHeadBlockSlots * kHeadSlotWords;
   static constexpr bool kHeadsFit = !STREAM && kHeadWaveWords <= 64 * (DP + kSwapWords) && kWaveFloats % kHeadSlotWords == 0;
   static constexpr int heads(bool wide, int wave) { return wave * (wide ? kHeadWaveWords : kWaveFloats); }
+  // A swap event that leaves the parked heads alone (event_keeps_heads, below: one-wavefront groups whose sweep is decided by
+  // the walk) publishes its two arrays in words no head read uses, from the wave's base: the log-densities (s_l) in the 64
+  // words of landed[], which the walk never writes and which lie behind the heads; the thresholds / uniforms (s_u) in the
+  // spare fourth word of the slots of block 0, kKeptUStride words apart.  The rows travel through the lanes (ds_bpermute),
+  // so nothing else of the event touches LDS below the parked words.
+  static constexpr int kKeptL = s_l(64) + kLanded * 64;
+  static constexpr int kKeptU = kHeadSlotWords - 1, kKeptUStride = kHeadSlotWords;
+  static constexpr bool kKeptFit = kHeadsFit && kKeptL >= kHeadWaveWords && kKeptL + 64 <= parked(64) &&
+                                   kKeptU + 63 * kKeptUStride < kHeadBlockSlots * kHeadSlotWords && kKeptU % kHeadSlotWords == 3;
 };
 namespace lds_check {
 using C = StepLds<30>;
@@ -129,7 +138,11 @@ static_assert(C::kHeadsFit && C::kHeadWaveWords == 2048 && C::heads(false, 3) + 
                   C::heads(true, 3) + C::kHeadWaveWords <= C::parked(256) && C::heads(true, 1) + C::kHeadWaveWords <= C::parked(128) &&
                   !StepLds<8>::kHeadsFit && !S::kHeadsFit,
               "parked heads: 16-byte slots over the rows and the swap scratch of the wave's group, below the parked words; width 8 has no room");
-static_assert(0 < C::kFlowUp && C::kFlowUp < C::kFlowDown && C::kFlowDown < C::kFlowIntsPerThread && C::flow_bytes(256) == 4096u &&
+static_assert(C::kKeptFit && C::kKeptL == C::kHeadWaveWords && C::kKeptL + 64 == C::parked(64) && C::kKeptU == 3 && C::kKeptUStride == 4 &&
+                  !StepLds<8>::kKeptFit && !S::kKeptFit && C::bytes(256, false) == 38912u,
+              "an event that keeps the heads: log-densities in the landed[] words right behind the heads and below the parked words, "
+              "thresholds in the spare word of block 0's slots (a head read uses words 0..2); no byte more of LDS");
+static_assert(0 < C::kFlowUp &&C::kFlowUp < C::kFlowDown && C::kFlowDown < C::kFlowIntsPerThread && C::flow_bytes(256) == 4096u &&
                   C::flow_bytes(kBlockThreads) == (unsigned)kWavesPerBlock * 64u * C::kFlowIntsPerThread * 4u,
               "flow region: two word buffers, up visits, down visits, one region per group; nothing of it in a launch without flow");
 }  // namespace lds_check
@@ -411,9 +424,11 @@ __device__ __forceinline__ void swap_decide(int T, int t, int base, int slot, in
 // b_j+1, my_l, l_j+1)) instead - also a function of (carrier, j) alone.  The rule is chosen per LADDER: a wavefront with a
 // literal ladder anywhere runs the loop in which every lane selects its own ladder's answer (cold: corner cases only), and a
 // plain ladder's answers there are the compares of the fast loop.
+// SU: the stride of s_u in words (an event that keeps the parked heads publishes it in the spare word of 16-byte slots,
+// StepLds::kKeptU).
 // LEAN (the fixture twins, whose speed nobody measures): the one general loop only - the library's size budget
 // (tools/kernel_stats.py --size) has no room for a fast loop in every twin.
-template <bool LEAN, class Sync>
+template <bool LEAN, int SU = 1, class Sync>
 __device__ __forceinline__ void swap_walk_decide(int T, int t, int base, int slot, const float *__restrict__ beta, float db,
                                                  float us, const float *s_l, float *s_u, float &my_l, int &src, bool &pair_acc,
                                                  Sync sync, bool plain) {
@@ -421,11 +436,11 @@ __device__ __forceinline__ void swap_walk_decide(int T, int t, int base, int slo
   if (plain) {
     // own pair's threshold in place of its uniform (swap_decide)
     const float lk = s_l[has_k ? slot + 1 : slot];
-    s_u[slot] = fmaf(-hw_ln(us), __builtin_amdgcn_rcpf(db), lk);  // (the last position's: b_t - b_t = 0, read by no pair)
+    s_u[slot * SU] = fmaf(-hw_ln(us), __builtin_amdgcn_rcpf(db), lk);  // (the last position's: b_t - b_t = 0, read by no pair)
   }
   sync();
   const uint64_t seg0 = __builtin_amdgcn_ballot_w64(slot == base);  // (an idle lane's base is 0; lane 0 is never idle)
-  const float *const pair = s_u + base;  // pair j of this lane's ladder: one address, j an immediate offset
+  const float *const pair = s_u + base * SU;  // pair j of this lane's ladder: one address, j an immediate offset
   const bool all_plain = __builtin_amdgcn_ballot_w64(!plain) == 0ull;
   SwapWalk w = swap_walk_begin(seg0);
   int j = 0;
@@ -434,14 +449,14 @@ __device__ __forceinline__ void swap_walk_decide(int T, int t, int base, int slo
     // out: a ballot is a convergent operation, and the compiler unrolls no loop of a run-time trip count around one.)
     if (all_plain)
       for (; j + 2 <= T - 1; j += 2) {
-        swap_walk_step(w, seg0, j, __builtin_amdgcn_ballot_w64(my_l < pair[j]));
-        swap_walk_step(w, seg0, j + 1, __builtin_amdgcn_ballot_w64(my_l < pair[j + 1]));
+        swap_walk_step(w, seg0, j, __builtin_amdgcn_ballot_w64(my_l < pair[j * SU]));
+        swap_walk_step(w, seg0, j + 1, __builtin_amdgcn_ballot_w64(my_l < pair[(j + 1) * SU]));
       }
   }
   // the general loop: the fast loop's odd last pair; the whole sweep of a wavefront with a literal ladder, or of a LEAN kernel
 #pragma unroll 1
   for (; j < T - 1; ++j) {
-    const float v = pair[j];  // the pair's threshold (plain ladders) or its uniform
+    const float v = pair[j * SU];  // the pair's threshold (plain ladders) or its uniform
     bool ok = my_l < v;
     if (!all_plain) {
       PTRWM_COLD_PATH();
@@ -692,6 +707,24 @@ constexpr int stream_register_waves(int dp) { return stream_waves_per_simd(dp) <
 // scan, and their machine code (profiles/r16_swap_walk.txt).
 constexpr bool swap_walk_in_kernel(int dp) { return dp <= 44; }
 
+// Which step kernels leave their parked heads alone in a swap event: those that park them, in the events of a one-wavefront
+// group that the walk decides (sequential order, exchange mode - a run-time condition of the launch, ptrwm_step_kernel).
+// Nothing a head depends on changes in an event - chain word, temperature index, key, step >> 32: states move between threads,
+// temperatures do not - so the only reason to rebuild them was that the event wrote over them.  Such an event publishes its two
+// arrays beside the heads (StepLds::kKeptL / kKeptU) and moves the rows through the lanes: one ds_bpermute_b32 per dimension
+// - the LDS pipe, but no LDS memory, and local to the wavefront: no barrier - in place of a ds_write, a barrier and a ds_read.
+// Wide ladders, even_odd order and reference_copy mode keep the slab exchange and the restore behind it.
+constexpr bool event_keeps_heads(int dp, bool exact, bool full, bool stream, int proposal_kind) {
+  return philox_heads_in_lds(dp, exact, full, stream, proposal_kind) && swap_walk_in_kernel(dp);
+}
+// Which step kernels carry the thread's lane index in ONE VGPR across the step loop and take the head slot, the squared-jump
+// slot and the event's slots from it, instead of rebuilding it from v_mbcnt at each of the three (thread_index_now: written
+// when these kernels sat at 127 of 128 VGPRs; with the heads parked they have a dozen to spare).  The kernels of
+// philox_heads_in_lds; the others keep the rebuilds, and their machine code, until they are measured.
+constexpr bool lane_index_carried(int dp, bool exact, bool full, bool stream, int proposal_kind) {
+  return philox_heads_in_lds(dp, exact, full, stream, proposal_kind);
+}
+
 // threads of this kernel's exchange group (rng_layout.h; the streaming form serves narrow ladders only: one wave, folded)
 template <bool STREAM>
 __device__ __forceinline__ int step_group_threads(int T) { return STREAM ? 64 : group_threads(T, 1); }
@@ -923,16 +956,27 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
   const unsigned long long gchain = (unsigned long long)(a.chain_offset + chain);
   constexpr bool kHeads = philox_heads_in_lds(DP, EXACT, FULL, STREAM, Proposal::kKind);
   static_assert(!kHeads || L::kHeadsFit, "the parked heads need room over the rows and the swap scratch");
+  constexpr bool kKeepHeads = event_keeps_heads(DP, EXACT, FULL, STREAM, Proposal::kKind);
+  static_assert(!kKeepHeads || L::kKeptFit, "an event that keeps the heads needs its words beside them");
+  // the thread's lane, one VGPR for the whole launch (lane_index_carried; opaque, so that it is neither rebuilt from
+  // threadIdx.x, which would then live across the loop beside it, nor folded into three addresses kept instead of one index)
+  constexpr bool kLane = lane_index_carried(DP, EXACT, FULL, STREAM, Proposal::kKind);
+  [[maybe_unused]] int lane_c = 0;
+  if constexpr (kLane) {
+    lane_c = (int)(threadIdx.x & 63);
+    PTRWM_VALUE_BARRIER("+v"(lane_c));
+  }
   typename std::conditional<kHeads, RngCtxHeads, RngCtx>::type rc;  // (counter words: rng_layout.h)
   rc.c2 = chain_word_c2(gchain);
   rc.k0 = a.k0;
   rc.k1 = a.k1;
   const uint32_t c3_base = chain_word_c3(gchain, (uint32_t)t);
-  // This thread's slot of block 0 of the parked heads, rebuilt from the hardware wherever it is needed (thread_index_now),
-  // and the store of all its heads for the counter word c0hi: in the prologue and behind every swap event's row exchange,
-  // each time behind the group's barrier (StepLds::heads).  c0hi holds for the launch: schedule.h cuts at 2^32 steps.
+  // This thread's slot of block 0 of the parked heads, from the carried lane index, and the store of all its heads for the
+  // counter word c0hi: in the prologue, and behind the row exchange of every swap event that goes through the slab
+  // (event_keeps_heads says which do not), each time behind the group's barrier (StepLds::heads).  c0hi holds for the
+  // launch: schedule.h cuts at 2^32 steps.
   [[maybe_unused]] auto head_slot0 = [&]() __attribute__((always_inline)) {
-    return reinterpret_cast<PhiloxHeadSlot *>(s_dyn + L::heads(wide, wave)) + (thread_index_now(wave) & 63);
+    return reinterpret_cast<PhiloxHeadSlot *>(s_dyn + L::heads(wide, wave)) + (kLane ? lane_c : (thread_index_now(wave) & 63));
   };
   [[maybe_unused]] auto store_heads = [&](uint32_t c0hi, uint32_t c3) __attribute__((always_inline)) {
     PhiloxHeadSlot *const slot0 = head_slot0();
@@ -1016,13 +1060,18 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
   auto finish_step = [&](bool count_on, bool acc, float j2, int D) __attribute__((always_inline)) {
     if (count_on) {
       n_acc += acc ? 1u : 0u;
-      const int tid_q = thread_index_now(wave);  // (the slot's address is rebuilt here, not carried across the step)
+      // (the slot's address is rebuilt here, not carried across the step - from the carried lane index where there is one)
+      const int tid_q = kLane ? wave * 64 + lane_c : thread_index_now(wave);
       const int gt_q = wide ? group_threads(T, 1) : 64;  // (not step_group_threads: that moved the production kernels' registers here)
       double *const sq_slot = reinterpret_cast<double *>(
                                   STREAM ? s_dyn + wave * kWaveFloats + L::sq_jump(64)
                                          : s_dyn + (wide ? 0 : wave * kWaveFloats) + L::sq_jump(gt_q)) +
-                              (wide ? tid_q : (tid_q & 63));
-      (void)__hip_atomic_fetch_add(sq_slot, (double)j2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+                              (wide ? tid_q : (kLane ? lane_c : (tid_q & 63)));
+      // (the counted jump's zero is selected on the float: left to the compiler, the select sinks below the conversion and
+      // becomes two v_cndmask on the halves of the double.  In the kernels above only: the others keep their machine code)
+      float j2c = j2;
+      if constexpr (kLane) PTRWM_VALUE_BARRIER("+v"(j2c));
+      (void)__hip_atomic_fetch_add(sq_slot, (double)j2c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
     if constexpr (FULL) {
       const bool trace_now = a.full.trace != nullptr && countdown_due(to_trace, a.full.trace_every);
@@ -1078,7 +1127,7 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       // product and runs 2-5 % faster for it - dims 24 / 48 / 50 in profiles/r04_scratch_ab.txt, table 6)
       // (with the heads parked that product is in the loop no more: only its high half is, one register)
       if constexpr (step_loop_at_register_cap(DP, STREAM) && !kHeads) asm volatile("" : "+v"(rc.c2));
-      if constexpr (kHeads) rc.heads = head_slot0();  // (the address is rebuilt per step, not carried: finish_step)
+      if constexpr (kHeads) rc.heads = head_slot0();  // (from the carried lane index: what is carried is that one register)
 
       long long srep = 0;
       const float *ext_raw = nullptr;
@@ -1118,12 +1167,16 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
     } else {
       // ---- temperature swaps on the post-MH log-densities (pt_rwm_gpu_optimized.py:594-633) ----
       // The exchange indices are rebuilt here from an opaque copy of threadIdx.x, so that none of them occupies a
-      // register (or a scratch slot) across the MH part of the step.
-      const int tid_s = thread_index_now(wave);
-      const int slot = wide ? tid_s : (tid_s & 63);  // this thread's slot in s_l / s_u and its row in s_stage
+      // register (or a scratch slot) across the MH part of the step (lane_index_carried: from the one index that does).
+      // (the index through a value barrier: what the event derives from it - slots, the parked words' address - is computed
+      // here, in one step of ten, and not hoisted out of the step loop into registers of its own)
+      int lane_s = lane_c;
+      if constexpr (kLane) PTRWM_VALUE_BARRIER("+v"(lane_s));
+      const int tid_s = kLane ? wave * 64 + lane_s : thread_index_now(wave);
+      const int slot = wide ? tid_s : (kLane ? lane_s : (tid_s & 63));  // this thread's slot in s_l / s_u and its row in s_stage
       const int group_threads = step_group_threads<STREAM>(T);
       float *const rows = STREAM ? s_dyn + wave * kWaveFloats + cur * L::kSlabFloats
-                                 : s_dyn + (wide ? 0 : (tid_s >> 6) * kWaveFloats);
+                                 : s_dyn + (wide ? 0 : (kLane ? wave : (tid_s >> 6)) * kWaveFloats);
       float *const s_l = STREAM ? s_dyn + wave * kWaveFloats + L::s_l(64) : rows + L::s_l(group_threads);
       float *const s_u = s_l + L::kSu * group_threads;
       int *const park = reinterpret_cast<int *>(s_l + L::kParked * group_threads) + slot;
@@ -1137,11 +1190,32 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       float us;
       if (ext) us = swap_uniform_ext(a.full.ext_swap_u, swap_in_call, a.n_chains, chain, T, t);
       else us = swap_uniform_philox(rc.c0hi, rc.c1, rc.c2, with_stream(c3_s, kStreamSwap), rc.k0, rc.k1);
+      // An event that the walk decides (below) leaves the parked heads alone (event_keeps_heads): it publishes beside them and
+      // moves the rows through the lanes.  Every other event of a kernel with parked heads writes over them, and stores them
+      // again at its end.  (Spelt out for these kernels only: every other kernel keeps its event, and its machine code.)
+      [[maybe_unused]] bool keep_heads = false;
+      [[maybe_unused]] float *kept_l = nullptr, *kept_u = nullptr;
+      if constexpr (kKeepHeads) {
+        keep_heads = !wide && a.swap_order == PTRWM_ORDER_SEQUENTIAL && a.swap_mode == PTRWM_SWAP_EXCHANGE;
+        kept_l = rows + L::kKeptL, kept_u = rows + L::kKeptU;  // (narrow: rows = the wave's base)
+      }
+      if constexpr (kKeepHeads) {
+        // (parked heads lie under the scratch words and the rows: every thread of the group has read this step's)
+        if (!keep_heads) sync_group();
+        if (keep_heads) {
+          kept_l[slot] = my_l;
+          kept_u[slot * L::kKeptUStride] = us;
+        } else {
+          s_l[slot] = my_l;
+          s_u[slot] = us;
+        }
+      } else {
       // (parked heads lie under the scratch words and the rows: every thread of the group has read this step's)
       if constexpr (kHeads) sync_group();
       // publish this thread's log-density and swap uniform; the sweep reads them back with broadcast ds_reads
       s_l[slot] = my_l;
       s_u[slot] = us;
+      }
       // may this ladder's sequential sweep take the threshold form in THIS event?  (swap_decide: a verdict of the ladder)
       const float db_pair = STREAM ? db_s : sub_rn(beta_t, a.beta[t < T - 1 ? t + 1 : t]);  // b_t - b_{t+1}; the last position: 0
       const bool pair_plain = swap_pair_plain(T, t, db_pair, my_l, us);
@@ -1155,9 +1229,12 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
         sync_group();
       }
       // (one-wavefront groups decide the sequential exchange sweep by lane masks and a scalar walk; wide ladders keep the scan)
-      if (swap_walk_in_kernel(DP) && !wide && a.swap_order == PTRWM_ORDER_SEQUENTIAL && a.swap_mode == PTRWM_SWAP_EXCHANGE)
-        swap_walk_decide<FULL>(T, t, base, slot, a.beta, db_pair, us, s_l, s_u, my_l, src, pair_acc, sync_group, swap_plain);
-      else
+      if (swap_walk_in_kernel(DP) && !wide && a.swap_order == PTRWM_ORDER_SEQUENTIAL && a.swap_mode == PTRWM_SWAP_EXCHANGE) {
+        if constexpr (kKeepHeads)
+          swap_walk_decide<FULL, L::kKeptUStride>(T, t, base, slot, a.beta, db_pair, us, kept_l, kept_u, my_l, src, pair_acc, sync_group, swap_plain);
+        else
+          swap_walk_decide<FULL>(T, t, base, slot, a.beta, db_pair, us, s_l, s_u, my_l, src, pair_acc, sync_group, swap_plain);
+      } else
         swap_decide<!(STREAM && swap_walk_in_kernel(DP))>(T, t, base, slot, a.swap_mode, a.swap_order, (ev_par0 + swap_in_call) & 1, a.beta, beta_t, us, s_l, s_u,
                     reinterpret_cast<int *>(s_u + (L::kLanded - L::kSu) * group_threads), my_l, src, pair_acc, sync_group, swap_plain);
       if (pair_acc) {
@@ -1168,22 +1245,42 @@ __global__ void __launch_bounds__(kBlockThreads, STREAM ? stream_register_waves(
       // fetches the row of slot `src` (rows exchanged through LDS: 2 LDS ops per dimension, no HBM)
       {
         float j2p[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // (a swap step's jump is taken from the rows, in the canonical order)
-        float *my_row = rows + slot * D;
-        PTRWM_DIM_LOOP(d, DP, D, { my_row[d] = acc ? y[d] : x[d]; })
-        sync_group();
-        const int Dr = fresh_dim<EXACT>(D0);  // generic widths: fresh d < dim compares instead of 2*DP live masks
-        const float *src_row = rows + src * Dr;
-        PTRWM_DIM_LOOP(d, DP, Dr, {
-          const float w = src_row[d];
-          const float dl = sub_rn(w, x[d]);
-          j2p[d / W] = fmaf(dl, dl, j2p[d / W]);
-          x[d] = w;
-          if ((d & 7) == 7) sched_fence_soft();
-        })
-        j2 = tree4_add(j2p);
-        if constexpr (kHeads) {
-          sync_group();  // every row of the group has been fetched: the heads go back over them
-          store_heads(rc.c0hi, with_stream(c3_s, kStreamMH));
+        if (keep_heads) {
+          // ... or, with the heads kept, straight from the lane that holds it: slot = lane in a one-wavefront group, every lane
+          // of the wavefront is here (idle ones shadow a live position), and src is a lane of a live ladder - or the thread's own
+          const int src_lane = src << 2;
+          // (y[d] through a value barrier: these selects are then not the slab path's, and stay here, eight at a time between
+          // the fences - seen as the same expression they were hoisted above the branch, all DP of them live beside x[] and
+          // the fetched row, and the kernel went from 113 to 127 VGPRs)
+          PTRWM_DIM_LOOP(d, DP, D, {
+            float yd = y[d];
+            PTRWM_VALUE_BARRIER("+v"(yd));
+            const float v = acc ? yd : x[d];
+            const float w = __int_as_float(__builtin_amdgcn_ds_bpermute(src_lane, __float_as_int(v)));
+            const float dl = sub_rn(w, x[d]);
+            j2p[d / W] = fmaf(dl, dl, j2p[d / W]);
+            x[d] = w;
+            if ((d & 7) == 7) sched_fence_soft();
+          })
+          j2 = tree4_add(j2p);
+        } else {
+          float *my_row = rows + slot * D;
+          PTRWM_DIM_LOOP(d, DP, D, { my_row[d] = acc ? y[d] : x[d]; })
+          sync_group();
+          const int Dr = fresh_dim<EXACT>(D0);  // generic widths: fresh d < dim compares instead of 2*DP live masks
+          const float *src_row = rows + src * Dr;
+          PTRWM_DIM_LOOP(d, DP, Dr, {
+            const float w = src_row[d];
+            const float dl = sub_rn(w, x[d]);
+            j2p[d / W] = fmaf(dl, dl, j2p[d / W]);
+            x[d] = w;
+            if ((d & 7) == 7) sched_fence_soft();
+          })
+          j2 = tree4_add(j2p);
+          if constexpr (kHeads) {
+            sync_group();  // every row of the group has been fetched: the heads go back over them
+            store_heads(rc.c0hi, with_stream(c3_s, kStreamMH));
+          }
         }
         if constexpr (FULL) {
           // replica flow (flow.h): the word travels as the row does - fetched from slot `src` behind the barrier above, which

@@ -190,6 +190,25 @@ __device__ __forceinline__ float div_rn(float a, float b) {
 // profiles/r02_form_sweep.txt - hence the finer classes there.)
 constexpr int canon_width(int dp) { return dp <= 32 ? 8 : (dp <= 64 ? 16 : (dp <= 80 ? 20 : (dp <= 96 ? 24 : 28))); }
 
+// "From the identity" is the definition; the thread form's ADDITIVE chains whose closing arithmetic is listed here start from
+// their first term instead (chain_add below) - one v_add_f32 per range and step that computes nothing - because no output
+// bit can tell the two apart:
+//   0 + x differs from x only for x = -0 (0 + -0 = +0), so a range's sum differs only if EVERY term of the range is -0, and
+//   then only in the sign of a zero.  The four-range tree keeps that: a zero of either sign added to anything else is
+//   that value, and zeros combine to a zero.
+//   philox_normal_step's jump[]: the total reaches only the squared jump j2, converted to double and added (ds_add_f64) to
+//   a sum that starts at +0.0 - s + (+0) and s + (-0) are the same bits for every s that sum can hold (it is never -0).
+//   RoughCarpetT::logp_fold's sm[]: the total feeds fmaf(sum + lg, kLn2, p7) with p7 = -dim ln sqrt(2 pi) != 0: a zero of
+//   either sign times kLn2 is a zero, and a zero added to p7 != 0 is p7.
+// (Products already fold: 1 * s is exact.)  tests/sum_first_term_test.cpp pins the argument on the CPU.  The lane-split form
+// and the oracle keep the spelling from zero; so do the widths above 44, whose machine code is held where it was measured
+// (swap_walk_in_kernel, kernel.h).
+constexpr bool sums_from_first_term(int dp) { return dp <= 44; }
+template <int DP, int W>
+__device__ __forceinline__ float chain_add(float partial, float term, int d) {
+  return (sums_from_first_term(DP) && d % W == 0) ? term : add_rn(partial, term);  // (d: a constant after unrolling)
+}
+
 __device__ __forceinline__ float tree4_add(const float (&p)[4]) { return add_rn(add_rn(p[0], p[1]), add_rn(p[2], p[3])); }
 __device__ __forceinline__ float tree4_neg_add(const float (&p)[4]) { return -tree4_add(p); }
 

@@ -167,7 +167,7 @@ __device__ __forceinline__ float philox_normal_step(float (&y)[DP], const float 
         const float ang = bm_turns(rb);
         y[d] = fmaf(rad, __builtin_amdgcn_sinf(ang), x[d]);
         y[d + 1] = fmaf(rad, __builtin_amdgcn_cosf(ang), x[d + 1]);
-        jump[d / W] = add_rn(jump[d / W], arg);
+        jump[d / W] = chain_add<DP, W>(jump[d / W], arg, d);
       }
       sched_fence();
     } else if (4 * c <= w_a) {
@@ -185,7 +185,7 @@ __device__ __forceinline__ float philox_normal_step(float (&y)[DP], const float 
           y[d0] = fmaf(rad, sn, x[d0]);
           if (d + 1 < DP && d + 1 < D) {
             y[d1] = fmaf(rad, __builtin_amdgcn_cosf(ang), x[d1]);
-            jump[d0 / W] = add_rn(jump[d0 / W], arg);
+            jump[d0 / W] = chain_add<DP, W>(jump[d0 / W], arg, d0);
           } else {
             const float i0 = mul_rn(rad, sn);  // the last dimension of an odd dim: half a pair
             jump[d0 / W] = fmaf(i0, i0, jump[d0 / W]);

@@ -161,9 +161,9 @@ struct RoughCarpetT {
       rc_fold_dim_term(d1, dn, wmid, wneg, wpos, mx, s);
 #ifdef PTRWM_RC_PROD_FIRST
       pr[d / W] = mul_rn(pr[d / W], s);
-      sm[d / W] = add_rn(sm[d / W], mx);
+      sm[d / W] = chain_add<DP, W>(sm[d / W], mx, d);
 #else
-      sm[d / W] = add_rn(sm[d / W], mx);
+      sm[d / W] = chain_add<DP, W>(sm[d / W], mx, d);
       pr[d / W] = mul_rn(pr[d / W], s);
 #endif
       if ((d & PTRWM_RC_FENCE_MASK) == PTRWM_RC_FENCE_MASK) sched_fence_soft();
