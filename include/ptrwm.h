@@ -555,6 +555,76 @@ int32_t ptrwm_adapt_reduce(const ptrwm_run_args *args, const ptrwm_adapt_args *a
  * histories written, pooled[0 .. n_temps] left zero.  One small workgroup. */
 int32_t ptrwm_adapt_update(const ptrwm_adapt_args *adapt, int32_t n_temps, int64_t window, void *stream);
 
+/* ---- warm-up tuning of the temperature ladder, on the device ---------------------------------------------------------------------
+ * The other tuning knob of parallel tempering: where the rungs sit.  During burn-in the library can move the interior betas
+ * towards equal swap rates between neighbours, pooled over every replica; both ends of the ladder keep their bits
+ * (csrc/ladder.h states the rule once).
+ * Windows: with V = every, window j is the steps [j V, (j + 1) V).  The K = until / V windows that end at or before `until`
+ * (<= burn_in) adapt; steps [K V, burn_in) are ordinary burn-in under the final ladder; past burn-in nothing adapts.
+ * Probes: step s of an adapting window is a probe step when (s + 1) % probe_every == 0 (probe_every divides every, so a
+ * window's last step is one).  Burn-in has no swap events and none is added: behind a probe step a small kernel reads logp
+ * and beta and adds, for every chain c and pair t = 0 .. n_temps - 2,
+ *   q = llrint(thr * 2^24),  thr = min(1, exp(lp)) exactly as the swap test forms it (a NaN: q = 0),
+ *   lp = beta[t] logp[c,t+1] + beta[t+1] logp[c,t] - beta[t] logp[c,t] - beta[t+1] logp[c,t+1]   (float, left to right)
+ * to pooled[t], and 1 per chain to pooled[n_temps - 1].  It moves nothing.  Integer sums: exact, whatever the order.
+ * Update, after window j, one thread, in double, sums over t ascending (pooled[n_temps - 1] = 0: the ladder is left alone):
+ *   r_t = pooled[t] / (pooled[n_temps - 1] 2^24),  rbar = mean r,  g_t = log beta_t - log beta_{t+1},  G = sum g,
+ *   h_t = log g_t + gain_j (r_t - rbar),  gain_j = gain / (j + 1)^decay (on the host),  w_t = exp(h_t - max h),  S = sum w,
+ *   beta[t + 1] = (float) ((double) beta_0 exp(-G (w_0 + ... + w_t) / S))        t = 0 .. n_temps - 3
+ * A new ladder that is not strictly decreasing after the rounding to float is dropped whole: the ladder is kept and
+ * *skipped += 1.  With rescale_scales = 1 the interior proposal scales follow, temp_scale[t] *= sqrt(beta_old[t] / beta_new[t])
+ * (in double, rounded once).  Suggested: gain 2, decay 0.5.
+ * How: NOT in the step kernels.  Every launch reads beta and temp_scale from device memory when it starts.  A launch that
+ * starts in an adapting window ends behind the next probe step at the latest; it is the ordinary burn-in launch, told
+ * nothing, so state and logp are bit-identical to the same steps run as plain burn-in under the same ladder and scales.
+ * The probe kernel follows it on the same stream and, at a window's end and unless defer_update, the update kernel (beta,
+ * temp_scale, the histories; pooled left zero).  Where a window of ptrwm_adapt_args ends at the same step the order is: scale
+ * reduce, scale update, ladder probe, ladder update.  Windows and probes come from step0: a run cut into calls anywhere
+ * gives the same bits, and a request at or past `until` adapts nothing.
+ * Shards: with defer_update = 1 a request ends at window ends (one that would step past the end of the adapting window its
+ * step0 lies in returns PTRWM_E_ARG before anything is enqueued); the caller all-reduces (SUM) `pooled` over the shards and
+ * calls ptrwm_ladder_update on each.
+ * Split steps: ordinary burn-in split steps; ptrwm_ladder_probe behind every probe step, ptrwm_ladder_update behind the last
+ * step of every adapting window.
+ * The library cannot read device memory before it enqueues: that beta is positive and strictly decreasing is the caller's
+ * to check. */
+typedef struct ptrwm_ladder_args {
+  uint32_t struct_size;    /* sizeof(ptrwm_ladder_args) */
+  int32_t every;           /* V >= 1: the window length */
+  int32_t probe_every;     /* >= 1 and a divisor of every: a probe behind every step s with (s + 1) % probe_every == 0 */
+  int64_t until;           /* 0..burn_in: windows that end at or before this step adapt */
+  float gain, decay;       /* gain_j = gain / (j + 1)^decay; gain > 0 and finite, decay in 0..1 */
+  int32_t rescale_scales;  /* 0: temp_scale is left alone.  1: interior scales follow their beta */
+  int32_t defer_update;   /* 0: update after every window.  1: the caller does (ptrwm_ladder_update), see "Shards" */
+  float *beta;             /* [n_temps] device, in/out; must be the memory args->beta points to */
+  float *temp_scale;       /* [n_temps] device, in/out; must be the memory proposal->temp_scale points to; NULL allowed with
+                              rescale_scales = 0 only */
+  int64_t *pooled;         /* [n_temps] device, zero before the run */
+  float *beta_history;     /* [K + 1, n_temps] device or NULL: row 0 the starting ladder, row j + 1 the one after window j */
+  int64_t *rate_history;   /* [K, n_temps] device or NULL: the pooled row of window j */
+  int64_t *skipped;        /* [1] device or NULL: updates dropped because the rounded ladder was not strictly decreasing */
+} ptrwm_ladder_args;
+
+/* ptrwm_run_with_adaptation, plus the ladder.  ladder == NULL: exactly ptrwm_run_with_adaptation.
+ * Checked before anything is enqueued, after the existing checks: PTRWM_E_STRUCT for a wrong ladder->struct_size;
+ * PTRWM_E_NULL for a NULL beta or pooled, or a NULL temp_scale with rescale_scales = 1; PTRWM_E_ARG for n_temps < 3,
+ * every < 1, probe_every < 1 or not a divisor of every, until outside 0..burn_in, gain not positive and finite, decay outside
+ * 0..1, rescale_scales or defer_update outside 0..1, beta != args->beta, a non-NULL temp_scale != proposal->temp_scale, or
+ * (defer_update = 1) a request that steps past a pending window end. */
+int32_t ptrwm_run_with_ladder(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                              const ptrwm_run_args *args, const ptrwm_moments_args *moments,
+                              const ptrwm_chain_moments_args *chain_moments, const ptrwm_flow_args *flow,
+                              const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder,
+                              void *stream);
+
+/* One probe, stand-alone (split steps; shards): reads args->logp [args->n_chains, args->n_temps] and ladder->beta, adds to
+ * ladder->pooled.  PTRWM_E_NULL / PTRWM_E_STRUCT / PTRWM_E_TEMPS / PTRWM_E_ARG as above (ladder->beta must equal args->beta);
+ * an empty batch: PTRWM_OK. */
+int32_t ptrwm_ladder_probe(const ptrwm_run_args *args, const ptrwm_ladder_args *ladder, void *stream);
+/* The update of window `window` (0 <= window < K = until / every, else PTRWM_E_ARG) from ladder->pooled: beta, temp_scale and
+ * the histories written, pooled left zero.  One small workgroup. */
+int32_t ptrwm_ladder_update(const ptrwm_ladder_args *ladder, int32_t n_temps, int64_t window, void *stream);
+
 /* One stand-alone swap event over the current states: what the reference's
  * ParallelTemperingRWM_GPU_Optimized._attempt_all_swaps() does when called on its own
  * (pt_rwm_gpu_optimized.py:594-633; tests/debug_pt_performance.py:156).  Exactly the swap part of a ptrwm_run step:

@@ -40,6 +40,15 @@ ptrwm_adapt_args), used by two small kernels between launches at the end of ever
     scale_history  float32 [K + 1, n_temps]           the scales before the first and after every window (NaN: not run yet)
     accept_history int64   [K, n_temps]               pooled acceptances of every window
 
+and, with adapt_ladder=True, the arrays of the warm-up tuning of the ladder (`_ladder`, a dict; include/ptrwm.h
+ptrwm_ladder_args), used by two more small kernels between launches - a probe behind every probe step, an update at the end of
+every window - which rewrite `beta` (the run's own tensor) and the run's copy of the scales in place:
+
+    pooled         int64   [n_temps]                  quantised swap probabilities per pair, chain-probes last (zero between windows)
+    beta_history   float32 [K + 1, n_temps]           the ladder before the first and after every window (NaN: not run yet)
+    rate_history   int64   [K, n_temps]               the pooled row of every window
+    skipped        int64   [1]                        updates dropped (two rungs would have rounded onto each other)
+
 `n_replicas` is the axis the reference does not have: independent copies of the whole chain /
 ladder, one Philox subsequence each (global replica id = chain_offset + local index), so a run is
 invariant to how replicas are sharded over GPUs.
@@ -200,6 +209,58 @@ def check_adapt_args(adapt_scale, burn_in: int, adapt_every=50, adapt_until=None
             "bounds": (lo, hi), "sync": adapt_sync, "windows": windows}
 
 
+def check_ladder_args(adapt_ladder, burn_in: int, beta_ladder=None, ladder_every=100, ladder_until=None, ladder_probe_every=None,
+                      ladder_gain=2.0, ladder_decay=0.5, adapt_sync=None) -> Optional[dict]:
+    """The arguments of the warm-up tuning of the temperature ladder (None: off), checked on the host so that bad arguments
+    fail the same way with and without a GPU - what the library would refuse (include/ptrwm.h ptrwm_ladder_args) plus what it
+    cannot see: a ladder of at least 3 temperatures, positive and strictly decreasing in float32.  A warning when no window
+    fits into burn-in."""
+    if not isinstance(adapt_ladder, (bool, np.bool_)):
+        raise ValueError(f"adapt_ladder must be True or False, got {adapt_ladder!r}")
+    if not adapt_ladder:
+        return None
+    burn_in = int(burn_in)
+
+    def integer(name, v, lo):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+        return int(v)
+
+    every = integer("ladder_every", ladder_every, 1)
+    if ladder_until is None:
+        ladder_until = burn_in
+    if isinstance(ladder_until, bool) or not isinstance(ladder_until, (int, np.integer)) or not 0 <= ladder_until <= burn_in:
+        raise ValueError(f"ladder_until must be an integer in 0..burn_in = {burn_in}, got {ladder_until!r}")
+    probe_every = every if ladder_probe_every is None else integer("ladder_probe_every", ladder_probe_every, 1)
+    if every % probe_every != 0:
+        raise ValueError(f"ladder_probe_every must divide ladder_every = {every}, got {ladder_probe_every!r}")
+
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{name} must be a finite number, got {v!r}")
+        return float(v)
+
+    gain, decay = number("ladder_gain", ladder_gain), number("ladder_decay", ladder_decay)
+    if not gain > 0.0:
+        raise ValueError(f"ladder_gain must be positive, got {ladder_gain!r}")
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f"ladder_decay must lie in 0..1, got {ladder_decay!r}")
+    if adapt_sync is not None and not callable(adapt_sync):
+        raise ValueError("adapt_sync must be None or a callable applied to the pooled int64 tensor")
+    if beta_ladder is not None:
+        b = np.asarray(list(beta_ladder), np.float32)
+        if b.size < 3:
+            raise ValueError(f"adapt_ladder=True moves the interior temperatures: beta_ladder needs at least 3, got {b.size}")
+        if not (b > 0).all() or not (b[:-1] > b[1:]).all():
+            raise ValueError("adapt_ladder=True needs a beta_ladder that is positive and strictly decreasing in float32")
+    windows = int(ladder_until) // every
+    if windows == 0:
+        warnings.warn(f"adapt_ladder=True but no window of ladder_every = {every} steps ends within the first "
+                      f"{ladder_until} burn-in steps: the ladder will not move")
+    return {"every": every, "until": int(ladder_until), "probe_every": probe_every, "gain": gain, "decay": decay,
+            "sync": adapt_sync, "windows": windows}
+
+
 def check_init_attempts(init_attempts) -> int:
     if isinstance(init_attempts, bool) or not isinstance(init_attempts, (int, np.integer)) or not 1 <= init_attempts <= 65535:
         raise ValueError(f"init_attempts must be an integer in 1..65535, got {init_attempts!r}")
@@ -247,9 +308,13 @@ class EngineRun:
                  init_attempts: int = 8, flow: bool = False, hist_temps: int = 0, hist_every: int = 1, hist_bins: int = 64,
                  hist_range=None, adapt_scale: bool = False, adapt_every: int = 50, adapt_until: Optional[int] = None,
                  adapt_target: float = 0.234, adapt_gain: float = 3.0, adapt_decay: float = 0.5,
-                 adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None):
+                 adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False, ladder_every: int = 100,
+                 ladder_until: Optional[int] = None, ladder_probe_every: Optional[int] = None, ladder_gain: float = 2.0,
+                 ladder_decay: float = 0.5):
         adapt = check_adapt_args(adapt_scale, max(0, int(burn_in)), adapt_every, adapt_until, adapt_target, adapt_gain,
                                  adapt_decay, adapt_scale_bounds, adapt_sync)
+        ladder = check_ladder_args(adapt_ladder, max(0, int(burn_in)), beta_ladder, ladder_every, ladder_until,
+                                   ladder_probe_every, ladder_gain, ladder_decay, adapt_sync)
         if swap_mode not in ptrwm_hip.SWAP_MODES:
             raise ValueError(f"swap_mode must be one of {sorted(ptrwm_hip.SWAP_MODES)}, got {swap_mode!r}")
         if swap_order not in ptrwm_hip.SWAP_ORDERS:
@@ -295,7 +360,7 @@ class EngineRun:
                                             or ptrwm_hip.has_quad_variant(self.target.kind, proposal.kind, dim, n_temps)):
             raise ValueError(f"no fused kernel for dim {dim} with a ladder of {n_temps} temperatures: above dim 64 a ladder "
                              "holds at most 128 temperatures (one 512-thread workgroup of the lane-split kernel)")
-        if adapt is not None:
+        if adapt is not None or ladder is not None:
             # the run rewrites its scales in place: a copy of its own (engine_proposal() may hand out a view of the proposal
             # object's tensors, which a reset() must find as they were)
             proposal = ptrwm_hip.Proposal(proposal.kind, proposal.temp_scale.clone(), proposal.dim_scale, proposal.inv_dim)
@@ -408,6 +473,23 @@ class EngineRun:
                                       target=adapt["target"], gain=adapt["gain"], decay=adapt["decay"], min_scale=lo,
                                       max_scale=hi, defer_update=adapt["sync"] is not None,
                                       scale_history=self._adapt["scale_history"], accept_history=self._adapt["accept_history"])
+        # warm-up tuning of the temperature ladder, by two more small kernels between launches (off: None).  `beta` is the
+        # run's own tensor: the update kernel rewrites it in place.
+        self.init_beta = self.beta.clone()
+        self._ladder = None
+        if ladder is not None:
+            K, V = ladder["windows"], ladder["every"]
+            self._ladder = {**ladder, "end": K * V,
+                            "pooled": torch.zeros(n_temps, device=device, dtype=torch.int64),
+                            "beta_history": torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
+                            # row j: the pooled row of window j - pair sums, and chain-probes in the last column
+                            "rate_history": torch.zeros(K, n_temps, device=device, dtype=torch.int64),
+                            "skipped": torch.zeros(1, device=device, dtype=torch.int64)}
+            self._ladder["beta_history"][0] = self.init_beta
+            self._plan.set_ladder(self._ladder["pooled"], every=V, probe_every=ladder["probe_every"], until=ladder["until"],
+                                  gain=ladder["gain"], decay=ladder["decay"], rescale_scales=True,
+                                  defer_update=ladder["sync"] is not None, beta_history=self._ladder["beta_history"],
+                                  rate_history=self._ladder["rate_history"], skipped=self._ladder["skipped"])
         if box is not None:
             self._draw_starts(box, x0.to(torch.float32).contiguous(), bool(init_per_temperature), attempts)
 
@@ -458,21 +540,30 @@ class EngineRun:
         if self.density_fn is not None:
             self._advance_split(n_steps, trace, trace_logp, trace_row0, max(1, int(trace_every)))
             return
-        if self._adapt is not None and self._adapt["sync"] is not None and self.steps_done < self._adapt["end"]:
-            # adapt_sync: one launch per window (the library refuses to step past a pending update), the caller's
-            # all-reduce of `pooled` and the update in between; ordinary launches from the end of warm-up
-            W, end = self._adapt["every"], self._adapt["end"]
+        pending = self._pending_sync()
+        if pending:
+            # adapt_sync: one launch up to the nearer pending window end of either tuning (the library refuses to step past a
+            # pending update), the caller's all-reduce of that window's `pooled` and the update in between - the scale's
+            # before the ladder's where both end at the same step; ordinary launches from the end of warm-up
             while n_steps > 0:
                 s = self.steps_done
-                n = min(n_steps, W - s % W) if s < end else n_steps
+                pending = self._pending_sync()
+                n = min([n_steps] + [tu["every"] - s % tu["every"] for tu in pending])
                 self._launch(n, trace, trace_logp, trace_row0, trace_every)
                 if trace is not None:
                     trace_row0 += ptrwm_hip.periodic_steps_in(s, s + n, max(1, int(trace_every)))
-                if s < end and (s + n) % W == 0:
-                    self._adapt_window_end((s + n) // W - 1, reduce=False)
+                if any(tu is self._adapt for tu in pending) and (s + n) % self._adapt["every"] == 0:
+                    self._adapt_window_end((s + n) // self._adapt["every"] - 1, reduce=False)
+                if any(tu is self._ladder for tu in pending) and (s + n) % self._ladder["every"] == 0:
+                    self._ladder_window_end((s + n) // self._ladder["every"] - 1)
                 n_steps -= n
             return
         self._launch(n_steps, trace, trace_logp, trace_row0, trace_every)
+
+    def _pending_sync(self) -> list:
+        """The tunings (scale, ladder) that defer their update to the caller and still have a window to end."""
+        return [tu for tu in (self._adapt, self._ladder)
+                if tu is not None and tu["sync"] is not None and self.steps_done < tu["end"]]
 
     def _launch(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> None:
         if trace is None and trace_logp is None:
@@ -492,6 +583,40 @@ class EngineRun:
             ad["sync"](ad["pooled"])
             ad["count_history"][window] = ad["pooled"][self.n_temps]
         self._plan.adapt_update(window)
+
+    def _ladder_window_end(self, window: int) -> None:
+        """What follows the last probe of adapting ladder window `window` where the library does not do it itself (split
+        steps; with adapt_sync): the caller's all-reduce of `pooled`, the update kernel."""
+        ld = self._ladder
+        if ld["sync"] is not None:
+            ld["sync"](ld["pooled"])
+        self._plan.ladder_update(window)
+
+    def _ladder_after_split(self, s: int, n: int) -> None:
+        """Split steps: n steps from s (inside an adapting ladder window, never across a probe step) have run - the stand-alone
+        probe behind a probe step, the update behind a window's last."""
+        ld = self._ladder
+        if (s + n) % ld["probe_every"] == 0:
+            self._plan.ladder_probe()
+            if (s + n) % ld["every"] == 0:
+                self._ladder_window_end((s + n) // ld["every"] - 1)
+
+    def beta_ladder(self) -> torch.Tensor:
+        """The current ladder: float32 [n_temps] on the device (a copy)."""
+        return self.beta.clone()
+
+    def ladder_history(self) -> Optional[dict]:
+        """None when the ladder's tuning is off, else "betas" float32 [K + 1, n_temps] (row 0 the initial ladder, row j + 1 the
+        one after window j; NaN for windows that have not run), "rates" float64 [K, n_temps - 1] (every pair's mean swap
+        probability over window j, from the integer history; NaN likewise), "probes" int64 [K] (chain-probes behind row j, every
+        shard's with adapt_sync), "pooled" the integer rows [K, n_temps] and "skipped" the updates dropped.  Device tensors."""
+        if self._ladder is None:
+            return None
+        ld = self._ladder
+        rows = ld["rate_history"].clone()
+        probes = rows[:, -1]
+        return {"betas": ld["beta_history"].clone(), "rates": rows[:, :-1].double() / (probes.double()[:, None] * 16777216.0),
+                "probes": probes.clone(), "pooled": rows, "skipped": int(ld["skipped"].item())}
 
     # ---- warm-up tuning: read-outs -------------------------------------------------------------------------------
     def proposal_scales(self) -> torch.Tensor:
@@ -628,14 +753,34 @@ class EngineRun:
 
     def _advance_split(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> None:
         """n_steps split steps; traced steps (step_counter a multiple of trace_every) are copied with torch."""
+        ld = self._ladder
+        while n_steps > 0 and ld is not None and self.steps_done < ld["end"]:
+            # the ladder's windows: the host loop - and with it every captured block - ends at every probe step; the
+            # stand-alone probe follows, and the update at window ends (behind the scale's own kernels, which
+            # _advance_split_warmup enqueues with the step that ends its window)
+            s = self.steps_done
+            k = min(n_steps, ld["probe_every"] - s % ld["probe_every"])
+            if self._adapt is not None and s < self._adapt["end"]:
+                k = min(k, self._adapt["end"] - s)
+                trace_row0 += self._advance_split_warmup(k, trace, trace_logp, trace_row0, trace_every)
+            else:
+                trace_row0 += self._advance_split_plain(k, trace, trace_logp, trace_row0, trace_every)
+            self._ladder_after_split(s, k)
+            n_steps -= k
+        if n_steps == 0:
+            return
         if self._adapt is not None and self.steps_done < self._adapt["end"]:
             k = min(n_steps, self._adapt["end"] - self.steps_done)
             trace_row0 += self._advance_split_warmup(k, trace, trace_logp, trace_row0, trace_every)
             n_steps -= k
             if n_steps == 0:
                 return
+        self._advance_split_plain(n_steps, trace, trace_logp, trace_row0, trace_every)
+
+    def _advance_split_plain(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> int:
+        """n_steps ordinary split steps - by graph replay where nothing is traced - and the rows traced."""
         if trace is None and n_steps >= 2 and self.use_graph and self._advance_split_graph(n_steps):
-            return
+            return 0
         C, T, D = self.n_replicas, self.n_temps, self.dim
         row = trace_row0
         for _ in range(n_steps):
@@ -652,6 +797,7 @@ class EngineRun:
                 if trace_logp is not None:
                     trace_logp[row] = self.logp[:tc, :tt]
                 row += 1
+        return row - trace_row0
 
     def swap_sweep(self) -> None:
         """One stand-alone swap event over the current states (`_attempt_all_swaps()` called on its own,
@@ -1109,3 +1255,57 @@ class ScaleAdaptation:
 
     def _adapt_diagnostics(self) -> dict:
         return {"adapted_scales": self.proposal_scales().cpu().tolist(), "init_scales": self._init_scales().cpu().tolist()}
+
+
+# ---- warm-up tuning of the temperature ladder in the PT class ---------------------------------------------------------------
+class LadderAdaptation:
+    """Readers of the temperature ladder and of its warm-up tuning (include/ptrwm.h ptrwm_ladder_args).  The host class calls
+    `_check_ladder_ctor` in its constructor once `beta_ladder` stands, passes `_ladder_kwargs()` to EngineRun and owns `_run`
+    and `beta_ladder` (a list, refreshed from the run while the ladder moves).  Every read synchronises."""
+
+    def _check_ladder_ctor(self, burn_in: int, adapt_ladder, beta_ladder, **kw) -> None:
+        self._ladder_args = check_ladder_args(adapt_ladder, max(0, int(burn_in)), beta_ladder, **kw)
+        self._ladder_kw = ({"adapt_ladder": True, **{k: v for k, v in kw.items() if k != "adapt_sync"}}
+                           if self._ladder_args is not None else {})
+        self._init_beta_ladder = list(beta_ladder)
+
+    def _ladder_kwargs(self) -> dict:
+        return dict(self._ladder_kw)
+
+    def _refresh_beta_ladder(self, steps_before: int) -> None:
+        """After an advance that began at `steps_before`: `beta_ladder` follows the run's ladder where it may have moved."""
+        la, run = getattr(self, "_ladder_args", None), getattr(self, "_run", None)
+        if la is not None and run is not None and steps_before < la["windows"] * la["every"]:
+            self.beta_ladder = [float(b) for b in run.beta.cpu().tolist()]
+            self.beta_tensor = run.beta.clone()
+
+    def adapted_beta_ladder(self) -> list:
+        """The current ladder as a list of floats: the initial one before the first step and after reset(), the tuned one once
+        warm-up has run."""
+        run = getattr(self, "_run", None)
+        return [float(b) for b in run.beta.cpu().tolist()] if run is not None else [float(np.float32(b)) for b in self._init_beta_ladder]
+
+    def ladder_history(self) -> dict:
+        """{"betas": float32 [K + 1, T], "rates": float64 [K, T - 1], "probes": int64 [K]} of the K = ladder_until //
+        ladder_every windows: row 0 of betas the initial ladder, row j + 1 the one after window j; rates every pair's mean
+        swap probability over window j (from the integer counts); probes the chain-probes behind it.  Rows of windows that
+        have not run yet are NaN (probes 0).  Device tensors."""
+        if getattr(self, "_ladder_args", None) is None:
+            raise RuntimeError("the ladder's tuning is off: construct the sampler with adapt_ladder=True")
+        run = getattr(self, "_run", None)
+        if run is not None:
+            h = run.ladder_history()
+            return {"betas": h["betas"], "rates": h["rates"], "probes": h["probes"]}
+        K, T = self._ladder_args["windows"], len(self._init_beta_ladder)
+        betas = torch.full((K + 1, T), float("nan"), dtype=torch.float32)
+        betas[0] = torch.tensor(self._init_beta_ladder, dtype=torch.float32)
+        return {"betas": betas, "rates": torch.full((K, T - 1), float("nan"), dtype=torch.float64),
+                "probes": torch.zeros(K, dtype=torch.int64)}
+
+    def _ladder_diagnostics(self) -> dict:
+        if getattr(self, "_ladder_args", None) is None:
+            return {}
+        run = getattr(self, "_run", None)
+        return {"adapted_beta_ladder": self.adapted_beta_ladder(),
+                "init_beta_ladder": [float(np.float32(b)) for b in self._init_beta_ladder],
+                "ladder_updates_skipped": int(run._ladder["skipped"].item()) if run is not None else 0}

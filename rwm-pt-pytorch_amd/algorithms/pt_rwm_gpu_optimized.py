@@ -32,8 +32,8 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import (EngineRun, MarginalHistograms, PosteriorMoments, ScaleAdaptation, check_class_starts, moments_temps,
-                           resolve_device)
+from ._engine_core import (EngineRun, LadderAdaptation, MarginalHistograms, PosteriorMoments, ScaleAdaptation,
+                           check_class_starts, moments_temps, resolve_device)
 from .sharding import flow_round_trip_rate, flow_up_fraction
 
 
@@ -47,7 +47,7 @@ def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
     return [float(beta_min ** (t / (n_temps - 1))) for t in range(n_temps)]
 
 
-class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, ScaleAdaptation, MHAlgorithm):
+class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, ScaleAdaptation, LadderAdaptation, MHAlgorithm):
     def __init__(self, dim: int, var: float, target_dist=None, symmetric: bool = True, beta_ladder: list = None,
                  iterative_temp_spacing: bool = False, geom_temp_spacing: bool = False,
                  swap_acceptance_rate: float = 0.234, beta_min_iterative: float = 0.01, N_samples_swap_est: int = 3000,
@@ -64,7 +64,9 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
                  hist: Optional[str] = None, hist_range=None, hist_bins: int = 64, hist_every: int = 1,
                  adapt_scale: bool = False, adapt_every: int = 50, adapt_until: Optional[int] = None,
                  adapt_target: float = 0.234, adapt_gain: float = 3.0, adapt_decay: float = 0.5,
-                 adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None):
+                 adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False, ladder_every: int = 100,
+                 ladder_until: Optional[int] = None, ladder_probe_every: Optional[int] = None, ladder_gain: float = 2.0,
+                 ladder_decay: float = 0.5):
         super().__init__(dim, var, target_dist, symmetric)
         # warm-up tuning of the proposal scale per temperature (include/ptrwm.h ptrwm_adapt_args): adapt_scale=True tunes towards
         # adapt_target in windows of adapt_every steps up to adapt_until (default: all of burn-in); adapt_scale_bounds are factors
@@ -124,6 +126,14 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
             if not geom_temp_spacing:
                 warnings.warn("No specific ladder construction method chosen. Using geometric spacing as default.")
 
+        # warm-up tuning of the ladder itself (include/ptrwm.h ptrwm_ladder_args): adapt_ladder=True moves the interior betas
+        # towards equal swap rates between neighbours in windows of ladder_every steps up to ladder_until (default: all of
+        # burn-in), from a probe of every replica behind every ladder_probe_every-th step (default: one per window); both ends
+        # stay, the proposal scales follow their temperature, and adapt_sync serves this tuning as it serves the scale's
+        self._check_ladder_ctor(self.burn_in, adapt_ladder, self.beta_ladder, ladder_every=ladder_every, ladder_until=ladder_until,
+                                ladder_probe_every=ladder_probe_every, ladder_gain=ladder_gain, ladder_decay=ladder_decay,
+                                adapt_sync=adapt_sync)
+        self._ladder_sync = adapt_sync
         self.num_chains = len(self.beta_ladder)  # = number of temperatures, as in the reference
         if self._flow_on and self.num_chains < 2:
             raise ValueError("flow=True tracks replicas through a ladder: it needs at least two temperatures")
@@ -268,7 +278,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
             swap_mode=self._swap_mode, swap_order=self._swap_order, seed=self._seed, chain_offset=self._chain_offset,
             dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, flow=self._flow_on,
-            **self._hist_kwargs(len(self.beta_ladder)), **self._adapt_kwargs())
+            **self._hist_kwargs(len(self.beta_ladder)), **self._adapt_kwargs(), **self._ladder_run_kwargs())
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
         self.current_log_densities = self._run.logp[0] if self.num_replicas == 1 else self._run.logp
@@ -279,7 +289,14 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
             self._rows_used = 1
 
     def _initial_proposal(self):
-        return self.proposal_dist.engine_proposal(self.beta_ladder)
+        return self.proposal_dist.engine_proposal(self._init_beta_ladder)
+
+    def _ladder_run_kwargs(self) -> dict:
+        """EngineRun's ladder arguments (adapt_sync travels with the scale's where that is on too)."""
+        kw = self._ladder_kwargs()
+        if kw and "adapt_sync" not in self._adapt_kwargs():
+            kw["adapt_sync"] = self._ladder_sync
+        return kw
 
     def _advance(self, n_steps: int):
         self._ensure_started()
@@ -305,6 +322,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
             self._rows_used += rows
         else:
             self._run.advance(n_steps)
+        self._refresh_beta_ladder(self.step_counter)
         self.step_counter += n_steps
         self._chain_cache = None
 
@@ -314,6 +332,8 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
 
     def reset(self):
         self._run = None
+        self.beta_ladder = list(self._init_beta_ladder)  # (a tuned ladder goes back to where it started)
+        self.beta_tensor = torch.tensor(self.beta_ladder, device=self.device, dtype=torch.float32)
         self.step_counter = 0
         self._chain_cache = None
         self.current_states = self.current_log_densities = None
@@ -506,6 +526,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
             **self._flow_diagnostics(),
             **self._hist_diagnostics(),
             **self._adapt_diagnostics(),
+            **self._ladder_diagnostics(),
         }
 
     def performance_summary(self):

@@ -63,8 +63,11 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, ScaleAdap
                  hist_bins: int = 64, hist_every: int = 1, adapt_scale: bool = False, adapt_every: int = 50,
                  adapt_until: Optional[int] = None,
                  adapt_target: float = 0.234, adapt_gain: float = 3.0, adapt_decay: float = 0.5,
-                 adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None):
+                 adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False):
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
+        if adapt_ladder:
+            raise ValueError("adapt_ladder=True tunes a temperature ladder: RandomWalkMH_GPU_Optimized has none "
+                             "(use ParallelTemperingRWM_GPU_Optimized)")
         # warm-up tuning of the proposal scale per temperature (include/ptrwm.h ptrwm_adapt_args): adapt_scale=True tunes towards
         # adapt_target in windows of adapt_every steps up to adapt_until (default: all of burn-in); adapt_scale_bounds are factors
         # on the initial scales; adapt_sync, a callable applied to the pooled [T + 1] counts at every window end, makes shards

@@ -177,10 +177,10 @@ def allreduce_histogram(sampler, group: Optional[dist.ProcessGroup] = None) -> d
     return {"counts": vec[:n].view(counts.shape), "count": vec[n:].view(count.shape), "edges": h.get("edges")}
 
 
-# ---- warm-up tuning of the proposal scale (include/ptrwm.h ptrwm_adapt_args) ---------------------------------------------------
+# ---- warm-up tuning of the proposal scale and of the ladder (include/ptrwm.h ptrwm_adapt_args, ptrwm_ladder_args) ---------------
 def adaptation_sync(group: Optional[dist.ProcessGroup] = None):
-    """The `adapt_sync=` callable of a sharded run: all-reduces (SUM) the pooled [n_temps + 1] int64 counts of a window in place,
-    over `group`.  Every rank then applies the same update to the same integers, so a sharded run adapts - and samples - exactly
+    """The `adapt_sync=` callable of a sharded run, for both tunings: all-reduces (SUM) the pooled int64 counts of a window in
+    place, over `group` - [n_temps + 1] for the scale's (adapt_scale=True), [n_temps] for the ladder's (adapt_ladder=True).  Every rank then applies the same update to the same integers, so a sharded run adapts - and samples - exactly
     as the unsharded one.  Without an initialised process group the counts are left as they are (one shard)."""
 
     def sync(pooled: torch.Tensor) -> torch.Tensor:

@@ -5,6 +5,7 @@
 
 #include "../../include/ptrwm.h"
 #include "adapt.h"
+#include "ladder.h"
 #include "hist.h"
 #include "schedule.h"
 #include "variants.h"
@@ -870,6 +871,97 @@ __global__ void __launch_bounds__(256) adapt_update_kernel(AdaptUpdateArgs a) {
   if (t == 0) a.pooled[T] = 0;
 }
 
+// ---- warm-up tuning of the temperature ladder (ladder.h; include/ptrwm.h ptrwm_ladder_args) -------------------------------------
+// Two more small kernels between launches; the step kernels are told nothing.  Behind every probe step ladder_probe_kernel
+// reads logp and beta and adds, per pair, the quantised probability with which the pair would swap to pooled[t]; at a window's
+// end ladder_update_kernel applies ladder.h's rule to beta (and temp_scale), which the next launch reads when it starts.
+//
+// Probe: tiled as adapt_reduce_kernel - a workgroup takes a tile of whole chains, about kAdaptTileElems elements of logp, one
+// contiguous run that starts at a chain, so element e of the tile is temperature e % n_temps.  Thread i takes elements i,
+// i + 256, ...: consecutive lanes read consecutive floats (and their right-hand neighbours, the same cache lines).  Element e
+// with t < n_temps - 1 is the pair (t, t + 1) of its chain; the last element of a chain is no pair.  A thread keeps a pair's
+// sum in a register for as long as its elements stay on that pair (for ever where n_temps divides 256) and adds it to the
+// workgroup's 64-bit LDS counter of the pair when they move on; one 64-bit global atomic per non-zero (workgroup, pair)
+// flushes, and one adds the tile's chains to pooled[n_temps - 1].  All integer: exact, whatever the order.
+struct LadderProbeArgs {
+  const float *logp;   // [n_chains, n_temps]
+  const float *beta;   // [n_temps]
+  long long *pooled;   // [n_temps]
+  long long n_chains;
+  int n_temps, tile_chains;  // tile_chains = adapt_tile_chains(n_temps)
+};
+
+__global__ void __launch_bounds__(256) ladder_probe_kernel(LadderProbeArgs a) {
+  __shared__ unsigned long long s_sum[PTRWM_MAX_TEMPS];
+  __shared__ float s_beta[PTRWM_MAX_TEMPS];
+  const int tid = (int)threadIdx.x, T = a.n_temps;
+  for (int t = tid; t < T; t += 256) s_sum[t] = 0ull, s_beta[t] = a.beta[t];
+  __syncthreads();
+  const long long c0 = (long long)blockIdx.x * a.tile_chains;
+  const long long c1 = (a.n_chains - c0 < a.tile_chains) ? a.n_chains : c0 + a.tile_chains;
+  const int n = (int)((c1 - c0) * T);  // the tile's elements (1 .. tile_chains * n_temps <= max(kAdaptTileElems, n_temps))
+  const float *const p = a.logp + c0 * T;
+  int cur = 0;
+  long long acc = 0;
+  for (int e = tid; e < n; e += 256) {
+    const int t = e % T;
+    if (t == T - 1) continue;  // (e + 1 < n: the pair's upper rung is in the same chain)
+    if (t != cur) {
+      if (acc != 0) atomicAdd(&s_sum[cur], (unsigned long long)acc);
+      cur = t, acc = 0;
+    }
+    const float lp = swap_log_prob(s_beta[t], s_beta[t + 1], p[e], p[e + 1]);
+    const float thr = (lp >= 0.0f) ? 1.0f : hw_exp(lp);  // the threshold of swap_accept_test
+    acc += ladder_quantum(thr);
+  }
+  if (acc != 0) atomicAdd(&s_sum[cur], (unsigned long long)acc);
+  __syncthreads();
+  for (int t = tid; t < T - 1; t += 256) {
+    const unsigned long long v = s_sum[t];
+    if (v != 0ull) count_add(&a.pooled[t], (long long)v);
+  }
+  if (tid == 0) count_add(&a.pooled[T - 1], c1 - c0);
+}
+
+// Update: one workgroup.  Thread 0 runs ladder.h's sequential rule into LDS; behind the barrier thread t < n_temps writes its
+// beta, its scale and the histories, and zeroes its counter (which only thread 0 read before the barrier, and itself after).
+struct LadderUpdateArgs {
+  float *beta;              // [n_temps] in/out
+  float *temp_scale;        // [n_temps] in/out, or NULL (rescale_scales = 0)
+  long long *pooled;        // [n_temps], zeroed
+  float *beta_history;      // [K + 1, n_temps] or NULL
+  long long *rate_history;  // [K, n_temps] or NULL
+  long long *skipped;       // [1] or NULL
+  long long window;         // j (0 <= j < K: checked on the host)
+  double gain_j;
+  int n_temps;
+};
+
+__global__ void __launch_bounds__(256) ladder_update_kernel(LadderUpdateArgs a) {
+  __shared__ float s_old[PTRWM_MAX_TEMPS], s_new[PTRWM_MAX_TEMPS];
+  __shared__ long long s_pooled[PTRWM_MAX_TEMPS];
+  __shared__ double s_work[PTRWM_MAX_TEMPS];
+  const int t = (int)threadIdx.x, T = a.n_temps;
+  if (t < T) s_old[t] = a.beta[t], s_pooled[t] = a.pooled[t];
+  __syncthreads();
+  if (t == 0) {
+    const int outcome = ladder_update(s_old, s_pooled, T, a.gain_j, s_new, s_work);
+    if (outcome == kLadderSkipped && a.skipped != nullptr) *a.skipped += 1;
+  }
+  __syncthreads();
+  if (t < T) {
+    const float b_old = s_old[t], b_new = s_new[t];
+    a.beta[t] = b_new;
+    if (a.temp_scale != nullptr && t > 0 && t < T - 1) a.temp_scale[t] = ladder_rescale(a.temp_scale[t], b_old, b_new);
+    if (a.beta_history != nullptr) {
+      if (a.window == 0) a.beta_history[t] = b_old;
+      a.beta_history[(a.window + 1) * T + t] = b_new;
+    }
+    if (a.rate_history != nullptr) a.rate_history[a.window * T + t] = s_pooled[t];
+    a.pooled[t] = 0;
+  }
+}
+
 // Starting points (ptrwm_init_states): row (c, t) of `state` drawn uniformly from the box [lo, hi], or set to `fallback`.
 // The draw is Philox stream kStreamInit (rng_layout.h: the counter layout; include/ptrwm.h restates it), keyed by the GLOBAL chain
 // id like every other random of a run, so the starts do not depend on how chains are sharded over devices.
@@ -1070,9 +1162,54 @@ static int32_t launch_adapt_update(const ptrwm_adapt_args *ad, int n_temps, long
 }
 static_assert(PTRWM_MAX_TEMPS <= 256, "adapt_update_kernel: one thread per temperature in one 256-thread workgroup");
 
+// the ladder checks shared by ptrwm_run_with_ladder, ptrwm_ladder_probe and ptrwm_ladder_update (none: ok); what needs the run
+// (until <= burn_in, the pointer identities, n_temps) is checked by the callers
+static int32_t check_ladder(const ptrwm_ladder_args *ld) {
+  if (ld == nullptr) return PTRWM_OK;
+  if (ld->struct_size != sizeof(ptrwm_ladder_args)) return PTRWM_E_STRUCT;
+  if (ld->beta == nullptr || ld->pooled == nullptr || (ld->rescale_scales == 1 && ld->temp_scale == nullptr)) return PTRWM_E_NULL;
+  if (!is_flag(ld->rescale_scales) || !is_flag(ld->defer_update)) return PTRWM_E_ARG;
+  if (ld->every < 1 || ld->probe_every < 1 || ld->every % ld->probe_every != 0 || ld->until < 0) return PTRWM_E_ARG;
+  if (!(ld->gain > 0.0f) || !std::isfinite(ld->gain)) return PTRWM_E_ARG;
+  if (!(ld->decay >= 0.0f && ld->decay <= 1.0f)) return PTRWM_E_ARG;
+  return PTRWM_OK;
+}
+
+// one probe of n_chains x n_temps log-densities added to pooled; everything checked, n_chains >= 1, n_temps >= 3
+static int32_t launch_ladder_probe(const ptrwm_ladder_args *ld, const float *logp, long long n_chains, int n_temps, hipStream_t stream) {
+  LadderProbeArgs a;
+  a.logp = logp;
+  a.beta = ld->beta;
+  a.pooled = (long long *)ld->pooled;
+  a.n_chains = n_chains;
+  a.n_temps = n_temps;
+  a.tile_chains = adapt_tile_chains(n_temps);
+  const long long blocks = (n_chains + a.tile_chains - 1) / a.tile_chains;
+  if (blocks > 0x7fffffffll) return PTRWM_E_ARG;
+  hipLaunchKernelGGL(ladder_probe_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}
+
+// the update of window j (0 <= j < K); everything checked
+static int32_t launch_ladder_update(const ptrwm_ladder_args *ld, int n_temps, long long window, hipStream_t stream) {
+  LadderUpdateArgs a;
+  a.beta = ld->beta;
+  a.temp_scale = ld->rescale_scales == 1 ? ld->temp_scale : nullptr;
+  a.pooled = (long long *)ld->pooled;
+  a.beta_history = ld->beta_history;
+  a.rate_history = (long long *)ld->rate_history;
+  a.skipped = (long long *)ld->skipped;
+  a.window = window;
+  a.gain_j = ladder_gain((double)ld->gain, (double)ld->decay, window);
+  a.n_temps = n_temps;
+  hipLaunchKernelGGL(ladder_update_kernel, dim3(1), dim3(256), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}
+static_assert(PTRWM_MAX_TEMPS <= 256, "ladder_update_kernel: one thread per temperature in one 256-thread workgroup");
+
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                         const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist = nullptr,
-                        const ptrwm_adapt_args *adapt = nullptr);
+                        const ptrwm_adapt_args *adapt = nullptr, const ptrwm_ladder_args *ladder = nullptr);
 static int32_t swap_sweep_impl(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
                                const ptrwm_flow_args *flow, void *stream);
 static int32_t split_accept_impl(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
@@ -1228,6 +1365,35 @@ int32_t ptrwm_adapt_update(const ptrwm_adapt_args *adapt, int32_t n_temps, int64
   if (int rc = check_adapt(adapt)) return rc;
   if (window < 0 || window >= adapt_window_count(adapt->every, adapt->until)) return PTRWM_E_ARG;  // (the histories have K rows)
   return launch_adapt_update(adapt, n_temps, window, (hipStream_t)stream);
+}
+
+int32_t ptrwm_run_with_ladder(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                              const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
+                              const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt,
+                              const ptrwm_ladder_args *ladder, void *stream) {
+  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // (as ptrwm_run_with_diagnostics)
+  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist, adapt, ladder);
+}
+
+int32_t ptrwm_ladder_probe(const ptrwm_run_args *args, const ptrwm_ladder_args *ladder, void *stream) {
+  if (args == nullptr || ladder == nullptr) return PTRWM_E_NULL;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
+  if (args->n_chains < 0) return PTRWM_E_ARG;
+  if (int rc = check_ladder(ladder)) return rc;
+  if (args->n_temps < 3 || ladder->beta != args->beta) return PTRWM_E_ARG;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->logp == nullptr) return PTRWM_E_NULL;
+  return launch_ladder_probe(ladder, args->logp, args->n_chains, args->n_temps, (hipStream_t)stream);
+}
+
+int32_t ptrwm_ladder_update(const ptrwm_ladder_args *ladder, int32_t n_temps, int64_t window, void *stream) {
+  if (ladder == nullptr) return PTRWM_E_NULL;
+  if (!temps_in_range(n_temps)) return PTRWM_E_TEMPS;
+  if (int rc = check_ladder(ladder)) return rc;
+  if (n_temps < 3) return PTRWM_E_ARG;
+  if (window < 0 || window >= ladder_window_count(ladder->every, ladder->until)) return PTRWM_E_ARG;  // (the histories have K rows)
+  return launch_ladder_update(ladder, n_temps, window, (hipStream_t)stream);
 }
 
 int32_t ptrwm_histogram(const ptrwm_run_args *args, int32_t dim, const ptrwm_hist_args *hist, void *stream) {
@@ -1443,7 +1609,7 @@ static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_de
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                         const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist,
-                        const ptrwm_adapt_args *adapt) {
+                        const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder) {
   bool empty = false;
   if (int rc = check_run(target, proposal, args, spec, flow, hist, &empty)) return rc;
   // adaptation (adapt.h): its own checks after the existing ones, all before anything is enqueued
@@ -1452,6 +1618,14 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
     if (adapt->until > args->burn_in || adapt->temp_scale != proposal->temp_scale) return PTRWM_E_ARG;
     // defer_update: the caller applies the update between requests, so none may step past a window end that awaits it
     if (adapt->defer_update == 1 && !adapt_request_within_window(args->step0, args->n_steps, adapt->every, adapt->until))
+      return PTRWM_E_ARG;
+  }
+  // the ladder (ladder.h): likewise
+  if (int rc = check_ladder(ladder)) return rc;
+  if (ladder != nullptr) {
+    if (args->n_temps < 3 || ladder->until > args->burn_in || ladder->beta != args->beta) return PTRWM_E_ARG;
+    if (ladder->temp_scale != nullptr && ladder->temp_scale != proposal->temp_scale) return PTRWM_E_ARG;
+    if (ladder->defer_update == 1 && !ladder_request_within_window(args->step0, args->n_steps, ladder->every, ladder->until))
       return PTRWM_E_ARG;
   }
   if (empty) return PTRWM_OK;
@@ -1482,6 +1656,11 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
     const AdaptCut ac = adapt != nullptr ? adapt_cut_at(args->step0 + done, adapt->every, adapt->until) : AdaptCut{false, 0, 0};
     long long lim = to_snap < cap ? to_snap : cap;
     if (ac.adapting && ac.to_end < lim) lim = ac.to_end;
+    // (the ladder: a launch that starts in an adapting ladder window ends behind the next probe step at the latest - the
+    // probe kernel reads logp between two launches - and is otherwise told nothing: an ordinary burn-in launch)
+    const LadderCut lc = ladder != nullptr ? ladder_cut_at(args->step0 + done, ladder->every, ladder->probe_every, ladder->until)
+                                           : LadderCut{false, 0, 0};
+    if (lc.adapting && lc.to_probe < lim) lim = lc.to_probe;
     const LaunchCut cut = launch_at(req, done, lim);
     k.step0 = cut.step0;
     k.n_steps = cut.n;
@@ -1509,6 +1688,11 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
       if (int rc = launch_adapt_reduce(adapt, args->n_chains, args->n_temps, (hipStream_t)hip_stream)) return rc;
       if (adapt->defer_update == 0)
         if (int rc = launch_adapt_update(adapt, args->n_temps, ac.window, (hipStream_t)hip_stream)) return rc;
+    }
+    if (lc.adapting && ladder_launch_ends_at_probe(cut.step0, cut.n, ladder->probe_every)) {  // (behind the scale's kernels)
+      if (int rc = launch_ladder_probe(ladder, args->logp, args->n_chains, args->n_temps, (hipStream_t)hip_stream)) return rc;
+      if (ladder->defer_update == 0 && ladder_launch_ends_window(cut.step0, cut.n, ladder->every))
+        if (int rc = launch_ladder_update(ladder, args->n_temps, lc.window, (hipStream_t)hip_stream)) return rc;
     }
   }
   return PTRWM_OK;

@@ -189,6 +189,26 @@ class AdaptArgs(C.Structure):
     ]
 
 
+class LadderArgs(C.Structure):
+    """ptrwm_ladder_args: warm-up tuning of the temperature ladder (include/ptrwm.h, csrc/ladder.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("every", C.c_int32),
+        ("probe_every", C.c_int32),
+        ("until", C.c_int64),
+        ("gain", C.c_float),
+        ("decay", C.c_float),
+        ("rescale_scales", C.c_int32),
+        ("defer_update", C.c_int32),
+        ("beta", C.c_void_p),
+        ("temp_scale", C.c_void_p),
+        ("pooled", C.c_void_p),
+        ("beta_history", C.c_void_p),
+        ("rate_history", C.c_void_p),
+        ("skipped", C.c_void_p),
+    ]
+
+
 class InitArgs(C.Structure):
     """ptrwm_init_args: starting points drawn from a box, or set to a fallback point (include/ptrwm.h)."""
     _fields_ = [
@@ -243,6 +263,12 @@ SYMBOLS = {
          C.POINTER(FlowArgs), C.POINTER(HistArgs), C.POINTER(AdaptArgs), C.c_void_p]),
     "ptrwm_adapt_reduce": (C.c_int32, [C.POINTER(RunArgs), C.POINTER(AdaptArgs), C.c_void_p]),
     "ptrwm_adapt_update": (C.c_int32, [C.POINTER(AdaptArgs), C.c_int32, C.c_int64, C.c_void_p]),
+    "ptrwm_run_with_ladder": (
+        C.c_int32,
+        [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.POINTER(ChainMomentsArgs),
+         C.POINTER(FlowArgs), C.POINTER(HistArgs), C.POINTER(AdaptArgs), C.POINTER(LadderArgs), C.c_void_p]),
+    "ptrwm_ladder_probe": (C.c_int32, [C.POINTER(RunArgs), C.POINTER(LadderArgs), C.c_void_p]),
+    "ptrwm_ladder_update": (C.c_int32, [C.POINTER(LadderArgs), C.c_int32, C.c_int64, C.c_void_p]),
     "ptrwm_swap_sweep_with_flow": (
         C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_int64, C.c_int32, C.POINTER(FlowArgs), C.c_void_p]),
     "ptrwm_split_accept_with_flow": (
@@ -651,6 +677,7 @@ class RunPlan:
         self._flow = None  # replica flow: (struct, byref, tensors)
         self._hist = None  # pooled marginal histograms: (struct, byref, tensors)
         self._adapt = None  # warm-up tuning of the proposal scale: (struct, byref, tensors)
+        self._ladder = None  # warm-up tuning of the temperature ladder: (struct, byref, tensors)
 
     # kind of accumulator -> (words of its messages, struct, entry point of launch(), entry point of split_moments())
     _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
@@ -833,6 +860,75 @@ class RunPlan:
         if rc != 0:
             raise PTRWMError(rc, "ptrwm_adapt_update")
 
+    def set_ladder(self, pooled: Optional[torch.Tensor], *, every: int = 100, probe_every: Optional[int] = None, until: int = 0,
+                   gain: float = 2.0, decay: float = 0.5, rescale_scales: bool = True, defer_update: bool = False,
+                   beta_history: Optional[torch.Tensor] = None, rate_history: Optional[torch.Tensor] = None,
+                   skipped: Optional[torch.Tensor] = None) -> None:
+        """Tune the temperature ladder during burn-in (include/ptrwm.h ptrwm_ladder_args) in every following ``launch``: the
+        plan's own ``beta`` (and, with ``rescale_scales``, ``proposal.temp_scale``) is rewritten in place after every window of
+        ``every`` steps that ends at or before ``until`` (<= burn_in), from probes behind every ``probe_every``-th step
+        (default: one per window).  ``pooled`` [n_temps] int64 is scratch, zero before the run; ``beta_history``
+        [K + 1, n_temps] float32, ``rate_history`` [K, n_temps] int64 (K = until // every) and ``skipped`` [1] int64 are
+        optional records.  ``defer_update``: ``launch`` stops at window ends and the caller all-reduces ``pooled`` and calls
+        ``ladder_update``.  The library cannot read the ladder before it enqueues: that ``beta`` is positive and strictly
+        decreasing is checked here, on the host (one read).  ``set_ladder(None)`` switches it off."""
+        if pooled is None:
+            self._ladder = None
+            return
+        _, T, _ = self.shape
+        every, until = int(every), int(until)
+        probe_every = every if probe_every is None else int(probe_every)
+        if T < 3:
+            raise ValueError(f"the ladder's tuning moves interior temperatures: it needs at least 3, got {T}")
+        if every < 1:
+            raise ValueError("ladder every must be >= 1")
+        if probe_every < 1 or every % probe_every != 0:
+            raise ValueError(f"ladder probe_every must be >= 1 and divide every = {every}, got {probe_every}")
+        if not 0 <= until <= self._a.burn_in:
+            raise ValueError(f"ladder until must be in 0..burn_in = {self._a.burn_in}, got {until}")
+        K = until // every
+        beta, scale = self._keep[4], self._keep[1].temp_scale
+        for name, t, shape in (("pooled", pooled, (T,)), ("beta_history", beta_history, (K + 1, T)),
+                               ("rate_history", rate_history, (K, T)), ("skipped", skipped, (1,))):
+            if t is None and name != "pooled":
+                continue
+            if t is None or tuple(t.shape) != shape or t.device != self.device:
+                raise ValueError(f"ladder {name} must be a {list(shape)} tensor on {self.device}")
+        b = beta.detach().cpu().numpy()
+        if not (b > 0).all() or not (b[:-1] > b[1:]).all():
+            raise ValueError("the ladder's tuning needs a positive, strictly decreasing beta ladder")
+        ld = LadderArgs()
+        ld.struct_size = C.sizeof(LadderArgs)
+        ld.every, ld.probe_every, ld.until = every, probe_every, until
+        ld.gain, ld.decay = float(gain), float(decay)
+        ld.rescale_scales, ld.defer_update = (1 if rescale_scales else 0), (1 if defer_update else 0)
+        ld.beta = _require_device(beta, "beta", torch.float32)
+        ld.temp_scale = _require_device(scale, "proposal.temp_scale", torch.float32)
+        ld.pooled = _require_device(pooled, "ladder pooled", torch.int64)
+        ld.beta_history = _opt(beta_history, "ladder beta_history", torch.float32)
+        ld.rate_history = _opt(rate_history, "ladder rate_history", torch.int64)
+        ld.skipped = _opt(skipped, "ladder skipped", torch.int64)
+        self._ladder = (ld, C.byref(ld), (beta, scale, pooled, beta_history, rate_history, skipped))
+
+    def ladder_probe(self) -> None:
+        """One probe of the current log-densities, stand-alone (ptrwm_ladder_probe): every pair's quantised swap probability
+        added to ``pooled``.  ``launch`` does this itself behind every probe step; split steps and tests call it."""
+        if self._ladder is None:
+            raise RuntimeError("ladder_probe: no ladder tuning set (set_ladder)")
+        with self._guard:
+            rc = self._lib.ptrwm_ladder_probe(self._refs[4], self._ladder[1], _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_ladder_probe")
+
+    def ladder_update(self, window: int) -> None:
+        """The ladder update of window ``window`` from ``pooled`` (ptrwm_ladder_update); ``pooled`` is left zero."""
+        if self._ladder is None:
+            raise RuntimeError("ladder_update: no ladder tuning set (set_ladder)")
+        with self._guard:
+            rc = self._lib.ptrwm_ladder_update(self._ladder[1], self.shape[1], int(window), _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_ladder_update")
+
     def split_warmup(self, on: bool) -> None:
         """Split steps inside an adapting window (include/ptrwm.h, the split-step recipe): while on, split_accept counts every
         step's acceptances into the adaptation's ``window_accept``, adds no squared jump and performs no swap event
@@ -963,7 +1059,16 @@ class RunPlan:
                 self._last_trace = (trace, trace_logp, trace_every)
         # ptrwm_run, or the accumulator's entry point with its struct in front of the stream
         name, mom = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
-        if self._adapt is not None:  # adaptation bound: the entry point that takes everything
+        if self._ladder is not None:  # ladder tuning bound: the entry point that takes everything, the scale's tuning included
+            name = "ptrwm_run_with_ladder"
+            pooled = self._mom[2] if self._mom is not None and self._mom[0] == "pooled" else None
+            chain = self._mom[2] if self._mom is not None and self._mom[0] == "chain" else None
+            flow = self._flow[1] if self._flow is not None else None
+            hist = self._hist[1] if self._hist is not None else None
+            adapt = self._adapt[1] if self._adapt is not None else None
+            with self._guard:
+                rc = self._lib.ptrwm_run_with_ladder(self._refs[2], self._refs[3], self._refs[4], pooled, chain, flow, hist, adapt, self._ladder[1], _stream(self.device))
+        elif self._adapt is not None:  # adaptation bound: the entry point that takes everything but the ladder
             name = "ptrwm_run_with_adaptation"
             pooled = self._mom[2] if self._mom is not None and self._mom[0] == "pooled" else None
             chain = self._mom[2] if self._mom is not None and self._mom[0] == "chain" else None
