@@ -32,7 +32,7 @@ snapshot kernel between launches at every hist_every-th step past burn-in:
     count        int64   [hist_temps]                       (replica, step) pairs added per temperature
     lo, scale    float32 [dim]                              the bin rule's constants (csrc/hist.h)
 
-and, with adapt_scale=True, the arrays of the warm-up tuning of the proposal scale (`_adapt`, a dict; include/ptrwm.h
+and, with adapt_scale=True, the arrays of the warm-up tuning of the proposal scale (`_adapt`, a ScaleTuning; include/ptrwm.h
 ptrwm_adapt_args), used by two small kernels between launches at the end of every adaptation window of burn-in:
 
     window_accept  int64   [n_replicas, n_temps]      acceptances of the current window (scratch, zero between windows)
@@ -40,7 +40,7 @@ ptrwm_adapt_args), used by two small kernels between launches at the end of ever
     scale_history  float32 [K + 1, n_temps]           the scales before the first and after every window (NaN: not run yet)
     accept_history int64   [K, n_temps]               pooled acceptances of every window
 
-and, with adapt_ladder=True, the arrays of the warm-up tuning of the ladder (`_ladder`, a dict; include/ptrwm.h
+and, with adapt_ladder=True, the arrays of the warm-up tuning of the ladder (`_ladder`, a WarmupTuning; include/ptrwm.h
 ptrwm_ladder_args), used by two more small kernels between launches - a probe behind every probe step, an update at the end of
 every window - which rewrite `beta` (the run's own tensor) and the run's copy of the scales in place:
 
@@ -163,6 +163,43 @@ def check_hist_args(hist_temps, hist_every, hist_bins, hist_range, n_temps: int,
     return check_hist_range(hist_range, dim)
 
 
+def _integer(name, v, lo: int) -> int:
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+        raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+    return int(v)
+
+
+def _number(name, v) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        raise ValueError(f"{name} must be a finite number, got {v!r}")
+    return float(v)
+
+
+def check_warmup_args(flag: str, name: str, burn_in: int, every, until, gain, decay, adapt_sync, pooled: str, idle: str, own) -> dict:
+    """What the arguments of the two warm-up tunings share (`flag` switches the tuning on, `name` prefixes its keywords): an
+    integer period, `until` in 0..burn_in (default: burn_in), a finite gain > 0, a decay in 0..1, adapt_sync None or a callable
+    (applied to the `pooled` tensor), windows = until // every, and a warning when that is none (the tuning is `idle`).
+    `own(every)` checks the tuning's other arguments once the period stands and returns their entries of the dict."""
+    every = _integer(f"{name}_every", every, 1)
+    if until is None:
+        until = burn_in
+    if isinstance(until, bool) or not isinstance(until, (int, np.integer)) or not 0 <= until <= burn_in:
+        raise ValueError(f"{name}_until must be an integer in 0..burn_in = {burn_in}, got {until!r}")
+    rest = own(every)
+    g, d = _number(f"{name}_gain", gain), _number(f"{name}_decay", decay)
+    if not g > 0.0:
+        raise ValueError(f"{name}_gain must be positive, got {gain!r}")
+    if not 0.0 <= d <= 1.0:
+        raise ValueError(f"{name}_decay must lie in 0..1, got {decay!r}")
+    if adapt_sync is not None and not callable(adapt_sync):
+        raise ValueError(f"adapt_sync must be None or a callable applied to the {pooled}")
+    windows = int(until) // every
+    if windows == 0:
+        warnings.warn(f"{flag}=True but no window of {name}_every = {every} steps ends within the first "
+                      f"{until} burn-in steps: {idle}")
+    return {"every": every, "until": int(until), "gain": g, "decay": d, "sync": adapt_sync, "windows": windows, **rest}
+
+
 def check_adapt_args(adapt_scale, burn_in: int, adapt_every=50, adapt_until=None, adapt_target=0.234, adapt_gain=3.0,
                      adapt_decay=0.5, adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None) -> Optional[dict]:
     """The warm-up tuning arguments of EngineRun and the sampler classes (no GPU needed): None when off, else a dict with
@@ -172,41 +209,22 @@ def check_adapt_args(adapt_scale, burn_in: int, adapt_every=50, adapt_until=None
         raise ValueError(f"adapt_scale must be True or False, got {adapt_scale!r}")
     if not adapt_scale:
         return None
-    burn_in = int(burn_in)
-    if isinstance(adapt_every, bool) or not isinstance(adapt_every, (int, np.integer)) or adapt_every < 1:
-        raise ValueError(f"adapt_every must be an integer >= 1, got {adapt_every!r}")
-    if adapt_until is None:
-        adapt_until = burn_in
-    if isinstance(adapt_until, bool) or not isinstance(adapt_until, (int, np.integer)) or not 0 <= adapt_until <= burn_in:
-        raise ValueError(f"adapt_until must be an integer in 0..burn_in = {burn_in}, got {adapt_until!r}")
 
-    def number(name, v):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-            raise ValueError(f"{name} must be a finite number, got {v!r}")
-        return float(v)
+    def own(every):
+        target = _number("adapt_target", adapt_target)
+        if not 0.0 < target < 1.0:
+            raise ValueError(f"adapt_target must lie in (0, 1), got {adapt_target!r}")
+        try:
+            lo, hi = adapt_scale_bounds
+        except (TypeError, ValueError):
+            raise ValueError("adapt_scale_bounds must be a pair (lo, hi) of factors on the initial scales") from None
+        lo, hi = _number("adapt_scale_bounds lo", lo), _number("adapt_scale_bounds hi", hi)
+        if not 0.0 < lo <= hi:
+            raise ValueError(f"adapt_scale_bounds must satisfy 0 < lo <= hi, got {adapt_scale_bounds!r}")
+        return {"target": target, "bounds": (lo, hi)}
 
-    target, gain, decay = number("adapt_target", adapt_target), number("adapt_gain", adapt_gain), number("adapt_decay", adapt_decay)
-    if not 0.0 < target < 1.0:
-        raise ValueError(f"adapt_target must lie in (0, 1), got {adapt_target!r}")
-    if not gain > 0.0:
-        raise ValueError(f"adapt_gain must be positive, got {adapt_gain!r}")
-    if not 0.0 <= decay <= 1.0:
-        raise ValueError(f"adapt_decay must lie in 0..1, got {adapt_decay!r}")
-    try:
-        lo, hi = adapt_scale_bounds
-    except (TypeError, ValueError):
-        raise ValueError("adapt_scale_bounds must be a pair (lo, hi) of factors on the initial scales") from None
-    lo, hi = number("adapt_scale_bounds lo", lo), number("adapt_scale_bounds hi", hi)
-    if not 0.0 < lo <= hi:
-        raise ValueError(f"adapt_scale_bounds must satisfy 0 < lo <= hi, got {adapt_scale_bounds!r}")
-    if adapt_sync is not None and not callable(adapt_sync):
-        raise ValueError("adapt_sync must be None or a callable applied to the pooled [n_temps + 1] int64 tensor")
-    windows = int(adapt_until) // int(adapt_every)
-    if windows == 0:
-        warnings.warn(f"adapt_scale=True but no window of adapt_every = {adapt_every} steps ends within the first "
-                      f"{adapt_until} burn-in steps: nothing will adapt")
-    return {"every": int(adapt_every), "until": int(adapt_until), "target": target, "gain": gain, "decay": decay,
-            "bounds": (lo, hi), "sync": adapt_sync, "windows": windows}
+    return check_warmup_args("adapt_scale", "adapt", int(burn_in), adapt_every, adapt_until, adapt_gain, adapt_decay, adapt_sync,
+                             "pooled [n_temps + 1] int64 tensor", "nothing will adapt", own)
 
 
 def check_ladder_args(adapt_ladder, burn_in: int, beta_ladder=None, ladder_every=100, ladder_until=None, ladder_probe_every=None,
@@ -219,46 +237,22 @@ def check_ladder_args(adapt_ladder, burn_in: int, beta_ladder=None, ladder_every
         raise ValueError(f"adapt_ladder must be True or False, got {adapt_ladder!r}")
     if not adapt_ladder:
         return None
-    burn_in = int(burn_in)
 
-    def integer(name, v, lo):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
-            raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
-        return int(v)
+    def own(every):
+        probe_every = every if ladder_probe_every is None else _integer("ladder_probe_every", ladder_probe_every, 1)
+        if every % probe_every != 0:
+            raise ValueError(f"ladder_probe_every must divide ladder_every = {every}, got {ladder_probe_every!r}")
+        if beta_ladder is not None:
+            b = np.asarray(list(beta_ladder), np.float32)
+            if b.size < 3:
+                raise ValueError(f"adapt_ladder=True moves the interior temperatures: beta_ladder needs at least 3, got {b.size}")
+            if not (b > 0).all() or not (b[:-1] > b[1:]).all():
+                raise ValueError("adapt_ladder=True needs a beta_ladder that is positive and strictly decreasing in float32")
+        return {"probe_every": probe_every}
 
-    every = integer("ladder_every", ladder_every, 1)
-    if ladder_until is None:
-        ladder_until = burn_in
-    if isinstance(ladder_until, bool) or not isinstance(ladder_until, (int, np.integer)) or not 0 <= ladder_until <= burn_in:
-        raise ValueError(f"ladder_until must be an integer in 0..burn_in = {burn_in}, got {ladder_until!r}")
-    probe_every = every if ladder_probe_every is None else integer("ladder_probe_every", ladder_probe_every, 1)
-    if every % probe_every != 0:
-        raise ValueError(f"ladder_probe_every must divide ladder_every = {every}, got {ladder_probe_every!r}")
+    return check_warmup_args("adapt_ladder", "ladder", int(burn_in), ladder_every, ladder_until, ladder_gain, ladder_decay, adapt_sync,
+                             "pooled int64 tensor", "the ladder will not move", own)
 
-    def number(name, v):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-            raise ValueError(f"{name} must be a finite number, got {v!r}")
-        return float(v)
-
-    gain, decay = number("ladder_gain", ladder_gain), number("ladder_decay", ladder_decay)
-    if not gain > 0.0:
-        raise ValueError(f"ladder_gain must be positive, got {ladder_gain!r}")
-    if not 0.0 <= decay <= 1.0:
-        raise ValueError(f"ladder_decay must lie in 0..1, got {ladder_decay!r}")
-    if adapt_sync is not None and not callable(adapt_sync):
-        raise ValueError("adapt_sync must be None or a callable applied to the pooled int64 tensor")
-    if beta_ladder is not None:
-        b = np.asarray(list(beta_ladder), np.float32)
-        if b.size < 3:
-            raise ValueError(f"adapt_ladder=True moves the interior temperatures: beta_ladder needs at least 3, got {b.size}")
-        if not (b > 0).all() or not (b[:-1] > b[1:]).all():
-            raise ValueError("adapt_ladder=True needs a beta_ladder that is positive and strictly decreasing in float32")
-    windows = int(ladder_until) // every
-    if windows == 0:
-        warnings.warn(f"adapt_ladder=True but no window of ladder_every = {every} steps ends within the first "
-                      f"{ladder_until} burn-in steps: the ladder will not move")
-    return {"every": every, "until": int(ladder_until), "probe_every": probe_every, "gain": gain, "decay": decay,
-            "sync": adapt_sync, "windows": windows}
 
 
 def check_init_attempts(init_attempts) -> int:
@@ -285,6 +279,37 @@ def check_class_starts(dim: int, n_replicas: int, n_temps: int, initial_states, 
         states = initial_states.detach().clone() if torch.is_tensor(initial_states) else initial_states
         return "states", states, None
     return ("box" if box is not None else "point"), None, box
+
+
+class WarmupTuning:
+    """One warm-up tuning of a run - the ladder's as it stands, the proposal scale's as ScaleTuning: windows of `every` steps that
+    end at or before `until`, the last of them at step `end`; `pooled`, the current window's counts on the device; `sync`, the
+    caller's all-reduce of them (None: the library updates by itself); the tuning's other arrays as attributes."""
+
+    def __init__(self, args: dict, pooled: torch.Tensor, update, **arrays):
+        self.every, self.until, self.end, self.sync = args["every"], args["until"], args["windows"] * args["every"], args["sync"]
+        self.pooled, self.update = pooled, update  # (update: the plan's stand-alone update kernel of one window)
+        self.__dict__.update(arrays)
+
+    def window_end(self, window: int) -> None:
+        """What follows the last step of adapting window `window` where the library does not do it itself (split steps; with
+        adapt_sync): the caller's all-reduce of `pooled`, the update kernel."""
+        if self.sync is not None:
+            self.sync(self.pooled)
+        self.update(window)
+
+
+class ScaleTuning(WarmupTuning):
+    """... of the proposal scale.  `reduce`: the plan's stand-alone kernel that sums the window's per-replica counts into `pooled`
+    (split steps; None where launch() has done it)."""
+
+    def window_end(self, window: int) -> None:
+        if self.reduce is not None:
+            self.reduce()
+        if self.sync is not None:
+            self.sync(self.pooled)
+            self.count_history[window] = self.pooled[-1]  # chain-steps of every shard
+        self.update(window)
 
 
 class EngineRun:
@@ -460,36 +485,37 @@ class EngineRun:
             tiny, huge = float(np.finfo(np.float32).tiny), float(np.finfo(np.float32).max)
             lo = min(max(adapt["bounds"][0] * float(self.init_scales.min().item()), tiny), huge)
             hi = min(max(adapt["bounds"][1] * float(self.init_scales.max().item()), lo), huge)
-            self._adapt = {**adapt, "min_scale": lo, "max_scale": hi, "end": K * W,
-                           "window_accept": torch.zeros(shape, device=device, dtype=torch.int64),
-                           "pooled": torch.zeros(n_temps + 1, device=device, dtype=torch.int64),
-                           "scale_history": torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
-                           "accept_history": torch.zeros(K, n_temps, device=device, dtype=torch.int64),
-                           # chain-steps behind every row of accept_history (with adapt_sync: of every shard, recorded)
-                           "count_history": torch.full((K,), 0 if adapt["sync"] is not None else n_replicas * W,
-                                                       device=device, dtype=torch.int64)}
-            self._adapt["scale_history"][0] = self.init_scales
-            self._plan.set_adaptation(self._adapt["window_accept"], self._adapt["pooled"], every=W, until=adapt["until"],
+            self._adapt = ScaleTuning(
+                adapt, torch.zeros(n_temps + 1, device=device, dtype=torch.int64), self._plan.adapt_update,
+                reduce=self._plan.adapt_reduce if self.density_fn is not None else None,
+                window_accept=torch.zeros(shape, device=device, dtype=torch.int64),
+                scale_history=torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
+                accept_history=torch.zeros(K, n_temps, device=device, dtype=torch.int64),
+                # chain-steps behind every row of accept_history (with adapt_sync: of every shard, recorded)
+                count_history=torch.full((K,), 0 if adapt["sync"] is not None else n_replicas * W, device=device, dtype=torch.int64))
+            self._adapt.scale_history[0] = self.init_scales
+            self._plan.set_adaptation(self._adapt.window_accept, self._adapt.pooled, every=W, until=adapt["until"],
                                       target=adapt["target"], gain=adapt["gain"], decay=adapt["decay"], min_scale=lo,
                                       max_scale=hi, defer_update=adapt["sync"] is not None,
-                                      scale_history=self._adapt["scale_history"], accept_history=self._adapt["accept_history"])
+                                      scale_history=self._adapt.scale_history, accept_history=self._adapt.accept_history)
         # warm-up tuning of the temperature ladder, by two more small kernels between launches (off: None).  `beta` is the
         # run's own tensor: the update kernel rewrites it in place.
         self.init_beta = self.beta.clone()
         self._ladder = None
         if ladder is not None:
             K, V = ladder["windows"], ladder["every"]
-            self._ladder = {**ladder, "end": K * V,
-                            "pooled": torch.zeros(n_temps, device=device, dtype=torch.int64),
-                            "beta_history": torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
-                            # row j: the pooled row of window j - pair sums, and chain-probes in the last column
-                            "rate_history": torch.zeros(K, n_temps, device=device, dtype=torch.int64),
-                            "skipped": torch.zeros(1, device=device, dtype=torch.int64)}
-            self._ladder["beta_history"][0] = self.init_beta
-            self._plan.set_ladder(self._ladder["pooled"], every=V, probe_every=ladder["probe_every"], until=ladder["until"],
+            self._ladder = WarmupTuning(
+                ladder, torch.zeros(n_temps, device=device, dtype=torch.int64), self._plan.ladder_update,
+                probe_every=ladder["probe_every"],
+                beta_history=torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
+                # row j: the pooled row of window j - pair sums, and chain-probes in the last column
+                rate_history=torch.zeros(K, n_temps, device=device, dtype=torch.int64),
+                skipped=torch.zeros(1, device=device, dtype=torch.int64))
+            self._ladder.beta_history[0] = self.init_beta
+            self._plan.set_ladder(self._ladder.pooled, every=V, probe_every=ladder["probe_every"], until=ladder["until"],
                                   gain=ladder["gain"], decay=ladder["decay"], rescale_scales=True,
-                                  defer_update=ladder["sync"] is not None, beta_history=self._ladder["beta_history"],
-                                  rate_history=self._ladder["rate_history"], skipped=self._ladder["skipped"])
+                                  defer_update=ladder["sync"] is not None, beta_history=self._ladder.beta_history,
+                                  rate_history=self._ladder.rate_history, skipped=self._ladder.skipped)
         if box is not None:
             self._draw_starts(box, x0.to(torch.float32).contiguous(), bool(init_per_temperature), attempts)
 
@@ -540,30 +566,27 @@ class EngineRun:
         if self.density_fn is not None:
             self._advance_split(n_steps, trace, trace_logp, trace_row0, max(1, int(trace_every)))
             return
-        pending = self._pending_sync()
-        if pending:
-            # adapt_sync: one launch up to the nearer pending window end of either tuning (the library refuses to step past a
-            # pending update), the caller's all-reduce of that window's `pooled` and the update in between - the scale's
-            # before the ladder's where both end at the same step; ordinary launches from the end of warm-up
-            while n_steps > 0:
-                s = self.steps_done
-                pending = self._pending_sync()
-                n = min([n_steps] + [tu["every"] - s % tu["every"] for tu in pending])
-                self._launch(n, trace, trace_logp, trace_row0, trace_every)
-                if trace is not None:
-                    trace_row0 += ptrwm_hip.periodic_steps_in(s, s + n, max(1, int(trace_every)))
-                if any(tu is self._adapt for tu in pending) and (s + n) % self._adapt["every"] == 0:
-                    self._adapt_window_end((s + n) // self._adapt["every"] - 1, reduce=False)
-                if any(tu is self._ladder for tu in pending) and (s + n) % self._ladder["every"] == 0:
-                    self._ladder_window_end((s + n) // self._ladder["every"] - 1)
-                n_steps -= n
-            return
-        self._launch(n_steps, trace, trace_logp, trace_row0, trace_every)
+        # adapt_sync: one launch up to the nearer pending window end of either tuning (the library refuses to step past a pending
+        # update), the caller's all-reduce of that window's `pooled` and the update in between - the scale's before the
+        # ladder's where both end at the same step; ordinary launches from the end of warm-up
+        while n_steps > 0:
+            s, pending = self.steps_done, self._pending_sync()
+            if not pending:
+                break
+            n = min([n_steps] + [tu.every - s % tu.every for tu in pending])
+            self._launch(n, trace, trace_logp, trace_row0, trace_every)
+            if trace is not None:
+                trace_row0 += ptrwm_hip.periodic_steps_in(s, s + n, max(1, int(trace_every)))
+            for tu in pending:
+                if (s + n) % tu.every == 0:
+                    tu.window_end((s + n) // tu.every - 1)
+            n_steps -= n
+        if n_steps > 0:
+            self._launch(n_steps, trace, trace_logp, trace_row0, trace_every)
 
     def _pending_sync(self) -> list:
         """The tunings (scale, ladder) that defer their update to the caller and still have a window to end."""
-        return [tu for tu in (self._adapt, self._ladder)
-                if tu is not None and tu["sync"] is not None and self.steps_done < tu["end"]]
+        return [tu for tu in (self._adapt, self._ladder) if tu is not None and tu.sync is not None and self.steps_done < tu.end]
 
     def _launch(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> None:
         if trace is None and trace_logp is None:
@@ -572,34 +595,6 @@ class EngineRun:
             self._plan.launch(self.steps_done, n_steps, trace=trace, trace_logp=trace_logp, trace_row0=trace_row0,
                               trace_every=trace_every, swap_event_offset=self.manual_sweeps)
         self.steps_done += n_steps
-
-    def _adapt_window_end(self, window: int, reduce: bool) -> None:
-        """What follows the last step of adapting window `window` where the library does not do it itself (split steps; with
-        adapt_sync the update): the reduce kernel, the caller's all-reduce of `pooled`, the update kernel."""
-        ad = self._adapt
-        if reduce:
-            self._plan.adapt_reduce()
-        if ad["sync"] is not None:
-            ad["sync"](ad["pooled"])
-            ad["count_history"][window] = ad["pooled"][self.n_temps]
-        self._plan.adapt_update(window)
-
-    def _ladder_window_end(self, window: int) -> None:
-        """What follows the last probe of adapting ladder window `window` where the library does not do it itself (split
-        steps; with adapt_sync): the caller's all-reduce of `pooled`, the update kernel."""
-        ld = self._ladder
-        if ld["sync"] is not None:
-            ld["sync"](ld["pooled"])
-        self._plan.ladder_update(window)
-
-    def _ladder_after_split(self, s: int, n: int) -> None:
-        """Split steps: n steps from s (inside an adapting ladder window, never across a probe step) have run - the stand-alone
-        probe behind a probe step, the update behind a window's last."""
-        ld = self._ladder
-        if (s + n) % ld["probe_every"] == 0:
-            self._plan.ladder_probe()
-            if (s + n) % ld["every"] == 0:
-                self._ladder_window_end((s + n) // ld["every"] - 1)
 
     def beta_ladder(self) -> torch.Tensor:
         """The current ladder: float32 [n_temps] on the device (a copy)."""
@@ -613,10 +608,10 @@ class EngineRun:
         if self._ladder is None:
             return None
         ld = self._ladder
-        rows = ld["rate_history"].clone()
+        rows = ld.rate_history.clone()
         probes = rows[:, -1]
-        return {"betas": ld["beta_history"].clone(), "rates": rows[:, :-1].double() / (probes.double()[:, None] * 16777216.0),
-                "probes": probes.clone(), "pooled": rows, "skipped": int(ld["skipped"].item())}
+        return {"betas": ld.beta_history.clone(), "rates": rows[:, :-1].double() / (probes.double()[:, None] * 16777216.0),
+                "probes": probes.clone(), "pooled": rows, "skipped": int(ld.skipped.item())}
 
     # ---- warm-up tuning: read-outs -------------------------------------------------------------------------------
     def proposal_scales(self) -> torch.Tensor:
@@ -630,34 +625,9 @@ class EngineRun:
         if self._adapt is None:
             return None
         ad = self._adapt
-        return {"scales": ad["scale_history"].clone(),
-                "acceptance": ad["accept_history"].double() / ad["count_history"].double()[:, None],
-                "accepted": ad["accept_history"].clone()}
-
-    def _advance_split_warmup(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> int:
-        """n_steps eager split steps inside adapting windows by the recipe of include/ptrwm.h (acceptances counted into the
-        window scratch, no swap event), the reduce and update kernels at window ends; returns the rows traced."""
-        C, T, D = self.n_replicas, self.n_temps, self.dim
-        W, row = self._adapt["every"], trace_row0
-        self._plan.split_warmup(True)
-        try:
-            for _ in range(n_steps):
-                s = self.steps_done
-                props = self._plan.split_propose(s)
-                lp_new = self._density(props.view(-1, D)).view(C, T)
-                self._plan.split_accept(s, lp_new, swap_event_offset=self.manual_sweeps)
-                self.steps_done += 1
-                if trace is not None and ptrwm_hip.periodic_steps_in(s, s + 1, trace_every):
-                    tc, tt = trace.shape[1], trace.shape[2]
-                    trace[row] = self.state[:tc, :tt]
-                    if trace_logp is not None:
-                        trace_logp[row] = self.logp[:tc, :tt]
-                    row += 1
-                if (s + 1) % W == 0:
-                    self._adapt_window_end((s + 1) // W - 1, reduce=True)
-        finally:
-            self._plan.split_warmup(False)
-        return row - trace_row0
+        return {"scales": ad.scale_history.clone(),
+                "acceptance": ad.accept_history.double() / ad.count_history.double()[:, None],
+                "accepted": ad.accept_history.clone()}
 
     # ---- split steps through a captured HIP graph ------------------------------------------------------------
     # A split step is four launches of this library (proposal, Metropolis rule, swap event, step counter) around the
@@ -753,50 +723,55 @@ class EngineRun:
 
     def _advance_split(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> None:
         """n_steps split steps; traced steps (step_counter a multiple of trace_every) are copied with torch."""
-        ld = self._ladder
-        while n_steps > 0 and ld is not None and self.steps_done < ld["end"]:
-            # the ladder's windows: the host loop - and with it every captured block - ends at every probe step; the
-            # stand-alone probe follows, and the update at window ends (behind the scale's own kernels, which
-            # _advance_split_warmup enqueues with the step that ends its window)
+        ad, ld = self._adapt, self._ladder
+        while n_steps > 0:
+            # the host loop - and with it every captured block - ends with every adapting window of the scale and behind
+            # every probe step of an adapting window of the ladder; the stand-alone kernels follow in the library's order:
+            # the scale's reduce and update, the ladder's probe and, at a window's end, its update
             s = self.steps_done
-            k = min(n_steps, ld["probe_every"] - s % ld["probe_every"])
-            if self._adapt is not None and s < self._adapt["end"]:
-                k = min(k, self._adapt["end"] - s)
-                trace_row0 += self._advance_split_warmup(k, trace, trace_logp, trace_row0, trace_every)
-            else:
-                trace_row0 += self._advance_split_plain(k, trace, trace_logp, trace_row0, trace_every)
-            self._ladder_after_split(s, k)
+            warm, probing = ad is not None and s < ad.end, ld is not None and s < ld.end
+            k = min([n_steps] + ([ad.every - s % ad.every] if warm else []) + ([ld.probe_every - s % ld.probe_every] if probing else []))
+            trace_row0 += (self._split_steps(k, trace, trace_logp, trace_row0, trace_every, warmup=True) if warm else
+                           self._advance_split_plain(k, trace, trace_logp, trace_row0, trace_every))
+            if warm and (s + k) % ad.every == 0:
+                ad.window_end((s + k) // ad.every - 1)
+            if probing and (s + k) % ld.probe_every == 0:
+                self._plan.ladder_probe()
+                if (s + k) % ld.every == 0:
+                    ld.window_end((s + k) // ld.every - 1)
             n_steps -= k
-        if n_steps == 0:
-            return
-        if self._adapt is not None and self.steps_done < self._adapt["end"]:
-            k = min(n_steps, self._adapt["end"] - self.steps_done)
-            trace_row0 += self._advance_split_warmup(k, trace, trace_logp, trace_row0, trace_every)
-            n_steps -= k
-            if n_steps == 0:
-                return
-        self._advance_split_plain(n_steps, trace, trace_logp, trace_row0, trace_every)
 
     def _advance_split_plain(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> int:
         """n_steps ordinary split steps - by graph replay where nothing is traced - and the rows traced."""
         if trace is None and n_steps >= 2 and self.use_graph and self._advance_split_graph(n_steps):
             return 0
+        return self._split_steps(n_steps, trace, trace_logp, trace_row0, trace_every)
+
+    def _split_steps(self, n_steps, trace, trace_logp, trace_row0, trace_every, warmup: bool = False) -> int:
+        """n_steps eager split steps, and the rows traced.  `warmup`: inside an adapting window of the scale, by the recipe of
+        include/ptrwm.h - acceptances counted into the window scratch, no swap event, and nothing for the moments and the
+        histograms, which count from the end of burn-in."""
         C, T, D = self.n_replicas, self.n_temps, self.dim
         row = trace_row0
-        for _ in range(n_steps):
-            s = self.steps_done
-            props = self._plan.split_propose(s)
-            lp_new = self._density(props.view(-1, D)).view(C, T)
-            self._plan.split_accept(s, lp_new, swap_event_offset=self.manual_sweeps)
-            self._plan.split_moments(s)
-            self._plan.split_histogram(s)
-            self.steps_done += 1
-            if trace is not None and ptrwm_hip.periodic_steps_in(s, s + 1, trace_every):
-                tc, tt = trace.shape[1], trace.shape[2]
-                trace[row] = self.state[:tc, :tt]
-                if trace_logp is not None:
-                    trace_logp[row] = self.logp[:tc, :tt]
-                row += 1
+        self._plan.split_warmup(warmup)
+        try:
+            for _ in range(n_steps):
+                s = self.steps_done
+                props = self._plan.split_propose(s)
+                lp_new = self._density(props.view(-1, D)).view(C, T)
+                self._plan.split_accept(s, lp_new, swap_event_offset=self.manual_sweeps)
+                if not warmup:
+                    self._plan.split_moments(s)
+                    self._plan.split_histogram(s)
+                self.steps_done += 1
+                if trace is not None and ptrwm_hip.periodic_steps_in(s, s + 1, trace_every):
+                    tc, tt = trace.shape[1], trace.shape[2]
+                    trace[row] = self.state[:tc, :tt]
+                    if trace_logp is not None:
+                        trace_logp[row] = self.logp[:tc, :tt]
+                    row += 1
+        finally:
+            self._plan.split_warmup(False)
         return row - trace_row0
 
     def swap_sweep(self) -> None:
@@ -1308,4 +1283,4 @@ class LadderAdaptation:
         run = getattr(self, "_run", None)
         return {"adapted_beta_ladder": self.adapted_beta_ladder(),
                 "init_beta_ladder": [float(np.float32(b)) for b in self._init_beta_ladder],
-                "ladder_updates_skipped": int(run._ladder["skipped"].item()) if run is not None else 0}
+                "ladder_updates_skipped": int(run._ladder.skipped.item()) if run is not None else 0}

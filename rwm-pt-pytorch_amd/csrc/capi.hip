@@ -1115,8 +1115,8 @@ static int32_t launch_hist(const ptrwm_run_args *args, int32_t dim, const ptrwm_
 }
 
 // the adaptation checks shared by ptrwm_run_with_adaptation, ptrwm_adapt_reduce and ptrwm_adapt_update (none: ok); what
-// needs the run (until <= burn_in, temp_scale == proposal->temp_scale) is checked by ptrwm_run_with_adaptation itself
-static int32_t check_adapt(const ptrwm_adapt_args *ad) {
+// needs the run (until <= burn_in, temp_scale == proposal->temp_scale) is checked by run_impl itself (tuning_fits_run)
+static int32_t check_tuning(const ptrwm_adapt_args *ad) {
   if (ad == nullptr) return PTRWM_OK;
   if (ad->struct_size != sizeof(ptrwm_adapt_args)) return PTRWM_E_STRUCT;
   if (ad->temp_scale == nullptr || ad->window_accept == nullptr || ad->pooled == nullptr) return PTRWM_E_NULL;
@@ -1152,7 +1152,7 @@ static int32_t launch_adapt_update(const ptrwm_adapt_args *ad, int n_temps, long
   a.scale_history = ad->scale_history;
   a.accept_history = (long long *)ad->accept_history;
   a.window = window;
-  a.gain_k = adapt_gain((double)ad->gain, (double)ad->decay, window);
+  a.gain_k = window_gain((double)ad->gain, (double)ad->decay, window);
   a.target = (double)ad->target;
   a.min_scale = ad->min_scale;
   a.max_scale = ad->max_scale;
@@ -1164,7 +1164,7 @@ static_assert(PTRWM_MAX_TEMPS <= 256, "adapt_update_kernel: one thread per tempe
 
 // the ladder checks shared by ptrwm_run_with_ladder, ptrwm_ladder_probe and ptrwm_ladder_update (none: ok); what needs the run
 // (until <= burn_in, the pointer identities, n_temps) is checked by the callers
-static int32_t check_ladder(const ptrwm_ladder_args *ld) {
+static int32_t check_tuning(const ptrwm_ladder_args *ld) {
   if (ld == nullptr) return PTRWM_OK;
   if (ld->struct_size != sizeof(ptrwm_ladder_args)) return PTRWM_E_STRUCT;
   if (ld->beta == nullptr || ld->pooled == nullptr || (ld->rescale_scales == 1 && ld->temp_scale == nullptr)) return PTRWM_E_NULL;
@@ -1200,12 +1200,34 @@ static int32_t launch_ladder_update(const ptrwm_ladder_args *ld, int n_temps, lo
   a.rate_history = (long long *)ld->rate_history;
   a.skipped = (long long *)ld->skipped;
   a.window = window;
-  a.gain_j = ladder_gain((double)ld->gain, (double)ld->decay, window);
+  a.gain_j = window_gain((double)ld->gain, (double)ld->decay, window);
   a.n_temps = n_temps;
   hipLaunchKernelGGL(ladder_update_kernel, dim3(1), dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 static_assert(PTRWM_MAX_TEMPS <= 256, "ladder_update_kernel: one thread per temperature in one 256-thread workgroup");
+
+// What the four stand-alone calls of the two tunings check first.  The calls between launches (ptrwm_adapt_reduce,
+// ptrwm_ladder_probe) take the run's arguments; the updates take n_temps and the window, one of the K the histories have rows for.
+template <class Tuning>
+static int32_t check_tuning_call(const Tuning *tu, bool per_run, const ptrwm_run_args *args, int32_t n_temps, int64_t window) {
+  if (tu == nullptr || (per_run && args == nullptr)) return PTRWM_E_NULL;
+  if (per_run && !has_abi_size(args)) return PTRWM_E_STRUCT;
+  if (!temps_in_range(per_run ? args->n_temps : n_temps)) return PTRWM_E_TEMPS;
+  if (per_run && args->n_chains < 0) return PTRWM_E_ARG;
+  if (int rc = check_tuning(tu)) return rc;
+  if (!per_run && (window < 0 || window >= window_count({tu->every, tu->until}))) return PTRWM_E_ARG;
+  return PTRWM_OK;
+}
+
+// What a tuning asks of the run it is bound to (tu != nullptr, its own checks passed): windows that end within burn-in, the
+// run's own array (the scale's temp_scale, the ladder's beta), and - where the caller applies the update between requests
+// (defer_update) - no request that steps past a window end that awaits it
+template <class Tuning>
+static bool tuning_fits_run(const Tuning *tu, const ptrwm_run_args *args, const void *tuned, const void *of_run) {
+  return tu->until <= args->burn_in && tuned == of_run &&
+         (tu->defer_update == 0 || request_within_window({tu->every, tu->until}, args->step0, args->n_steps));
+}
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                         const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist = nullptr,
@@ -1350,20 +1372,13 @@ int32_t ptrwm_run_with_adaptation(const ptrwm_target_desc *target, const ptrwm_p
 }
 
 int32_t ptrwm_adapt_reduce(const ptrwm_run_args *args, const ptrwm_adapt_args *adapt, void *stream) {
-  if (args == nullptr || adapt == nullptr) return PTRWM_E_NULL;
-  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
-  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
-  if (args->n_chains < 0) return PTRWM_E_ARG;
-  if (int rc = check_adapt(adapt)) return rc;
+  if (int rc = check_tuning_call(adapt, true, args, 0, 0)) return rc;
   if (args->n_chains == 0) return PTRWM_OK;
   return launch_adapt_reduce(adapt, args->n_chains, args->n_temps, (hipStream_t)stream);
 }
 
 int32_t ptrwm_adapt_update(const ptrwm_adapt_args *adapt, int32_t n_temps, int64_t window, void *stream) {
-  if (adapt == nullptr) return PTRWM_E_NULL;
-  if (!temps_in_range(n_temps)) return PTRWM_E_TEMPS;
-  if (int rc = check_adapt(adapt)) return rc;
-  if (window < 0 || window >= adapt_window_count(adapt->every, adapt->until)) return PTRWM_E_ARG;  // (the histories have K rows)
+  if (int rc = check_tuning_call(adapt, false, nullptr, n_temps, window)) return rc;
   return launch_adapt_update(adapt, n_temps, window, (hipStream_t)stream);
 }
 
@@ -1376,11 +1391,7 @@ int32_t ptrwm_run_with_ladder(const ptrwm_target_desc *target, const ptrwm_propo
 }
 
 int32_t ptrwm_ladder_probe(const ptrwm_run_args *args, const ptrwm_ladder_args *ladder, void *stream) {
-  if (args == nullptr || ladder == nullptr) return PTRWM_E_NULL;
-  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
-  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
-  if (args->n_chains < 0) return PTRWM_E_ARG;
-  if (int rc = check_ladder(ladder)) return rc;
+  if (int rc = check_tuning_call(ladder, true, args, 0, 0)) return rc;
   if (args->n_temps < 3 || ladder->beta != args->beta) return PTRWM_E_ARG;
   if (args->n_chains == 0) return PTRWM_OK;
   if (args->logp == nullptr) return PTRWM_E_NULL;
@@ -1388,11 +1399,8 @@ int32_t ptrwm_ladder_probe(const ptrwm_run_args *args, const ptrwm_ladder_args *
 }
 
 int32_t ptrwm_ladder_update(const ptrwm_ladder_args *ladder, int32_t n_temps, int64_t window, void *stream) {
-  if (ladder == nullptr) return PTRWM_E_NULL;
-  if (!temps_in_range(n_temps)) return PTRWM_E_TEMPS;
-  if (int rc = check_ladder(ladder)) return rc;
-  if (n_temps < 3) return PTRWM_E_ARG;
-  if (window < 0 || window >= ladder_window_count(ladder->every, ladder->until)) return PTRWM_E_ARG;  // (the histories have K rows)
+  if (int rc = check_tuning_call(ladder, false, nullptr, n_temps, window)) return rc;
+  if (n_temps < 3) return PTRWM_E_ARG;  // (the same code as a window out of range: their order does not show)
   return launch_ladder_update(ladder, n_temps, window, (hipStream_t)stream);
 }
 
@@ -1612,26 +1620,21 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
                         const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder) {
   bool empty = false;
   if (int rc = check_run(target, proposal, args, spec, flow, hist, &empty)) return rc;
-  // adaptation (adapt.h): its own checks after the existing ones, all before anything is enqueued
-  if (int rc = check_adapt(adapt)) return rc;
-  if (adapt != nullptr) {
-    if (adapt->until > args->burn_in || adapt->temp_scale != proposal->temp_scale) return PTRWM_E_ARG;
-    // defer_update: the caller applies the update between requests, so none may step past a window end that awaits it
-    if (adapt->defer_update == 1 && !adapt_request_within_window(args->step0, args->n_steps, adapt->every, adapt->until))
-      return PTRWM_E_ARG;
-  }
-  // the ladder (ladder.h): likewise
-  if (int rc = check_ladder(ladder)) return rc;
+  // the two tunings (adapt.h, ladder.h): their own checks after the existing ones, all before anything is enqueued
+  if (int rc = check_tuning(adapt)) return rc;
+  if (adapt != nullptr && !tuning_fits_run(adapt, args, adapt->temp_scale, proposal->temp_scale)) return PTRWM_E_ARG;
+  if (int rc = check_tuning(ladder)) return rc;
   if (ladder != nullptr) {
-    if (args->n_temps < 3 || ladder->until > args->burn_in || ladder->beta != args->beta) return PTRWM_E_ARG;
+    if (args->n_temps < 3 || !tuning_fits_run(ladder, args, ladder->beta, args->beta)) return PTRWM_E_ARG;
     if (ladder->temp_scale != nullptr && ladder->temp_scale != proposal->temp_scale) return PTRWM_E_ARG;
-    if (ladder->defer_update == 1 && !ladder_request_within_window(args->step0, args->n_steps, ladder->every, ladder->until))
-      return PTRWM_E_ARG;
   }
   if (empty) return PTRWM_OK;
+  // (every = 0: no such tuning, schedule.h)
+  const WarmupWindows scale_w = adapt != nullptr ? WarmupWindows{adapt->every, adapt->until} : WarmupWindows{0, 0};
+  const WarmupWindows ladder_w = ladder != nullptr ? WarmupWindows{ladder->every, ladder->until} : WarmupWindows{0, 0};
   // (a request that touches an adapting window keeps to the classic kernels: the streaming form prefetches the counters
   // it adds to, and a warm-up launch has no squared-jump sum)
-  const bool adapts = adapt != nullptr && adapt_step_adapts(args->step0, adapt->every, adapt->until);
+  const bool adapts = step_adapts(scale_w, args->step0);
   const RunChoice c = choose_kernel(target, proposal, args, spec, flow != nullptr, (hipStream_t)hip_stream, !adapts);
   if (c.status != PTRWM_OK) return c.status;
   KArgs k = fill_kargs(target, proposal, args, spec, flow, c);
@@ -1650,25 +1653,22 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   for (long long done = 0; done < args->n_steps; done += k.n_steps) {
     // (histograms: a launch also ends at every due snapshot step - the snapshot kernel reads the state between launches)
     const long long to_snap = hist != nullptr ? steps_to_next_due(args->step0 + done, args->burn_in, hist->every) : cap;
-    // (adaptation: a launch inside an adapting window ends with the window at the latest - the reduce and update kernels
-    // run between two launches - and is the production kernel told to count from its first step, into the window scratch,
-    // and that no multiple of swap_every lies in it: count_on holds and swap_due never does, kernel.h)
-    const AdaptCut ac = adapt != nullptr ? adapt_cut_at(args->step0 + done, adapt->every, adapt->until) : AdaptCut{false, 0, 0};
-    long long lim = to_snap < cap ? to_snap : cap;
-    if (ac.adapting && ac.to_end < lim) lim = ac.to_end;
-    // (the ladder: a launch that starts in an adapting ladder window ends behind the next probe step at the latest - the
+    // (the tunings, schedule.h warmup_launch_at: a launch inside an adapting window of the scale ends with the window at the
+    // latest - the reduce and update kernels run between two launches - and is the production kernel told to count from its
+    // first step, into the window scratch, and that no multiple of swap_every lies in it: count_on holds and swap_due never
+    // does, kernel.h.  One that starts in an adapting window of the ladder ends behind the next probe step at the latest - the
     // probe kernel reads logp between two launches - and is otherwise told nothing: an ordinary burn-in launch)
-    const LadderCut lc = ladder != nullptr ? ladder_cut_at(args->step0 + done, ladder->every, ladder->probe_every, ladder->until)
-                                           : LadderCut{false, 0, 0};
-    if (lc.adapting && lc.to_probe < lim) lim = lc.to_probe;
-    const LaunchCut cut = launch_at(req, done, lim);
+    const WarmupLaunch wl = warmup_launch_at(args->step0 + done, launch_steps(req, done, to_snap < cap ? to_snap : cap), scale_w,
+                                             adapt != nullptr && adapt->defer_update == 1, ladder_w,
+                                             ladder != nullptr ? ladder->probe_every : 1, ladder != nullptr && ladder->defer_update == 1);
+    const LaunchCut cut = launch_at(req, done, wl.n);
     k.step0 = cut.step0;
     k.n_steps = cut.n;
-    k.burn_left = ac.adapting ? 0 : cut.burn_left;
+    k.burn_left = wl.warmup ? 0 : cut.burn_left;
     k.first_swap_event = cut.first_swap_event;
-    k.steps_to_swap = ac.adapting ? kNoStepInLaunch : cut.steps_to_swap;
-    k.n_accept = ac.adapting ? (long long *)adapt->window_accept : (long long *)args->n_accept;
-    k.sq_jump = ac.adapting ? nullptr : args->sq_jump;
+    k.steps_to_swap = wl.warmup ? kNoStepInLaunch : cut.steps_to_swap;
+    k.n_accept = wl.warmup ? (long long *)adapt->window_accept : (long long *)args->n_accept;
+    k.sq_jump = wl.warmup ? nullptr : args->sq_jump;
     k.full.ext_prop = ext ? args->ext_prop + done * reps * raw * (args->state_f64 == 1 ? 2 : 1) : nullptr;  // (f64: a double array)
     k.full.ext_u = ext ? args->ext_u + done * reps : nullptr;
     k.full.ext_swap_u = (ext && args->ext_swap_u != nullptr) ? args->ext_swap_u + cut.events_before * args->n_chains * (args->n_temps - 1) : nullptr;
@@ -1684,16 +1684,14 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
     if (c.fn(k, c.n_blocks, c.mode, (hipStream_t)hip_stream) != hipSuccess) return PTRWM_E_LAUNCH;
     if (hist != nullptr && periodic_step_due(cut.step0 + cut.n, args->burn_in, hist->every))
       if (int rc = launch_hist(args, target->dim, hist, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
-    if (ac.adapting && adapt_launch_ends_window(cut.step0, cut.n, adapt->every)) {
+    if (wl.scale_reduce)
       if (int rc = launch_adapt_reduce(adapt, args->n_chains, args->n_temps, (hipStream_t)hip_stream)) return rc;
-      if (adapt->defer_update == 0)
-        if (int rc = launch_adapt_update(adapt, args->n_temps, ac.window, (hipStream_t)hip_stream)) return rc;
-    }
-    if (lc.adapting && ladder_launch_ends_at_probe(cut.step0, cut.n, ladder->probe_every)) {  // (behind the scale's kernels)
+    if (wl.scale_update)
+      if (int rc = launch_adapt_update(adapt, args->n_temps, wl.scale_window, (hipStream_t)hip_stream)) return rc;
+    if (wl.ladder_probe)  // (behind the scale's kernels)
       if (int rc = launch_ladder_probe(ladder, args->logp, args->n_chains, args->n_temps, (hipStream_t)hip_stream)) return rc;
-      if (ladder->defer_update == 0 && ladder_launch_ends_window(cut.step0, cut.n, ladder->every))
-        if (int rc = launch_ladder_update(ladder, args->n_temps, lc.window, (hipStream_t)hip_stream)) return rc;
-    }
+    if (wl.ladder_update)
+      if (int rc = launch_ladder_update(ladder, args->n_temps, wl.ladder_window, (hipStream_t)hip_stream)) return rc;
   }
   return PTRWM_OK;
 }

@@ -1,13 +1,12 @@
-// Warm-up tuning of the temperature ladder, stated once: which steps of burn-in belong to an adapting ladder window, which of
-// them are probe steps, what a probe adds to the pooled counts, and the update of the ladder from one window's counts.  Plain
-// C++ (no HIP include): the probe and update kernels and the host paths of capi.hip use it, and tests/ladder_test.cpp replays
-// it on the CPU against a brute-force loop and NumPy float64 (tests/ladder_reference.py).
+// Warm-up tuning of the temperature ladder: what a probe adds to the pooled counts, and the update of the ladder from one
+// window's counts.  Plain C++ (no HIP include): the probe and update kernels of capi.hip use it, and tests/ladder_test.cpp checks
+// it on the CPU against NumPy float64 (tests/ladder_reference.py).
 //
-// Windows.  With V = every, window j is the steps [j V, (j + 1) V) (steps are numbered from 0, schedule.h).  The ADAPTING
-// windows are those that end at or before `until` ((j + 1) V <= until, until <= burn_in): K = until / V of them, the steps
-// [0, K V).  Steps [K V, burn_in) are ordinary burn-in under the final ladder, and past burn-in nothing adapts: what is
-// sampled is a fixed-ladder chain.  Everything is a function of the step index counted from the start of the RUN, so a run cut
-// into calls anywhere adapts at the same steps.
+// Windows.  With V = every, window j is the steps [j V, (j + 1) V); the ADAPTING windows are those that end at or before `until`
+// (<= burn_in).  Steps behind them are ordinary burn-in under the final ladder, and past burn-in nothing adapts: what is sampled
+// is a fixed-ladder chain.  Everything is a function of the step index counted from the start of the RUN, so a run cut into
+// calls anywhere adapts at the same steps.  The arithmetic of the windows and of the probe steps, and what follows a launch that
+// ends behind one, is schedule.h's (WarmupWindows, warmup_launch_at).
 //
 // Probes.  Step s of an adapting window is a PROBE step when (s + 1) % probe_every == 0; probe_every divides V, so a window's
 // last step is always one.  Burn-in has no swap events and the probe adds none: it measures, from the states as they stand
@@ -24,7 +23,7 @@
 //   r_t   = pooled[t] / (pooled[T - 1] * 2^24)                  the pair's mean swap probability over the window
 //   rbar  = (r_0 + r_1 + ... + r_{T-2}) / (T - 1)
 //   g_t   = log(beta_t) - log(beta_{t+1}),   G = g_0 + ... + g_{T-2}
-//   h_t   = log(g_t) + gain_j (r_t - rbar)                      gain_j = gain / (j + 1)^decay, on the host (ladder_gain)
+//   h_t   = log(g_t) + gain_j (r_t - rbar)                      gain_j = gain / (j + 1)^decay, on the host (window_gain)
 //   w_t   = exp(h_t - max h),   S = w_0 + ... + w_{T-2},   c_t = w_0 + ... + w_t
 //   beta_new[t + 1] = (float) ((double) beta_0 * exp(-G c_t / S))        t = 0 .. T - 3
 // beta_0 and beta_{T-1} keep their bits.  A pair that swaps more often than the average is widened, one that swaps less is
@@ -37,72 +36,12 @@
 
 #include <cmath>
 
-#ifndef PTRWM_HD
-#ifdef __HIPCC__
-#define PTRWM_HD __host__ __device__
-#else
-#define PTRWM_HD
-#endif
-#endif
+#include "schedule.h"
 
 namespace ptrwm {
 
-// K: the adapting windows of a run (every >= 1, until >= 0)
-PTRWM_HD inline long long ladder_window_count(long long every, long long until) { return until / every; }
-
-// the window step s lies in
-PTRWM_HD inline long long ladder_window_of(long long step, long long every) { return step / every; }
-
-// does window j adapt?
-PTRWM_HD inline bool ladder_window_adapts(long long j, long long every, long long until) { return (j + 1) * every <= until; }
-
-// does step s lie in an adapting window?  (s < K V)
-PTRWM_HD inline bool ladder_step_adapts(long long step, long long every, long long until) {
-  return ladder_window_adapts(ladder_window_of(step, every), every, until);
-}
-
-// is step s a probe step?  (probe_every divides every)
-PTRWM_HD inline bool ladder_step_probes(long long step, long long every, long long probe_every, long long until) {
-  return ladder_step_adapts(step, every, until) && (step + 1) % probe_every == 0;
-}
-
-// steps from s up to and including the next step with (s' + 1) % probe_every == 0 (1 = s is one itself): a launch of that
-// many steps from s ends exactly behind it.  ptrwm_run_with_ladder min-s it into the cap of launch_at for a step of an
-// adapting window.
-PTRWM_HD inline long long ladder_steps_to_probe(long long step, long long probe_every) { return probe_every - step % probe_every; }
-
-// steps from s to the end of its window (1 = s is the window's last step)
-PTRWM_HD inline long long ladder_steps_to_window_end(long long step, long long every) { return every - step % every; }
-
-// gain_j = gain / (j + 1)^decay, on the host in double (as adapt_gain)
-inline double ladder_gain(double gain, double decay, long long window) { return gain / std::pow((double)(window + 1), decay); }
-
 // what one (chain, pair, probe) adds to pooled[t], from the threshold of swap_accept_test
 PTRWM_HD inline long long ladder_quantum(float thr) { return thr == thr ? llrint((double)thr * 16777216.0) : 0ll; }
-
-// What one launch of a request is told about the ladder's tuning (host).
-struct LadderCut {
-  bool adapting;       // the launch's first step lies in an adapting window: it ends behind the next probe step at the latest
-  long long window;    // its window (adapting only)
-  long long to_probe;  // steps up to and including the next probe step: the launch's cap (adapting only)
-};
-inline LadderCut ladder_cut_at(long long step, long long every, long long probe_every, long long until) {
-  LadderCut c;
-  c.adapting = ladder_step_adapts(step, every, until);
-  c.window = ladder_window_of(step, every);
-  c.to_probe = ladder_steps_to_probe(step, probe_every);
-  return c;
-}
-
-// did a launch of n steps from `step` (inside an adapting window, n <= to_probe) end behind a probe step / end its window?
-inline bool ladder_launch_ends_at_probe(long long step, long long n, long long probe_every) { return (step + n) % probe_every == 0; }
-inline bool ladder_launch_ends_window(long long step, long long n, long long every) { return (step + n) % every == 0; }
-
-// defer_update: may a request of n steps from step0 run?  Not if it would step past the end of the adapting window step0 lies
-// in - that window's update is then still pending (the caller all-reduces pooled and calls ptrwm_ladder_update first).
-inline bool ladder_request_within_window(long long step0, long long n, long long every, long long until) {
-  return !ladder_step_adapts(step0, every, until) || n <= ladder_steps_to_window_end(step0, every);
-}
 
 enum LadderOutcome { kLadderUpdated = 0, kLadderNoProbes = 1, kLadderSkipped = 2 };
 

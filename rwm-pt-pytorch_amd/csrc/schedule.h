@@ -1,12 +1,15 @@
 // The step schedule of a run, stated once: which step counters are past burn-in, which of them carry a swap event, a traced
 // row or an accumulated step of the moments, how many of each lie in a range of steps, and where ptrwm_run cuts a long
-// request into launches.  Plain C++ (no HIP include): the kernels and host paths of capi.hip use it, and
-// tests/schedule_test.cpp replays it step by step on the CPU.
+// request into launches - and the warm-up windows of burn-in: which steps the proposal scale's and the ladder's tuning (adapt.h,
+// ladder.h) adapt in, where their windows end, and what follows a launch that ends there.  Plain C++ (no HIP include): the
+// kernels and host paths of capi.hip use it, and tests/schedule_test.cpp replays it step by step on the CPU.
 //
 // Steps are numbered from 0; step s has step_counter sc = s + 1 (the reference counts a step when it has happened), so a
 // call with step0 covers the step counters (step0, step0 + n_steps].  What is periodic happens at the multiples of its
 // period, counted from the start of the RUN (not of the call): that is what makes a cut, or a resumed run, invisible.
 #pragma once
+
+#include <cmath>
 
 #ifdef __HIPCC__
 #define PTRWM_HD __host__ __device__
@@ -94,13 +97,16 @@ struct LaunchCut {
 inline long long steps_to_step_word_wrap(long long step0) { return (1ll << 32) - (step0 & 0xffffffffll); }
 
 // The launch of `r` that starts `done` steps into it, at most `cap` steps long (1 <= cap <= 2^16: max_steps_per_launch) and
-// ending where the step index's high word changes, if that comes first
+// ending where the step index's high word changes, if that comes first: its length, and all of it
+inline long long launch_steps(const StepRequest &r, long long done, long long cap) {
+  const long long to_wrap = steps_to_step_word_wrap(r.step0 + done);
+  if (to_wrap < cap) cap = to_wrap;
+  return r.n_steps - done < cap ? r.n_steps - done : cap;
+}
 inline LaunchCut launch_at(const StepRequest &r, long long done, long long cap) {
   LaunchCut c;
   c.step0 = r.step0 + done;
-  const long long to_wrap = steps_to_step_word_wrap(c.step0);
-  if (to_wrap < cap) cap = to_wrap;
-  const long long n = r.n_steps - done < cap ? r.n_steps - done : cap;
+  const long long n = launch_steps(r, done, cap);
   c.n = (int)n;
   const long long burn_left = r.burn_in - c.step0;
   c.burn_left = burn_left <= 0 ? 0 : (burn_left > n ? (int)n : (int)burn_left);
@@ -112,6 +118,74 @@ inline LaunchCut launch_at(const StepRequest &r, long long done, long long cap) 
   c.steps_to_trace = (int)steps_to_next_multiple(c.step0, r.trace_every);
   c.steps_to_mom = (int)steps_to_next_multiple(c.step0, r.moments_every);
   return c;
+}
+
+// ---- warm-up windows -----------------------------------------------------------------------------------------------------------
+// A tuning of burn-in (the proposal scale's, adapt.h; the ladder's, ladder.h) works in windows of `every` steps: window k is the
+// steps [k every, (k + 1) every), and the ADAPTING windows are those that end at or before `until` (<= burn_in): K = until /
+// every of them, the steps [0, K every).  What lies behind is ordinary burn-in.  every = 0: no such tuning, nothing adapts.
+struct WarmupWindows {
+  long long every, until;
+};
+
+// K: the adapting windows of a run
+inline long long window_count(const WarmupWindows &w) { return w.every > 0 ? w.until / w.every : 0; }
+
+// the window step s lies in
+inline long long window_of(const WarmupWindows &w, long long step) { return step / w.every; }
+
+// does step s lie in an adapting window?  (s < K every)
+inline bool step_adapts(const WarmupWindows &w, long long step) { return w.every > 0 && window_of(w, step) < window_count(w); }
+
+// steps from s to the end of its window (1 = s is the window's last step): a launch of that many steps from s ends exactly
+// where the window does
+inline long long steps_to_window_end(const WarmupWindows &w, long long step) { return steps_to_next_multiple(step, w.every); }
+
+// did a launch of n steps from `step` (inside an adapting window, n <= steps_to_window_end) end its window?
+inline bool launch_ends_window(const WarmupWindows &w, long long step, long long n) { return (step + n) % w.every == 0; }
+
+// A tuning that defers its update to the caller: may a request of n steps from step0 run?  Not if it would step past the end of
+// the adapting window step0 lies in - that window's update is then still pending (the caller all-reduces the pooled counts and
+// calls the stand-alone update first).
+inline bool request_within_window(const WarmupWindows &w, long long step0, long long n) {
+  return !step_adapts(w, step0) || n <= steps_to_window_end(w, step0);
+}
+
+// the gain of window k's update, gain / (k + 1)^decay: on the host in double, the device needs no pow
+inline double window_gain(double gain, double decay, long long window) { return gain / std::pow((double)(window + 1), decay); }
+
+// One launch of a request under the two tunings, and the small kernels behind it - in this order, after the histogram's
+// snapshot: the scale's reduce and update, the ladder's probe and update.
+struct WarmupLaunch {
+  long long n;                       // its steps (<= cap)
+  bool warmup;                       // it runs with the scale's warm-up overrides: acceptances counted from its first step, into
+                                     // the window scratch, and no swap event
+  bool scale_reduce, scale_update;   // it ends a window of the scale: the window's counts are pooled; the update follows
+  bool ladder_probe, ladder_update;  // it ends behind a probe step of the ladder; ... a window's last: the update follows
+  long long scale_window, ladder_window;  // the windows of the two updates
+};
+
+// The launch from `step` of at most `cap` steps (launch_steps: what the request and the step kernels allow).  Inside an adapting
+// window of the scale it ends with the window at the latest, inside one of the ladder behind the next probe step - the steps s
+// with (s + 1) % probe_every == 0; probe_every divides ladder.every, so a window's last step is one.  A tuning that defers its
+// update (defer_*) gets the kernels that pool its counts and leaves the update to the caller.
+inline WarmupLaunch warmup_launch_at(long long step, long long cap, const WarmupWindows &scale, bool defer_scale,
+                                     const WarmupWindows &ladder, long long probe_every, bool defer_ladder) {
+  WarmupLaunch l = {cap, step_adapts(scale, step), false, false, false, false, 0, 0};
+  const bool probing = step_adapts(ladder, step);
+  if (l.warmup && steps_to_window_end(scale, step) < l.n) l.n = steps_to_window_end(scale, step);
+  if (probing && steps_to_next_multiple(step, probe_every) < l.n) l.n = steps_to_next_multiple(step, probe_every);
+  if (l.warmup) {
+    l.scale_window = window_of(scale, step);
+    l.scale_reduce = launch_ends_window(scale, step, l.n);
+    l.scale_update = l.scale_reduce && !defer_scale;
+  }
+  if (probing) {
+    l.ladder_window = window_of(ladder, step);
+    l.ladder_probe = (step + l.n) % probe_every == 0;
+    l.ladder_update = l.ladder_probe && !defer_ladder && launch_ends_window(ladder, step, l.n);
+  }
+  return l;
 }
 
 }  // namespace ptrwm

@@ -801,6 +801,33 @@ class RunPlan:
         h.count = _opt(count, "histogram count", torch.int64)
         self._hist = (h, C.byref(h), (counts, lo, scale, count))
 
+    def _tuning_windows(self, what: str, every, until) -> tuple:
+        """every, until and K = until // every of a warm-up tuning (`what` starts its messages), checked against the plan"""
+        every, until = int(every), int(until)
+        if every < 1:
+            raise ValueError(f"{what} every must be >= 1")
+        if not 0 <= until <= self._a.burn_in:
+            raise ValueError(f"{what} until must be in 0..burn_in = {self._a.burn_in}, got {until}")
+        return every, until, until // every
+
+    def _tuning_tensors(self, what: str, tensors) -> None:
+        """(name, tensor, shape, required) of a warm-up tuning: every tensor given - and every required one - has its shape and
+        sits on the plan's device"""
+        for name, t, shape, required in tensors:
+            if (t is None and required) or (t is not None and (tuple(t.shape) != shape or t.device != self.device)):
+                raise ValueError(f"{what} {name} must be a {list(shape)} tensor on {self.device}")
+
+    def _tuning_call(self, name: str, bound, missing: str, window: Optional[int] = None) -> None:
+        """A stand-alone kernel of a warm-up tuning, ptrwm_<name>: the ones between launches take the run's arguments, the
+        updates (`window` given) n_temps and the window"""
+        if bound is None:
+            raise RuntimeError(f"{name}: no {missing}")
+        args = (self._refs[4], bound[1]) if window is None else (bound[1], self.shape[1], int(window))
+        with self._guard:
+            rc = getattr(self._lib, "ptrwm_" + name)(*args, _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_" + name)
+
     def set_adaptation(self, window_accept: Optional[torch.Tensor], pooled: Optional[torch.Tensor] = None, *, every: int = 50,
                        until: int = 0, target: float = 0.234, gain: float = 3.0, decay: float = 0.5,
                        min_scale: float = 1e-30, max_scale: float = 1e30, defer_update: bool = False,
@@ -815,19 +842,11 @@ class RunPlan:
             self._adapt = None
             return
         Cn, T, _ = self.shape
-        every, until = int(every), int(until)
-        if every < 1:
-            raise ValueError("adaptation every must be >= 1")
-        if not 0 <= until <= self._a.burn_in:
-            raise ValueError(f"adaptation until must be in 0..burn_in = {self._a.burn_in}, got {until}")
-        K = until // every
+        every, until, K = self._tuning_windows("adaptation", every, until)
         scale = self._keep[1].temp_scale
-        for name, t, shape in (("window_accept", window_accept, (Cn, T)), ("pooled", pooled, (T + 1,)),
-                               ("scale_history", scale_history, (K + 1, T)), ("accept_history", accept_history, (K, T))):
-            if t is None and name in ("scale_history", "accept_history"):
-                continue
-            if t is None or tuple(t.shape) != shape or t.device != self.device:
-                raise ValueError(f"adaptation {name} must be a {list(shape)} tensor on {self.device}")
+        self._tuning_tensors("adaptation", (("window_accept", window_accept, (Cn, T), True), ("pooled", pooled, (T + 1,), True),
+                                            ("scale_history", scale_history, (K + 1, T), False),
+                                            ("accept_history", accept_history, (K, T), False)))
         ad = AdaptArgs()
         ad.struct_size = C.sizeof(AdaptArgs)
         ad.every, ad.until = every, until
@@ -844,21 +863,11 @@ class RunPlan:
     def adapt_reduce(self) -> None:
         """The end of an adapting window, stand-alone (ptrwm_adapt_reduce): ``window_accept`` summed over chains into
         ``pooled``, the scratch left zero.  ``launch`` does this itself; split steps and tests call it."""
-        if self._adapt is None:
-            raise RuntimeError("adapt_reduce: no adaptation set (set_adaptation)")
-        with self._guard:
-            rc = self._lib.ptrwm_adapt_reduce(self._refs[4], self._adapt[1], _stream(self.device))
-        if rc != 0:
-            raise PTRWMError(rc, "ptrwm_adapt_reduce")
+        self._tuning_call("adapt_reduce", self._adapt, "adaptation set (set_adaptation)")
 
     def adapt_update(self, window: int) -> None:
         """The scale update of window ``window`` from ``pooled`` (ptrwm_adapt_update); ``pooled`` is left zero."""
-        if self._adapt is None:
-            raise RuntimeError("adapt_update: no adaptation set (set_adaptation)")
-        with self._guard:
-            rc = self._lib.ptrwm_adapt_update(self._adapt[1], self.shape[1], int(window), _stream(self.device))
-        if rc != 0:
-            raise PTRWMError(rc, "ptrwm_adapt_update")
+        self._tuning_call("adapt_update", self._adapt, "adaptation set (set_adaptation)", window)
 
     def set_ladder(self, pooled: Optional[torch.Tensor], *, every: int = 100, probe_every: Optional[int] = None, until: int = 0,
                    gain: float = 2.0, decay: float = 0.5, rescale_scales: bool = True, defer_update: bool = False,
@@ -876,24 +885,15 @@ class RunPlan:
             self._ladder = None
             return
         _, T, _ = self.shape
-        every, until = int(every), int(until)
-        probe_every = every if probe_every is None else int(probe_every)
         if T < 3:
             raise ValueError(f"the ladder's tuning moves interior temperatures: it needs at least 3, got {T}")
-        if every < 1:
-            raise ValueError("ladder every must be >= 1")
+        every, until, K = self._tuning_windows("ladder", every, until)
+        probe_every = every if probe_every is None else int(probe_every)
         if probe_every < 1 or every % probe_every != 0:
             raise ValueError(f"ladder probe_every must be >= 1 and divide every = {every}, got {probe_every}")
-        if not 0 <= until <= self._a.burn_in:
-            raise ValueError(f"ladder until must be in 0..burn_in = {self._a.burn_in}, got {until}")
-        K = until // every
         beta, scale = self._keep[4], self._keep[1].temp_scale
-        for name, t, shape in (("pooled", pooled, (T,)), ("beta_history", beta_history, (K + 1, T)),
-                               ("rate_history", rate_history, (K, T)), ("skipped", skipped, (1,))):
-            if t is None and name != "pooled":
-                continue
-            if t is None or tuple(t.shape) != shape or t.device != self.device:
-                raise ValueError(f"ladder {name} must be a {list(shape)} tensor on {self.device}")
+        self._tuning_tensors("ladder", (("pooled", pooled, (T,), True), ("beta_history", beta_history, (K + 1, T), False),
+                                        ("rate_history", rate_history, (K, T), False), ("skipped", skipped, (1,), False)))
         b = beta.detach().cpu().numpy()
         if not (b > 0).all() or not (b[:-1] > b[1:]).all():
             raise ValueError("the ladder's tuning needs a positive, strictly decreasing beta ladder")
@@ -913,21 +913,11 @@ class RunPlan:
     def ladder_probe(self) -> None:
         """One probe of the current log-densities, stand-alone (ptrwm_ladder_probe): every pair's quantised swap probability
         added to ``pooled``.  ``launch`` does this itself behind every probe step; split steps and tests call it."""
-        if self._ladder is None:
-            raise RuntimeError("ladder_probe: no ladder tuning set (set_ladder)")
-        with self._guard:
-            rc = self._lib.ptrwm_ladder_probe(self._refs[4], self._ladder[1], _stream(self.device))
-        if rc != 0:
-            raise PTRWMError(rc, "ptrwm_ladder_probe")
+        self._tuning_call("ladder_probe", self._ladder, "ladder tuning set (set_ladder)")
 
     def ladder_update(self, window: int) -> None:
         """The ladder update of window ``window`` from ``pooled`` (ptrwm_ladder_update); ``pooled`` is left zero."""
-        if self._ladder is None:
-            raise RuntimeError("ladder_update: no ladder tuning set (set_ladder)")
-        with self._guard:
-            rc = self._lib.ptrwm_ladder_update(self._ladder[1], self.shape[1], int(window), _stream(self.device))
-        if rc != 0:
-            raise PTRWMError(rc, "ptrwm_ladder_update")
+        self._tuning_call("ladder_update", self._ladder, "ladder tuning set (set_ladder)", window)
 
     def split_warmup(self, on: bool) -> None:
         """Split steps inside an adapting window (include/ptrwm.h, the split-step recipe): while on, split_accept counts every
@@ -1057,39 +1047,18 @@ class RunPlan:
             self._plain = plain
             if trace is not None and ext_prop is None and ext_u is None and ext_swap_u is None and accept_flags is None:
                 self._last_trace = (trace, trace_logp, trace_every)
-        # ptrwm_run, or the accumulator's entry point with its struct in front of the stream
-        name, mom = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
-        if self._ladder is not None:  # ladder tuning bound: the entry point that takes everything, the scale's tuning included
-            name = "ptrwm_run_with_ladder"
-            pooled = self._mom[2] if self._mom is not None and self._mom[0] == "pooled" else None
-            chain = self._mom[2] if self._mom is not None and self._mom[0] == "chain" else None
-            flow = self._flow[1] if self._flow is not None else None
-            hist = self._hist[1] if self._hist is not None else None
-            adapt = self._adapt[1] if self._adapt is not None else None
-            with self._guard:
-                rc = self._lib.ptrwm_run_with_ladder(self._refs[2], self._refs[3], self._refs[4], pooled, chain, flow, hist, adapt, self._ladder[1], _stream(self.device))
-        elif self._adapt is not None:  # adaptation bound: the entry point that takes everything but the ladder
-            name = "ptrwm_run_with_adaptation"
-            pooled = self._mom[2] if self._mom is not None and self._mom[0] == "pooled" else None
-            chain = self._mom[2] if self._mom is not None and self._mom[0] == "chain" else None
-            flow = self._flow[1] if self._flow is not None else None
-            hist = self._hist[1] if self._hist is not None else None
-            with self._guard:
-                rc = self._lib.ptrwm_run_with_adaptation(self._refs[2], self._refs[3], self._refs[4], pooled, chain, flow, hist, self._adapt[1], _stream(self.device))
-        elif self._flow is not None or self._hist is not None:  # flow or histograms bound: the entry points that take every diagnostic
-            name = "ptrwm_run_with_diagnostics" if self._hist is None else "ptrwm_run_with_histogram"
-            pooled = self._mom[2] if self._mom is not None and self._mom[0] == "pooled" else None
-            chain = self._mom[2] if self._mom is not None and self._mom[0] == "chain" else None
-            flow = self._flow[1] if self._flow is not None else None
-            if self._hist is None:
-                with self._guard:
-                    rc = self._lib.ptrwm_run_with_diagnostics(self._refs[2], self._refs[3], self._refs[4], pooled, chain, flow, _stream(self.device))
-            else:
-                with self._guard:
-                    rc = self._lib.ptrwm_run_with_histogram(self._refs[2], self._refs[3], self._refs[4], pooled, chain, flow, self._hist[1], _stream(self.device))
-        else:
-            with self._guard:
-                rc = getattr(self._lib, name)(self._refs[2], self._refs[3], self._refs[4], *mom, _stream(self.device))
+        # ptrwm_run, or the accumulator's entry point with its struct in front of the stream; with anything else bound, the
+        # first of ptrwm_run_with_diagnostics / _histogram / _adaptation / _ladder that takes all that is bound: each takes what
+        # the one before it takes and one struct more, behind the two accumulators (pooled, per chain)
+        name, opt = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
+        if self._flow is not None or self._hist is not None or self._adapt is not None or self._ladder is not None:
+            more = [b[1] if b is not None else None for b in (self._flow, self._hist, self._adapt, self._ladder)]
+            last = max(i for i, b in enumerate(more) if b is not None)
+            name = ("ptrwm_run_with_diagnostics", "ptrwm_run_with_histogram", "ptrwm_run_with_adaptation", "ptrwm_run_with_ladder")[last]
+            kind, mom = (self._mom[0], self._mom[2]) if self._mom is not None else (None, None)
+            opt = (mom if kind == "pooled" else None, mom if kind == "chain" else None, *more[:last + 1])
+        with self._guard:
+            rc = getattr(self._lib, name)(self._refs[2], self._refs[3], self._refs[4], *opt, _stream(self.device))
         if rc != 0:
             raise PTRWMError(rc, name)
 

@@ -1,18 +1,19 @@
 // csrc/adapt.h on the CPU (plain C++, built under AddressSanitizer and UBSan by tests/test_adapt_host.py).
-//   adapt_test            the window helpers against a brute-force loop, the launches / reduce / update sequence of
-//                         ptrwm_run_with_adaptation's loop replayed step by step for uncut runs and runs cut into two requests at
-//                         every position, and a few fixed points of the update rule
+//   adapt_test            the launches / reduce / update sequence that schedule.h's warmup_launch_at - the function run_impl
+//                         (capi.hip) cuts its requests by - gives for uncut runs and runs cut into two requests at every
+//                         position, verified step by step against a brute-force loop over the windows, and a few fixed points of
+//                         the update rule (the window helpers themselves: tests/schedule_test.cpp)
 //   adapt_test update     reads lines "s_old_bits accepted counted gain_k target min_bits max_bits" (floats as their uint32 bit
 //                         patterns, doubles as %.17g) and prints the bit pattern of adapt_update's result, one per line: the NumPy
 //                         comparison of test_adapt_host.py
 #include <cinttypes>
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "../rwm-pt-pytorch_amd/csrc/adapt.h"
+#include "warmup_test_util.h"
 
 using namespace ptrwm;
 
@@ -24,48 +25,24 @@ static int g_fail = 0;
     }                                                              \
   } while (0)
 
-static float from_bits(uint32_t b) {
-  float f;
-  std::memcpy(&f, &b, 4);
-  return f;
-}
-static uint32_t to_bits(float f) {
-  uint32_t b;
-  std::memcpy(&b, &f, 4);
-  return b;
-}
-
-// brute force: window k adapts iff it ends at or before `until`; step s adapts iff the window it lies in does
-static bool bf_step_adapts(long long s, long long W, long long until, long long *window) {
-  for (long long k = 0; (k + 1) * W <= until; ++k)
-    if (k * W <= s && s < (k + 1) * W) {
-      *window = k;
-      return true;
-    }
-  return false;
-}
-
 struct Event {
   int kind;  // 0: launch (a = first step, b = steps, c = adapting), 1: reduce (a = window), 2: update (a = window)
   long long a, b;
   bool c;
 };
 
-// the loop of run_impl (capi.hip) as far as adaptation goes: a launch inside an adapting window ends with the window at the
-// latest; the reduce kernel and, unless deferred, the update kernel follow the launch that ends window k
+// one request as run_impl (capi.hip) cuts it: every launch, and what follows it, is what warmup_launch_at says (the scale's
+// tuning alone; next to the ladder's: tests/ladder_test.cpp)
 static void request(long long step0, long long n, long long W, long long until, long long cap, bool defer, std::vector<Event> &out) {
   long long m = 0;
   for (long long done = 0; done < n; done += m) {
     const long long s = step0 + done;
-    const AdaptCut ac = adapt_cut_at(s, W, until);
-    long long lim = cap;
-    if (ac.adapting && ac.to_end < lim) lim = ac.to_end;
-    m = n - done < lim ? n - done : lim;
-    out.push_back({0, s, m, ac.adapting});
-    if (ac.adapting && adapt_launch_ends_window(s, m, W)) {
-      out.push_back({1, ac.window, 0, false});
-      if (!defer) out.push_back({2, ac.window, 0, false});
-    }
+    const WarmupLaunch l = warmup_launch_at(s, n - done < cap ? n - done : cap, {W, until}, defer, {0, 0}, 1, false);
+    m = l.n;
+    out.push_back({0, s, m, l.warmup});
+    if (l.scale_reduce) out.push_back({1, l.scale_window, 0, false});
+    if (l.scale_update) out.push_back({2, l.scale_window, 0, false});
+    CHECK(!l.ladder_probe && !l.ladder_update);  // (no ladder)
   }
 }
 
@@ -101,7 +78,7 @@ static void check_events(const std::vector<Event> &ev, long long N, long long W,
     }
   }
   CHECK(next == N);
-  CHECK(next_window == adapt_window_count(W, until));
+  CHECK(next_window == window_count({W, until}));
 }
 
 static std::vector<Event> kernels_only(const std::vector<Event> &ev) {
@@ -138,26 +115,6 @@ int main(int argc, char **argv) {
     const long long burn_in = 4 * W + 7, N = burn_in + 5;
     const long long untils[] = {0, W - 1, W, 3 * W + 7, burn_in};
     for (long long until : untils) {
-      const long long K = adapt_window_count(W, until);
-      // the helpers, step by step
-      long long k_bf = 0;
-      while ((k_bf + 1) * W <= until) ++k_bf;
-      CHECK(K == k_bf);
-      for (long long s = 0; s < N + 2 * W; ++s) {
-        long long w = -1;
-        const bool ad = bf_step_adapts(s, W, until, &w);
-        CHECK(adapt_step_adapts(s, W, until) == ad);
-        CHECK(ad == (s < K * W));
-        CHECK(adapt_window_of(s, W) == s / W);
-        if (ad) CHECK(adapt_window_of(s, W) == w && adapt_window_adapts(w, W, until));
-        long long to_end = 1;
-        while ((s + to_end) % W != 0) ++to_end;
-        CHECK(adapt_steps_to_window_end(s, W) == to_end);
-        // defer_update: a request may not step past the end of the adapting window it starts in
-        for (long long n = 0; n <= 2 * W + 1; ++n) CHECK(adapt_request_within_window(s, n, W, until) == (!ad || n <= to_end));
-        ++n_checked;
-      }
-      for (long long k = 0; k < K + 3; ++k) CHECK(adapt_window_adapts(k, W, until) == (k < K));
       // the launch sequence: uncut, and cut into two requests at every position, for several launch caps
       const long long caps[] = {1, 3, 1ll << 16};
       for (int defer = 0; defer < 2; ++defer)
@@ -189,7 +146,6 @@ int main(int argc, char **argv) {
   CHECK(adapt_update(2.0f, 0, 1000, 3.0, 0.234, 1e-3f, 1e3f) < 2.0f);         // never accepts: smaller steps
   CHECK(adapt_update(2.0f, 1000, 1000, 3.0, 0.234, 1e-3f, 2.5f) == 2.5f);     // the clamps bind exactly
   CHECK(adapt_update(2.0f, 0, 1000, 3.0, 0.234, 1.75f, 1e3f) == 1.75f);
-  CHECK(adapt_gain(3.0, 0.5, 0) == 3.0 && adapt_gain(3.0, 0.5, 3) == 1.5 && adapt_gain(3.0, 0.0, 99) == 3.0 && adapt_gain(3.0, 1.0, 2) == 1.0);
   if (g_fail != 0) {
     std::printf("adapt FAILED: %d check(s)\n", g_fail);
     return 1;

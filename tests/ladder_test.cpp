@@ -1,20 +1,20 @@
 // csrc/ladder.h on the CPU (plain C++, built under AddressSanitizer and UBSan by tests/test_ladder_host.py).
-//   ladder_test           the window and probe helpers against a brute-force loop; the launches / probe / update sequence of
-//                         ptrwm_run_with_ladder's loop replayed for uncut runs, runs cut into two requests at every position
-//                         and runs cut into single steps, alone and next to the scale's adaptation (W = 7 beside V = 6); a few
-//                         fixed points of the update rule
+//   ladder_test           the launches / probe / update sequence that schedule.h's warmup_launch_at - the function run_impl
+//                         (capi.hip) cuts its requests by - gives for uncut runs, runs cut into two requests at every position
+//                         and runs cut into single steps, alone and next to the scale's adaptation (W = 7 beside V = 6),
+//                         verified against a brute-force loop over the windows; a few fixed points of the update rule (the
+//                         window helpers themselves: tests/schedule_test.cpp)
 //   ladder_test update    reads lines "T gain_j beta_bits[T] pooled[T] scale_bits[T]" (floats as their uint32 bit patterns,
 //                         gain_j as %.17g) and prints "outcome beta_new_bits[T] scale_new_bits[T]": the NumPy comparison of
 //                         test_ladder_host.py
 #include <cinttypes>
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "../rwm-pt-pytorch_amd/csrc/adapt.h"
 #include "../rwm-pt-pytorch_amd/csrc/ladder.h"
+#include "warmup_test_util.h"
 
 using namespace ptrwm;
 
@@ -25,27 +25,6 @@ static int g_fail = 0;
       if (g_fail++ < 20) std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); \
     }                                                              \
   } while (0)
-
-static float from_bits(uint32_t b) {
-  float f;
-  std::memcpy(&f, &b, 4);
-  return f;
-}
-static uint32_t to_bits(float f) {
-  uint32_t b;
-  std::memcpy(&b, &f, 4);
-  return b;
-}
-
-// brute force: window j adapts iff it ends at or before `until`; step s adapts iff the window it lies in does
-static bool bf_step_adapts(long long s, long long V, long long until, long long *window) {
-  for (long long j = 0; (j + 1) * V <= until; ++j)
-    if (j * V <= s && s < (j + 1) * V) {
-      *window = j;
-      return true;
-    }
-  return false;
-}
 
 enum { kLaunch, kScaleReduce, kScaleUpdate, kProbe, kLadderUpdate };
 struct Event {
@@ -60,26 +39,19 @@ struct Setup {
   bool defer;
 };
 
-// the loop of run_impl (capi.hip) as far as the two tunings go
+// one request as run_impl (capi.hip) cuts it: every launch, and what follows it in run_impl's order, is what warmup_launch_at
+// says
 static void request(long long step0, long long n, const Setup &u, std::vector<Event> &out) {
   long long m = 0;
   for (long long done = 0; done < n; done += m) {
     const long long s = step0 + done;
-    const AdaptCut ac = u.W > 0 ? adapt_cut_at(s, u.W, u.adapt_until) : AdaptCut{false, 0, 0};
-    const LadderCut lc = ladder_cut_at(s, u.V, u.P, u.until);
-    long long lim = u.cap;
-    if (ac.adapting && ac.to_end < lim) lim = ac.to_end;
-    if (lc.adapting && lc.to_probe < lim) lim = lc.to_probe;
-    m = n - done < lim ? n - done : lim;
+    const WarmupLaunch l = warmup_launch_at(s, n - done < u.cap ? n - done : u.cap, {u.W, u.adapt_until}, u.defer, {u.V, u.until}, u.P, u.defer);
+    m = l.n;
     out.push_back({kLaunch, s, m});
-    if (ac.adapting && adapt_launch_ends_window(s, m, u.W)) {
-      out.push_back({kScaleReduce, ac.window, 0});
-      if (!u.defer) out.push_back({kScaleUpdate, ac.window, 0});
-    }
-    if (lc.adapting && ladder_launch_ends_at_probe(s, m, u.P)) {
-      out.push_back({kProbe, s + m - 1, 0});
-      if (!u.defer && ladder_launch_ends_window(s, m, u.V)) out.push_back({kLadderUpdate, lc.window, 0});
-    }
+    if (l.scale_reduce) out.push_back({kScaleReduce, l.scale_window, 0});
+    if (l.scale_update) out.push_back({kScaleUpdate, l.scale_window, 0});
+    if (l.ladder_probe) out.push_back({kProbe, s + m - 1, 0});
+    if (l.ladder_update) out.push_back({kLadderUpdate, l.ladder_window, 0});
   }
 }
 
@@ -116,7 +88,7 @@ static void check_events(const std::vector<Event> &ev, long long N, const Setup 
     CHECK(i + 1 + want.size() == ev.size() || ev[i + 1 + want.size()].kind == kLaunch);
   }
   CHECK(next == N);
-  const long long K = ladder_window_count(u.V, u.until);
+  const long long K = window_count({u.V, u.until});
   CHECK(updates == K && probes == K * (u.V / u.P));
 }
 
@@ -174,27 +146,6 @@ int main(int argc, char **argv) {
     if (V % 2 == 0) Ps.push_back(V / 2);
     for (long long P : Ps)
       for (long long until : untils) {
-        const long long K = ladder_window_count(V, until);
-        long long k_bf = 0;
-        while ((k_bf + 1) * V <= until) ++k_bf;
-        CHECK(K == k_bf);
-        for (long long s = 0; s < N + 2 * V; ++s) {
-          long long w = -1;
-          const bool ad = bf_step_adapts(s, V, until, &w);
-          CHECK(ladder_step_adapts(s, V, until) == ad);
-          CHECK(ad == (s < K * V));
-          CHECK(ladder_window_of(s, V) == s / V);
-          if (ad) CHECK(ladder_window_of(s, V) == w && ladder_window_adapts(w, V, until));
-          CHECK(ladder_step_probes(s, V, P, until) == (ad && (s + 1) % P == 0));
-          if (ad && (s + 1) % V == 0) CHECK(ladder_step_probes(s, V, P, until));  // a window's last step is a probe step
-          long long to_probe = 1, to_end = 1;
-          while ((s + to_probe) % P != 0) ++to_probe;
-          while ((s + to_end) % V != 0) ++to_end;
-          CHECK(ladder_steps_to_probe(s, P) == to_probe && ladder_steps_to_window_end(s, V) == to_end && to_probe <= to_end);
-          for (long long n = 0; n <= 2 * V + 1; ++n) CHECK(ladder_request_within_window(s, n, V, until) == (!ad || n <= to_end));
-          ++n_checked;
-        }
-        for (long long j = 0; j < K + 3; ++j) CHECK(ladder_window_adapts(j, V, until) == (j < K));
         // the launch sequence: uncut, cut in two at every position, cut into single steps - alone, and (V = 6) next to the
         // scale's adaptation with W = 7
         const long long caps[] = {1, 3, 1ll << 16};
@@ -255,7 +206,6 @@ int main(int argc, char **argv) {
     const long long skew[4] = {0, 10 << 24, 0, 10};  // the middle pair widens: beta_1 rounds back onto beta_0
     CHECK(ladder_update(tight, skew, 4, 2.0, out, work) == kLadderSkipped && std::memcmp(out, tight, sizeof tight) == 0);
     CHECK(ladder_rescale(3.0f, 0.5f, 0.5f) == 3.0f && ladder_rescale(3.0f, 0.5f, 0.125f) == 6.0f);
-    CHECK(ladder_gain(2.0, 0.5, 0) == 2.0 && ladder_gain(2.0, 0.5, 3) == 1.0 && ladder_gain(2.0, 0.0, 99) == 2.0);
   }
   if (g_fail != 0) {
     std::printf("ladder FAILED: %d check(s)\n", g_fail);

@@ -5,6 +5,7 @@
 #include <cstdlib>
 
 #include "../rwm-pt-pytorch_amd/csrc/schedule.h"
+#include "warmup_test_util.h"
 
 using namespace ptrwm;
 
@@ -113,6 +114,53 @@ int main() {
                 }
                 CHECK(done == n_steps, "request overrun");
               }
-  std::printf("schedule ok: %lld launches, %lld checks\n", launches, g_checks);
+  // the warm-up windows against a loop over the windows, for the periods and ends the two tunings' own tests (adapt_test.cpp,
+  // ladder_test.cpp) run with; the probe steps of a launch of one step; the rule of a deferred update
+  long long positions = 0;
+  const long long everys[] = {1, 6, 7, 50};
+  for (long long W : everys) {
+    const long long N = 4 * W + 7 + 5;
+    const long long untils[] = {0, W - 1, W, 3 * W + 5, 3 * W + 7, 4 * W + 5, 4 * W + 7};
+    for (long long until : untils) {
+      const WarmupWindows w = {W, until};
+      const long long K = window_count(w);
+      long long k_bf = 0;
+      while ((k_bf + 1) * W <= until) ++k_bf;
+      CHECK(K == k_bf, "every %lld until %lld", W, until);
+      for (long long k = 0; k < K + 3; ++k) CHECK(((k + 1) * W <= until) == (k < K), "every %lld until %lld window %lld", W, until, k);
+      for (long long s = 0; s < N + 2 * W; ++s) {
+#define WHERE "every %lld until %lld step %lld", W, until, s
+        long long bw = -1;
+        const bool ad = bf_step_adapts(s, W, until, &bw);
+        CHECK(step_adapts(w, s) == ad && ad == (s < K * W), WHERE);
+        CHECK(window_of(w, s) == s / W, WHERE);
+        if (ad) CHECK(window_of(w, s) == bw && bw < K, WHERE);
+        long long to_end = 1;
+        while ((s + to_end) % W != 0) ++to_end;
+        CHECK(steps_to_window_end(w, s) == to_end, WHERE);
+        for (long long n = 1; n <= to_end; ++n) CHECK(launch_ends_window(w, s, n) == (n == to_end), WHERE);
+        // a deferred update: a request may not step past the end of the adapting window it starts in
+        for (long long n = 0; n <= 2 * W + 1; ++n) CHECK(request_within_window(w, s, n) == (!ad || n <= to_end), WHERE);
+        // probe steps: (s + 1) % P == 0 inside an adapting window, P a divisor of the period - a window's last step is one
+        for (long long P = 1; P <= W; ++P) {
+          if (W % P != 0) continue;
+          long long to_probe = 1;
+          while ((s + to_probe) % P != 0) ++to_probe;
+          CHECK(steps_to_next_multiple(s, P) == to_probe && to_probe <= to_end, WHERE);
+          const WarmupLaunch one = warmup_launch_at(s, 1, {0, 0}, false, w, P, false);
+          CHECK(one.n == 1 && !one.warmup && !one.scale_reduce && !one.scale_update, WHERE);
+          CHECK(one.ladder_probe == (ad && (s + 1) % P == 0), WHERE);
+          CHECK(one.ladder_update == (ad && (s + 1) % W == 0) && (!one.ladder_update || (one.ladder_probe && one.ladder_window == bw)), WHERE);
+        }
+#undef WHERE
+        ++positions;
+      }
+    }
+  }
+  const WarmupWindows none = {0, 0};  // no such tuning
+  CHECK(window_count(none) == 0 && !step_adapts(none, 0) && !step_adapts(none, 7) && request_within_window(none, 3, 1000), "every 0");
+  CHECK(window_gain(3.0, 0.5, 0) == 3.0 && window_gain(3.0, 0.5, 3) == 1.5 && window_gain(3.0, 0.0, 99) == 3.0 && window_gain(3.0, 1.0, 2) == 1.0, "gain 3");
+  CHECK(window_gain(2.0, 0.5, 0) == 2.0 && window_gain(2.0, 0.5, 3) == 1.0 && window_gain(2.0, 0.0, 99) == 2.0, "gain 2");
+  std::printf("schedule ok: %lld launches, %lld window positions, %lld checks\n", launches, positions, g_checks);
   return 0;
 }

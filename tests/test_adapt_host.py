@@ -31,10 +31,11 @@ def adapt_exe(tmp_path_factory):
 
 
 def test_window_helpers_and_cuts_against_brute_force(adapt_exe):
-    """W in {1, 7, 50}, until in {0, W - 1, W, 3 W + 7, burn_in}: every helper of csrc/adapt.h step by step against a loop over
-    the windows; the loop of ptrwm_run_with_adaptation replayed uncut, cut into two requests at every position of a 4-window
-    run and cut into single steps - each step covered once, no adapting launch across a window end, the same (reduce, update)
-    sequence whatever the cut."""
+    """W in {1, 7, 50}, until in {0, W - 1, W, 3 W + 7, burn_in}: the launches csrc/schedule.h's warmup_launch_at - what
+    ptrwm_run_with_adaptation's loop asks - cuts a run into, uncut, cut into two requests at every position of a 4-window run
+    and cut into single steps, against a loop over the windows - each step covered once, no adapting launch across a window
+    end, the same (reduce, update) sequence whatever the cut.  (The window helpers themselves: schedule_test.cpp,
+    test_host_logic.py.)"""
     out = subprocess.run([adapt_exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "adapt ok:" in out.stdout

@@ -497,3 +497,73 @@ def test_classes(device, dtype):
     assert calls == [(4,)] * Kc
     hs = sy.ladder_history()
     assert torch.equal(hs["betas"], h["betas"]) and torch.equal(hs["rates"], h["rates"])
+
+
+# ---- both tunings at once, cut anywhere ----------------------------------------------------------------------------------------
+def own_density(target):
+    """The library's own density of `target` behind log_density() alone: without engine_target() the classes run it in split
+    steps."""
+    from interfaces import TorchTargetDistribution
+
+    class OwnDensity(TorchTargetDistribution):
+        def get_name(self):
+            return "OwnDensity"
+
+        def log_density(self, x):
+            return target.log_density(x)
+
+        def density(self, x):
+            return torch.exp(self.log_density(x))
+
+    return OwnDensity(target.dim, target.device)
+
+
+def _both_tunings(device, split, sync, cuts):
+    """36 steps of a 4 x 4 x 3 Gaussian run under both tunings, advanced by `cuts`; everything the run holds, on the host."""
+    from algorithms import ParallelTemperingRWM_GPU_Optimized
+    from target_distributions import MultivariateNormalTorch
+
+    target = MultivariateNormalTorch(3, device=device)
+    np.random.seed(4)  # (the samplers draw their 1e-8 N(0, 1) starting point from NumPy's global generator)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")  # (a target without a fused kernel says that it runs split steps)
+        alg = ParallelTemperingRWM_GPU_Optimized(3, 2.0, own_density(target) if split else target, beta_ladder=LADDER4, swap_every=3,
+                                                 burn_in=26, device=device, num_replicas=4, seed=SEED, trace="none",
+                                                 adapt_scale=True, adapt_every=6, adapt_ladder=True, ladder_every=4,
+                                                 ladder_probe_every=2, adapt_sync=(lambda pooled: pooled) if sync else None)
+        for n in cuts:
+            alg._advance(n)
+    run = alg._run
+    assert (run.density_fn is not None) == split and run.steps_done == sum(cuts) == 36
+    torch.cuda.synchronize()
+    out = {"state": run.state, "logp": run.logp, "n_accept": run.n_accept, "swap_accept": run.swap_accept,
+           "scales": alg.proposal_scales(), "beta": run.beta_ladder(),
+           **{"scale " + k: v for k, v in run.adaptation_history().items()},
+           **{"ladder " + k: v for k, v in run.ladder_history().items()}}
+    assert alg.beta_ladder == out["beta"].tolist()
+    return {k: v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v) for k, v in out.items()}
+
+
+@gpu
+@pytest.mark.parametrize("split", [False, True], ids=["fused", "split"])
+def test_both_tunings_cut_anywhere(device, split):
+    """adapt_every = 6 next to ladder_every = 4 with a probe every 2 steps, burn_in = 26: the scale's windows end behind steps
+    5, 11, 17, 23, the ladder's behind 3, 7, .., 23 - interleaved, and together behind 11 and 23 - then two steps of plain
+    burn-in and 10 steps with swap events.  Advanced in calls of every size 1 .. 13 (the size repeated until 36 steps are done),
+    with and without adapt_sync (a callable that leaves the counts alone: the deferred-update path), every output has the bits
+    of the single call: state, logp, scales, ladder, both histories, the acceptance counts."""
+    outs = {}
+    for sync in (False, True):
+        whole = outs[sync] = _both_tunings(device, split, sync, [36])
+        assert whole["ladder betas"].shape == (7, 4) and whole["scale scales"].shape == (5, 4) and whole["ladder skipped"] == 0
+        assert np.isfinite(whole["ladder betas"]).all() and np.isfinite(whole["scale scales"]).all()  # every window has run
+        assert (whole["ladder betas"][6][1:3] != whole["ladder betas"][0][1:3]).all() and (whole["scale scales"][4] != whole["scale scales"][0]).all()
+        assert whole["ladder probes"].tolist() == [4 * 2] * 6 and whole["swap_accept"].sum() > 0 and whole["n_accept"].max() <= 10
+        for size in range(1, 14):
+            cuts = [size] * (36 // size) + ([36 % size] if 36 % size else [])
+            got = _both_tunings(device, split, sync, cuts)
+            assert got.keys() == whole.keys()
+            for k in whole:
+                assert np.array_equal(got[k], whole[k], equal_nan=True), f"calls of {size} steps, adapt_sync {sync}: {k}"
+    for k in outs[False]:
+        assert np.array_equal(outs[False][k], outs[True][k], equal_nan=True), f"adapt_sync against none: {k}"

@@ -479,7 +479,9 @@ def test_periodic_steps_in_is_the_brute_force_count():
 def test_step_schedule_header_against_brute_force(tmp_path):
     """csrc/schedule.h - the schedule every kernel and host path of csrc/capi.hip cuts ptrwm_run's launches from - compiled
     as plain C++ under AddressSanitizer and UBSan into tests/schedule_test.cpp, a program of its own that replays every launch
-    of a grid of requests (burn-in x the three periods x step0 x n_steps x the cut) step by step."""
+    of a grid of requests (burn-in x the three periods x step0 x n_steps x the cut) step by step, and every helper of the
+    warm-up windows (every in {1, 6, 7, 50}, until from 0 to past four windows, every divisor as the probe period) against a
+    loop over the windows."""
     import os
     import subprocess
 
@@ -489,7 +491,7 @@ def test_step_schedule_header_against_brute_force(tmp_path):
                            "-fno-sanitize-recover=all", src, "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "schedule ok: 2092800 launches" in out.stdout
+    assert "schedule ok: 2092800 launches, 3024 window positions" in out.stdout
 
 
 def test_rng_layout_header_against_literal_restatements(tmp_path):

@@ -32,11 +32,12 @@ def ladder_exe(tmp_path_factory):
 
 
 def test_window_helpers_and_cuts_against_brute_force(ladder_exe):
-    """V in {1, 6, 50}, probe_every in {1, V / 2, V}, until in {0, V - 1, V, 3 V + 5, burn_in}: every helper of csrc/ladder.h
-    step by step against a loop over the windows; the loop of ptrwm_run_with_ladder replayed uncut, cut in two at every step of
-    a 4-window run and cut into single steps - each step covered once, no launch across a probe step, the same (probe, update)
-    sequence whatever the cut; with the scale's adaptation at W = 7 next to V = 6 the order scale reduce, scale update, ladder
-    probe, ladder update at shared ends."""
+    """V in {1, 6, 50}, probe_every in {1, V / 2, V}, until in {0, V - 1, V, 3 V + 5, burn_in}: the launches
+    csrc/schedule.h's warmup_launch_at - what ptrwm_run_with_ladder's loop asks - cuts a run into, uncut, cut in two at every
+    step of a 4-window run and cut into single steps, against a loop over the windows - each step covered once, no launch
+    across a probe step, the same (probe, update) sequence whatever the cut; with the scale's adaptation at W = 7 next to V = 6
+    the order scale reduce, scale update, ladder probe, ladder update at shared ends.  (The window helpers themselves:
+    schedule_test.cpp, test_host_logic.py.)"""
     out = subprocess.run([ladder_exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     assert "ladder ok:" in out.stdout
