@@ -625,6 +625,65 @@ int32_t ptrwm_ladder_probe(const ptrwm_run_args *args, const ptrwm_ladder_args *
  * the histories written, pooled left zero.  One small workgroup. */
 int32_t ptrwm_ladder_update(const ptrwm_ladder_args *ladder, int32_t n_temps, int64_t window, void *stream);
 
+/* ---- pooled lagged autocovariance: autocorrelation time and effective sample size without a trace --------------------------------
+ * How correlated are successive draws?  An autocovariance accumulator covers the first `temps` temperatures.  A snapshot is
+ * due at every step whose step_counter > burn_in and step_counter % every == 0 (the histograms' rule); its 0-based number is
+ * j = step_counter / every - burn_in / every - 1, from the step counter alone.  ring [max_lag, n_chains, temps * dim], of the
+ * state's own type (float; double with state_f64), keeps the last max_lag snapshots: snapshot j lives in slot j % max_lag.  At
+ * snapshot j, for every covered temperature t, coordinate d and lag k = 0 .. min(j, max_lag), summed over the local chains:
+ *   sxy[t, k, d]  += x_j[t, d] * x_{j-k}[t, d]      head[t, k, d] += x_j[t, d]      tail[t, k, d] += x_{j-k}[t, d]
+ *   pairs[k]      += n_chains
+ * where x is the replica's state after the whole step (MH move and that step's swap event) - the values a trace with
+ * trace_every = every records.  Each product is one double product of the two values converted to double, rounded once and
+ * not fused with the sum: a replay reproduces every term bit for bit and only the order of the additions is free (tile sums
+ * are flushed with fp64 atomics, as the pooled moments are).  On the host:
+ *   c_k = sxy_k / pairs_k - (head_k / pairs_k)(tail_k / pairs_k),   rho_k = c_k / c_0.
+ * The rule is csrc/acf.h's.  Everything is added to (+=): launches, calls and shards compose (sum the shards' sums).
+ * ptrwm_swap_sweep events are not steps and add nothing.  The ring needs no zeroing: a slot is written before it is read.
+ * Contract: EVERY due step is snapshotted, in order - a skipped one leaves a stale slot that later snapshots pair with.
+ * ptrwm_run_with_autocorr guarantees it; a stand-alone caller of ptrwm_autocorr is responsible for it.
+ * How: NOT in the step kernels.  A small stand-alone snapshot kernel reads `state` between launches, as the histograms' does:
+ * a workgroup takes a tile of chains and a group of the temps * dim columns (csrc/acf.h acf_geometry), keeps its x_j in
+ * registers, streams the ring slots of the available lags past it, and flushes one fp64 atomic per non-zero tile sum.  It
+ * reads (min(j, max_lag) + 1) * n_chains * temps * dim elements and writes one slot.  The accumulators and the ring must be
+ * ordinary device memory of the current device. */
+#define PTRWM_ACF_MAX_LAG 1024
+typedef struct ptrwm_acf_args {
+  uint32_t struct_size; /* sizeof(ptrwm_acf_args) */
+  int32_t temps;        /* 1..n_temps: the first `temps` temperatures */
+  int32_t every;        /* >= 1: a snapshot at every step past burn-in whose step_counter is a multiple */
+  int32_t max_lag;      /* 1..PTRWM_ACF_MAX_LAG: lags 0..max_lag, in snapshots */
+  void *ring;           /* device [max_lag, n_chains, temps * dim], float or double as the state; scratch */
+  double *sxy;          /* device [temps, max_lag + 1, dim], += */
+  double *head;         /* device [temps, max_lag + 1, dim], += */
+  double *tail;         /* device [temps, max_lag + 1, dim], += */
+  int64_t *pairs;       /* device [max_lag + 1], += */
+} ptrwm_acf_args;
+
+/* One snapshot: the state as it stands after step args->step0 (device-step mode: *device_step + step0 - read on the device,
+ * so the call can sit inside a captured block of split steps, after ptrwm_split_accept); a step that is not due adds
+ * nothing.  Reads from `args`: n_temps, n_chains, state, state_f64, burn_in, step0, device_step.
+ * Checked, in this order, before anything is enqueued: PTRWM_E_NULL for a NULL args / acf; PTRWM_E_STRUCT for a wrong
+ * struct_size of args; PTRWM_E_DIM / PTRWM_E_TEMPS as everywhere; PTRWM_E_ARG for state_f64 outside 0..1 or a negative
+ * n_chains, step0 or burn_in; then the block's own checks as below; an empty batch returns PTRWM_OK; PTRWM_E_NULL for a NULL
+ * state. */
+int32_t ptrwm_autocorr(const ptrwm_run_args *args, int32_t dim, const ptrwm_acf_args *acf, void *stream);
+
+/* ptrwm_run_with_ladder, plus the autocovariance.  acf == NULL: exactly ptrwm_run_with_ladder.
+ * A launch of the request additionally ends at every step whose step_counter is past burn_in and a multiple of acf->every,
+ * and the snapshot kernel is enqueued right after it on `stream` (behind the histogram's, where both are due); a request
+ * without such a step performs exactly the launches it performs without `acf`.  No step kernel is told about it, and
+ * everything else of the run is bit-identical with and without `acf`, with the one exception that holds for any change of
+ * where a run is cut into launches (ptrwm_run_args.sq_jump above).
+ * Checked before anything is enqueued, after every other block's checks: PTRWM_E_STRUCT for a wrong acf->struct_size;
+ * PTRWM_E_ARG for temps outside 1..n_temps, every < 1 or max_lag outside 1..PTRWM_ACF_MAX_LAG; PTRWM_E_NULL for a NULL ring,
+ * sxy, head, tail or pairs.  An empty batch returns PTRWM_OK. */
+int32_t ptrwm_run_with_autocorr(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                                const ptrwm_run_args *args, const ptrwm_moments_args *moments,
+                                const ptrwm_chain_moments_args *chain_moments, const ptrwm_flow_args *flow,
+                                const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder,
+                                const ptrwm_acf_args *acf, void *stream);
+
 /* One stand-alone swap event over the current states: what the reference's
  * ParallelTemperingRWM_GPU_Optimized._attempt_all_swaps() does when called on its own
  * (pt_rwm_gpu_optimized.py:594-633; tests/debug_pt_performance.py:156).  Exactly the swap part of a ptrwm_run step:

@@ -49,6 +49,13 @@ every window - which rewrite `beta` (the run's own tensor) and the run's copy of
     rate_history   int64   [K, n_temps]               the pooled row of every window
     skipped        int64   [1]                        updates dropped (two rungs would have rounded onto each other)
 
+and, with acf_temps > 0, the pooled lagged autocovariance (`_acf`, a dict; include/ptrwm.h ptrwm_acf_args, csrc/acf.h), added to
+by a snapshot kernel between launches at every acf_every-th step past burn-in, with `_acf_ring`, the last acf_max_lag snapshots
+(scratch, the state's dtype, [acf_max_lag, n_replicas, acf_temps, dim]):
+
+    sxy, head, tail  float64 [acf_temps, acf_max_lag + 1, dim]   sums of x_j x_{j-k}, of x_j and of x_{j-k} over replicas and snapshots
+    pairs            int64   [acf_max_lag + 1]                   (replica, snapshot) pairs added per lag
+
 `n_replicas` is the axis the reference does not have: independent copies of the whole chain /
 ladder, one Philox subsequence each (global replica id = chain_offset + local index), so a run is
 invariant to how replicas are sharded over GPUs.
@@ -335,7 +342,8 @@ class EngineRun:
                  adapt_target: float = 0.234, adapt_gain: float = 3.0, adapt_decay: float = 0.5,
                  adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False, ladder_every: int = 100,
                  ladder_until: Optional[int] = None, ladder_probe_every: Optional[int] = None, ladder_gain: float = 2.0,
-                 ladder_decay: float = 0.5):
+                 ladder_decay: float = 0.5, acf_temps: int = 0, acf_every: int = 1, acf_max_lag: int = 32,
+                 acf_ring_limit: Optional[int] = None):
         adapt = check_adapt_args(adapt_scale, max(0, int(burn_in)), adapt_every, adapt_until, adapt_target, adapt_gain,
                                  adapt_decay, adapt_scale_bounds, adapt_sync)
         ladder = check_ladder_args(adapt_ladder, max(0, int(burn_in)), beta_ladder, ladder_every, ladder_until,
@@ -355,6 +363,7 @@ class EngineRun:
         if not 1 <= dim <= ptrwm_hip.MAX_DIM:
             raise ValueError(f"dim must be in 1..{ptrwm_hip.MAX_DIM} for the fused kernel, got {dim}")
         hist_box = check_hist_args(hist_temps, hist_every, hist_bins, hist_range, n_temps, dim)
+        acf_on = check_acf_args(acf_temps, acf_every, acf_max_lag, n_temps, dim, n_replicas, acf_ring_limit)
         # the starts (host-side checks, before the device is asked for: bad arguments fail the same way without a GPU)
         axes = start_shape(initial_state, dim, n_replicas, n_temps)
         box = check_init_box(init_box, dim)
@@ -476,6 +485,16 @@ class EngineRun:
             self._hist_edges = hist_edges(lo, hi, self.hist_bins)
             self._plan.set_histogram(self._hist["counts"], self._hist["lo"], self._hist["scale"], n_bins=self.hist_bins,
                                      temps=self.hist_temps, every=self.hist_every, count=self._hist["count"])
+        # pooled lagged autocovariance, summed by a snapshot kernel between launches (off: None); the ring is scratch
+        self.acf_temps, self.acf_every, self.acf_max_lag = int(acf_temps), int(acf_every), int(acf_max_lag)
+        self._acf = None
+        if acf_on:
+            L, at = self.acf_max_lag, self.acf_temps
+            self._acf = {**{k: torch.zeros(at, L + 1, dim, device=device, dtype=torch.float64) for k in ("sxy", "head", "tail")},
+                         "pairs": torch.zeros(L + 1, device=device, dtype=torch.int64)}
+            self._acf_ring = torch.empty(L, n_replicas, at, dim, device=device, dtype=dtype)
+            self._plan.set_autocorr(self._acf_ring, self._acf["sxy"], self._acf["head"], self._acf["tail"], self._acf["pairs"],
+                                    every=self.acf_every)
         # warm-up tuning of the proposal scale, per temperature, by two small kernels between launches (off: None)
         self.init_scales = self.proposal.temp_scale.clone()
         self._adapt = None
@@ -646,6 +665,7 @@ class EngineRun:
         self._plan.split_accept(offset, lp_new, swap_event_offset=self.manual_sweeps, no_sweep=no_sweep)
         self._plan.split_moments(offset)  # (decides on the device whether this step counts; no-op without moments)
         self._plan.split_histogram(offset)  # (likewise; no-op without a histogram)
+        self._plan.split_autocorr(offset)  # (likewise; no-op without an autocovariance accumulator)
         if advance:
             self._plan.split_advance(advance)
 
@@ -763,6 +783,7 @@ class EngineRun:
                 if not warmup:
                     self._plan.split_moments(s)
                     self._plan.split_histogram(s)
+                    self._plan.split_autocorr(s)
                 self.steps_done += 1
                 if trace is not None and ptrwm_hip.periodic_steps_in(s, s + 1, trace_every):
                     tc, tt = trace.shape[1], trace.shape[2]
@@ -830,6 +851,18 @@ class EngineRun:
         if self._hist is not None:
             self._hist["counts"].zero_()
             self._hist["count"].zero_()
+
+    def autocorr_sums(self) -> Optional[dict]:
+        """The pooled lagged autocovariance sums of this shard, or None when they are off: sxy / head / tail
+        [acf_temps, acf_max_lag + 1, dim] float64 and pairs [acf_max_lag + 1] int64 (device tensors, no synchronisation), and
+        every."""
+        return {**self._acf, "every": self.acf_every} if self._acf is not None else None
+
+    def reset_autocorr(self) -> None:
+        """Zero the autocovariance sums (the chains keep their states).  The ring stays valid: snapshots are numbered from the
+        step counter, so the next one pairs with the ones before the reset."""
+        for t in (self._acf or {}).values():
+            t.zero_()
 
     def flow(self) -> Optional[dict]:
         """Replica flow of this shard (device tensors, no synchronisation), or None when flow is off: walker (int32 flow
@@ -1013,6 +1046,148 @@ class PosteriorMoments:
             "posterior_variance": (m["sum_sq"] / n[:, None] - mean * mean).cpu(),
             "mean_log_density": (m["sum_logp"] / n).cpu(),
         }
+
+
+# ---- pooled lagged autocovariance: estimators and the drop-in classes' readers -------------------------------------------
+ACF_RING_LIMIT = 1 << 31  # elements (8 GiB of float states): what a ring may hold unless the caller says otherwise
+
+
+def check_acf_args(acf_temps, acf_every, acf_max_lag, n_temps: int, dim: int, n_replicas: int, ring_limit=None) -> bool:
+    """EngineRun's autocovariance arguments (no GPU needed): False when off.  The ring holds acf_max_lag x replicas x acf_temps
+    x dim elements of the state's type; above `ring_limit` elements (default ACF_RING_LIMIT = 2^31) that is refused, naming the
+    size, because it is rarely what the caller means - thin with acf_every instead of raising acf_max_lag."""
+    for name, v in (("acf_temps", acf_temps), ("acf_every", acf_every), ("acf_max_lag", acf_max_lag)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not 0 <= acf_temps <= n_temps:
+        raise ValueError(f"acf_temps must be in 0..{n_temps}, got {acf_temps}")
+    if not acf_temps:
+        return False
+    if acf_every < 1:
+        raise ValueError(f"acf_every must be >= 1, got {acf_every}")
+    if not 1 <= acf_max_lag <= ptrwm_hip.ACF_MAX_LAG:
+        raise ValueError(f"acf_max_lag must be in 1..{ptrwm_hip.ACF_MAX_LAG}, got {acf_max_lag}")
+    limit = ACF_RING_LIMIT if ring_limit is None else int(ring_limit)
+    elems = int(acf_max_lag) * int(n_replicas) * int(acf_temps) * int(dim)
+    if elems > limit:
+        raise ValueError(f"the autocovariance ring would hold acf_max_lag x replicas x temperatures x dim = {acf_max_lag} x "
+                         f"{n_replicas} x {acf_temps} x {dim} = {elems} elements ({elems * 4 / 2**30:.1f} GiB of float32 states), "
+                         f"above the limit of {limit}: lower acf_max_lag and reach long lags with acf_every, cover acf='cold', "
+                         "or raise acf_ring_limit")
+    return True
+
+
+def acf_temps(mode, n_temps: int) -> int:
+    """Temperatures an `acf=` mode covers (0: off)."""
+    if mode not in (None, "cold", "all"):
+        raise ValueError(f"acf must be None, 'cold' or 'all', got {mode!r}")
+    return {None: 0, "cold": 1, "all": n_temps}[mode]
+
+
+def acf_autocovariance(sxy, head, tail, pairs) -> torch.Tensor:
+    """c_k = sxy_k / n_k - (head_k / n_k)(tail_k / n_k) from the sums of one temperature: sxy / head / tail [lags, dim], pairs
+    [lags]; float64 [lags, dim] on the CPU, NaN at a lag without pairs."""
+    sxy, head, tail = (torch.as_tensor(t).detach().cpu().to(torch.float64) for t in (sxy, head, tail))
+    n = torch.as_tensor(pairs).detach().cpu().to(torch.float64)[:, None]
+    if sxy.dim() != 2 or head.shape != sxy.shape or tail.shape != sxy.shape or n.shape[0] != sxy.shape[0]:
+        raise ValueError("sxy, head and tail must be [lags, dim] and pairs [lags]")
+    n = torch.where(n > 0, n, torch.full_like(n, float("nan")))
+    return sxy / n - (head / n) * (tail / n)
+
+
+def acf_autocorrelation(sxy, head, tail, pairs) -> torch.Tensor:
+    """rho_k = c_k / c_0: float64 [lags, dim]; NaN where c_0 is not positive."""
+    c = acf_autocovariance(sxy, head, tail, pairs)
+    c0 = torch.where(c[0] > 0, c[0], torch.full_like(c[0], float("nan")))
+    return c / c0
+
+
+def sokal_window(rho, c: float = 5.0) -> tuple:
+    """Integrated autocorrelation time by Sokal's automatic window, per coordinate, from rho [lags, dim] (rho[0] = 1):
+    tau(M) = 1 + 2 sum_{k=1..M} rho_k and the window is the smallest M >= 1 with M >= c tau(M).  Returns (tau [dim] float64,
+    window [dim] int64, reached [dim] bool).  Lags from the first NaN on (no pairs yet: a run shorter than the ring) are not
+    there.  Where no M up to the last lag there is qualifies, `reached` is False, window is that last lag and tau is tau(last
+    lag): a LOWER BOUND, not an estimate.  A coordinate without any lag: tau NaN, window 0, reached False."""
+    rho = torch.as_tensor(rho).detach().cpu().to(torch.float64)
+    if rho.dim() != 2 or rho.shape[0] < 2:
+        raise ValueError("rho must be [lags >= 2, dim]")
+    if not c > 0:
+        raise ValueError("c must be positive")
+    L = rho.shape[0] - 1
+    there = torch.cumprod(torch.isfinite(rho).to(torch.int64), 0)[1:].bool()  # [L, dim]: lag M and every lag below it is finite
+    taus = 1.0 + 2.0 * torch.cumsum(torch.where(there, rho[1:], torch.zeros_like(rho[1:])), 0)  # tau(M), M = 1..L
+    M = torch.arange(1, L + 1, dtype=torch.float64)[:, None]
+    ok = there & (M >= c * taus)
+    reached = ok.any(0)
+    n_there = there.sum(0)
+    at = torch.where(reached, ok.to(torch.int64).argmax(0), (n_there - 1).clamp(min=0))  # index of the window in taus
+    tau = torch.where(n_there > 0, taus.gather(0, at[None, :])[0], torch.full((rho.shape[1],), float("nan"), dtype=torch.float64))
+    return tau, torch.where(n_there > 0, at + 1, torch.zeros_like(at)), reached
+
+
+class Autocorrelation:
+    """Estimates from the pooled lagged autocovariance (include/ptrwm.h ptrwm_acf_args, csrc/acf.h): how correlated successive
+    snapshots of a coordinate are, pooled over every replica of the run.  The host class calls `_check_acf_ctor` in its
+    constructor, passes `_acf_kwargs(n_temps)` to EngineRun and owns `_run`.  Every read synchronises; results are CPU tensors."""
+
+    def _check_acf_ctor(self, dim: int, acf, acf_every, acf_max_lag, acf_ring_limit=None) -> None:
+        """The constructor's autocovariance arguments, checked before anything is built (no GPU needed; the ring's size is
+        checked again where the number of replicas is known)."""
+        if acf_temps(acf, 1):
+            check_acf_args(1, acf_every, acf_max_lag, 1, dim, 1, acf_ring_limit)
+        self._acf_mode, self._acf_every, self._acf_max_lag, self._acf_ring_limit = acf, acf_every, acf_max_lag, acf_ring_limit
+
+    def _acf_kwargs(self, n_temps: int) -> dict:
+        """EngineRun's autocovariance arguments."""
+        if self._acf_mode is None:
+            return {}
+        return {"acf_temps": acf_temps(self._acf_mode, n_temps), "acf_every": self._acf_every, "acf_max_lag": self._acf_max_lag,
+                "acf_ring_limit": self._acf_ring_limit}
+
+    def _acf_data(self, temperature) -> tuple:
+        if getattr(self, "_acf_mode", None) is None:
+            raise RuntimeError("the autocovariance is off: construct the sampler with acf='cold' or 'all'")
+        temps = acf_temps(self._acf_mode, len(getattr(self, "beta_ladder", [1.0])))
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, np.integer)) or not 0 <= temperature < temps:
+            raise ValueError(f"temperature must be in 0..{temps - 1} (the autocovariance covers the first {temps}), got {temperature!r}")
+        run = getattr(self, "_run", None)
+        if run is None or run.autocorr_sums() is None:  # nothing run yet, or reset(): empty sums
+            z = torch.zeros(self._acf_max_lag + 1, self.dim, dtype=torch.float64)
+            return z, z.clone(), z.clone(), torch.zeros(self._acf_max_lag + 1, dtype=torch.int64)
+        a = run.autocorr_sums()
+        t = int(temperature)
+        return a["sxy"][t].cpu(), a["head"][t].cpu(), a["tail"][t].cpu(), a["pairs"].cpu()
+
+    def autocovariance(self, temperature: int = 0) -> torch.Tensor:
+        """c_k of every coordinate at lags k = 0 .. acf_max_lag (in snapshots: acf_every steps apart), pooled over every replica
+        and every snapshot: float64 [acf_max_lag + 1, dim]; NaN at a lag no snapshot has reached yet."""
+        return acf_autocovariance(*self._acf_data(temperature))
+
+    def autocorrelation(self, temperature: int = 0) -> torch.Tensor:
+        """rho_k = c_k / c_0: float64 [acf_max_lag + 1, dim]."""
+        return acf_autocorrelation(*self._acf_data(temperature))
+
+    def integrated_autocorr_time(self, temperature: int = 0, c: float = 5.0) -> tuple:
+        """(tau [dim] float64, window [dim] int64, reached [dim] bool): the integrated autocorrelation time of every coordinate
+        by Sokal's automatic window - the smallest M with M >= c tau(M), tau(M) = 1 + 2 sum_{k <= M} rho_k.  tau is in units of
+        SNAPSHOTS: multiply by acf_every for steps only when acf_every is much shorter than tau (a thinned sequence's tau is
+        not the full one's divided by the thinning otherwise).  Where no window up to acf_max_lag qualifies, `reached` is False
+        and tau is the value at acf_max_lag - a lower bound on the autocorrelation time, not an estimate of it."""
+        return sokal_window(self.autocorrelation(temperature), c)
+
+    def ess_autocorr(self, temperature: int = 0) -> torch.Tensor:
+        """Effective sample size of every coordinate: pairs[0] / tau - the (replica, snapshot) pairs so far over the integrated
+        autocorrelation time (in snapshots).  Where the window was not reached tau is a lower bound, so this is an UPPER bound;
+        check integrated_autocorr_time()[2].  float64 [dim]."""
+        tau = self.integrated_autocorr_time(temperature)[0]
+        return float(self._acf_data(temperature)[3][0]) / tau
+
+    def _acf_diagnostics(self) -> dict:
+        if getattr(self, "_acf_mode", None) is None:
+            return {}
+        tau, _, reached = self.integrated_autocorr_time(0)
+        ok = bool(torch.isfinite(tau).all())
+        return {"act_max": float(tau.max()) if ok else float("nan"), "act_window_reached": bool(reached.all())}
 
 
 # ---- pooled marginal histograms of the drop-in classes -------------------------------------------------------------

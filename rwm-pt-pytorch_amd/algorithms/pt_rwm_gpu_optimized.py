@@ -32,7 +32,7 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import (EngineRun, LadderAdaptation, MarginalHistograms, PosteriorMoments, ScaleAdaptation,
+from ._engine_core import (Autocorrelation, EngineRun, LadderAdaptation, MarginalHistograms, PosteriorMoments, ScaleAdaptation,
                            check_class_starts, moments_temps, resolve_device)
 from .sharding import flow_round_trip_rate, flow_up_fraction
 
@@ -47,7 +47,7 @@ def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
     return [float(beta_min ** (t / (n_temps - 1))) for t in range(n_temps)]
 
 
-class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, ScaleAdaptation, LadderAdaptation, MHAlgorithm):
+class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, ScaleAdaptation, LadderAdaptation, MHAlgorithm):
     def __init__(self, dim: int, var: float, target_dist=None, symmetric: bool = True, beta_ladder: list = None,
                  iterative_temp_spacing: bool = False, geom_temp_spacing: bool = False,
                  swap_acceptance_rate: float = 0.234, beta_min_iterative: float = 0.01, N_samples_swap_est: int = 3000,
@@ -66,7 +66,8 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
                  adapt_target: float = 0.234, adapt_gain: float = 3.0, adapt_decay: float = 0.5,
                  adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False, ladder_every: int = 100,
                  ladder_until: Optional[int] = None, ladder_probe_every: Optional[int] = None, ladder_gain: float = 2.0,
-                 ladder_decay: float = 0.5):
+                 ladder_decay: float = 0.5, acf: Optional[str] = None, acf_every: int = 1, acf_max_lag: int = 32,
+                 acf_ring_limit: Optional[int] = None):
         super().__init__(dim, var, target_dist, symmetric)
         # warm-up tuning of the proposal scale per temperature (include/ptrwm.h ptrwm_adapt_args): adapt_scale=True tunes towards
         # adapt_target in windows of adapt_every steps up to adapt_until (default: all of burn-in); adapt_scale_bounds are factors
@@ -78,6 +79,10 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
         # pooled marginal histograms over every replica (include/ptrwm.h ptrwm_hist_args): hist='cold' or 'all' temperatures,
         # hist_range=(lo, hi) the range of the hist_bins bins, a snapshot every hist_every-th step past burn-in
         self._check_hist_ctor(dim, hist, hist_range, hist_bins, hist_every)
+        # pooled lagged autocovariance over every replica (include/ptrwm.h ptrwm_acf_args): acf='cold' or 'all' temperatures, a
+        # snapshot every acf_every-th step past burn-in, lags 0..acf_max_lag in snapshots; acf_ring_limit overrides the largest
+        # ring (elements) the constructor accepts
+        self._check_acf_ctor(dim, acf, acf_every, acf_max_lag, acf_ring_limit)
         self._flow_on = bool(flow)
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         self._moments_mode, self._moments_every = moments, int(moments_every)
@@ -278,7 +283,8 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
             swap_mode=self._swap_mode, swap_order=self._swap_order, seed=self._seed, chain_offset=self._chain_offset,
             dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, flow=self._flow_on,
-            **self._hist_kwargs(len(self.beta_ladder)), **self._adapt_kwargs(), **self._ladder_run_kwargs())
+            **self._hist_kwargs(len(self.beta_ladder)), **self._adapt_kwargs(), **self._ladder_run_kwargs(),
+            **self._acf_kwargs(len(self.beta_ladder)))
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
         self.current_log_densities = self._run.logp[0] if self.num_replicas == 1 else self._run.logp
@@ -525,6 +531,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, S
             **self._moments_diagnostics(),
             **self._flow_diagnostics(),
             **self._hist_diagnostics(),
+            **self._acf_diagnostics(),
             **self._adapt_diagnostics(),
             **self._ladder_diagnostics(),
         }

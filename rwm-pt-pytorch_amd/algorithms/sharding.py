@@ -177,6 +177,29 @@ def allreduce_histogram(sampler, group: Optional[dist.ProcessGroup] = None) -> d
     return {"counts": vec[:n].view(counts.shape), "count": vec[n:].view(count.shape), "edges": h.get("edges")}
 
 
+def allreduce_autocorr(sampler, group: Optional[dist.ProcessGroup] = None) -> dict:
+    """Whole-job pooled lagged autocovariance sums from every rank's shard: ONE float64 SUM all-reduce of `sxy`, `head`, `tail`
+    and `pairs` packed into one vector (the pair counts ride as doubles: exact below 2^53).  `sampler`: a sampler constructed
+    with acf=, its EngineRun, or the dict EngineRun.autocorr_sums() returns.  Returns new tensors {"sxy", "head", "tail",
+    "pairs"} on the shards' device plus "every"; the shard's own arrays are not modified.  The estimators
+    (algorithms._engine_core.acf_autocovariance, acf_autocorrelation, sokal_window) take one temperature's rows of them."""
+    a = sampler
+    if not isinstance(a, dict):
+        run = getattr(sampler, "_run", sampler)
+        a = run.autocorr_sums() if run is not None and hasattr(run, "autocorr_sums") else None
+        if a is None:
+            raise RuntimeError("allreduce_autocorr: the autocovariance is off, or nothing has run yet")
+    parts = [a[k] for k in ("sxy", "head", "tail", "pairs")]
+    vec = torch.cat([p.reshape(-1).to(torch.float64) for p in parts])
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=group)
+    out, at = {"every": a.get("every")}, 0
+    for k, p in zip(("sxy", "head", "tail", "pairs"), parts):
+        out[k] = vec[at:at + p.numel()].view(p.shape).to(p.dtype)
+        at += p.numel()
+    return out
+
+
 # ---- warm-up tuning of the proposal scale and of the ladder (include/ptrwm.h ptrwm_adapt_args, ptrwm_ladder_args) ---------------
 def adaptation_sync(group: Optional[dist.ProcessGroup] = None):
     """The `adapt_sync=` callable of a sharded run, for both tunings: all-reduces (SUM) the pooled int64 counts of a window in

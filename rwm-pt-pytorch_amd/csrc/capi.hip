@@ -4,6 +4,7 @@
 #include <cmath>
 
 #include "../../include/ptrwm.h"
+#include "acf.h"
 #include "adapt.h"
 #include "ladder.h"
 #include "hist.h"
@@ -768,6 +769,112 @@ __global__ void __launch_bounds__(256) hist_snapshot_kernel(HistSnapArgs a) {
     for (int t = tid; t < a.temps; t += 256) count_add(&a.count[t], c1 - c0);
 }
 
+// Pooled lagged autocovariance (ptrwm_autocorr, and the snapshots of ptrwm_run_with_autocorr; acf.h states the rule and the
+// geometry): one snapshot of `state`, shaped as hist_snapshot_kernel - a workgroup takes a tile of a.chains chains (blockIdx.x)
+// and a group of a.cols of the first temps * dim elements of every chain's run (blockIdx.y); consecutive threads read
+// consecutive elements of a chain, and where a group has fewer than 256 columns the threads take a.per chains at a time.  A
+// thread keeps its column of kAcfChainsPerThread chains of x_j in registers (read once), streams the same elements of the ring
+// slot of every available lag past them - kAcfChainsPerThread independent loads in flight per lag - and sums its products and
+// the ring's values in double.  Per lag the a.per threads of a column meet in LDS (ds_add_f64 into one of two buffers, taken
+// in turn: one barrier per lag), and the column's first thread flushes the tile's three sums, one no-return fp64 atomic per
+// non-zero sum.  (head: the sum of x_j, the same for every lag - it is the lag-0 `tail`.)  Then the thread overwrites its
+// elements of slot j % max_lag: nobody else reads or writes them.
+struct AcfSnapArgs {
+  const void *state;  // float or double [n_chains, n_temps, dim]
+  void *ring;         // the same type [max_lag, n_chains, temps * dim]
+  double *sxy, *head, *tail;
+  long long *pairs;
+  long long n_chains, step, burn_in, every;
+  const long long *device_step;
+  int n_temps, dim, temps, max_lag, cols, per, chains;
+};
+
+template <class state_t>
+__global__ void __launch_bounds__(kAcfThreads) acf_snapshot_kernel(AcfSnapArgs a) {
+  // is the step just performed a due one?  (grid-uniform, as SplitMomentsArgs::step_counts)
+  const long long sc = (a.device_step != nullptr ? *a.device_step + a.step : a.step) + 1;
+  if (!periodic_step_due(sc, a.burn_in, a.every)) return;
+  constexpr int R = kAcfChainsPerThread;
+  __shared__ double s_red[2][2][kAcfThreads];  // [buffer][sxy, tail][column of the group]
+  const long long j = periodic_step_number(sc, a.burn_in, a.every);
+  const int lags = acf_lags(j, a.max_lag);
+  const int tid = (int)threadIdx.x, td = a.temps * a.dim;
+  const int sub = tid / a.cols, kk = tid - sub * a.cols, k = (int)blockIdx.y * a.cols + kk;
+  const bool live = sub < a.per && k < td;
+  const bool first = live && sub == 0;
+  const bool pooled = a.per > 1;  // (grid-uniform)
+  const long long c0 = (long long)blockIdx.x * a.chains + sub;  // this thread's chains: c0, c0 + per, ...
+  long long left = live ? (a.n_chains - c0 + a.per - 1) / a.per : 0;
+  const int nv = left < 0 ? 0 : (left > R ? R : (int)left);  // ... nv of them
+  if (pooled) {
+    s_red[0][0][tid] = s_red[0][1][tid] = s_red[1][0][tid] = s_red[1][1][tid] = 0.0;
+    __syncthreads();
+  }
+  const long long run = (long long)a.n_temps * a.dim, cstep = (long long)a.per * td;
+  const long long slot_elems = a.n_chains * td, own = c0 * td + k;  // (of a slot: this thread's first element)
+  state_t x[R];
+  {
+    const state_t *__restrict__ p = reinterpret_cast<const state_t *>(a.state) + c0 * run + k;
+#pragma unroll
+    for (int i = 0; i < R; ++i) x[i] = i < nv ? p[(long long)i * a.per * run] : state_t(0);
+  }
+  state_t *ring = reinterpret_cast<state_t *>(a.ring);
+  const int t = k / a.dim, d = k - t * a.dim;
+  const long long acc0 = (long long)t * (a.max_lag + 1) * a.dim + d;  // element [t, 0, d] of the sums
+  double hsum = 0.0;
+  for (int lag = 0; lag <= lags; ++lag) {
+    double sx = 0.0, tl = 0.0;
+    if (lag == 0) {
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        const double v = (double)x[i];
+        sx += acf_term(v, v);
+        tl += v;
+      }
+    } else if (nv > 0) {
+      const state_t *r = ring + (long long)acf_lag_slot(j, lag, a.max_lag) * slot_elems + own;
+      state_t y[R];
+#pragma unroll
+      for (int i = 0; i < R; ++i) y[i] = i < nv ? r[(long long)i * cstep] : state_t(0);
+#pragma unroll
+      for (int i = 0; i < R; ++i) {
+        const double v = (double)y[i];
+        sx += acf_term((double)x[i], v);
+        tl += v;
+      }
+    }
+    if (pooled) {
+      const int b = lag & 1;
+      if (live) {
+        if (sx != 0.0) unsafeAtomicAdd(&s_red[b][0][kk], sx);
+        if (tl != 0.0) unsafeAtomicAdd(&s_red[b][1][kk], tl);
+      }
+      __syncthreads();
+      if (first) {
+        sx = s_red[b][0][kk];
+        tl = s_red[b][1][kk];
+        s_red[b][0][kk] = 0.0;  // (added to again two lags on, behind the next barrier)
+        s_red[b][1][kk] = 0.0;
+      }
+    }
+    if (first) {
+      if (lag == 0) hsum = tl;
+      const long long e = acc0 + (long long)lag * a.dim;
+      if (sx != 0.0) unsafeAtomicAdd(a.sxy + e, sx);
+      if (hsum != 0.0) unsafeAtomicAdd(a.head + e, hsum);
+      if (tl != 0.0) unsafeAtomicAdd(a.tail + e, tl);
+    }
+  }
+  if (nv > 0) {
+    state_t *w = ring + (long long)acf_slot(j, a.max_lag) * slot_elems + own;
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+      if (i < nv) w[(long long)i * cstep] = x[i];
+  }
+  if (blockIdx.x == 0 && blockIdx.y == 0)
+    for (int lag = tid; lag <= lags; lag += kAcfThreads) count_add(&a.pairs[lag], a.n_chains);
+}
+
 // ---- warm-up tuning of the proposal scale (adapt.h; include/ptrwm.h ptrwm_adapt_args) ---------------------------------------
 // Two small kernels between launches, as the histogram's snapshot: the step kernels are told nothing.  A launch inside an
 // adapting window adds its acceptances to window_accept [n_chains, n_temps]; at the window's end adapt_reduce_kernel sums
@@ -1114,6 +1221,49 @@ static int32_t launch_hist(const ptrwm_run_args *args, int32_t dim, const ptrwm_
   return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 
+// the autocovariance checks shared by ptrwm_run_with_autocorr and ptrwm_autocorr (args already checked); none: ok
+static int32_t check_acf(const ptrwm_run_args *args, const ptrwm_acf_args *ac) {
+  if (ac == nullptr) return PTRWM_OK;
+  if (ac->struct_size != sizeof(ptrwm_acf_args)) return PTRWM_E_STRUCT;
+  if (ac->temps < 1 || ac->temps > args->n_temps || ac->every < 1 || ac->max_lag < 1 || ac->max_lag > PTRWM_ACF_MAX_LAG) return PTRWM_E_ARG;
+  if (ac->ring == nullptr || ac->sxy == nullptr || ac->head == nullptr || ac->tail == nullptr || ac->pairs == nullptr) return PTRWM_E_NULL;
+  return PTRWM_OK;
+}
+static_assert(PTRWM_ACF_MAX_LAG == kAcfMaxLag, "acf.h and include/ptrwm.h: one lag limit");
+
+// One snapshot of the state after step `step` (device_step != NULL: *device_step + step); everything checked
+static int32_t launch_acf(const ptrwm_run_args *args, int32_t dim, const ptrwm_acf_args *ac, long long step,
+                          const long long *device_step, hipStream_t stream) {
+  AcfSnapArgs a;
+  a.state = args->state;
+  a.ring = ac->ring;
+  a.sxy = ac->sxy;
+  a.head = ac->head;
+  a.tail = ac->tail;
+  a.pairs = (long long *)ac->pairs;
+  a.n_chains = args->n_chains;
+  a.step = step;
+  a.burn_in = args->burn_in;
+  a.every = ac->every;
+  a.device_step = device_step;
+  a.n_temps = args->n_temps;
+  a.dim = dim;
+  a.temps = ac->temps;
+  a.max_lag = ac->max_lag;
+  const AcfGeometry g = acf_geometry(ac->temps * dim);
+  a.cols = g.cols;
+  a.per = g.per;
+  a.chains = g.chains;
+  const long long gx = (args->n_chains + g.chains - 1) / g.chains;
+  if (gx > 0x7fffffffll) return PTRWM_E_ARG;
+  const dim3 grid((unsigned)gx, (unsigned)g.groups);  // (y <= 104)
+  if (args->state_f64 == 1)
+    hipLaunchKernelGGL(acf_snapshot_kernel<double>, grid, dim3(kAcfThreads), 0, stream, a);
+  else
+    hipLaunchKernelGGL(acf_snapshot_kernel<float>, grid, dim3(kAcfThreads), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}
+
 // the adaptation checks shared by ptrwm_run_with_adaptation, ptrwm_adapt_reduce and ptrwm_adapt_update (none: ok); what
 // needs the run (until <= burn_in, temp_scale == proposal->temp_scale) is checked by run_impl itself (tuning_fits_run)
 static int32_t check_tuning(const ptrwm_adapt_args *ad) {
@@ -1231,7 +1381,8 @@ static bool tuning_fits_run(const Tuning *tu, const ptrwm_run_args *args, const 
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                         const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist = nullptr,
-                        const ptrwm_adapt_args *adapt = nullptr, const ptrwm_ladder_args *ladder = nullptr);
+                        const ptrwm_adapt_args *adapt = nullptr, const ptrwm_ladder_args *ladder = nullptr,
+                        const ptrwm_acf_args *acf = nullptr);
 static int32_t swap_sweep_impl(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
                                const ptrwm_flow_args *flow, void *stream);
 static int32_t split_accept_impl(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
@@ -1390,6 +1541,14 @@ int32_t ptrwm_run_with_ladder(const ptrwm_target_desc *target, const ptrwm_propo
   return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist, adapt, ladder);
 }
 
+int32_t ptrwm_run_with_autocorr(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                                const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
+                                const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt,
+                                const ptrwm_ladder_args *ladder, const ptrwm_acf_args *acf, void *stream) {
+  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // (as ptrwm_run_with_diagnostics)
+  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist, adapt, ladder, acf);
+}
+
 int32_t ptrwm_ladder_probe(const ptrwm_run_args *args, const ptrwm_ladder_args *ladder, void *stream) {
   if (int rc = check_tuning_call(ladder, true, args, 0, 0)) return rc;
   if (args->n_temps < 3 || ladder->beta != args->beta) return PTRWM_E_ARG;
@@ -1416,6 +1575,20 @@ int32_t ptrwm_histogram(const ptrwm_run_args *args, int32_t dim, const ptrwm_his
   if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, hist->every))
     return PTRWM_OK;  // (known on the host: no snapshot is due)
   return launch_hist(args, dim, hist, args->step0, (const long long *)args->device_step, (hipStream_t)stream);
+}
+
+int32_t ptrwm_autocorr(const ptrwm_run_args *args, int32_t dim, const ptrwm_acf_args *acf, void *stream) {
+  if (args == nullptr || acf == nullptr) return PTRWM_E_NULL;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
+  if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
+  if (!is_flag(args->state_f64) || args->n_chains < 0 || args->step0 < 0 || args->burn_in < 0) return PTRWM_E_ARG;
+  if (int rc = check_acf(args, acf)) return rc;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->state == nullptr) return PTRWM_E_NULL;
+  if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, acf->every))
+    return PTRWM_OK;  // (known on the host: no snapshot is due)
+  return launch_acf(args, dim, acf, args->step0, (const long long *)args->device_step, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1617,7 +1790,7 @@ static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_de
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                         const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist,
-                        const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder) {
+                        const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder, const ptrwm_acf_args *acf) {
   bool empty = false;
   if (int rc = check_run(target, proposal, args, spec, flow, hist, &empty)) return rc;
   // the two tunings (adapt.h, ladder.h): their own checks after the existing ones, all before anything is enqueued
@@ -1628,6 +1801,7 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
     if (args->n_temps < 3 || !tuning_fits_run(ladder, args, ladder->beta, args->beta)) return PTRWM_E_ARG;
     if (ladder->temp_scale != nullptr && ladder->temp_scale != proposal->temp_scale) return PTRWM_E_ARG;
   }
+  if (int rc = check_acf(args, acf)) return rc;  // (the autocovariance: after every existing block's checks)
   if (empty) return PTRWM_OK;
   // (every = 0: no such tuning, schedule.h)
   const WarmupWindows scale_w = adapt != nullptr ? WarmupWindows{adapt->every, adapt->until} : WarmupWindows{0, 0};
@@ -1652,7 +1826,9 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   const auto countdown = [](int steps) { return (unsigned)(steps < kNoStepInLaunch ? steps : kNoStepInLaunch); };  // (a launch: <= 2^16 steps)
   for (long long done = 0; done < args->n_steps; done += k.n_steps) {
     // (histograms: a launch also ends at every due snapshot step - the snapshot kernel reads the state between launches)
-    const long long to_snap = hist != nullptr ? steps_to_next_due(args->step0 + done, args->burn_in, hist->every) : cap;
+    long long to_snap = hist != nullptr ? steps_to_next_due(args->step0 + done, args->burn_in, hist->every) : cap;
+    // (the autocovariance: likewise, at its own period)
+    if (acf != nullptr) to_snap = std::min(to_snap, steps_to_next_due(args->step0 + done, args->burn_in, acf->every));
     // (the tunings, schedule.h warmup_launch_at: a launch inside an adapting window of the scale ends with the window at the
     // latest - the reduce and update kernels run between two launches - and is the production kernel told to count from its
     // first step, into the window scratch, and that no multiple of swap_every lies in it: count_on holds and swap_due never
@@ -1684,6 +1860,8 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
     if (c.fn(k, c.n_blocks, c.mode, (hipStream_t)hip_stream) != hipSuccess) return PTRWM_E_LAUNCH;
     if (hist != nullptr && periodic_step_due(cut.step0 + cut.n, args->burn_in, hist->every))
       if (int rc = launch_hist(args, target->dim, hist, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
+    if (acf != nullptr && periodic_step_due(cut.step0 + cut.n, args->burn_in, acf->every))
+      if (int rc = launch_acf(args, target->dim, acf, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
     if (wl.scale_reduce)
       if (int rc = launch_adapt_reduce(adapt, args->n_chains, args->n_temps, (hipStream_t)hip_stream)) return rc;
     if (wl.scale_update)

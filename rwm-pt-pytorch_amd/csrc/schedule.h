@@ -49,9 +49,13 @@ PTRWM_HD inline long long steps_to_next_due(long long step0, long long burn_in, 
   return (base / period + 1) * period - step0;
 }
 
-// 0-based number, since the start of the run, of the swap event of the swap step sc (periodic_step_due(sc, ...) holds)
+// 0-based number, since the start of the run, of the due step sc of a period (periodic_step_due(sc, ...) holds): the swap
+// event of a swap step, the snapshot of a snapshot step (acf.h).  It comes from the step counter alone - nobody counts.
+PTRWM_HD inline long long periodic_step_number(long long sc, long long burn_in, long long period) {
+  return sc / period - burn_in / period - 1;
+}
 PTRWM_HD inline long long swap_event_number(long long sc, long long burn_in, long long swap_every) {
-  return sc / swap_every - burn_in / swap_every - 1;
+  return periodic_step_number(sc, burn_in, swap_every);
 }
 
 // One split step (ptrwm_split_accept): do its acceptances count, and does a swap event follow it?

@@ -209,6 +209,24 @@ class LadderArgs(C.Structure):
     ]
 
 
+class AcfArgs(C.Structure):
+    """ptrwm_acf_args: pooled lagged autocovariance of the first ``temps`` temperatures (include/ptrwm.h, csrc/acf.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("temps", C.c_int32),
+        ("every", C.c_int32),
+        ("max_lag", C.c_int32),
+        ("ring", C.c_void_p),
+        ("sxy", C.c_void_p),
+        ("head", C.c_void_p),
+        ("tail", C.c_void_p),
+        ("pairs", C.c_void_p),
+    ]
+
+
+ACF_MAX_LAG = 1024
+
+
 class InitArgs(C.Structure):
     """ptrwm_init_args: starting points drawn from a box, or set to a fallback point (include/ptrwm.h)."""
     _fields_ = [
@@ -269,6 +287,11 @@ SYMBOLS = {
          C.POINTER(FlowArgs), C.POINTER(HistArgs), C.POINTER(AdaptArgs), C.POINTER(LadderArgs), C.c_void_p]),
     "ptrwm_ladder_probe": (C.c_int32, [C.POINTER(RunArgs), C.POINTER(LadderArgs), C.c_void_p]),
     "ptrwm_ladder_update": (C.c_int32, [C.POINTER(LadderArgs), C.c_int32, C.c_int64, C.c_void_p]),
+    "ptrwm_run_with_autocorr": (
+        C.c_int32,
+        [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.POINTER(ChainMomentsArgs),
+         C.POINTER(FlowArgs), C.POINTER(HistArgs), C.POINTER(AdaptArgs), C.POINTER(LadderArgs), C.POINTER(AcfArgs), C.c_void_p]),
+    "ptrwm_autocorr": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(AcfArgs), C.c_void_p]),
     "ptrwm_swap_sweep_with_flow": (
         C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_int64, C.c_int32, C.POINTER(FlowArgs), C.c_void_p]),
     "ptrwm_split_accept_with_flow": (
@@ -678,6 +701,7 @@ class RunPlan:
         self._hist = None  # pooled marginal histograms: (struct, byref, tensors)
         self._adapt = None  # warm-up tuning of the proposal scale: (struct, byref, tensors)
         self._ladder = None  # warm-up tuning of the temperature ladder: (struct, byref, tensors)
+        self._acf = None  # pooled lagged autocovariance: (struct, byref, tensors)
 
     # kind of accumulator -> (words of its messages, struct, entry point of launch(), entry point of split_moments())
     _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
@@ -800,6 +824,58 @@ class RunPlan:
         h.counts = _require_device(counts, "histogram counts", torch.int64)
         h.count = _opt(count, "histogram count", torch.int64)
         self._hist = (h, C.byref(h), (counts, lo, scale, count))
+
+    def set_autocorr(self, ring: Optional[torch.Tensor], sxy: Optional[torch.Tensor] = None, head: Optional[torch.Tensor] = None,
+                     tail: Optional[torch.Tensor] = None, pairs: Optional[torch.Tensor] = None, *, every: int = 1) -> None:
+        """Accumulate the pooled lagged autocovariance (include/ptrwm.h ptrwm_acf_args) in every following ``launch`` and
+        ``split_autocorr``: ``ring`` [max_lag, n_chains, temps, dim] of the state's dtype (scratch: the last ``max_lag``
+        snapshots), ``sxy`` / ``head`` / ``tail`` [temps, max_lag + 1, dim] float64 and ``pairs`` [max_lag + 1] int64, all on the
+        run's device; the sums are added to (+=).  ``temps`` and ``max_lag`` are read off ``ring``.  ``launch`` then ends a
+        kernel launch at every due step and enqueues the snapshot kernel behind it.  Every due step must be snapshotted, in
+        order (csrc/acf.h).  ``set_autocorr(None)`` switches it off."""
+        if ring is None:
+            self._acf = None
+            return
+        Cn, T, D = self.shape
+        if ring.dim() != 4 or ring.shape[1] != Cn or ring.shape[3] != D:
+            raise ValueError(f"autocorr ring must be [max_lag, {Cn}, temps, {D}]")
+        max_lag, temps, every = int(ring.shape[0]), int(ring.shape[2]), int(every)
+        if not 1 <= max_lag <= ACF_MAX_LAG:
+            raise ValueError(f"autocorr max_lag must be in 1..{ACF_MAX_LAG}, got {max_lag}")
+        if not 1 <= temps <= T:
+            raise ValueError(f"autocorr temps must be in 1..{T}, got {temps}")
+        if every < 1:
+            raise ValueError("autocorr every must be >= 1")
+        for name, t in (("sxy", sxy), ("head", head), ("tail", tail)):
+            if t is None or tuple(t.shape) != (temps, max_lag + 1, D):
+                raise ValueError(f"autocorr {name} must be [{temps}, {max_lag + 1}, {D}]")
+        if pairs is None or tuple(pairs.shape) != (max_lag + 1,):
+            raise ValueError(f"autocorr pairs must be [{max_lag + 1}]")
+        for name, t in (("ring", ring), ("sxy", sxy), ("head", head), ("tail", tail), ("pairs", pairs)):
+            if t.device != self.device:
+                raise ValueError(f"autocorr {name} is on {t.device}, state on {self.device}")
+        ac = AcfArgs()
+        ac.struct_size = C.sizeof(AcfArgs)
+        ac.temps, ac.every, ac.max_lag = temps, every, max_lag
+        ac.ring = _require_device(ring, "autocorr ring", self.state_dtype)
+        ac.sxy = _require_device(sxy, "autocorr sxy", torch.float64)
+        ac.head = _require_device(head, "autocorr head", torch.float64)
+        ac.tail = _require_device(tail, "autocorr tail", torch.float64)
+        ac.pairs = _require_device(pairs, "autocorr pairs", torch.int64)
+        self._acf = (ac, C.byref(ac), (ring, sxy, head, tail, pairs))
+
+    def split_autocorr(self, step: int) -> None:
+        """Autocovariance snapshot of the state after the split step ``step`` just performed (ptrwm_autocorr; device-step mode:
+        counter + step - decided on the device, so the call can sit in a captured block).  Enqueue after ``split_accept``
+        (and ``split_histogram``), behind EVERY step: the library skips the steps that are not due.  No-op without an
+        accumulator."""
+        if self._acf is None:
+            return
+        self._a.step0 = step
+        with self._guard:
+            rc = self._lib.ptrwm_autocorr(self._refs[4], self.shape[2], self._acf[1], _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_autocorr")
 
     def _tuning_windows(self, what: str, every, until) -> tuple:
         """every, until and K = until // every of a warm-up tuning (`what` starts its messages), checked against the plan"""
@@ -1048,13 +1124,14 @@ class RunPlan:
             if trace is not None and ext_prop is None and ext_u is None and ext_swap_u is None and accept_flags is None:
                 self._last_trace = (trace, trace_logp, trace_every)
         # ptrwm_run, or the accumulator's entry point with its struct in front of the stream; with anything else bound, the
-        # first of ptrwm_run_with_diagnostics / _histogram / _adaptation / _ladder that takes all that is bound: each takes what
-        # the one before it takes and one struct more, behind the two accumulators (pooled, per chain)
+        # first of ptrwm_run_with_diagnostics / _histogram / _adaptation / _ladder / _autocorr that takes all that is bound: each
+        # takes what the one before it takes and one struct more, behind the two accumulators (pooled, per chain)
         name, opt = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
-        if self._flow is not None or self._hist is not None or self._adapt is not None or self._ladder is not None:
-            more = [b[1] if b is not None else None for b in (self._flow, self._hist, self._adapt, self._ladder)]
+        if any(b is not None for b in (self._flow, self._hist, self._adapt, self._ladder, self._acf)):
+            more = [b[1] if b is not None else None for b in (self._flow, self._hist, self._adapt, self._ladder, self._acf)]
             last = max(i for i, b in enumerate(more) if b is not None)
-            name = ("ptrwm_run_with_diagnostics", "ptrwm_run_with_histogram", "ptrwm_run_with_adaptation", "ptrwm_run_with_ladder")[last]
+            name = ("ptrwm_run_with_diagnostics", "ptrwm_run_with_histogram", "ptrwm_run_with_adaptation", "ptrwm_run_with_ladder",
+                    "ptrwm_run_with_autocorr")[last]
             kind, mom = (self._mom[0], self._mom[2]) if self._mom is not None else (None, None)
             opt = (mom if kind == "pooled" else None, mom if kind == "chain" else None, *more[:last + 1])
         with self._guard:
