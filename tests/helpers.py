@@ -262,9 +262,12 @@ def step_log_ratios(spec, prop, pre_state, ext_row, beta):
     if np.asarray(pre_state).dtype == np.float64:
         # state_f64 mode (Normal proposal): y = x + scale * z, one double product and one double sum, as the reference's
         # dtype=torch.float64 path and the kernel's F64 form compute it
-        assert prop.kind == O.PROPOSAL_NORMAL
         x = np.ascontiguousarray(pre_state, dtype=np.float64)
-        y = x + np.asarray(ext_row, np.float64) * np.asarray(prop.temp_scale, f32).astype(np.float64)[:, None]
+        if prop.kind == O.PROPOSAL_NORMAL:
+            y = x + np.asarray(ext_row, np.float64) * np.asarray(prop.temp_scale, f32).astype(np.float64)[:, None]
+        else:
+            # Laplace / UniformRadius (Philox mode only): the kernel adds its FLOAT increment to the double state
+            y = x + O.propose(prop.oracle(), D, 1, ext_raw=np.ascontiguousarray(ext_row, dtype=f32)[None])[0]
     else:
         inc = O.propose(prop.oracle(), D, 1, ext_raw=np.ascontiguousarray(ext_row, dtype=f32)[None])[0]  # fp32 arithmetic
         x = np.ascontiguousarray(pre_state, dtype=f32)
@@ -555,9 +558,12 @@ def check_parity_philox(run, spec, prop, *, state, logp, beta, n_steps, burn_in,
     if f64:
         # the kernel adds its float increment to the double state; the oracle's double path multiplies the same float
         # normal by the float scale in double: equal to ~1e-8 of the increment, compared with the usual state tolerance
-        assert prop.kind == O.PROPOSAL_NORMAL, "state_f64 comparisons against the oracle: Normal proposal"
         ext_prop = ext_prop.astype(np.float64)
     run_a, run_b = philox_runner(run, seed), oracle_runner(spec, prop)
+    if f64 and prop.kind != O.PROPOSAL_NORMAL:
+        # the oracle's double path takes external randoms for the Normal proposal only; with any proposal it draws from
+        # Philox itself, the same words (increments in double where the kernel's are float: within the state tolerance)
+        run_b = philox_runner(run_b, seed)
     common = dict(beta=beta, burn_in=burn_in, swap_every=swap_every, swap_mode=swap_mode, swap_order=swap_order,
                   chain_offset=chain_offset, exact_states=False, **tol)
     if segment is None or segment >= n_steps:

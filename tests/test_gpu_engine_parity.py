@@ -1250,19 +1250,23 @@ def test_float64_golden_trajectory(device):
     logp_close(got["trace_logp"][:, 0], f["logp_chains"].T[1:], extra_abs=3e-4)
 
 
-F64_CASES = [("rc15_d30", 8, 5), ("tm_d50", 20, 3), ("even_d30", 3, 11), ("gamma_d5", 1, 40), ("hyb_5_4", 70, 2)]
+F64_CASES = [("rc15_d30", 8, 5, "Normal"), ("tm_d50", 20, 3, "Normal"), ("even_d30", 3, 11, "Normal"), ("gamma_d5", 1, 40, "Normal"),
+             ("hyb_5_4", 70, 2, "Normal"), ("rc15_d30", 8, 5, "Laplace"), ("gamma_d5", 4, 40, "UniformRadius")]
 
 
-@pytest.mark.parametrize("tkey,T,Cn", F64_CASES, ids=[f"{c[0]}-T{c[1]}" for c in F64_CASES])
-def test_float64_states_vs_oracle(device, tkey, T, Cn):
+@pytest.mark.parametrize("tkey,T,Cn,pname", F64_CASES,
+                         ids=[f"{c[0]}-T{c[1]}" + ("" if c[3] == "Normal" else f"-{c[3]}") for c in F64_CASES])
+def test_float64_states_vs_oracle(device, tkey, T, Cn, pname):
     """The F64 form on other targets, ladder shapes (one temperature, a wavefront's worth, wider than a wavefront) and
     every swap semantics: external double normals (states bit-identical to the oracle's double path between proven flips)
-    and the in-kernel Philox stream (every differing decision proven)."""
+    and the in-kernel Philox stream (every differing decision proven).  The Laplace and UniformRadius cases run the Philox
+    stream only: the double path takes external randoms for the Normal proposal alone."""
     spec = H.target_spec(tkey)
-    rng = np.random.default_rng(zlib.crc32(f"f64-{tkey}-{T}".encode()))
+    rng = np.random.default_rng(zlib.crc32((f"f64-{tkey}-{T}" + ("" if pname == "Normal" else f"-{pname}")).encode()))
     beta = (0.05 ** (np.arange(T) / max(1, T - 1))).astype(np.float32)
     scale = 0.01 if "Rosenbrock" in spec.cls else (0.3 if "Gamma" in spec.cls else 2.38**2 / spec.dim)
-    prop = H.proposal_spec("Normal", spec.dim, beta, base_variance_scalar=scale)
+    prop = H.proposal_spec(pname, spec.dim, beta, base_variance_scalar=scale, base_variance_vector=np.full(spec.dim, scale, np.float32),
+                           base_radius=np.sqrt(scale * (spec.dim + 2)))
     st32, lp = start_state(spec, Cn, T, rng)
     st = st32.astype(np.float64) + 1e-9 * rng.standard_normal(st32.shape)  # genuinely double starting points
     lp = O.logdensity(spec.oracle(), st.reshape(-1, spec.dim), "f64").astype(np.float32).reshape(Cn, T)
@@ -1271,9 +1275,10 @@ def test_float64_states_vs_oracle(device, tkey, T, Cn):
     for mode, order in (("exchange", "sequential"), ("reference_copy", "even_odd")):
         kw = dict(state=st, logp=lp, beta=beta, n_steps=N, burn_in=burn, swap_every=se, swap_mode=E.SWAP_MODES[mode],
                   swap_order=E.SWAP_ORDERS[order])
-        H.check_parity(gpu_runner(spec, prop, device), H.oracle_runner(spec, prop), spec, prop, exact_states=True,
-                       ext_prop=rng.standard_normal((N, Cn, T, spec.dim)), ext_u=rng.random((N, Cn, T)).astype(np.float32),
-                       ext_swap_u=rng.random((n_ev, Cn, T - 1)).astype(np.float32) if T > 1 else None, **kw)
+        if pname == "Normal":
+            H.check_parity(gpu_runner(spec, prop, device), H.oracle_runner(spec, prop), spec, prop, exact_states=True,
+                           ext_prop=rng.standard_normal((N, Cn, T, spec.dim)), ext_u=rng.random((N, Cn, T)).astype(np.float32),
+                           ext_swap_u=rng.random((n_ev, Cn, T - 1)).astype(np.float32) if T > 1 else None, **kw)
         H.check_parity_philox(gpu_runner(spec, prop, device), spec, prop, seed=77, chain_offset=5, segment=PHILOX_SEGMENT, **kw)
 
 
