@@ -684,6 +684,58 @@ int32_t ptrwm_run_with_autocorr(const ptrwm_target_desc *target, const ptrwm_pro
                                 const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder,
                                 const ptrwm_acf_args *acf, void *stream);
 
+/* ---- pooled posterior covariance: how coordinates move together, without a trace --------------------------------------------------
+ * A covariance accumulator covers the first `temps` temperatures.  A snapshot is due at every step whose step_counter > burn_in
+ * and step_counter % every == 0 (the histograms' and the autocovariance's rule).  At a due step, for every covered
+ * temperature t, summed over the local chains:
+ *   sxx[t, i, j] += x[t, i] * x[t, j]   for j <= i < dim      sx[t, i] += x[t, i]      count += n_chains
+ * where x is the replica's state after the whole step (MH move and that step's swap event) - the values a trace with
+ * trace_every = every records.  Only the lower triangle of sxx (j <= i, diagonal included) is ever written; the strict upper
+ * triangle stays as the caller left it.  One term is both values converted to double and multiplied: exact for float states;
+ * for state_f64 states the product may be fused into the running sum.  Only the order of the additions is free (tile sums are
+ * flushed with fp64 atomics, as the pooled moments are).  On the host, with n = count:
+ *   cov[i, j] = sxx[i, j] / n - (sx[i] / n)(sx[j] / n),   mirrored to both triangles.
+ * These are raw sums: fp64 loses about log10(1 + mean^2 / var) digits per coordinate, as the moments' sum_sq does.
+ * The rule is csrc/cov.h's.  Everything is added to (+=): launches, calls and shards compose (sum the shards' sums).
+ * ptrwm_swap_sweep events are not steps and add nothing.
+ * How: NOT in the step kernels.  A small stand-alone snapshot kernel reads `state` between launches, as the histograms' does:
+ * a workgroup takes one covered temperature and a tile of chains, stages their rows through LDS as doubles, accumulates the
+ * lower-triangle 16 x 16 blocks of the Gram matrix with the fp64 matrix instruction (K runs over chains) and flushes one fp64
+ * atomic per non-zero element.  It reads n_chains * temps * dim elements.  The accumulators must be ordinary device memory of
+ * the current device. */
+typedef struct ptrwm_cov_args {
+  uint32_t struct_size; /* sizeof(ptrwm_cov_args) */
+  int32_t temps;        /* 1..n_temps: the first `temps` temperatures */
+  int32_t every;        /* >= 1: a snapshot at every step past burn-in whose step_counter is a multiple */
+  double *sxx;          /* device [temps, dim, dim], += on j <= i */
+  double *sx;           /* device [temps, dim], += */
+  int64_t *count;       /* device [1], += */
+} ptrwm_cov_args;
+
+/* One snapshot: the state as it stands after step args->step0 (device-step mode: *device_step + step0 - read on the device,
+ * so the call can sit inside a captured block of split steps, after ptrwm_split_accept); a step that is not due adds
+ * nothing.  Reads from `args`: n_temps, n_chains, state, state_f64, burn_in, step0, device_step.
+ * Checked, in this order, before anything is enqueued: PTRWM_E_NULL for a NULL args / cov; PTRWM_E_STRUCT for a wrong
+ * struct_size of args; PTRWM_E_DIM / PTRWM_E_TEMPS as everywhere; PTRWM_E_ARG for state_f64 outside 0..1 or a negative
+ * n_chains, step0 or burn_in; then the block's own checks as below; an empty batch returns PTRWM_OK; PTRWM_E_NULL for a NULL
+ * state. */
+int32_t ptrwm_covariance(const ptrwm_run_args *args, int32_t dim, const ptrwm_cov_args *cov, void *stream);
+
+/* ptrwm_run_with_autocorr, plus the covariance.  cov == NULL: exactly ptrwm_run_with_autocorr.
+ * A launch of the request additionally ends at every step whose step_counter is past burn_in and a multiple of cov->every,
+ * and the snapshot kernel is enqueued right after it on `stream` (behind the histogram's and the autocovariance's, where
+ * those are due at the same step); a request without such a step performs exactly the launches it performs without `cov`.
+ * No step kernel is told about it, and everything else of the run is bit-identical with and without `cov`, with the one
+ * exception that holds for any change of where a run is cut into launches (ptrwm_run_args.sq_jump above).
+ * Checked before anything is enqueued, after every other block's checks: PTRWM_E_STRUCT for a wrong cov->struct_size;
+ * PTRWM_E_ARG for temps outside 1..n_temps or every < 1; PTRWM_E_NULL for a NULL sxx, sx or count.  An empty batch returns
+ * PTRWM_OK. */
+int32_t ptrwm_run_with_covariance(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                                  const ptrwm_run_args *args, const ptrwm_moments_args *moments,
+                                  const ptrwm_chain_moments_args *chain_moments, const ptrwm_flow_args *flow,
+                                  const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder,
+                                  const ptrwm_acf_args *acf, const ptrwm_cov_args *cov, void *stream);
+
 /* One stand-alone swap event over the current states: what the reference's
  * ParallelTemperingRWM_GPU_Optimized._attempt_all_swaps() does when called on its own
  * (pt_rwm_gpu_optimized.py:594-633; tests/debug_pt_performance.py:156).  Exactly the swap part of a ptrwm_run step:

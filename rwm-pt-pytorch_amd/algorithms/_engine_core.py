@@ -56,6 +56,13 @@ by a snapshot kernel between launches at every acf_every-th step past burn-in, w
     sxy, head, tail  float64 [acf_temps, acf_max_lag + 1, dim]   sums of x_j x_{j-k}, of x_j and of x_{j-k} over replicas and snapshots
     pairs            int64   [acf_max_lag + 1]                   (replica, snapshot) pairs added per lag
 
+and, with cov_temps > 0, the pooled posterior covariance sums (`_cov`, a dict; include/ptrwm.h ptrwm_cov_args, csrc/cov.h), added
+to by a snapshot kernel between launches at every cov_every-th step past burn-in:
+
+    sxx    float64 [cov_temps, dim, dim]   sums of x_i x_j over replicas and snapshots, the lower triangle (j <= i) only
+    sx     float64 [cov_temps, dim]        sums of x_i
+    count  int64   [1]                     (replica, snapshot) pairs added
+
 `n_replicas` is the axis the reference does not have: independent copies of the whole chain /
 ladder, one Philox subsequence each (global replica id = chain_offset + local index), so a run is
 invariant to how replicas are sharded over GPUs.
@@ -343,7 +350,7 @@ class EngineRun:
                  adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False, ladder_every: int = 100,
                  ladder_until: Optional[int] = None, ladder_probe_every: Optional[int] = None, ladder_gain: float = 2.0,
                  ladder_decay: float = 0.5, acf_temps: int = 0, acf_every: int = 1, acf_max_lag: int = 32,
-                 acf_ring_limit: Optional[int] = None):
+                 acf_ring_limit: Optional[int] = None, cov_temps: int = 0, cov_every: int = 1):
         adapt = check_adapt_args(adapt_scale, max(0, int(burn_in)), adapt_every, adapt_until, adapt_target, adapt_gain,
                                  adapt_decay, adapt_scale_bounds, adapt_sync)
         ladder = check_ladder_args(adapt_ladder, max(0, int(burn_in)), beta_ladder, ladder_every, ladder_until,
@@ -364,6 +371,7 @@ class EngineRun:
             raise ValueError(f"dim must be in 1..{ptrwm_hip.MAX_DIM} for the fused kernel, got {dim}")
         hist_box = check_hist_args(hist_temps, hist_every, hist_bins, hist_range, n_temps, dim)
         acf_on = check_acf_args(acf_temps, acf_every, acf_max_lag, n_temps, dim, n_replicas, acf_ring_limit)
+        cov_on = check_cov_args(cov_temps, cov_every, n_temps)
         # the starts (host-side checks, before the device is asked for: bad arguments fail the same way without a GPU)
         axes = start_shape(initial_state, dim, n_replicas, n_temps)
         box = check_init_box(init_box, dim)
@@ -495,6 +503,14 @@ class EngineRun:
             self._acf_ring = torch.empty(L, n_replicas, at, dim, device=device, dtype=dtype)
             self._plan.set_autocorr(self._acf_ring, self._acf["sxy"], self._acf["head"], self._acf["tail"], self._acf["pairs"],
                                     every=self.acf_every)
+        # pooled posterior covariance sums, added to by a snapshot kernel between launches (off: None)
+        self.cov_temps, self.cov_every = int(cov_temps), int(cov_every)
+        self._cov = None
+        if cov_on:
+            self._cov = {"sxx": torch.zeros(self.cov_temps, dim, dim, device=device, dtype=torch.float64),
+                         "sx": torch.zeros(self.cov_temps, dim, device=device, dtype=torch.float64),
+                         "count": torch.zeros(1, device=device, dtype=torch.int64)}
+            self._plan.set_covariance(self._cov["sxx"], self._cov["sx"], self._cov["count"], every=self.cov_every)
         # warm-up tuning of the proposal scale, per temperature, by two small kernels between launches (off: None)
         self.init_scales = self.proposal.temp_scale.clone()
         self._adapt = None
@@ -666,6 +682,7 @@ class EngineRun:
         self._plan.split_moments(offset)  # (decides on the device whether this step counts; no-op without moments)
         self._plan.split_histogram(offset)  # (likewise; no-op without a histogram)
         self._plan.split_autocorr(offset)  # (likewise; no-op without an autocovariance accumulator)
+        self._plan.split_covariance(offset)  # (likewise; no-op without a covariance accumulator)
         if advance:
             self._plan.split_advance(advance)
 
@@ -784,6 +801,7 @@ class EngineRun:
                     self._plan.split_moments(s)
                     self._plan.split_histogram(s)
                     self._plan.split_autocorr(s)
+                    self._plan.split_covariance(s)
                 self.steps_done += 1
                 if trace is not None and ptrwm_hip.periodic_steps_in(s, s + 1, trace_every):
                     tc, tt = trace.shape[1], trace.shape[2]
@@ -862,6 +880,16 @@ class EngineRun:
         """Zero the autocovariance sums (the chains keep their states).  The ring stays valid: snapshots are numbered from the
         step counter, so the next one pairs with the ones before the reset."""
         for t in (self._acf or {}).values():
+            t.zero_()
+
+    def covariance_sums(self) -> Optional[dict]:
+        """The pooled covariance sums of this shard, or None when they are off: sxx [cov_temps, dim, dim] (lower triangle) and sx
+        [cov_temps, dim] float64, count [1] int64 (device tensors, no synchronisation), and every."""
+        return {**self._cov, "every": self.cov_every} if self._cov is not None else None
+
+    def reset_covariance(self) -> None:
+        """Zero the covariance sums (the chains keep their states)."""
+        for t in (self._cov or {}).values():
             t.zero_()
 
     def flow(self) -> Optional[dict]:
@@ -1188,6 +1216,128 @@ class Autocorrelation:
         tau, _, reached = self.integrated_autocorr_time(0)
         ok = bool(torch.isfinite(tau).all())
         return {"act_max": float(tau.max()) if ok else float("nan"), "act_window_reached": bool(reached.all())}
+
+
+# ---- pooled posterior covariance: estimators and the drop-in classes' readers ------------------------------------------------
+def check_cov_args(cov_temps, cov_every, n_temps: int) -> bool:
+    """EngineRun's covariance arguments (no GPU needed): False when off."""
+    for name, v in (("cov_temps", cov_temps), ("cov_every", cov_every)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not 0 <= cov_temps <= n_temps:
+        raise ValueError(f"cov_temps must be in 0..{n_temps}, got {cov_temps}")
+    if not cov_temps:
+        return False
+    if cov_every < 1:
+        raise ValueError(f"cov_every must be >= 1, got {cov_every}")
+    return True
+
+
+def cov_temps(mode, n_temps: int) -> int:
+    """Temperatures a `cov=` mode covers (0: off)."""
+    if mode not in (None, "cold", "all"):
+        raise ValueError(f"cov must be None, 'cold' or 'all', got {mode!r}")
+    return {None: 0, "cold": 1, "all": n_temps}[mode]
+
+
+def cov_covariance(sxx, sx, count) -> torch.Tensor:
+    """sxx / n - mean mean^T from the sums of one temperature, mirrored to both triangles: sxx [dim, dim] (only its lower
+    triangle, j <= i, is read), sx [dim], count a scalar; float64 [dim, dim] on the CPU, NaN without a snapshot.  It divides by
+    n, as the pooled variance does.  Raw sums: about log10(1 + mean^2 / var) digits of a coordinate are lost."""
+    sxx = torch.as_tensor(sxx).detach().cpu().to(torch.float64)
+    sx = torch.as_tensor(sx).detach().cpu().to(torch.float64)
+    n = float(torch.as_tensor(count).reshape(-1)[0]) if not isinstance(count, (int, float)) else float(count)
+    if sxx.dim() != 2 or sxx.shape[0] != sxx.shape[1] or sx.shape != sxx.shape[:1]:
+        raise ValueError("sxx must be [dim, dim] and sx [dim]")
+    if not n > 0:
+        return torch.full_like(sxx, float("nan"))
+    low = torch.tril(sxx)
+    full = low + torch.tril(sxx, -1).T
+    m = sx / n
+    c = full / n - torch.outer(m, m)
+    return (c + c.T) / 2  # (exactly symmetric; halves of equal numbers are exact)
+
+
+def cov_correlation(cov) -> torch.Tensor:
+    """cov[i, j] / sqrt(cov[i, i] cov[j, j]): float64 [dim, dim] with a unit diagonal; a coordinate whose variance is not
+    positive gives NaN off its diagonal."""
+    cov = torch.as_tensor(cov).detach().cpu().to(torch.float64)
+    var = torch.diagonal(cov)
+    sd = torch.sqrt(torch.where(var > 0, var, torch.full_like(var, float("nan"))))
+    r = cov / torch.outer(sd, sd)
+    r.fill_diagonal_(1.0)
+    return r
+
+
+def cov_principal_axes(cov) -> tuple:
+    """(eigenvalues descending [dim], eigenvectors as columns [dim, dim]) of the float64 matrix, from torch.linalg.eigh."""
+    w, v = torch.linalg.eigh(torch.as_tensor(cov).detach().cpu().to(torch.float64))
+    return torch.flip(w, (0,)), torch.flip(v, (1,))
+
+
+def cov_condition(cov) -> float:
+    """Largest over smallest eigenvalue; inf where the smallest is <= 0; NaN for a matrix with a NaN."""
+    cov = torch.as_tensor(cov).detach().cpu().to(torch.float64)
+    if not bool(torch.isfinite(cov).all()):
+        return float("nan")
+    w = torch.linalg.eigvalsh(cov)
+    lo, hi = float(w[0]), float(w[-1])
+    return hi / lo if lo > 0 else float("inf")
+
+
+class PosteriorCovariance:
+    """Estimates from the pooled covariance sums (include/ptrwm.h ptrwm_cov_args, csrc/cov.h): how the coordinates move
+    together, pooled over every replica of the run.  The host class calls `_check_cov_ctor` in its constructor, passes
+    `_cov_kwargs(n_temps)` to EngineRun and owns `_run`.  Every read synchronises; results are CPU tensors."""
+
+    def _check_cov_ctor(self, cov, cov_every) -> None:
+        """The constructor's covariance arguments, checked before anything is built (no GPU needed)."""
+        if cov_temps(cov, 1):
+            check_cov_args(1, cov_every, 1)
+        self._cov_mode, self._cov_every = cov, cov_every
+
+    def _cov_kwargs(self, n_temps: int) -> dict:
+        """EngineRun's covariance arguments."""
+        if self._cov_mode is None:
+            return {}
+        return {"cov_temps": cov_temps(self._cov_mode, n_temps), "cov_every": self._cov_every}
+
+    def _cov_data(self, temperature) -> tuple:
+        if getattr(self, "_cov_mode", None) is None:
+            raise RuntimeError("the covariance is off: construct the sampler with cov='cold' or 'all'")
+        temps = cov_temps(self._cov_mode, len(getattr(self, "beta_ladder", [1.0])))
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, np.integer)) or not 0 <= temperature < temps:
+            raise ValueError(f"temperature must be in 0..{temps - 1} (the covariance covers the first {temps}), got {temperature!r}")
+        run = getattr(self, "_run", None)
+        if run is None or run.covariance_sums() is None:  # nothing run yet, or reset(): empty sums
+            return (torch.zeros(self.dim, self.dim, dtype=torch.float64), torch.zeros(self.dim, dtype=torch.float64),
+                    torch.zeros(1, dtype=torch.int64))
+        a = run.covariance_sums()
+        t = int(temperature)
+        return a["sxx"][t].cpu(), a["sx"][t].cpu(), a["count"].cpu()
+
+    @property
+    def covariance_count(self) -> int:
+        """(replica, step) pairs accumulated so far."""
+        return int(self._cov_data(0)[2][0])
+
+    def posterior_covariance(self, temperature: int = 0) -> torch.Tensor:
+        """Covariance of the coordinates, pooled over every replica and every snapshot: sxx / n - mean mean^T, float64
+        [dim, dim], symmetric; it divides by n, as posterior_variance does.  NaN before the first snapshot."""
+        return cov_covariance(*self._cov_data(temperature))
+
+    def posterior_correlation(self, temperature: int = 0) -> torch.Tensor:
+        """Correlation matrix: float64 [dim, dim]; a coordinate of zero variance gives NaN off its diagonal."""
+        return cov_correlation(self.posterior_covariance(temperature))
+
+    def principal_axes(self, temperature: int = 0) -> tuple:
+        """(eigenvalues descending [dim], eigenvectors as columns [dim, dim]) of posterior_covariance(temperature)."""
+        return cov_principal_axes(self.posterior_covariance(temperature))
+
+    def _cov_diagnostics(self) -> dict:
+        if getattr(self, "_cov_mode", None) is None:
+            return {}
+        return {"cov_condition": cov_condition(self.posterior_covariance(0)), "cov_count": self.covariance_count}
 
 
 # ---- pooled marginal histograms of the drop-in classes -------------------------------------------------------------

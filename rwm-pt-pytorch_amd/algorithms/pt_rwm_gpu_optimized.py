@@ -32,8 +32,8 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import (Autocorrelation, EngineRun, LadderAdaptation, MarginalHistograms, PosteriorMoments, ScaleAdaptation,
-                           check_class_starts, moments_temps, resolve_device)
+from ._engine_core import (Autocorrelation, EngineRun, LadderAdaptation, MarginalHistograms, PosteriorCovariance,
+                           PosteriorMoments, ScaleAdaptation, check_class_starts, moments_temps, resolve_device)
 from .sharding import flow_round_trip_rate, flow_up_fraction
 
 
@@ -47,7 +47,8 @@ def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
     return [float(beta_min ** (t / (n_temps - 1))) for t in range(n_temps)]
 
 
-class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, ScaleAdaptation, LadderAdaptation, MHAlgorithm):
+class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, PosteriorCovariance, ScaleAdaptation,
+                                         LadderAdaptation, MHAlgorithm):
     def __init__(self, dim: int, var: float, target_dist=None, symmetric: bool = True, beta_ladder: list = None,
                  iterative_temp_spacing: bool = False, geom_temp_spacing: bool = False,
                  swap_acceptance_rate: float = 0.234, beta_min_iterative: float = 0.01, N_samples_swap_est: int = 3000,
@@ -67,7 +68,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
                  adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False, ladder_every: int = 100,
                  ladder_until: Optional[int] = None, ladder_probe_every: Optional[int] = None, ladder_gain: float = 2.0,
                  ladder_decay: float = 0.5, acf: Optional[str] = None, acf_every: int = 1, acf_max_lag: int = 32,
-                 acf_ring_limit: Optional[int] = None):
+                 acf_ring_limit: Optional[int] = None, cov: Optional[str] = None, cov_every: int = 1):
         super().__init__(dim, var, target_dist, symmetric)
         # warm-up tuning of the proposal scale per temperature (include/ptrwm.h ptrwm_adapt_args): adapt_scale=True tunes towards
         # adapt_target in windows of adapt_every steps up to adapt_until (default: all of burn-in); adapt_scale_bounds are factors
@@ -83,6 +84,9 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
         # snapshot every acf_every-th step past burn-in, lags 0..acf_max_lag in snapshots; acf_ring_limit overrides the largest
         # ring (elements) the constructor accepts
         self._check_acf_ctor(dim, acf, acf_every, acf_max_lag, acf_ring_limit)
+        # pooled posterior covariance over every replica (include/ptrwm.h ptrwm_cov_args): cov='cold' or 'all' temperatures,
+        # a snapshot every cov_every-th step past burn-in
+        self._check_cov_ctor(cov, cov_every)
         self._flow_on = bool(flow)
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         self._moments_mode, self._moments_every = moments, int(moments_every)
@@ -284,7 +288,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
             dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, flow=self._flow_on,
             **self._hist_kwargs(len(self.beta_ladder)), **self._adapt_kwargs(), **self._ladder_run_kwargs(),
-            **self._acf_kwargs(len(self.beta_ladder)))
+            **self._acf_kwargs(len(self.beta_ladder)), **self._cov_kwargs(len(self.beta_ladder)))
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
         self.current_log_densities = self._run.logp[0] if self.num_replicas == 1 else self._run.logp
@@ -532,6 +536,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
             **self._flow_diagnostics(),
             **self._hist_diagnostics(),
             **self._acf_diagnostics(),
+            **self._cov_diagnostics(),
             **self._adapt_diagnostics(),
             **self._ladder_diagnostics(),
         }

@@ -22,8 +22,8 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import (Autocorrelation, EngineRun, MarginalHistograms, PosteriorMoments, ScaleAdaptation, check_class_starts, moments_temps,
-                           resolve_device)
+from ._engine_core import (Autocorrelation, EngineRun, MarginalHistograms, PosteriorCovariance, PosteriorMoments,
+                           ScaleAdaptation, check_class_starts, moments_temps, resolve_device)
 
 
 def ultra_fused_mcmc_step_basic(current_state, current_log_density, increment, random_val, beta, log_density_proposed):
@@ -53,7 +53,8 @@ def _rebuild_proposal(p: ProposalDistribution, dim, beta, device, dtype, rng):
     )
 
 
-class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, ScaleAdaptation, MHAlgorithm):
+class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, PosteriorCovariance, ScaleAdaptation,
+                                 MHAlgorithm):
     def __init__(self, dim: int, var: float = None, target_dist=None, symmetric: bool = True, beta: float = 1.0,
                  burn_in: int = 0, device: str = None, pre_allocate_steps: int = None, use_efficient_rng: bool = True,
                  compile_mode: str = None, proposal_distribution: ProposalDistribution = None, *,
@@ -64,7 +65,8 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
                  adapt_until: Optional[int] = None,
                  adapt_target: float = 0.234, adapt_gain: float = 3.0, adapt_decay: float = 0.5,
                  adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False, acf: Optional[str] = None,
-                 acf_every: int = 1, acf_max_lag: int = 32, acf_ring_limit: Optional[int] = None):
+                 acf_every: int = 1, acf_max_lag: int = 32, acf_ring_limit: Optional[int] = None, cov: Optional[str] = None,
+                 cov_every: int = 1):
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         if adapt_ladder:
             raise ValueError("adapt_ladder=True tunes a temperature ladder: RandomWalkMH_GPU_Optimized has none "
@@ -83,6 +85,9 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
         # snapshot every acf_every-th step past burn-in, lags 0..acf_max_lag in snapshots; acf_ring_limit overrides the largest
         # ring (elements) the constructor accepts
         self._check_acf_ctor(dim, acf, acf_every, acf_max_lag, acf_ring_limit)
+        # pooled posterior covariance over every replica (include/ptrwm.h ptrwm_cov_args): cov='cold' (= 'all' here: one
+        # temperature), a snapshot every cov_every-th step past burn-in
+        self._check_cov_ctor(cov, cov_every)
         # where the chains start (EngineRun's docstring): by default all from the reference's one point; `initial_states`
         # [num_chains, dim] (or [dim] / [num_chains, 1, dim]) gives every chain its own - a warm restart is
         # initial_states=previous.current_states; `init_box` = (lo, hi) draws over-dispersed starts in the library, redrawing
@@ -197,6 +202,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
             chain_offset=self._chain_offset, moments_temps=moments_temps(self._moments_mode, 1, self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, init_box=self._init_box,
             init_attempts=self._init_attempts, **self._hist_kwargs(1), **self._adapt_kwargs(), **self._acf_kwargs(1),
+            **self._cov_kwargs(1),
         )
         self.current_state = self._run.state[0, 0]  # views: always the live values
         self.current_states = self._run.state[:, 0]
@@ -292,6 +298,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
             **self._moments_diagnostics(),
             **self._hist_diagnostics(),
             **self._acf_diagnostics(),
+            **self._cov_diagnostics(),
             **self._adapt_diagnostics(),
         }
 

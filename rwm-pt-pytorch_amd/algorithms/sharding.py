@@ -200,6 +200,32 @@ def allreduce_autocorr(sampler, group: Optional[dist.ProcessGroup] = None) -> di
     return out
 
 
+def allreduce_covariance(sampler, group: Optional[dist.ProcessGroup] = None) -> dict:
+    """Whole-job pooled covariance from every rank's shard: ONE float64 SUM all-reduce of `sxx`, `sx` and `count` packed into
+    one vector (the count rides as a double: exact below 2^53).  `sampler`: a sampler constructed with cov=, its EngineRun, or
+    the dict EngineRun.covariance_sums() returns.  Returns new tensors {"sxx", "sx", "count"} on the shards' device, "every",
+    and "covariance": float64 [temps, dim, dim] on the CPU, the whole job's covariance of every covered temperature
+    (algorithms._engine_core.cov_covariance); the shard's own arrays are not modified."""
+    from ._engine_core import cov_covariance
+
+    a = sampler
+    if not isinstance(a, dict):
+        run = getattr(sampler, "_run", sampler)
+        a = run.covariance_sums() if run is not None and hasattr(run, "covariance_sums") else None
+        if a is None:
+            raise RuntimeError("allreduce_covariance: the covariance is off, or nothing has run yet")
+    parts = [a[k] for k in ("sxx", "sx", "count")]
+    vec = torch.cat([p.reshape(-1).to(torch.float64) for p in parts])
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=group)
+    out, at = {"every": a.get("every")}, 0
+    for k, p in zip(("sxx", "sx", "count"), parts):
+        out[k] = vec[at:at + p.numel()].view(p.shape).to(p.dtype)
+        at += p.numel()
+    out["covariance"] = torch.stack([cov_covariance(out["sxx"][t], out["sx"][t], out["count"]) for t in range(out["sxx"].shape[0])])
+    return out
+
+
 # ---- warm-up tuning of the proposal scale and of the ladder (include/ptrwm.h ptrwm_adapt_args, ptrwm_ladder_args) ---------------
 def adaptation_sync(group: Optional[dist.ProcessGroup] = None):
     """The `adapt_sync=` callable of a sharded run, for both tunings: all-reduces (SUM) the pooled int64 counts of a window in

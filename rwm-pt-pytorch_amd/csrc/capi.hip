@@ -6,6 +6,7 @@
 #include "../../include/ptrwm.h"
 #include "acf.h"
 #include "adapt.h"
+#include "cov.h"
 #include "ladder.h"
 #include "hist.h"
 #include "schedule.h"
@@ -875,6 +876,99 @@ __global__ void __launch_bounds__(kAcfThreads) acf_snapshot_kernel(AcfSnapArgs a
     for (int lag = tid; lag <= lags; lag += kAcfThreads) count_add(&a.pairs[lag], a.n_chains);
 }
 
+// Pooled posterior covariance (ptrwm_covariance, and the snapshots of ptrwm_run_with_covariance; cov.h states the rule and the
+// geometry): one snapshot of `state`.  A workgroup takes one covered temperature (blockIdx.y) and a tile of kCovChains chains
+// (blockIdx.x), which pass through LDS in sub-tiles of kCovSubTile chains: rows of doubles, one per chain, consecutive lanes
+// reading consecutive elements of a chain; the pad columns are zeroed once and never written, the rows past the last chain are
+// written as zeros.  The Gram matrix of the tile is the lower triangle of 16 x 16 coordinate blocks; a block pair is one
+// accumulator of v_mfma_f64_16x16x4_f64 (8 VGPRs), K running over the chains, and a wave owns its pairs for the whole tile
+// (cov_pair_wave / cov_pair_slot): pair w + 4 q sits in the wave's accumulator q.  Per K-step and pair a lane reads its two
+// operands from LDS, ONE double each - coordinate 16 bi + (lane & 15), and 16 bj + (lane & 15), of chain 4 ks + (lane >> 4) -
+// and the owner of a diagonal pair adds the value to that block's sx.  The loop over a wave's pairs is unrolled over the
+// compile-time maximum and guarded wave-uniformly, so that the accumulators are indexed statically (registers, no scratch).
+// Flush: one no-return fp64 atomic per non-zero (i, j), j <= i < dim, and per sx element.
+// The kernel only reads `state`.
+struct CovSnapArgs {
+  const void *state;  // float or double [n_chains, n_temps, dim]
+  double *sxx, *sx;
+  long long *count;
+  long long n_chains, step, burn_in, every;
+  const long long *device_step;
+  int n_temps, dim;
+};
+
+typedef double cov_acc_t __attribute__((ext_vector_type(4)));
+
+template <class state_t>
+__global__ void __launch_bounds__(kCovThreads, 2) cov_snapshot_kernel(CovSnapArgs a) {
+  // is the step just performed a due one?  (grid-uniform, as SplitMomentsArgs::step_counts)
+  const long long sc = (a.device_step != nullptr ? *a.device_step + a.step : a.step) + 1;
+  if (!periodic_step_due(sc, a.burn_in, a.every)) return;
+  extern __shared__ double s_cov[];  // [kCovSubTile][cov_row_stride(dim)]
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int dim = a.dim;
+  const int t = (int)blockIdx.y;
+  const long long c0 = (long long)blockIdx.x * kCovChains, run = (long long)a.n_temps * dim;
+  const state_t *__restrict__ base = reinterpret_cast<const state_t *>(a.state) + (long long)t * dim;
+  for (int e = tid; e < cov_lds_doubles(dim); e += kCovThreads) s_cov[e] = 0.0;  // (the pad columns stay zero)
+  // this wave's pairs: accumulator q holds pair cov_wave_pair(w, q), q < nq
+  const int nq = cov_wave_pairs(w, cov_pairs(cov_blocks(dim)));
+  cov_acc_t acc[kCovPairsPerWave];
+  double s[kCovPairsPerWave];
+  int bi[kCovPairsPerWave], bj[kCovPairsPerWave];
+#pragma unroll
+  for (int q = 0; q < kCovPairsPerWave; ++q) {
+    const int p = cov_wave_pair(w, q);
+    bi[q] = cov_pair_row(p);
+    bj[q] = cov_pair_col(p);
+    acc[q] = cov_acc_t{0.0, 0.0, 0.0, 0.0};
+    s[q] = 0.0;
+  }
+  const int per = kCovSubTile * dim;
+  for (int sub = 0; sub < kCovSubTiles; ++sub) {
+    const long long cs = c0 + (long long)sub * kCovSubTile;
+    if (cs >= a.n_chains) break;  // (workgroup-uniform)
+    __syncthreads();              // (the zeroing, or the previous sub-tile's reads)
+    for (int e = tid; e < per; e += kCovThreads) {
+      const int ch = cov_stage_chain(e, dim), d = cov_stage_coord(e, dim);
+      const long long c = cs + ch;
+      s_cov[cov_lds_at(ch, d, dim)] = c < a.n_chains ? (double)base[c * run + d] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int ks = 0; ks < kCovKSteps; ++ks) {
+      const double *row = s_cov + cov_lds_at(cov_operand_chain(ks, lane), 0, dim);
+#pragma unroll
+      for (int q = 0; q < kCovPairsPerWave; ++q)
+        if (q < nq) {
+          const double vi = row[cov_operand_coord(bi[q], lane)], vj = row[cov_operand_coord(bj[q], lane)];
+          acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(vi, vj, acc[q], 0, 0, 0);
+          s[q] += vi;  // (flushed for a diagonal pair only)
+        }
+    }
+  }
+  double *__restrict__ sxx = a.sxx + (long long)t * dim * dim;
+#pragma unroll
+  for (int q = 0; q < kCovPairsPerWave; ++q)
+    if (q < nq) {
+      const int j = cov_flush_j(bj[q], lane);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = cov_flush_i(bi[q], lane, r);
+        const double val = acc[q][r];
+        if (cov_flushed(i, j, dim) && val != 0.0) unsafeAtomicAdd(sxx + (long long)i * dim + j, val);
+      }
+      if (bi[q] == bj[q]) {        // the diagonal pair of a block: its sx (cov_sx_wave)
+        double m = s[q];           // (the four K-quarters of a column meet: lanes l, l + 16, l + 32, l + 48)
+        m += __shfl_xor(m, 16);
+        m += __shfl_xor(m, 32);
+        if (cov_sx_flushed(bi[q], lane, dim) && m != 0.0) unsafeAtomicAdd(a.sx + (long long)t * dim + kCovBlock * bi[q] + lane, m);
+      }
+    }
+  if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) count_add(a.count, a.n_chains);
+}
+
 // ---- warm-up tuning of the proposal scale (adapt.h; include/ptrwm.h ptrwm_adapt_args) ---------------------------------------
 // Two small kernels between launches, as the histogram's snapshot: the step kernels are told nothing.  A launch inside an
 // adapting window adds its acceptances to window_accept [n_chains, n_temps]; at the window's end adapt_reduce_kernel sums
@@ -1264,6 +1358,42 @@ static int32_t launch_acf(const ptrwm_run_args *args, int32_t dim, const ptrwm_a
   return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 
+// the covariance checks shared by ptrwm_run_with_covariance and ptrwm_covariance (args already checked); none: ok
+static int32_t check_cov(const ptrwm_run_args *args, const ptrwm_cov_args *cv) {
+  if (cv == nullptr) return PTRWM_OK;
+  if (cv->struct_size != sizeof(ptrwm_cov_args)) return PTRWM_E_STRUCT;
+  if (cv->temps < 1 || cv->temps > args->n_temps || cv->every < 1) return PTRWM_E_ARG;
+  if (cv->sxx == nullptr || cv->sx == nullptr || cv->count == nullptr) return PTRWM_E_NULL;
+  return PTRWM_OK;
+}
+static_assert(PTRWM_MAX_DIM == kCovMaxDim, "cov.h and include/ptrwm.h: one largest dim");
+
+// One snapshot of the state after step `step` (device_step != NULL: *device_step + step); everything checked
+static int32_t launch_cov(const ptrwm_run_args *args, int32_t dim, const ptrwm_cov_args *cv, long long step,
+                          const long long *device_step, hipStream_t stream) {
+  CovSnapArgs a;
+  a.state = args->state;
+  a.sxx = cv->sxx;
+  a.sx = cv->sx;
+  a.count = (long long *)cv->count;
+  a.n_chains = args->n_chains;
+  a.step = step;
+  a.burn_in = args->burn_in;
+  a.every = cv->every;
+  a.device_step = device_step;
+  a.n_temps = args->n_temps;
+  a.dim = dim;
+  const CovGeometry g = cov_geometry(dim);
+  const long long gx = (args->n_chains + g.chains - 1) / g.chains;
+  if (gx > 0x7fffffffll) return PTRWM_E_ARG;
+  const dim3 grid((unsigned)gx, (unsigned)cv->temps);  // (y <= 256)
+  if (args->state_f64 == 1)
+    hipLaunchKernelGGL(cov_snapshot_kernel<double>, grid, dim3(kCovThreads), (size_t)g.lds_bytes, stream, a);
+  else
+    hipLaunchKernelGGL(cov_snapshot_kernel<float>, grid, dim3(kCovThreads), (size_t)g.lds_bytes, stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}
+
 // the adaptation checks shared by ptrwm_run_with_adaptation, ptrwm_adapt_reduce and ptrwm_adapt_update (none: ok); what
 // needs the run (until <= burn_in, temp_scale == proposal->temp_scale) is checked by run_impl itself (tuning_fits_run)
 static int32_t check_tuning(const ptrwm_adapt_args *ad) {
@@ -1382,7 +1512,7 @@ static bool tuning_fits_run(const Tuning *tu, const ptrwm_run_args *args, const 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                         const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist = nullptr,
                         const ptrwm_adapt_args *adapt = nullptr, const ptrwm_ladder_args *ladder = nullptr,
-                        const ptrwm_acf_args *acf = nullptr);
+                        const ptrwm_acf_args *acf = nullptr, const ptrwm_cov_args *cov = nullptr);
 static int32_t swap_sweep_impl(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
                                const ptrwm_flow_args *flow, void *stream);
 static int32_t split_accept_impl(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
@@ -1549,6 +1679,14 @@ int32_t ptrwm_run_with_autocorr(const ptrwm_target_desc *target, const ptrwm_pro
   return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist, adapt, ladder, acf);
 }
 
+int32_t ptrwm_run_with_covariance(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                                  const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
+                                  const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt,
+                                  const ptrwm_ladder_args *ladder, const ptrwm_acf_args *acf, const ptrwm_cov_args *cov, void *stream) {
+  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // (as ptrwm_run_with_diagnostics)
+  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist, adapt, ladder, acf, cov);
+}
+
 int32_t ptrwm_ladder_probe(const ptrwm_run_args *args, const ptrwm_ladder_args *ladder, void *stream) {
   if (int rc = check_tuning_call(ladder, true, args, 0, 0)) return rc;
   if (args->n_temps < 3 || ladder->beta != args->beta) return PTRWM_E_ARG;
@@ -1589,6 +1727,20 @@ int32_t ptrwm_autocorr(const ptrwm_run_args *args, int32_t dim, const ptrwm_acf_
   if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, acf->every))
     return PTRWM_OK;  // (known on the host: no snapshot is due)
   return launch_acf(args, dim, acf, args->step0, (const long long *)args->device_step, (hipStream_t)stream);
+}
+
+int32_t ptrwm_covariance(const ptrwm_run_args *args, int32_t dim, const ptrwm_cov_args *cov, void *stream) {
+  if (args == nullptr || cov == nullptr) return PTRWM_E_NULL;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
+  if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
+  if (!is_flag(args->state_f64) || args->n_chains < 0 || args->step0 < 0 || args->burn_in < 0) return PTRWM_E_ARG;
+  if (int rc = check_cov(args, cov)) return rc;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->state == nullptr) return PTRWM_E_NULL;
+  if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, cov->every))
+    return PTRWM_OK;  // (known on the host: no snapshot is due)
+  return launch_cov(args, dim, cov, args->step0, (const long long *)args->device_step, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -1790,7 +1942,8 @@ static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_de
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                         const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist,
-                        const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder, const ptrwm_acf_args *acf) {
+                        const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder, const ptrwm_acf_args *acf,
+                        const ptrwm_cov_args *cov) {
   bool empty = false;
   if (int rc = check_run(target, proposal, args, spec, flow, hist, &empty)) return rc;
   // the two tunings (adapt.h, ladder.h): their own checks after the existing ones, all before anything is enqueued
@@ -1802,6 +1955,7 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
     if (ladder->temp_scale != nullptr && ladder->temp_scale != proposal->temp_scale) return PTRWM_E_ARG;
   }
   if (int rc = check_acf(args, acf)) return rc;  // (the autocovariance: after every existing block's checks)
+  if (int rc = check_cov(args, cov)) return rc;  // (the covariance: after those)
   if (empty) return PTRWM_OK;
   // (every = 0: no such tuning, schedule.h)
   const WarmupWindows scale_w = adapt != nullptr ? WarmupWindows{adapt->every, adapt->until} : WarmupWindows{0, 0};
@@ -1829,6 +1983,7 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
     long long to_snap = hist != nullptr ? steps_to_next_due(args->step0 + done, args->burn_in, hist->every) : cap;
     // (the autocovariance: likewise, at its own period)
     if (acf != nullptr) to_snap = std::min(to_snap, steps_to_next_due(args->step0 + done, args->burn_in, acf->every));
+    if (cov != nullptr) to_snap = std::min(to_snap, steps_to_next_due(args->step0 + done, args->burn_in, cov->every));
     // (the tunings, schedule.h warmup_launch_at: a launch inside an adapting window of the scale ends with the window at the
     // latest - the reduce and update kernels run between two launches - and is the production kernel told to count from its
     // first step, into the window scratch, and that no multiple of swap_every lies in it: count_on holds and swap_due never
@@ -1862,6 +2017,8 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
       if (int rc = launch_hist(args, target->dim, hist, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
     if (acf != nullptr && periodic_step_due(cut.step0 + cut.n, args->burn_in, acf->every))
       if (int rc = launch_acf(args, target->dim, acf, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
+    if (cov != nullptr && periodic_step_due(cut.step0 + cut.n, args->burn_in, cov->every))
+      if (int rc = launch_cov(args, target->dim, cov, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
     if (wl.scale_reduce)
       if (int rc = launch_adapt_reduce(adapt, args->n_chains, args->n_temps, (hipStream_t)hip_stream)) return rc;
     if (wl.scale_update)

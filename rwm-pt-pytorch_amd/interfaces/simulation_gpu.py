@@ -130,6 +130,21 @@ class MCMCSimulation_GPU:
         self._require_run()
         return self.algorithm.posterior_variance(temperature)
 
+    def posterior_covariance(self, temperature: int = 0):
+        """The sampler's posterior covariance pooled over every replica (needs cov='cold' or 'all', forwarded to it)."""
+        self._require_run()
+        return self.algorithm.posterior_covariance(temperature)
+
+    def posterior_correlation(self, temperature: int = 0):
+        """The sampler's posterior correlation matrix pooled over every replica (needs cov='cold' or 'all')."""
+        self._require_run()
+        return self.algorithm.posterior_correlation(temperature)
+
+    def principal_axes(self, temperature: int = 0):
+        """(eigenvalues descending, eigenvectors as columns) of the sampler's posterior covariance (needs cov='cold' or 'all')."""
+        self._require_run()
+        return self.algorithm.principal_axes(temperature)
+
     def rhat(self, temperature: int = 0):
         """Gelman-Rubin R-hat per coordinate over the sampler's chains (needs moments_per_chain=True, forwarded to it)."""
         self._require_run()

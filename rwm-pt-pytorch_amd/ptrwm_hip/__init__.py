@@ -227,6 +227,18 @@ class AcfArgs(C.Structure):
 ACF_MAX_LAG = 1024
 
 
+class CovArgs(C.Structure):
+    """ptrwm_cov_args: pooled posterior covariance sums of the first ``temps`` temperatures (include/ptrwm.h, csrc/cov.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("temps", C.c_int32),
+        ("every", C.c_int32),
+        ("sxx", C.c_void_p),
+        ("sx", C.c_void_p),
+        ("count", C.c_void_p),
+    ]
+
+
 class InitArgs(C.Structure):
     """ptrwm_init_args: starting points drawn from a box, or set to a fallback point (include/ptrwm.h)."""
     _fields_ = [
@@ -292,6 +304,12 @@ SYMBOLS = {
         [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.POINTER(ChainMomentsArgs),
          C.POINTER(FlowArgs), C.POINTER(HistArgs), C.POINTER(AdaptArgs), C.POINTER(LadderArgs), C.POINTER(AcfArgs), C.c_void_p]),
     "ptrwm_autocorr": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(AcfArgs), C.c_void_p]),
+    "ptrwm_run_with_covariance": (
+        C.c_int32,
+        [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.POINTER(ChainMomentsArgs),
+         C.POINTER(FlowArgs), C.POINTER(HistArgs), C.POINTER(AdaptArgs), C.POINTER(LadderArgs), C.POINTER(AcfArgs),
+         C.POINTER(CovArgs), C.c_void_p]),
+    "ptrwm_covariance": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(CovArgs), C.c_void_p]),
     "ptrwm_swap_sweep_with_flow": (
         C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_int64, C.c_int32, C.POINTER(FlowArgs), C.c_void_p]),
     "ptrwm_split_accept_with_flow": (
@@ -702,6 +720,7 @@ class RunPlan:
         self._adapt = None  # warm-up tuning of the proposal scale: (struct, byref, tensors)
         self._ladder = None  # warm-up tuning of the temperature ladder: (struct, byref, tensors)
         self._acf = None  # pooled lagged autocovariance: (struct, byref, tensors)
+        self._cov = None  # pooled posterior covariance: (struct, byref, tensors)
 
     # kind of accumulator -> (words of its messages, struct, entry point of launch(), entry point of split_moments())
     _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
@@ -876,6 +895,52 @@ class RunPlan:
             rc = self._lib.ptrwm_autocorr(self._refs[4], self.shape[2], self._acf[1], _stream(self.device))
         if rc != 0:
             raise PTRWMError(rc, "ptrwm_autocorr")
+
+    def set_covariance(self, sxx: Optional[torch.Tensor], sx: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                       *, every: int = 1) -> None:
+        """Accumulate the pooled posterior covariance sums (include/ptrwm.h ptrwm_cov_args) in every following ``launch`` and
+        ``split_covariance``: ``sxx`` [temps, dim, dim] float64 (only the lower triangle, j <= i, is added to), ``sx``
+        [temps, dim] float64 and ``count`` [1] int64, all on the run's device; the sums are added to (+=).  ``temps`` is read
+        off ``sxx``.  ``launch`` then ends a kernel launch at every due step and enqueues the snapshot kernel behind it.
+        ``set_covariance(None)`` switches it off."""
+        if sxx is None:
+            self._cov = None
+            return
+        Cn, T, D = self.shape
+        if sxx.dim() != 3 or sxx.shape[1] != D or sxx.shape[2] != D:
+            raise ValueError(f"covariance sxx must be [temps, {D}, {D}]")
+        temps, every = int(sxx.shape[0]), int(every)
+        if not 1 <= temps <= T:
+            raise ValueError(f"covariance temps must be in 1..{T}, got {temps}")
+        if every < 1:
+            raise ValueError("covariance every must be >= 1")
+        if sx is None or tuple(sx.shape) != (temps, D):
+            raise ValueError(f"covariance sx must be [{temps}, {D}]")
+        if count is None or tuple(count.shape) != (1,):
+            raise ValueError("covariance count must be [1]")
+        for name, t in (("sxx", sxx), ("sx", sx), ("count", count)):
+            if t.device != self.device:
+                raise ValueError(f"covariance {name} is on {t.device}, state on {self.device}")
+        cv = CovArgs()
+        cv.struct_size = C.sizeof(CovArgs)
+        cv.temps, cv.every = temps, every
+        cv.sxx = _require_device(sxx, "covariance sxx", torch.float64)
+        cv.sx = _require_device(sx, "covariance sx", torch.float64)
+        cv.count = _require_device(count, "covariance count", torch.int64)
+        self._cov = (cv, C.byref(cv), (sxx, sx, count))
+
+    def split_covariance(self, step: int) -> None:
+        """Covariance snapshot of the state after the split step ``step`` just performed (ptrwm_covariance; device-step mode:
+        counter + step - decided on the device, so the call can sit in a captured block).  Enqueue after ``split_accept``
+        (and ``split_histogram`` / ``split_autocorr``), behind every step: the library skips the steps that are not due.
+        No-op without an accumulator."""
+        if self._cov is None:
+            return
+        self._a.step0 = step
+        with self._guard:
+            rc = self._lib.ptrwm_covariance(self._refs[4], self.shape[2], self._cov[1], _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_covariance")
 
     def _tuning_windows(self, what: str, every, until) -> tuple:
         """every, until and K = until // every of a warm-up tuning (`what` starts its messages), checked against the plan"""
@@ -1124,14 +1189,14 @@ class RunPlan:
             if trace is not None and ext_prop is None and ext_u is None and ext_swap_u is None and accept_flags is None:
                 self._last_trace = (trace, trace_logp, trace_every)
         # ptrwm_run, or the accumulator's entry point with its struct in front of the stream; with anything else bound, the
-        # first of ptrwm_run_with_diagnostics / _histogram / _adaptation / _ladder / _autocorr that takes all that is bound: each
+        # first of ptrwm_run_with_diagnostics / _histogram / _adaptation / _ladder / _autocorr / _covariance that takes all that is bound: each
         # takes what the one before it takes and one struct more, behind the two accumulators (pooled, per chain)
         name, opt = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
-        if any(b is not None for b in (self._flow, self._hist, self._adapt, self._ladder, self._acf)):
-            more = [b[1] if b is not None else None for b in (self._flow, self._hist, self._adapt, self._ladder, self._acf)]
+        if any(b is not None for b in (self._flow, self._hist, self._adapt, self._ladder, self._acf, self._cov)):
+            more = [b[1] if b is not None else None for b in (self._flow, self._hist, self._adapt, self._ladder, self._acf, self._cov)]
             last = max(i for i, b in enumerate(more) if b is not None)
             name = ("ptrwm_run_with_diagnostics", "ptrwm_run_with_histogram", "ptrwm_run_with_adaptation", "ptrwm_run_with_ladder",
-                    "ptrwm_run_with_autocorr")[last]
+                    "ptrwm_run_with_autocorr", "ptrwm_run_with_covariance")[last]
             kind, mom = (self._mom[0], self._mom[2]) if self._mom is not None else (None, None)
             opt = (mom if kind == "pooled" else None, mom if kind == "chain" else None, *more[:last + 1])
         with self._guard:
