@@ -597,6 +597,91 @@ def prop_from_engine(proposal) -> ProposalSpec:
     return ProposalSpec(proposal.kind, host(proposal.temp_scale), host(proposal.dim_scale), float(proposal.inv_dim))
 
 
+STAT_KEYS = ("n_accept", "sq_jump", "swap_accept", "last_swap_ordinal")
+RESULT_KEYS = ("state", "logp") + STAT_KEYS
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def _twin_in_launches(spec, prop, device, *, state, logp, stats0, beta, launches, **sched):
+    """The fixture twin (per-step trace and accept flags attached, as gpu_runner attaches them) run in the given launches
+    [(step0, n_steps), ...] - consecutive steps - on statistics that start at `stats0`: what gpu_run returns."""
+    import torch
+
+    import ptrwm_hip as E
+
+    Cn, T, D = state.shape
+    first, total = launches[0][0], sum(n for _, n in launches)
+    sdt = torch.float64 if np.asarray(state).dtype == np.float64 else torch.float32
+    st, lp = dev_t(state, device, sdt), dev_t(logp, device).reshape(Cn, T).contiguous()
+    res = {k: dev_t(stats0[k], device, torch.float64 if k == "sq_jump" else torch.int64).reshape(Cn, T).contiguous()
+           for k in STAT_KEYS}
+    trace = torch.zeros(total, Cn, T, D, device=device, dtype=sdt)
+    trace_logp = torch.zeros(total, Cn, T, device=device)
+    flags = torch.zeros(total, Cn, T, dtype=torch.uint8, device=device)
+    plan = E.RunPlan(spec.engine(device), prop.engine(device), state=st, logp=lp, beta=dev_t(beta, device), **res, **sched)
+    at = first
+    for s0, n in launches:
+        assert s0 == at and n > 0, "the launches must cover consecutive steps"
+        plan.launch(s0, n, trace=trace, trace_logp=trace_logp, trace_row0=s0 - first, accept_flags=flags[s0 - first:s0 - first + n])
+        at = s0 + n
+    torch.cuda.synchronize()
+    out = {k: v.cpu().numpy() for k, v in res.items()}
+    out.update(state=st.cpu().numpy(), logp=lp.cpu().numpy(), trace=trace.cpu().numpy(), trace_logp=trace_logp.cpu().numpy(),
+               accept_flags=flags.cpu().numpy())
+    return out
+
+
+def check_production_ladders(spec, prop, device, produced, *, l0, state, logp, beta, launches, burn_in, swap_every, seed,
+                             chain_offset=0, swap_mode=O.SWAP_EXCHANGE, swap_order=O.ORDER_SEQUENTIAL, stats0=None, segment=50):
+    """A contiguous block of ladders [l0, l0 + n) of a finished PRODUCTION run (the non-fixture kernel variant, no per-step
+    trace, whatever kernel form served it) tied to the oracle without any agreement-rate threshold, in two links:
+      1. the fixture variant of the same kernel, run on the same Philox stream over just these ladders (chain_offset + l0)
+         from their own starting rows and starting statistics, with a per-step trace and accept flags attached, reproduces
+         the production run's final states, log-densities and all four statistics BIT FOR BIT;
+      2. that traced run follows the oracle decision for decision over the full horizon, every differing decision
+         proven (check_parity_philox).
+    Everything is given as plain host arrays of just these ladders: `produced` the run's final state [n, T, D], logp and
+    the four statistics [n, T]; `state` / `logp` where the ladders started; `stats0` the statistics they started with
+    (None: zeros); `launches` [(step0, n_steps), ...] the launches the production run was made in (consecutive steps).
+    A run made in ONE launch from zero statistics is its twin's one traced launch.  Otherwise the twin repeats the
+    production run's launches on the starting statistics (an fp64 squared-jump sum is old + the LAUNCH's sum: its bits
+    depend on the cuts), and between the links the same twin in one launch from zero statistics - the run that link 2
+    follows - is shown to walk the same path: trace, log-densities, accept flags bit for bit, the integer statistics
+    start + delta, the last-swap ordinals max(start, new), the squared-jump sums start + sum to fp64 rounding of a sum
+    of a few dozen terms (rtol 1e-12, as for any run cut into launches)."""
+    state = np.ascontiguousarray(state, dtype=np.float64 if np.asarray(state).dtype == np.float64 else f32)
+    n, T, D = state.shape
+    logp = np.ascontiguousarray(logp, dtype=f32).reshape(n, T)
+    first, total = launches[0][0], sum(k for _, k in launches)
+    sched = dict(burn_in=burn_in, swap_every=swap_every, swap_mode=swap_mode, swap_order=swap_order, chain_offset=chain_offset + l0)
+    kw = dict(state=state, logp=logp, beta=np.asarray(beta, f32), n_steps=total, **sched)
+    runner = gpu_runner(spec, prop, device)
+    one_launch = len(launches) == 1 and stats0 is None
+    if one_launch:
+        twin = runner(step0=first, seed=seed, **kw)
+    else:
+        zeros = {k: np.zeros((n, T), np.float64 if k == "sq_jump" else np.int64) for k in STAT_KEYS}
+        stats0 = zeros if stats0 is None else {k: np.asarray(stats0[k]).reshape(n, T) for k in STAT_KEYS}
+        twin = _twin_in_launches(spec, prop, device, state=state, logp=logp, stats0=stats0, beta=kw["beta"], launches=launches,
+                                 seed=seed, **sched)
+    for k in RESULT_KEYS:
+        assert _same_bits(np.asarray(produced[k]), twin[k]), \
+            f"production run and its traced fixture twin differ in `{k}` (ladders {l0}..{l0 + n - 1})"
+    if not one_launch:
+        full = runner(step0=first, seed=seed, **kw)
+        for k in ("state", "logp", "trace", "trace_logp", "accept_flags"):
+            assert _same_bits(full[k], twin[k]), f"the twin's path depends on how it is cut into launches: `{k}`"
+        for k in ("n_accept", "swap_accept"):
+            assert np.array_equal(twin[k], stats0[k] + full[k]), k
+        assert np.array_equal(twin["last_swap_ordinal"], np.maximum(stats0["last_swap_ordinal"], full["last_swap_ordinal"]))
+        assert np.allclose(twin["sq_jump"], stats0["sq_jump"] + full["sq_jump"], rtol=1e-12, atol=0.0)
+    return check_parity_philox(runner, spec, prop, seed=seed, step0=first, segment=segment, **kw)
+
+
 def check_production_run(run, x0, n_cmp, segment=50):
     """The first `n_cmp` ladders of a finished PRODUCTION run of a sampler class (`run`: its algorithms._engine_core
     EngineRun - the non-fixture kernel variant, no per-step trace, whatever kernel form the batch size selected) tied to
@@ -620,13 +705,10 @@ def check_production_run(run, x0, n_cmp, segment=50):
     sdt = np.float64 if getattr(run, "dtype", torch.float32) == torch.float64 else f32
     state = np.broadcast_to(np.asarray(x0, sdt), (n_cmp, T, D)).copy()
     logp = E.logdensity(run.target, dev_t(state.reshape(-1, D), device)).cpu().numpy().reshape(n_cmp, T)
-    kw = dict(state=state, logp=logp, beta=run.beta.cpu().numpy(), n_steps=run.steps_done, burn_in=run.burn_in,
-              swap_every=run.swap_every, swap_mode=run.swap_mode, swap_order=run.swap_order, chain_offset=run.chain_offset)
-    full = gpu_runner(spec, prop, device)(step0=0, seed=run.seed, **kw)
     produced = {"state": run.state, "logp": run.logp, "n_accept": run.n_accept, "sq_jump": run.sq_jump,
                 "swap_accept": run.swap_accept, "last_swap_ordinal": run.last_ord}
-    for k, v in produced.items():
-        v = v[:n_cmp].cpu().numpy()
-        assert v.shape == full[k].shape and np.array_equal(v.view(np.uint8), np.ascontiguousarray(full[k]).view(np.uint8)), \
-            f"production run and its traced fixture twin differ in `{k}`"
-    return check_parity_philox(gpu_runner(spec, prop, device), spec, prop, seed=run.seed, segment=segment, **kw)
+    # the block [0, n_cmp) of check_production_ladders, the run taken as one launch from zero statistics
+    return check_production_ladders(spec, prop, device, {k: v[:n_cmp].cpu().numpy() for k, v in produced.items()}, l0=0,
+                                    state=state, logp=logp, beta=run.beta.cpu().numpy(), launches=[(0, run.steps_done)],
+                                    burn_in=run.burn_in, swap_every=run.swap_every, swap_mode=run.swap_mode,
+                                    swap_order=run.swap_order, seed=run.seed, chain_offset=run.chain_offset, segment=segment)
