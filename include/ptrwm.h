@@ -776,6 +776,72 @@ int32_t ptrwm_split_accept(const ptrwm_run_args *args, int32_t dim, float *propo
  * device-step mode. */
 int32_t ptrwm_split_advance(const ptrwm_run_args *args, void *stream);
 
+/* ---- preconditioned Gaussian proposals: increments s_t L z, and the factor learned during burn-in ---------------------
+ * Every Normal proposal above is x + s_t z with one scalar per temperature: its efficiency is set by the conditioning of the
+ * posterior covariance (ptrwm_cov_args measures it).  ptrwm_split_propose_precond is ptrwm_split_propose for
+ * PTRWM_PROPOSAL_NORMAL with a lower-triangular factor L, L L^T ~ the posterior covariance, shared by all temperatures:
+ *   inc_i = acc after  acc = +0;  acc = fmaf(L[i][k], z[k], acc)  for k = 0, 1, ..., 16 (i / 16 + 1) - 1 ascending
+ *   y_i   = fmaf(s_t, inc_i, x_i)                                           s_t = proposal->temp_scale[t]
+ * with L[i][k] taken as zero for k > i and z[k] as zero for k >= dim (csrc/precond.h states the rule and the kernel's index
+ * maps).  `chol` is float [dim, dim], row-major; only its entries k <= i are ever read.  z is the Box-Muller normals of the
+ * step's Philox blocks at unit scale - the words, counter layout and stream of the Normal proposal; the accept uniform is
+ * word 2 ceil(dim / 2), as there - or ext_prop (dim raw values per row) with ext_u as the accept uniform.  Plane 1 of accept_u
+ * is -1: ptrwm_split_accept takes the squared jump from the states.  The same fields of `args` are read as by
+ * ptrwm_split_propose, device-step mode included, and the same scratch contract holds: ptrwm_split_accept, the sweep and the
+ * moments / histogram / autocovariance / covariance snapshots follow it unchanged.  It is a split-step proposal only: the fused
+ * step kernels know nothing of it.
+ * How: one run-time-dim kernel.  A 256-thread workgroup stages L into LDS once and walks tiles of 64 rows; the product
+ * Z [rows, dim] L^T is taken on the f32 matrix unit (v_mfma_f32_16x16x4_f32, whose result is the k-ordered fmaf chain above).
+ * Checked, in this order, before anything is enqueued: PTRWM_E_NULL for a NULL proposal or precond; the checks of
+ * ptrwm_split_propose on args and dim (PTRWM_E_ARG for state_f64); PTRWM_E_KIND for any proposal kind but
+ * PTRWM_PROPOSAL_NORMAL; PTRWM_E_STRUCT for a wrong precond->struct_size; an empty batch returns PTRWM_OK; PTRWM_E_NULL for a
+ * NULL state, proposals, accept_u, temp_scale or chol, and for ext_prop without ext_u. */
+typedef struct ptrwm_precond_args {
+  uint32_t struct_size; /* sizeof(ptrwm_precond_args) */
+  uint32_t reserved;    /* 0 */
+  const float *chol;    /* device [dim, dim]: the factor, entries k <= i read */
+} ptrwm_precond_args;
+int32_t ptrwm_split_propose_precond(const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args, int32_t dim,
+                                    const ptrwm_precond_args *precond, float *proposals, float *accept_u, void *stream);
+
+/* The factor learned from one warm-up window.  The window's sums are ptrwm_covariance's of ONE temperature (sxx lower
+ * triangle, sx, count - its layout with temps = 1), gathered by the caller at the probe steps of the window.  With the running
+ * triple (run_xx, run_x, run_w), all double, every operation rounded on its own:
+ *   run_xx = memory run_xx + sxx,   run_x = memory run_x + sx,   run_w = memory run_w + count;   the window sums are zeroed
+ *   run_w < min_count: skip
+ *   m = run_x / run_w,   A = run_xx / run_w - m m^T,   A += jitter (tr A / dim) I
+ *   C = the left-looking column Cholesky factor of A, inner products over k ascending; a pivot that is not finite or not > 0,
+ *       or an entry that does not fit a float: skip
+ * On success chol[i][j] = (float) C[i][j] for j <= i (the strict upper triangle of chol is not touched).  On a skip chol keeps
+ * its bits and *skipped += 1; the running triple keeps what the window added either way.  Row 0 of chol_history is written by
+ * window 0 (the factor that window ran with), row window + 1 by every window (the factor in force behind it; zeros above the
+ * diagonal); weight_history[window] = run_w.  memory = 1 is the all-history estimate of Haario et al. (2001).
+ * The sums come from fp64 atomics, so the factor is reproducible up to the order of those additions - unlike the integer
+ * tunings above, not bit for bit across launch cuts or shards.  Shards: all-reduce (SUM) sxx, sx and count before the call.
+ * One workgroup; enqueues only: neither allocates nor synchronises.
+ * Checked, in this order, before anything is enqueued: PTRWM_E_NULL for NULL args; PTRWM_E_STRUCT for a wrong struct_size;
+ * PTRWM_E_DIM; PTRWM_E_ARG for memory not in (0, 1], jitter not finite or < 0, min_count not >= 1, windows < 1 or a window
+ * outside 0..windows - 1; PTRWM_E_NULL for a NULL chol, sxx, sx, count, run_xx, run_x or run_w. */
+typedef struct ptrwm_precond_update_args {
+  uint32_t struct_size;   /* sizeof(ptrwm_precond_update_args) */
+  uint32_t reserved;      /* 0 */
+  float *chol;            /* device [dim, dim], in/out (entries j <= i) */
+  double *sxx;            /* device [dim, dim]: the window's sums, zeroed */
+  double *sx;             /* device [dim], zeroed */
+  int64_t *count;         /* device [1], zeroed */
+  double *run_xx;         /* device [dim, dim], in/out (entries j <= i) */
+  double *run_x;          /* device [dim], in/out */
+  double *run_w;          /* device [1], in/out */
+  double memory;          /* in (0, 1] */
+  double jitter;          /* >= 0, relative to the mean variance */
+  double min_count;       /* >= 1 */
+  int64_t windows;        /* K >= 1: the histories have rows for windows 0 .. K - 1 */
+  float *chol_history;    /* device [K + 1, dim, dim] or NULL */
+  double *weight_history; /* device [K] or NULL */
+  int64_t *skipped;       /* device [1] or NULL, += 1 per skipped update */
+} ptrwm_precond_update_args;
+int32_t ptrwm_precond_update(const ptrwm_precond_update_args *update, int32_t dim, int64_t window, void *stream);
+
 /* ---- starting points: over-dispersed starts for multi-chain runs ----------------------------------------------------
  * Writes rows of `state` before step 0: each coordinate drawn uniformly from the box [lo[d], hi[d]], or copied from
  * `fallback`.  R-hat over many chains (ptrwm_chain_moments_args) says something about mixing between modes only when the

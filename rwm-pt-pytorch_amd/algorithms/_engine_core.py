@@ -268,6 +268,78 @@ def check_ladder_args(adapt_ladder, burn_in: int, beta_ladder=None, ladder_every
                              "pooled int64 tensor", "the ladder will not move", own)
 
 
+def check_proposal_cov(proposal_cov, dim: int) -> Optional[np.ndarray]:
+    """`proposal_cov` (None: no factor), a [dim, dim] symmetric positive-definite covariance as a NumPy array or a tensor,
+    factored on the host in float64: the lower-triangular float32 factor L, L L^T = proposal_cov, zeros above the diagonal.
+    ValueError for a wrong shape, a matrix that is not symmetric (beyond 1e-6 of its largest entry) or not positive definite."""
+    if proposal_cov is None:
+        return None
+    c = proposal_cov.detach().cpu().numpy() if torch.is_tensor(proposal_cov) else np.asarray(proposal_cov)
+    if c.shape != (dim, dim):
+        raise ValueError(f"proposal_cov must be a [dim, dim] = [{dim}, {dim}] matrix, got shape {tuple(c.shape)}")
+    c = np.asarray(c, np.float64)
+    if not np.isfinite(c).all() or np.abs(c - c.T).max() > 1e-6 * np.abs(c).max():
+        raise ValueError("proposal_cov must be symmetric (and finite)")
+    try:
+        chol = np.linalg.cholesky((c + c.T) / 2)
+    except np.linalg.LinAlgError:
+        raise ValueError("proposal_cov must be positive definite") from None
+    with np.errstate(over="ignore"):
+        out = np.tril(chol).astype(np.float32)
+    if not np.isfinite(out).all() or not (np.diagonal(out) > 0).all():
+        raise ValueError("proposal_cov must be positive definite in float32")
+    return out
+
+
+def check_proposal_chol(proposal_chol, dim: int) -> Optional[np.ndarray]:
+    """EngineRun's `proposal_chol` (None: no factor): a [dim, dim] factor, read on its lower triangle, as float32 with zeros
+    above the diagonal.  ValueError for a wrong shape, an entry that is not finite or a diagonal that is not positive."""
+    if proposal_chol is None:
+        return None
+    c = proposal_chol.detach().cpu().numpy() if torch.is_tensor(proposal_chol) else np.asarray(proposal_chol)
+    if c.shape != (dim, dim):
+        raise ValueError(f"proposal_chol must be a [dim, dim] = [{dim}, {dim}] matrix, got shape {tuple(c.shape)}")
+    low = np.tril_indices(dim)
+    out = np.zeros((dim, dim), np.float32)
+    out[low] = np.asarray(c, np.float32)[low]  # (whatever stands above the diagonal is never read)
+    if not np.isfinite(out).all() or not (np.diagonal(out) > 0).all():
+        raise ValueError("proposal_chol must be finite on its lower triangle with a positive diagonal")
+    return out
+
+
+def check_cov_adapt_args(adapt_cov, burn_in: int, dim: int, cov_adapt_every=200, cov_adapt_until=None, cov_adapt_probe_every=None,
+                         cov_adapt_memory=0.5, cov_adapt_jitter=1e-6, cov_adapt_min_count=None, adapt_sync=None) -> Optional[dict]:
+    """The arguments of the warm-up tuning of the proposal factor (None: off), checked on the host so that bad arguments fail the
+    same way with and without a GPU - what the library would refuse (include/ptrwm.h ptrwm_precond_update_args) and a probe
+    period that does not divide the window.  A warning when no window fits into burn-in."""
+    if not isinstance(adapt_cov, (bool, np.bool_)):
+        raise ValueError(f"adapt_cov must be True or False, got {adapt_cov!r}")
+    if not adapt_cov:
+        return None
+    every = _integer("cov_adapt_every", cov_adapt_every, 1)
+    until = burn_in if cov_adapt_until is None else cov_adapt_until
+    if isinstance(until, bool) or not isinstance(until, (int, np.integer)) or not 0 <= until <= burn_in:
+        raise ValueError(f"cov_adapt_until must be an integer in 0..burn_in = {burn_in}, got {until!r}")
+    probe_every = every if cov_adapt_probe_every is None else _integer("cov_adapt_probe_every", cov_adapt_probe_every, 1)
+    if every % probe_every != 0:
+        raise ValueError(f"cov_adapt_probe_every must divide cov_adapt_every = {every}, got {cov_adapt_probe_every!r}")
+    memory, jitter = _number("cov_adapt_memory", cov_adapt_memory), _number("cov_adapt_jitter", cov_adapt_jitter)
+    if not 0.0 < memory <= 1.0:
+        raise ValueError(f"cov_adapt_memory must lie in (0, 1], got {cov_adapt_memory!r}")
+    if jitter < 0.0:
+        raise ValueError(f"cov_adapt_jitter must be >= 0, got {cov_adapt_jitter!r}")
+    min_count = float(4 * dim) if cov_adapt_min_count is None else _number("cov_adapt_min_count", cov_adapt_min_count)
+    if not min_count >= 1.0:
+        raise ValueError(f"cov_adapt_min_count must be >= 1, got {cov_adapt_min_count!r}")
+    if adapt_sync is not None and not callable(adapt_sync):
+        raise ValueError("adapt_sync must be None or a callable applied to the window's covariance sums")
+    windows = int(until) // every
+    if windows == 0:
+        warnings.warn(f"adapt_cov=True but no window of cov_adapt_every = {every} steps ends within the first "
+                      f"{until} burn-in steps: the proposal factor will not move")
+    return {"every": every, "until": int(until), "probe_every": probe_every, "memory": memory, "jitter": jitter,
+            "min_count": min_count, "sync": adapt_sync, "windows": windows}
+
 
 def check_init_attempts(init_attempts) -> int:
     if isinstance(init_attempts, bool) or not isinstance(init_attempts, (int, np.integer)) or not 1 <= init_attempts <= 65535:
@@ -326,6 +398,17 @@ class ScaleTuning(WarmupTuning):
         self.update(window)
 
 
+class FactorTuning(WarmupTuning):
+    """... of the proposal factor (include/ptrwm.h ptrwm_precond_update_args).  There is no pooled row: the window's counts are
+    the covariance sums `sxx`, `sx`, `count` of temperature 0, and `sync` is applied to each of the three."""
+
+    def window_end(self, window: int) -> None:
+        if self.sync is not None:
+            for t in (self.sxx, self.sx, self.count):
+                self.sync(t)
+        self.update(window)
+
+
 class EngineRun:
     """`initial_state`: one point [dim] for every replica and temperature, or [n_replicas, dim] (the temperatures of a ladder
     share their replica's row), or [n_replicas, n_temps, dim] - a NumPy array or a torch tensor on any device (a device tensor
@@ -350,11 +433,29 @@ class EngineRun:
                  adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False, ladder_every: int = 100,
                  ladder_until: Optional[int] = None, ladder_probe_every: Optional[int] = None, ladder_gain: float = 2.0,
                  ladder_decay: float = 0.5, acf_temps: int = 0, acf_every: int = 1, acf_max_lag: int = 32,
-                 acf_ring_limit: Optional[int] = None, cov_temps: int = 0, cov_every: int = 1):
+                 acf_ring_limit: Optional[int] = None, cov_temps: int = 0, cov_every: int = 1, proposal_chol=None,
+                 adapt_cov: bool = False, cov_adapt_every: int = 200, cov_adapt_until: Optional[int] = None,
+                 cov_adapt_probe_every: Optional[int] = None, cov_adapt_memory: float = 0.5, cov_adapt_jitter: float = 1e-6,
+                 cov_adapt_min_count: Optional[float] = None):
         adapt = check_adapt_args(adapt_scale, max(0, int(burn_in)), adapt_every, adapt_until, adapt_target, adapt_gain,
                                  adapt_decay, adapt_scale_bounds, adapt_sync)
         ladder = check_ladder_args(adapt_ladder, max(0, int(burn_in)), beta_ladder, ladder_every, ladder_until,
                                    ladder_probe_every, ladder_gain, ladder_decay, adapt_sync)
+        # preconditioned proposals x + s_t L z (include/ptrwm.h ptrwm_split_propose_precond): `proposal_chol`, the factor
+        # [dim, dim] (lower triangle), and with adapt_cov=True its warm-up tuning from the cold chain's covariance - the factor
+        # then starts from `proposal_chol`, or from the identity
+        chol = check_proposal_chol(proposal_chol, int(dim))
+        factor = check_cov_adapt_args(adapt_cov, max(0, int(burn_in)), int(dim), cov_adapt_every, cov_adapt_until,
+                                      cov_adapt_probe_every, cov_adapt_memory, cov_adapt_jitter, cov_adapt_min_count, adapt_sync)
+        if factor is not None and chol is None:
+            chol = np.eye(int(dim), dtype=np.float32)
+        if chol is not None:
+            if proposal is not None and proposal.kind != ptrwm_hip.PROPOSAL_NORMAL:
+                raise ValueError("proposal_chol / adapt_cov precondition the Normal proposal: Laplace and UniformRadius have no "
+                                 "preconditioned form")
+            if dtype == torch.float64:
+                raise NotImplementedError("dtype=torch.float64 needs the fused kernel; preconditioned proposals run in split "
+                                          "steps, which carry float32 states")
         if swap_mode not in ptrwm_hip.SWAP_MODES:
             raise ValueError(f"swap_mode must be one of {sorted(ptrwm_hip.SWAP_MODES)}, got {swap_mode!r}")
         if swap_order not in ptrwm_hip.SWAP_ORDERS:
@@ -398,8 +499,16 @@ class EngineRun:
             self.density_fn = target_dist.log_density
             warnings.warn(f"{type(target_dist).__name__} has no fused kernel: running split steps (HIP proposal / "
                           "accept / swap kernels around its log_density, three launches per step).")
-        if self.target is not None and not (ptrwm_hip.has_thread_variant(self.target.kind, proposal.kind, dim)
-                                            or ptrwm_hip.has_quad_variant(self.target.kind, proposal.kind, dim, n_temps)):
+        # One flag says how the run steps.  Split steps: a density the library has no kernel for, or a proposal factor - the
+        # preconditioned proposal is a split-step kernel, and a target that has engine_target() then runs split steps with
+        # ptrwm_hip.logdensity as its density (_density).
+        self.split = self.density_fn is not None or chol is not None
+        if chol is not None and self.density_fn is None:
+            warnings.warn("preconditioned proposals run in split steps (HIP proposal / log-density / accept / swap kernels, "
+                          "several launches per step), not in the fused step kernel")
+        if self.target is not None and not self.split and not (
+                ptrwm_hip.has_thread_variant(self.target.kind, proposal.kind, dim)
+                or ptrwm_hip.has_quad_variant(self.target.kind, proposal.kind, dim, n_temps)):
             raise ValueError(f"no fused kernel for dim {dim} with a ladder of {n_temps} temperatures: above dim 64 a ladder "
                              "holds at most 128 temperatures (one 512-thread workgroup of the lane-split kernel)")
         if adapt is not None or ladder is not None:
@@ -421,7 +530,7 @@ class EngineRun:
         self.beta = torch.tensor(list(beta_ladder), device=device, dtype=torch.float32)
         if dtype not in (torch.float32, torch.float64):
             raise TypeError(f"state dtype must be torch.float32 or torch.float64, got {dtype}")
-        if dtype == torch.float64 and self.density_fn is not None:
+        if dtype == torch.float64 and self.split:
             raise NotImplementedError("dtype=torch.float64 needs a target with a fused kernel (split steps carry float32 "
                                       "states)")
         self.dtype = dtype  # float64: the engine's state_f64 mode (the reference's dtype=torch.float64)
@@ -522,7 +631,7 @@ class EngineRun:
             hi = min(max(adapt["bounds"][1] * float(self.init_scales.max().item()), lo), huge)
             self._adapt = ScaleTuning(
                 adapt, torch.zeros(n_temps + 1, device=device, dtype=torch.int64), self._plan.adapt_update,
-                reduce=self._plan.adapt_reduce if self.density_fn is not None else None,
+                reduce=self._plan.adapt_reduce if self.split else None,
                 window_accept=torch.zeros(shape, device=device, dtype=torch.int64),
                 scale_history=torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
                 accept_history=torch.zeros(K, n_temps, device=device, dtype=torch.int64),
@@ -551,8 +660,46 @@ class EngineRun:
                                   gain=ladder["gain"], decay=ladder["decay"], rescale_scales=True,
                                   defer_update=ladder["sync"] is not None, beta_history=self._ladder.beta_history,
                                   rate_history=self._ladder.rate_history, skipped=self._ladder.skipped)
+        # the proposal factor (off: None), and its warm-up tuning by a covariance probe of temperature 0 and one update kernel
+        # between steps (off: None).  `chol` is the run's own tensor: the update kernel rewrites it in place, so captured
+        # blocks of split steps keep working.
+        self.chol = self.init_chol = self._factor = None
+        if chol is not None:
+            self.chol = torch.from_numpy(chol).to(device)
+            self.init_chol = self.chol.clone()
+            self._plan.set_preconditioner(self.chol)
+        if factor is not None:
+            K = factor["windows"]
+            f64 = lambda *s: torch.zeros(*s, device=device, dtype=torch.float64)  # noqa: E731
+            self._factor = FactorTuning(
+                factor, None, self._plan.precond_update, probe_every=factor["probe_every"],
+                # the window's sums - the tuning's own, never the user's cov= ones - and the running triple
+                sxx=f64(dim, dim), sx=f64(dim), count=torch.zeros(1, device=device, dtype=torch.int64),
+                run_xx=f64(dim, dim), run_x=f64(dim), run_w=f64(1),
+                chol_history=torch.full((K + 1, dim, dim), float("nan"), device=device, dtype=torch.float32),
+                weight_history=torch.full((K,), float("nan"), device=device, dtype=torch.float64),
+                skipped=torch.zeros(1, device=device, dtype=torch.int64))
+            fa = self._factor
+            fa.chol_history[0] = self.init_chol
+            self._plan.set_precond_update(fa.sxx, fa.sx, fa.count, fa.run_xx, fa.run_x, fa.run_w, windows=max(K, 1),
+                                          probe_every=fa.probe_every, memory=factor["memory"], jitter=factor["jitter"],
+                                          min_count=factor["min_count"], chol_history=fa.chol_history if K else None,
+                                          weight_history=fa.weight_history if K else None, skipped=fa.skipped)
         if box is not None:
             self._draw_starts(box, x0.to(torch.float32).contiguous(), bool(init_per_temperature), attempts)
+
+    def proposal_factor(self) -> Optional[torch.Tensor]:
+        """The current proposal factor: float32 [dim, dim] on the device, zeros above the diagonal (a copy); None without one."""
+        return None if self.chol is None else torch.tril(self.chol)
+
+    def preconditioner_history(self) -> Optional[dict]:
+        """None when the factor's tuning is off, else "factors" float32 [K + 1, dim, dim] (row 0 the initial factor, row k + 1
+        the one in force behind window k; NaN for windows that have not run), "weights" float64 [K] (the running weight w after
+        window k; NaN likewise) and "skipped", the updates dropped.  Device tensors."""
+        if self._factor is None:
+            return None
+        fa = self._factor
+        return {"factors": fa.chol_history.clone(), "weights": fa.weight_history.clone(), "skipped": int(fa.skipped.item())}
 
     def _draw_starts(self, box: tuple, point: torch.Tensor, per_temperature: bool, attempts: int) -> None:
         """Starts from the box (class docstring): attempt 0 for every row, a redraw per further attempt for the rows the
@@ -598,7 +745,7 @@ class EngineRun:
         """Enqueue n_steps fused steps (no host synchronisation)."""
         if n_steps <= 0:
             return
-        if self.density_fn is not None:
+        if self.split:
             self._advance_split(n_steps, trace, trace_logp, trace_row0, max(1, int(trace_every)))
             return
         # adapt_sync: one launch up to the nearer pending window end of either tuning (the library refuses to step past a pending
@@ -760,14 +907,17 @@ class EngineRun:
 
     def _advance_split(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> None:
         """n_steps split steps; traced steps (step_counter a multiple of trace_every) are copied with torch."""
-        ad, ld = self._adapt, self._ladder
+        ad, ld, fa = self._adapt, self._ladder, self._factor
         while n_steps > 0:
             # the host loop - and with it every captured block - ends with every adapting window of the scale and behind
-            # every probe step of an adapting window of the ladder; the stand-alone kernels follow in the library's order:
-            # the scale's reduce and update, the ladder's probe and, at a window's end, its update
+            # every probe step of an adapting window of the ladder and of the proposal factor; the stand-alone kernels follow
+            # in the library's order: the scale's reduce and update, the ladder's probe and, at a window's end, its update,
+            # then the factor's probe and update
             s = self.steps_done
             warm, probing = ad is not None and s < ad.end, ld is not None and s < ld.end
-            k = min([n_steps] + ([ad.every - s % ad.every] if warm else []) + ([ld.probe_every - s % ld.probe_every] if probing else []))
+            learning = fa is not None and s < fa.end
+            k = min([n_steps] + ([ad.every - s % ad.every] if warm else []) + ([ld.probe_every - s % ld.probe_every] if probing else [])
+                    + ([fa.probe_every - s % fa.probe_every] if learning else []))
             trace_row0 += (self._split_steps(k, trace, trace_logp, trace_row0, trace_every, warmup=True) if warm else
                            self._advance_split_plain(k, trace, trace_logp, trace_row0, trace_every))
             if warm and (s + k) % ad.every == 0:
@@ -776,6 +926,10 @@ class EngineRun:
                 self._plan.ladder_probe()
                 if (s + k) % ld.every == 0:
                     ld.window_end((s + k) // ld.every - 1)
+            if learning and (s + k) % fa.probe_every == 0:
+                self._plan.precond_probe(s + k - 1)
+                if (s + k) % fa.every == 0:
+                    fa.window_end((s + k) // fa.every - 1)
             n_steps -= k
 
     def _advance_split_plain(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> int:
@@ -1555,6 +1709,87 @@ class ScaleAdaptation:
 
     def _adapt_diagnostics(self) -> dict:
         return {"adapted_scales": self.proposal_scales().cpu().tolist(), "init_scales": self._init_scales().cpu().tolist()}
+
+
+# ---- preconditioned proposals in the drop-in classes ------------------------------------------------------------------------------
+class Preconditioning:
+    """`proposal_cov=` and `adapt_cov=` of the sampler classes, and the readers of the proposal factor (include/ptrwm.h
+    ptrwm_split_propose_precond / ptrwm_precond_update, csrc/precond.h).  The host class calls `_check_precond_ctor` in its
+    constructor, passes `_precond_kwargs()` to EngineRun and owns `_run` and `dim`.  Every read synchronises; results are CPU
+    tensors."""
+
+    def _check_precond_ctor(self, dim: int, burn_in: int, proposal_cov, adapt_cov, proposal_distribution, dtype, **kw) -> None:
+        """The constructor's arguments, checked before anything is built (no GPU needed).  `proposal_distribution`: the
+        proposal object the caller passed (None: the class builds a Normal one)."""
+        chol = check_proposal_cov(proposal_cov, int(dim))
+        self._factor_args = check_cov_adapt_args(adapt_cov, max(0, int(burn_in)), int(dim), **kw)
+        on = chol is not None or self._factor_args is not None
+        if on and proposal_distribution is not None and type(proposal_distribution).__name__ != "NormalProposal":
+            raise ValueError("proposal_cov / adapt_cov precondition the Normal proposal: "
+                             f"{type(proposal_distribution).__name__} has no preconditioned form")
+        if on and dtype == torch.float64:
+            raise NotImplementedError("dtype=torch.float64 needs the fused kernel; preconditioned proposals run in split "
+                                      "steps, which carry float32 states")
+        if on and chol is None:
+            chol = np.eye(int(dim), dtype=np.float32)
+        self._init_chol = chol
+        self._precond_kw = {}
+        if on:
+            self._precond_kw = {"proposal_chol": chol}
+            if self._factor_args is not None:
+                self._precond_kw.update(adapt_cov=True, **{k: v for k, v in kw.items() if k != "adapt_sync"})
+
+    def _precond_kwargs(self, *others: dict) -> dict:
+        """EngineRun's arguments; `others`: the dicts of the other tunings (adapt_sync travels with one of them where it is
+        on, else with this one)."""
+        kw = dict(self._precond_kw)
+        if self._factor_args is not None and not any("adapt_sync" in o for o in others):
+            kw["adapt_sync"] = self._factor_args["sync"]
+        return kw
+
+    def _precond_on(self) -> None:
+        if getattr(self, "_init_chol", None) is None:
+            raise RuntimeError("proposals are not preconditioned: construct the sampler with proposal_cov= or adapt_cov=True")
+
+    def proposal_factor(self) -> torch.Tensor:
+        """The lower-triangular factor L of the proposal, increments s_t L z: float32 [dim, dim], zeros above the diagonal - the
+        initial factor before the first step and after reset(), the learned one once warm-up has run."""
+        self._precond_on()
+        run = getattr(self, "_run", None)
+        return run.proposal_factor().cpu() if run is not None else torch.from_numpy(self._init_chol.copy())
+
+    def proposal_covariance(self) -> torch.Tensor:
+        """L L^T in float64 [dim, dim]: the covariance of the increments up to the factor (var / beta_t) of every temperature."""
+        f = self.proposal_factor().double()
+        return f @ f.T
+
+    def preconditioner_history(self) -> dict:
+        """{"factors": float32 [K + 1, dim, dim], "weights": float64 [K], "skipped": int} of the K = cov_adapt_until //
+        cov_adapt_every windows: row 0 of factors the initial factor, row k + 1 the one in force behind window k; weights the
+        running weight w behind window k.  Rows of windows that have not run yet are NaN."""
+        self._precond_on()
+        if self._factor_args is None:
+            raise RuntimeError("the factor's tuning is off: construct the sampler with adapt_cov=True")
+        run = getattr(self, "_run", None)
+        if run is not None:
+            h = run.preconditioner_history()
+            return {"factors": h["factors"].cpu(), "weights": h["weights"].cpu(), "skipped": h["skipped"]}
+        K, D = self._factor_args["windows"], self._init_chol.shape[0]
+        factors = torch.full((K + 1, D, D), float("nan"), dtype=torch.float32)
+        factors[0] = torch.from_numpy(self._init_chol)
+        return {"factors": factors, "weights": torch.full((K,), float("nan"), dtype=torch.float64), "skipped": 0}
+
+    def _precond_diagnostics(self) -> dict:
+        if getattr(self, "_init_chol", None) is None:
+            return {"preconditioned": False}
+        out = {"preconditioned": True, "precond_condition": cov_condition(self.proposal_covariance())}
+        if self._factor_args is not None:
+            h = self.preconditioner_history()
+            done = int((~torch.isnan(h["weights"])).sum())
+            out.update(precond_updates=done - h["skipped"], precond_updates_skipped=h["skipped"])
+        else:
+            out.update(precond_updates=0, precond_updates_skipped=0)
+        return out
 
 
 # ---- warm-up tuning of the temperature ladder in the PT class ---------------------------------------------------------------

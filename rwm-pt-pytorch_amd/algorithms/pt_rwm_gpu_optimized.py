@@ -33,7 +33,7 @@ from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
 from ._engine_core import (Autocorrelation, EngineRun, LadderAdaptation, MarginalHistograms, PosteriorCovariance,
-                           PosteriorMoments, ScaleAdaptation, check_class_starts, moments_temps, resolve_device)
+                           PosteriorMoments, Preconditioning, ScaleAdaptation, check_class_starts, moments_temps, resolve_device)
 from .sharding import flow_round_trip_rate, flow_up_fraction
 
 
@@ -48,7 +48,7 @@ def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
 
 
 class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, PosteriorCovariance, ScaleAdaptation,
-                                         LadderAdaptation, MHAlgorithm):
+                                         Preconditioning, LadderAdaptation, MHAlgorithm):
     def __init__(self, dim: int, var: float, target_dist=None, symmetric: bool = True, beta_ladder: list = None,
                  iterative_temp_spacing: bool = False, geom_temp_spacing: bool = False,
                  swap_acceptance_rate: float = 0.234, beta_min_iterative: float = 0.01, N_samples_swap_est: int = 3000,
@@ -68,7 +68,10 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
                  adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False, ladder_every: int = 100,
                  ladder_until: Optional[int] = None, ladder_probe_every: Optional[int] = None, ladder_gain: float = 2.0,
                  ladder_decay: float = 0.5, acf: Optional[str] = None, acf_every: int = 1, acf_max_lag: int = 32,
-                 acf_ring_limit: Optional[int] = None, cov: Optional[str] = None, cov_every: int = 1):
+                 acf_ring_limit: Optional[int] = None, cov: Optional[str] = None, cov_every: int = 1,
+                 proposal_cov=None, adapt_cov: bool = False, cov_adapt_every: int = 200,
+                 cov_adapt_until: Optional[int] = None, cov_adapt_probe_every: Optional[int] = None,
+                 cov_adapt_memory: float = 0.5, cov_adapt_jitter: float = 1e-6, cov_adapt_min_count: Optional[float] = None):
         super().__init__(dim, var, target_dist, symmetric)
         # warm-up tuning of the proposal scale per temperature (include/ptrwm.h ptrwm_adapt_args): adapt_scale=True tunes towards
         # adapt_target in windows of adapt_every steps up to adapt_until (default: all of burn-in); adapt_scale_bounds are factors
@@ -87,6 +90,15 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
         # pooled posterior covariance over every replica (include/ptrwm.h ptrwm_cov_args): cov='cold' or 'all' temperatures,
         # a snapshot every cov_every-th step past burn-in
         self._check_cov_ctor(cov, cov_every)
+        # preconditioned proposals (include/ptrwm.h ptrwm_split_propose_precond): proposal_cov, a [dim, dim] covariance factored on
+        # the host, gives increments N(0, (var / beta_t) proposal_cov); adapt_cov=True learns the factor during burn-in from the
+        # cold chain's covariance, in windows of cov_adapt_every steps probed every cov_adapt_probe_every steps, up to
+        # cov_adapt_until (default: all of burn-in).  Such runs are split steps.
+        self._check_precond_ctor(dim, burn_in, proposal_cov, adapt_cov, proposal_distribution, dtype,
+                                 cov_adapt_every=cov_adapt_every, cov_adapt_until=cov_adapt_until,
+                                 cov_adapt_probe_every=cov_adapt_probe_every,
+                                 cov_adapt_memory=cov_adapt_memory, cov_adapt_jitter=cov_adapt_jitter,
+                                 cov_adapt_min_count=cov_adapt_min_count, adapt_sync=adapt_sync)
         self._flow_on = bool(flow)
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         self._moments_mode, self._moments_every = moments, int(moments_every)
@@ -288,7 +300,8 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
             dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, flow=self._flow_on,
             **self._hist_kwargs(len(self.beta_ladder)), **self._adapt_kwargs(), **self._ladder_run_kwargs(),
-            **self._acf_kwargs(len(self.beta_ladder)), **self._cov_kwargs(len(self.beta_ladder)))
+            **self._acf_kwargs(len(self.beta_ladder)), **self._cov_kwargs(len(self.beta_ladder)),
+            **self._precond_kwargs(self._adapt_kwargs(), self._ladder_run_kwargs()))
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
         self.current_log_densities = self._run.logp[0] if self.num_replicas == 1 else self._run.logp
@@ -537,6 +550,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
             **self._hist_diagnostics(),
             **self._acf_diagnostics(),
             **self._cov_diagnostics(),
+            **self._precond_diagnostics(),
             **self._adapt_diagnostics(),
             **self._ladder_diagnostics(),
         }

@@ -23,7 +23,7 @@ from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
 from ._engine_core import (Autocorrelation, EngineRun, MarginalHistograms, PosteriorCovariance, PosteriorMoments,
-                           ScaleAdaptation, check_class_starts, moments_temps, resolve_device)
+                           Preconditioning, ScaleAdaptation, check_class_starts, moments_temps, resolve_device)
 
 
 def ultra_fused_mcmc_step_basic(current_state, current_log_density, increment, random_val, beta, log_density_proposed):
@@ -54,7 +54,7 @@ def _rebuild_proposal(p: ProposalDistribution, dim, beta, device, dtype, rng):
 
 
 class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, PosteriorCovariance, ScaleAdaptation,
-                                 MHAlgorithm):
+                                 Preconditioning, MHAlgorithm):
     def __init__(self, dim: int, var: float = None, target_dist=None, symmetric: bool = True, beta: float = 1.0,
                  burn_in: int = 0, device: str = None, pre_allocate_steps: int = None, use_efficient_rng: bool = True,
                  compile_mode: str = None, proposal_distribution: ProposalDistribution = None, *,
@@ -66,7 +66,9 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
                  adapt_target: float = 0.234, adapt_gain: float = 3.0, adapt_decay: float = 0.5,
                  adapt_scale_bounds=(1e-6, 1e6), adapt_sync=None, adapt_ladder: bool = False, acf: Optional[str] = None,
                  acf_every: int = 1, acf_max_lag: int = 32, acf_ring_limit: Optional[int] = None, cov: Optional[str] = None,
-                 cov_every: int = 1):
+                 cov_every: int = 1, proposal_cov=None, adapt_cov: bool = False, cov_adapt_every: int = 200,
+                 cov_adapt_until: Optional[int] = None, cov_adapt_probe_every: Optional[int] = None,
+                 cov_adapt_memory: float = 0.5, cov_adapt_jitter: float = 1e-6, cov_adapt_min_count: Optional[float] = None):
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         if adapt_ladder:
             raise ValueError("adapt_ladder=True tunes a temperature ladder: RandomWalkMH_GPU_Optimized has none "
@@ -88,6 +90,15 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
         # pooled posterior covariance over every replica (include/ptrwm.h ptrwm_cov_args): cov='cold' (= 'all' here: one
         # temperature), a snapshot every cov_every-th step past burn-in
         self._check_cov_ctor(cov, cov_every)
+        # preconditioned proposals (include/ptrwm.h ptrwm_split_propose_precond): proposal_cov, a [dim, dim] covariance factored on
+        # the host, gives increments N(0, (var / beta_t) proposal_cov); adapt_cov=True learns the factor during burn-in from the
+        # cold chain's covariance, in windows of cov_adapt_every steps probed every cov_adapt_probe_every steps, up to
+        # cov_adapt_until (default: all of burn-in).  Such runs are split steps.
+        self._check_precond_ctor(dim, burn_in, proposal_cov, adapt_cov, proposal_distribution, torch.float32,
+                                 cov_adapt_every=cov_adapt_every, cov_adapt_until=cov_adapt_until,
+                                 cov_adapt_probe_every=cov_adapt_probe_every,
+                                 cov_adapt_memory=cov_adapt_memory, cov_adapt_jitter=cov_adapt_jitter,
+                                 cov_adapt_min_count=cov_adapt_min_count, adapt_sync=adapt_sync)
         # where the chains start (EngineRun's docstring): by default all from the reference's one point; `initial_states`
         # [num_chains, dim] (or [dim] / [num_chains, 1, dim]) gives every chain its own - a warm restart is
         # initial_states=previous.current_states; `init_box` = (lo, hi) draws over-dispersed starts in the library, redrawing
@@ -202,7 +213,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
             chain_offset=self._chain_offset, moments_temps=moments_temps(self._moments_mode, 1, self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, init_box=self._init_box,
             init_attempts=self._init_attempts, **self._hist_kwargs(1), **self._adapt_kwargs(), **self._acf_kwargs(1),
-            **self._cov_kwargs(1),
+            **self._cov_kwargs(1), **self._precond_kwargs(self._adapt_kwargs()),
         )
         self.current_state = self._run.state[0, 0]  # views: always the live values
         self.current_states = self._run.state[:, 0]
@@ -299,6 +310,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
             **self._hist_diagnostics(),
             **self._acf_diagnostics(),
             **self._cov_diagnostics(),
+            **self._precond_diagnostics(),
             **self._adapt_diagnostics(),
         }
 

@@ -9,6 +9,7 @@
 #include "cov.h"
 #include "ladder.h"
 #include "hist.h"
+#include "precond.h"
 #include "schedule.h"
 #include "variants.h"
 
@@ -967,6 +968,213 @@ __global__ void __launch_bounds__(kCovThreads, 2) cov_snapshot_kernel(CovSnapArg
       }
     }
   if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) count_add(a.count, a.n_chains);
+}
+
+// ---- preconditioned Gaussian proposals (precond.h; include/ptrwm.h ptrwm_split_propose_precond) -----------------------------------
+// ptrwm_split_propose's job for the Normal proposal with increments s_t L z: one run-time-dim kernel.  Geometry and index maps in
+// precond.h.  A workgroup stages the factor into LDS once - zeros above the diagonal and in the pad; the caller's strict upper
+// triangle is never read - and then walks tiles of kPrecRows rows: the tile's states come in through stage_copy, the step's
+// normals are computed one Philox block per work item into the z slab, wave w multiplies its 16 rows by the factor on the matrix
+// unit - block rows in pairs, so that two independent accumulators are in flight - and the epilogue is fmaf(s_t, acc, x) in place,
+// behind which the slab leaves through stage_copy as the proposals.
+struct PrecondProposeArgs {
+  const float *state, *chol, *temp_scale, *ext_raw, *ext_u;
+  float *proposals, *accept_u;
+  long long n_reps, chain_offset;
+  unsigned long long step;
+  const long long *device_step;
+  int n_temps, dim;
+  unsigned k0, k1;
+};
+
+typedef float prec_acc_t __attribute__((ext_vector_type(4)));
+
+// (two waves per SIMD as the register budget, as cov_snapshot_kernel: the accumulators then stay in VGPRs - the build gate admits
+// no AGPRs)
+__global__ void __launch_bounds__(kPrecThreads, 2) precond_propose_kernel(PrecondProposeArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float s_prec[];
+  const int tid = (int)threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int D = a.dim, T = a.n_temps;
+  const int B = prec_blocks(D);
+  unsigned long long step = a.step;
+  if (a.device_step != nullptr) step += (unsigned long long)*a.device_step;
+  {
+    const int passes = prec_l_passes(D);
+    for (int p = 0; p < passes; ++p) {
+      const int i = prec_l_stage_i(p, tid), k = prec_l_stage_k(p, tid);
+      s_prec[prec_l_at(i, k, D)] = prec_l_live(i, k, D) ? a.chol[i * D + k] : 0.0f;
+    }
+  }
+  const long long n_tiles = (a.n_reps + kPrecRows - 1) / kPrecRows;
+  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const long long first = tile * kPrecRows;
+    const int n_rows = (a.n_reps - first < kPrecRows) ? (int)(a.n_reps - first) : kPrecRows;
+    const int total = n_rows * D;
+    float *__restrict__ gx = const_cast<float *>(a.state) + first * D;
+    float *__restrict__ gy = a.proposals + first * D;
+    float *const xs = s_prec + prec_x_offset(D);
+    const int head = stage_head(gy);
+    __syncthreads();  // (the previous tile's copy out has read the slab)
+    // the states land where the proposals leave from: in vectors where the two runs are aligned alike, else one by one
+    if (stage_head(gx) == head) stage_copy<true>(xs, gx, total, tid, kPrecThreads);
+    else
+      for (int e = tid; e < total; e += kPrecThreads) xs[head + e] = gx[e];
+    // the normals: item e is Philox block c of row r
+    const int n_items = prec_z_items(D), c_acc = prec_accept_word(D) / 4, nb = prec_philox_blocks(D);
+    for (int e = tid; e < n_items; e += kPrecThreads) {
+      const int r = prec_z_item_row(e), c = prec_z_item_block(e);
+      if (r >= n_rows) continue;
+      const long long i = first + r;
+      float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (a.ext_raw != nullptr) {
+        const float *er = a.ext_raw + i * D;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (4 * c + q < D) z[q] = er[4 * c + q];
+        if (c == c_acc) a.accept_u[i] = a.ext_u[i];
+      } else if (c < nb) {
+        const long long chain = i / T;
+        const int t = (int)(i - chain * T);
+        const unsigned long long gchain = (unsigned long long)(a.chain_offset + chain);
+        const u32x4 rr = philox4x32_10(step_word_c0hi(step) | (uint32_t)c, step_word_c1(step), chain_word_c2(gchain),
+                                       with_stream(chain_word_c3(gchain, (uint32_t)t), kStreamMH), a.k0, a.k1);
+        if (4 * c < D) box_muller(rr.x, rr.y, z[0], z[1]);
+        if (4 * c + 2 < D) box_muller(rr.z, rr.w, z[2], z[3]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (4 * c + q >= D) z[q] = 0.0f;
+        if (c == c_acc) a.accept_u[i] = u01((prec_accept_word(D) & 2) ? rr.z : rr.x);
+      }
+      if (prec_z_written(c, D)) {
+        float *zr = s_prec + prec_z_at(r, 4 * c, D);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) zr[q] = z[q];
+      }
+      if (c == c_acc) a.accept_u[a.n_reps + i] = -1.0f;  // the squared jump is taken from the states
+    }
+    __syncthreads();
+    // wave w: rows 16 w .. 16 w + 15, block rows bi and bi + 1 together
+    if (kPrecBlock * w < n_rows) {
+      const int row = prec_acc_row(w, lane);
+      const long long ir = first + (row < n_rows ? row : 0);
+      const float s_t = a.temp_scale[(int)(ir % T)];
+      const float *zb = s_prec + prec_z_at(prec_b_row(w, lane), prec_operand_k(0, lane), D);
+      for (int bi = 0; bi < B; bi += 2) {
+        const bool two = bi + 1 < B;
+        const float *la0 = s_prec + prec_l_at(prec_a_row(bi, lane), prec_operand_k(0, lane), D);
+        const float *la1 = s_prec + prec_l_at(prec_a_row(two ? bi + 1 : bi, lane), prec_operand_k(0, lane), D);
+        prec_acc_t acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = {0.0f, 0.0f, 0.0f, 0.0f};
+        const int ks0 = prec_ksteps(bi);
+        for (int ks = 0; ks < ks0; ++ks) {
+          const float zv = zb[kPrecK * ks];
+          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(la0[kPrecK * ks], zv, acc0, 0, 0, 0);
+          if (two) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(la1[kPrecK * ks], zv, acc1, 0, 0, 0);
+        }
+        if (two)
+          for (int ks = ks0; ks < prec_ksteps(bi + 1); ++ks)
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(la1[kPrecK * ks], zb[kPrecK * ks], acc1, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int d0 = prec_acc_dim(bi, lane, r), d1 = prec_acc_dim(bi + 1, lane, r);
+          if (prec_acc_live(row, d0, n_rows, D)) {
+            float *px = s_prec + prec_x_at(head, row, d0, D);
+            *px = fmaf(s_t, acc0[r], *px);
+          }
+          if (two && prec_acc_live(row, d1, n_rows, D)) {
+            float *px = s_prec + prec_x_at(head, row, d1, D);
+            *px = fmaf(s_t, acc1[r], *px);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    stage_copy<false>(xs, gy, total, tid, kPrecThreads);
+  }
+}
+
+// The update of the factor from one window's sums (precond.h): one workgroup, thread i owns row i, the work matrix is the packed
+// lower triangle in LDS, every inner product runs over k ascending - the result is the host function's, bit for bit.
+struct PrecondUpdateArgs {
+  float *chol;
+  double *sxx, *sx;
+  long long *count;
+  double *run_xx, *run_x, *run_w;
+  float *chol_history;     // [K + 1, dim, dim] or NULL
+  double *weight_history;  // [K] or NULL
+  long long *skipped;      // [1] or NULL
+  double memory, jitter, min_count;
+  long long window;
+  int dim;
+};
+
+__global__ void __launch_bounds__(kPrecUpdateThreads) precond_update_kernel(PrecondUpdateArgs a) {
+  extern __shared__ double s_upd[];  // A: prec_tri_size(dim), then m: dim
+  __shared__ double s_piv, s_w;
+  __shared__ int s_fail;
+  const int i = (int)threadIdx.x, D = a.dim;
+  double *const A = s_upd, *const m = s_upd + prec_tri_size(D);
+  const bool mine = i < D;
+  if (i == 0) s_fail = 0;
+  // history row 0: the factor the first window ran with
+  if (a.chol_history != nullptr && a.window == 0 && mine)
+    for (int j = 0; j < D; ++j) a.chol_history[i * D + j] = j <= i ? a.chol[i * D + j] : 0.0f;
+  if (mine) {
+    for (int j = 0; j <= i; ++j) {
+      a.run_xx[i * D + j] = prec_decay_add(a.memory, a.run_xx[i * D + j], a.sxx[i * D + j]);
+      a.sxx[i * D + j] = 0.0;
+    }
+    a.run_x[i] = prec_decay_add(a.memory, a.run_x[i], a.sx[i]);
+    a.sx[i] = 0.0;
+  }
+  if (i == 0) {
+    const double wn = prec_decay_add(a.memory, *a.run_w, (double)*a.count);
+    *a.run_w = wn;
+    *a.count = 0;
+    s_w = wn;
+    if (a.weight_history != nullptr) a.weight_history[a.window] = wn;
+  }
+  __syncthreads();
+  const double wt = s_w;
+  bool ok = prec_weight_ok(wt, a.min_count);  // (workgroup-uniform)
+  if (ok) {
+    if (mine) m[i] = a.run_x[i] / wt;
+    __syncthreads();
+    if (mine)
+      for (int j = 0; j <= i; ++j) A[prec_tri(i, j)] = prec_centered(a.run_xx[i * D + j], wt, m[i], m[j]);
+    __syncthreads();
+    double tr = 0.0;
+    for (int k = 0; k < D; ++k) tr = tr + A[prec_tri(k, k)];
+    __syncthreads();
+    if (mine) A[prec_tri(i, i)] = A[prec_tri(i, i)] + prec_jitter_term(a.jitter, tr, D);
+    __syncthreads();
+    for (int j = 0; j < D; ++j) {
+      double s = 0.0;
+      if (mine && i >= j) {
+        s = A[prec_tri(i, j)];
+        for (int k = 0; k < j; ++k) s = prec_sub_prod(s, A[prec_tri(i, k)], A[prec_tri(j, k)]);
+        if (i == j) {
+          if (prec_pivot_ok(s)) s_piv = sqrt(s);
+          else s_fail = 1;
+        }
+      }
+      __syncthreads();
+      if (s_fail != 0) break;  // (workgroup-uniform)
+      if (mine && i >= j) A[prec_tri(i, j)] = i == j ? s_piv : s / s_piv;
+      __syncthreads();
+    }
+    if (s_fail == 0 && mine)
+      for (int j = 0; j <= i; ++j)
+        if (!prec_finite((double)(float)A[prec_tri(i, j)])) s_fail = 1;
+    __syncthreads();
+    ok = s_fail == 0;
+  }
+  if (ok && mine)
+    for (int j = 0; j <= i; ++j) a.chol[i * D + j] = (float)A[prec_tri(i, j)];
+  if (!ok && i == 0 && a.skipped != nullptr) *a.skipped += 1;
+  // history row window + 1: the factor in force behind this window (a thread reads back its own row)
+  if (a.chol_history != nullptr && mine)
+    for (int j = 0; j < D; ++j) a.chol_history[((a.window + 1) * D + i) * D + j] = j <= i ? a.chol[i * D + j] : 0.0f;
 }
 
 // ---- warm-up tuning of the proposal scale (adapt.h; include/ptrwm.h ptrwm_adapt_args) ---------------------------------------
@@ -2116,6 +2324,82 @@ int32_t ptrwm_split_propose(const ptrwm_proposal_desc *proposal, const ptrwm_run
   }
 #undef PTRWM_SPLIT_CALL
   return err == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}
+
+static_assert(PTRWM_MAX_DIM == kPrecMaxDim, "precond.h and include/ptrwm.h: one largest dim");
+
+int32_t ptrwm_split_propose_precond(const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args, int32_t dim,
+                                    const ptrwm_precond_args *precond, float *proposals, float *accept_u, void *stream) {
+  if (proposal == nullptr || precond == nullptr) return PTRWM_E_NULL;
+  if (int rc = split_common_checks(args, dim)) return rc;
+  if (proposal->kind != PTRWM_PROPOSAL_NORMAL) return PTRWM_E_KIND;
+  if (precond->struct_size != sizeof(ptrwm_precond_args)) return PTRWM_E_STRUCT;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->state == nullptr || proposals == nullptr || accept_u == nullptr || proposal->temp_scale == nullptr ||
+      precond->chol == nullptr)
+    return PTRWM_E_NULL;
+  if (args->ext_prop != nullptr && args->ext_u == nullptr) return PTRWM_E_NULL;
+  PrecondProposeArgs a;
+  a.state = args->state;
+  a.chol = precond->chol;
+  a.temp_scale = proposal->temp_scale;
+  a.ext_raw = args->ext_prop;
+  a.ext_u = args->ext_prop != nullptr ? args->ext_u : nullptr;
+  a.proposals = proposals;
+  a.accept_u = accept_u;
+  a.n_reps = args->n_chains * (long long)args->n_temps;
+  a.chain_offset = args->chain_offset;
+  a.step = (unsigned long long)args->step0;
+  a.device_step = (const long long *)args->device_step;
+  a.n_temps = args->n_temps;
+  a.dim = dim;
+  a.k0 = philox_key(args->seed).k0;
+  a.k1 = philox_key(args->seed).k1;
+  const unsigned lds = (unsigned)prec_lds_bytes(dim);
+  if (lds > 48u * 1024u) {  // (above the default dynamic-LDS allowance; raised once per device)
+    static unsigned long long raised_mask = 0;
+    if (raise_dynamic_lds((const void *)precond_propose_kernel, (const void *)precond_propose_kernel,
+                          prec_lds_bytes(PTRWM_MAX_DIM), raised_mask) != hipSuccess)
+      return PTRWM_E_LAUNCH;
+  }
+  // a workgroup stages the factor once and walks tiles: no more workgroups than keep every compute unit busy
+  const long long tiles = (a.n_reps + kPrecRows - 1) / kPrecRows;
+  const long long cap = 8ll * (device_cus() > 0 ? device_cus() : 256);
+  hipLaunchKernelGGL(precond_propose_kernel, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(kPrecThreads), lds,
+                     (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+}
+
+int32_t ptrwm_precond_update(const ptrwm_precond_update_args *up, int32_t dim, int64_t window, void *stream) {
+  if (up == nullptr) return PTRWM_E_NULL;
+  if (up->struct_size != sizeof(ptrwm_precond_update_args)) return PTRWM_E_STRUCT;
+  if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
+  if (!(up->memory > 0.0 && up->memory <= 1.0) || !(up->jitter >= 0.0) || !std::isfinite(up->jitter) ||
+      !(up->min_count >= 1.0) || up->windows < 1 || window < 0 || window >= up->windows)
+    return PTRWM_E_ARG;
+  if (up->chol == nullptr || up->sxx == nullptr || up->sx == nullptr || up->count == nullptr || up->run_xx == nullptr ||
+      up->run_x == nullptr || up->run_w == nullptr)
+    return PTRWM_E_NULL;
+  PrecondUpdateArgs a;
+  a.chol = up->chol;
+  a.sxx = up->sxx;
+  a.sx = up->sx;
+  a.count = (long long *)up->count;
+  a.run_xx = up->run_xx;
+  a.run_x = up->run_x;
+  a.run_w = up->run_w;
+  a.chol_history = up->chol_history;
+  a.weight_history = up->weight_history;
+  a.skipped = (long long *)up->skipped;
+  a.memory = up->memory;
+  a.jitter = up->jitter;
+  a.min_count = up->min_count;
+  a.window = window;
+  a.dim = dim;
+  static_assert(prec_update_lds_bytes(PTRWM_MAX_DIM) <= 48 * 1024, "precond_update_kernel: within the default dynamic-LDS allowance");
+  hipLaunchKernelGGL(precond_update_kernel, dim3(1), dim3(kPrecUpdateThreads), (size_t)prec_update_lds_bytes(dim),
+                     (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 
 }  // extern "C"

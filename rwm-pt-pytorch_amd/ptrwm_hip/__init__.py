@@ -239,6 +239,37 @@ class CovArgs(C.Structure):
     ]
 
 
+class PrecondArgs(C.Structure):
+    """ptrwm_precond_args: the factor of a preconditioned Normal proposal (include/ptrwm.h, csrc/precond.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("chol", C.c_void_p),
+    ]
+
+
+class PrecondUpdateArgs(C.Structure):
+    """ptrwm_precond_update_args: the factor learned from one warm-up window's covariance sums (include/ptrwm.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("chol", C.c_void_p),
+        ("sxx", C.c_void_p),
+        ("sx", C.c_void_p),
+        ("count", C.c_void_p),
+        ("run_xx", C.c_void_p),
+        ("run_x", C.c_void_p),
+        ("run_w", C.c_void_p),
+        ("memory", C.c_double),
+        ("jitter", C.c_double),
+        ("min_count", C.c_double),
+        ("windows", C.c_int64),
+        ("chol_history", C.c_void_p),
+        ("weight_history", C.c_void_p),
+        ("skipped", C.c_void_p),
+    ]
+
+
 class InitArgs(C.Structure):
     """ptrwm_init_args: starting points drawn from a box, or set to a fallback point (include/ptrwm.h)."""
     _fields_ = [
@@ -319,6 +350,9 @@ SYMBOLS = {
         C.c_int32, [C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ptrwm_split_accept": (
         C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ptrwm_split_propose_precond": (
+        C.c_int32, [C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.c_int32, C.POINTER(PrecondArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ptrwm_precond_update": (C.c_int32, [C.POINTER(PrecondUpdateArgs), C.c_int32, C.c_int64, C.c_void_p]),
     "ptrwm_split_advance": (C.c_int32, [C.POINTER(RunArgs), C.c_void_p]),
     "ptrwm_init_states": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(InitArgs), C.c_void_p]),
     "ptrwm_logdensity": (C.c_int32, [C.POINTER(TargetDesc), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
@@ -721,6 +755,8 @@ class RunPlan:
         self._ladder = None  # warm-up tuning of the temperature ladder: (struct, byref, tensors)
         self._acf = None  # pooled lagged autocovariance: (struct, byref, tensors)
         self._cov = None  # pooled posterior covariance: (struct, byref, tensors)
+        self._precond = None  # preconditioned proposals: (struct, byref, chol)
+        self._precond_update = None  # ... and the factor's update: (struct, byref, tensors)
 
     # kind of accumulator -> (words of its messages, struct, entry point of launch(), entry point of split_moments())
     _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
@@ -1255,12 +1291,116 @@ class RunPlan:
             if tuple(ext_prop.shape) != (Cn, T, raw) or ext_u is None or tuple(ext_u.shape) != (Cn, T):
                 raise ValueError("ext_prop / ext_u of one step must be [n_chains, n_temps, raw] / [n_chains, n_temps]")
         self._plain = False
+        precond = self._precond
+        if precond is not None:  # increments s_t L z (ptrwm_split_propose_precond)
+            with self._guard:
+                rc = self._lib.ptrwm_split_propose_precond(self._refs[3], self._refs[4], D, precond[1], props.data_ptr(),
+                                                           acc_u.data_ptr(), _stream(self.device))
+            if rc != 0:
+                raise PTRWMError(rc, "ptrwm_split_propose_precond")
+            return props
         with self._guard:
             rc = self._lib.ptrwm_split_propose(self._refs[3], self._refs[4], D, props.data_ptr(), acc_u.data_ptr(),
                                                _stream(self.device))
         if rc != 0:
             raise PTRWMError(rc, "ptrwm_split_propose")
         return props
+
+    def set_preconditioner(self, chol: Optional[torch.Tensor]) -> None:
+        """Bind the factor of a preconditioned Normal proposal (include/ptrwm.h ptrwm_precond_args): ``chol`` is a float32
+        [dim, dim] tensor on the run's device, read on its lower triangle only; every following ``split_propose`` then
+        proposes x + s_t L z through ptrwm_split_propose_precond.  The tensor's memory is what is bound: rewriting it in place
+        (``precond_update``) changes the factor of the steps that follow, captured ones included.  ``None`` switches it off."""
+        if chol is None:
+            self._precond = None
+            return
+        D = self.shape[2]
+        if self.proposal_kind != PROPOSAL_NORMAL:
+            raise ValueError("a preconditioner needs the Normal proposal")
+        if tuple(chol.shape) != (D, D) or chol.device != self.device:
+            raise ValueError(f"preconditioner chol must be a [{D}, {D}] tensor on {self.device}")
+        pa = PrecondArgs()
+        pa.struct_size = C.sizeof(PrecondArgs)
+        pa.chol = _require_device(chol, "preconditioner chol", torch.float32)
+        self._precond = (pa, C.byref(pa), chol)
+
+    def set_precond_update(self, sxx: Optional[torch.Tensor], sx: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
+                           run_xx: Optional[torch.Tensor] = None, run_x: Optional[torch.Tensor] = None,
+                           run_w: Optional[torch.Tensor] = None, *, windows: int = 1, probe_every: int = 1, memory: float = 0.5,
+                           jitter: float = 1e-6,
+                           min_count: Optional[float] = None, chol_history: Optional[torch.Tensor] = None,
+                           weight_history: Optional[torch.Tensor] = None, skipped: Optional[torch.Tensor] = None) -> None:
+        """What ``precond_update`` learns the bound factor from (include/ptrwm.h ptrwm_precond_update_args): the window sums
+        ``sxx`` [dim, dim], ``sx`` [dim] float64 and ``count`` [1] int64 - ptrwm_covariance's of one temperature - and the
+        running triple ``run_xx`` [dim, dim], ``run_x`` [dim], ``run_w`` [1] float64; ``chol_history`` [windows + 1, dim, dim]
+        float32, ``weight_history`` [windows] float64 and ``skipped`` [1] int64 are optional records.  ``probe_every`` is the
+        period of ``precond_probe``.  ``None`` switches it off."""
+        if sxx is None:
+            self._precond_update = None
+            return
+        if int(probe_every) < 1:
+            raise ValueError("preconditioner probe_every must be >= 1")
+        if self._precond is None:
+            raise RuntimeError("set_precond_update: no preconditioner bound (set_preconditioner)")
+        D, K = self.shape[2], int(windows)
+        if K < 1:
+            raise ValueError("preconditioner windows must be >= 1")
+        self._tuning_tensors("preconditioner", (("sxx", sxx, (D, D), True), ("sx", sx, (D,), True), ("count", count, (1,), True),
+                                                ("run_xx", run_xx, (D, D), True), ("run_x", run_x, (D,), True),
+                                                ("run_w", run_w, (1,), True), ("chol_history", chol_history, (K + 1, D, D), False),
+                                                ("weight_history", weight_history, (K,), False), ("skipped", skipped, (1,), False)))
+        up = PrecondUpdateArgs()
+        up.struct_size = C.sizeof(PrecondUpdateArgs)
+        up.chol = self._precond[0].chol
+        up.sxx = _require_device(sxx, "preconditioner sxx", torch.float64)
+        up.sx = _require_device(sx, "preconditioner sx", torch.float64)
+        up.count = _require_device(count, "preconditioner count", torch.int64)
+        up.run_xx = _require_device(run_xx, "preconditioner run_xx", torch.float64)
+        up.run_x = _require_device(run_x, "preconditioner run_x", torch.float64)
+        up.run_w = _require_device(run_w, "preconditioner run_w", torch.float64)
+        up.memory, up.jitter = float(memory), float(jitter)
+        up.min_count = float(4 * D if min_count is None else min_count)
+        up.windows = K
+        up.chol_history = _opt(chol_history, "preconditioner chol_history", torch.float32)
+        up.weight_history = _opt(weight_history, "preconditioner weight_history", torch.float64)
+        up.skipped = _opt(skipped, "preconditioner skipped", torch.int64)
+        # the probe: ptrwm_covariance of temperature 0 into the window's sums (their layout with temps = 1)
+        cv = CovArgs()
+        cv.struct_size = C.sizeof(CovArgs)
+        cv.temps, cv.every = 1, int(probe_every)
+        cv.sxx, cv.sx, cv.count = up.sxx, up.sx, up.count
+        self._precond_update = (up, C.byref(up), (sxx, sx, count, run_xx, run_x, run_w, chol_history, weight_history, skipped),
+                                cv, C.byref(cv))
+
+    def precond_probe(self, step: int) -> None:
+        """One probe of the factor's tuning behind step ``step`` (ptrwm_covariance on temperature 0 into the bound window sums,
+        driven with burn-in 0 and ``every`` = the probe period: a step whose step counter is no multiple of it adds nothing).
+        Host-step mode: the call sits between blocks of steps, never inside a captured one."""
+        bound = self._precond_update
+        if bound is None:
+            raise RuntimeError("precond_probe: no update bound (set_precond_update)")
+        a = self._a
+        burn_in, dstep = a.burn_in, a.device_step
+        a.step0, a.burn_in, a.device_step = step, 0, None
+        try:
+            with self._guard:
+                rc = self._lib.ptrwm_covariance(self._refs[4], self.shape[2], bound[4], _stream(self.device))
+        finally:
+            a.burn_in, a.device_step = burn_in, dstep
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_covariance")
+
+    def precond_update(self, window: int) -> None:
+        """The factor's update of window ``window`` from the bound sums (ptrwm_precond_update): the bound ``chol`` is rewritten
+        in place - or kept, and ``skipped`` counted, where the sums do not give a positive-definite matrix - and the window
+        sums are left zero.  Enqueues one small kernel."""
+        bound = self._precond_update
+        if bound is None:
+            raise RuntimeError("precond_update: no update bound (set_precond_update)")
+        with self._guard:
+            rc = self._lib.ptrwm_precond_update(bound[1], self.shape[2], int(window), _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, "ptrwm_precond_update")
 
     def split_accept(self, step: int, logp_proposed: torch.Tensor, ext_swap_u: Optional[torch.Tensor] = None,
                      accept_flags: Optional[torch.Tensor] = None, swap_event_offset: int = 0, no_sweep: bool = False) -> None:
