@@ -26,11 +26,11 @@ and, with flow=True, the replica-flow arrays (`_flow`, a dict; include/ptrwm.h p
     n_up, n_down int64   [n_replicas, n_temps]        visits by replicas that last touched the cold / the hot end
 
 and, with hist_temps > 0, the pooled marginal histograms (`_hist`, a dict; include/ptrwm.h ptrwm_hist_args), added to by a
-snapshot kernel between launches at every hist_every-th step past burn-in:
+snapshot kernel between launches at every hist_every-th step past burn-in (the bin rule's constants lo, scale - float32 [dim],
+csrc/hist.h - are the plan's):
 
     counts       int64   [hist_temps, dim, hist_bins + 2]   bin 0 underflow (and NaN), bin hist_bins + 1 overflow
     count        int64   [hist_temps]                       (replica, step) pairs added per temperature
-    lo, scale    float32 [dim]                              the bin rule's constants (csrc/hist.h)
 
 and, with adapt_scale=True, the arrays of the warm-up tuning of the proposal scale (`_adapt`, a ScaleTuning; include/ptrwm.h
 ptrwm_adapt_args), used by two small kernels between launches at the end of every adaptation window of burn-in:
@@ -591,35 +591,32 @@ class EngineRun:
                           **{k: torch.empty(shape, device=device, dtype=torch.int64) for k in ("round_trips", "n_up", "n_down")}}
             self.reset_flow()
             self._plan.set_flow(self._flow["walker"], self._flow["round_trips"], self._flow["n_up"], self._flow["n_down"])
-        # pooled marginal histograms, counted by a snapshot kernel between launches (off: None)
+        # The snapshot accumulators - pooled marginal histograms, lagged autocovariance, posterior covariance - each added to by
+        # a snapshot kernel between launches.  One description each: the dict of its sums under the attribute's name, zeroed by
+        # _reset_snapshot and read out by _snapshot_sums (off: None); scratch - the bin rule's constants, the ring - stays out of it.
         self.hist_temps, self.hist_every, self.hist_bins = int(hist_temps), int(hist_every), int(hist_bins)
-        self._hist = None
+        self.acf_temps, self.acf_every, self.acf_max_lag = int(acf_temps), int(acf_every), int(acf_max_lag)
+        self.cov_temps, self.cov_every = int(cov_temps), int(cov_every)
+
+        def zeros(*shape, dtype=torch.float64):
+            return torch.zeros(*shape, device=device, dtype=dtype)
+
+        self._hist = self._acf = self._cov = None
         if hist_box is not None:
             lo, hi = hist_box
-            self._hist = {"counts": torch.zeros(self.hist_temps, dim, self.hist_bins + 2, device=device, dtype=torch.int64),
-                          "count": torch.zeros(self.hist_temps, device=device, dtype=torch.int64),
-                          "lo": torch.from_numpy(lo).to(device), "scale": torch.from_numpy(hist_scale(lo, hi, self.hist_bins)).to(device)}
             self._hist_edges = hist_edges(lo, hi, self.hist_bins)
-            self._plan.set_histogram(self._hist["counts"], self._hist["lo"], self._hist["scale"], n_bins=self.hist_bins,
-                                     temps=self.hist_temps, every=self.hist_every, count=self._hist["count"])
-        # pooled lagged autocovariance, summed by a snapshot kernel between launches (off: None); the ring is scratch
-        self.acf_temps, self.acf_every, self.acf_max_lag = int(acf_temps), int(acf_every), int(acf_max_lag)
-        self._acf = None
+            h = self._hist = {"counts": zeros(self.hist_temps, dim, self.hist_bins + 2, dtype=torch.int64),
+                              "count": zeros(self.hist_temps, dtype=torch.int64)}
+            self._plan.set_histogram(h["counts"], torch.from_numpy(lo).to(device), torch.from_numpy(hist_scale(lo, hi, self.hist_bins)).to(device),
+                                     n_bins=self.hist_bins, temps=self.hist_temps, every=self.hist_every, count=h["count"])
         if acf_on:
             L, at = self.acf_max_lag, self.acf_temps
-            self._acf = {**{k: torch.zeros(at, L + 1, dim, device=device, dtype=torch.float64) for k in ("sxy", "head", "tail")},
-                         "pairs": torch.zeros(L + 1, device=device, dtype=torch.int64)}
+            a = self._acf = {**{k: zeros(at, L + 1, dim) for k in ("sxy", "head", "tail")}, "pairs": zeros(L + 1, dtype=torch.int64)}
             self._acf_ring = torch.empty(L, n_replicas, at, dim, device=device, dtype=dtype)
-            self._plan.set_autocorr(self._acf_ring, self._acf["sxy"], self._acf["head"], self._acf["tail"], self._acf["pairs"],
-                                    every=self.acf_every)
-        # pooled posterior covariance sums, added to by a snapshot kernel between launches (off: None)
-        self.cov_temps, self.cov_every = int(cov_temps), int(cov_every)
-        self._cov = None
+            self._plan.set_autocorr(self._acf_ring, a["sxy"], a["head"], a["tail"], a["pairs"], every=self.acf_every)
         if cov_on:
-            self._cov = {"sxx": torch.zeros(self.cov_temps, dim, dim, device=device, dtype=torch.float64),
-                         "sx": torch.zeros(self.cov_temps, dim, device=device, dtype=torch.float64),
-                         "count": torch.zeros(1, device=device, dtype=torch.int64)}
-            self._plan.set_covariance(self._cov["sxx"], self._cov["sx"], self._cov["count"], every=self.cov_every)
+            c = self._cov = {"sxx": zeros(self.cov_temps, dim, dim), "sx": zeros(self.cov_temps, dim), "count": zeros(1, dtype=torch.int64)}
+            self._plan.set_covariance(c["sxx"], c["sx"], c["count"], every=self.cov_every)
         # warm-up tuning of the proposal scale, per temperature, by two small kernels between launches (off: None)
         self.init_scales = self.proposal.temp_scale.clone()
         self._adapt = None
@@ -826,10 +823,7 @@ class EngineRun:
         props = self._plan.split_propose(offset)
         lp_new = self._density(props.view(-1, D)).view(C, T)
         self._plan.split_accept(offset, lp_new, swap_event_offset=self.manual_sweeps, no_sweep=no_sweep)
-        self._plan.split_moments(offset)  # (decides on the device whether this step counts; no-op without moments)
-        self._plan.split_histogram(offset)  # (likewise; no-op without a histogram)
-        self._plan.split_autocorr(offset)  # (likewise; no-op without an autocovariance accumulator)
-        self._plan.split_covariance(offset)  # (likewise; no-op without a covariance accumulator)
+        self._plan.split_snapshots(offset)  # (each bound accumulator decides on the device whether this step counts)
         if advance:
             self._plan.split_advance(advance)
 
@@ -952,10 +946,7 @@ class EngineRun:
                 lp_new = self._density(props.view(-1, D)).view(C, T)
                 self._plan.split_accept(s, lp_new, swap_event_offset=self.manual_sweeps)
                 if not warmup:
-                    self._plan.split_moments(s)
-                    self._plan.split_histogram(s)
-                    self._plan.split_autocorr(s)
-                    self._plan.split_covariance(s)
+                    self._plan.split_snapshots(s)
                 self.steps_done += 1
                 if trace is not None and ptrwm_hip.periodic_steps_in(s, s + 1, trace_every):
                     tc, tt = trace.shape[1], trace.shape[2]
@@ -1011,40 +1002,43 @@ class EngineRun:
         for t in (self._mom or {}).values():
             t.zero_()
 
+    def _snapshot_sums(self, name: str, **extra) -> Optional[dict]:
+        """The read-out of the snapshot accumulator under attribute `name`: its sums and `extra`, or None when it is off."""
+        sums = getattr(self, name)
+        return {**sums, **extra} if sums is not None else None
+
+    def _reset_snapshot(self, name: str) -> None:
+        for t in (getattr(self, name) or {}).values():
+            t.zero_()
+
     def histogram(self) -> Optional[dict]:
         """The pooled marginal histograms of this shard, or None when they are off: counts [hist_temps, dim, hist_bins + 2]
         and count [hist_temps] (int64 device tensors, no synchronisation) and edges [dim, hist_bins + 1] (float64, CPU)."""
-        if self._hist is None:
-            return None
-        return {"counts": self._hist["counts"], "count": self._hist["count"], "edges": self._hist_edges}
+        return self._snapshot_sums("_hist", edges=getattr(self, "_hist_edges", None))
 
     def reset_histogram(self) -> None:
         """Zero the histogram counters (the chains keep their states)."""
-        if self._hist is not None:
-            self._hist["counts"].zero_()
-            self._hist["count"].zero_()
+        self._reset_snapshot("_hist")
 
     def autocorr_sums(self) -> Optional[dict]:
         """The pooled lagged autocovariance sums of this shard, or None when they are off: sxy / head / tail
         [acf_temps, acf_max_lag + 1, dim] float64 and pairs [acf_max_lag + 1] int64 (device tensors, no synchronisation), and
         every."""
-        return {**self._acf, "every": self.acf_every} if self._acf is not None else None
+        return self._snapshot_sums("_acf", every=self.acf_every)
 
     def reset_autocorr(self) -> None:
         """Zero the autocovariance sums (the chains keep their states).  The ring stays valid: snapshots are numbered from the
         step counter, so the next one pairs with the ones before the reset."""
-        for t in (self._acf or {}).values():
-            t.zero_()
+        self._reset_snapshot("_acf")
 
     def covariance_sums(self) -> Optional[dict]:
         """The pooled covariance sums of this shard, or None when they are off: sxx [cov_temps, dim, dim] (lower triangle) and sx
         [cov_temps, dim] float64, count [1] int64 (device tensors, no synchronisation), and every."""
-        return {**self._cov, "every": self.cov_every} if self._cov is not None else None
+        return self._snapshot_sums("_cov", every=self.cov_every)
 
     def reset_covariance(self) -> None:
         """Zero the covariance sums (the chains keep their states)."""
-        for t in (self._cov or {}).values():
-            t.zero_()
+        self._reset_snapshot("_cov")
 
     def flow(self) -> Optional[dict]:
         """Replica flow of this shard (device tensors, no synchronisation), or None when flow is off: walker (int32 flow
@@ -1234,6 +1228,13 @@ class PosteriorMoments:
 ACF_RING_LIMIT = 1 << 31  # elements (8 GiB of float states): what a ring may hold unless the caller says otherwise
 
 
+def covered_temperature(temperature, temps: int, what: str) -> int:
+    """`temperature` as an index into the first `temps` temperatures a snapshot accumulator covers (`what`: "the ... cover(s)")"""
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, np.integer)) or not 0 <= temperature < temps:
+        raise ValueError(f"temperature must be in 0..{temps - 1} ({what} the first {temps}), got {temperature!r}")
+    return int(temperature)
+
+
 def check_acf_args(acf_temps, acf_every, acf_max_lag, n_temps: int, dim: int, n_replicas: int, ring_limit=None) -> bool:
     """EngineRun's autocovariance arguments (no GPU needed): False when off.  The ring holds acf_max_lag x replicas x acf_temps
     x dim elements of the state's type; above `ring_limit` elements (default ACF_RING_LIMIT = 2^31) that is refused, naming the
@@ -1330,14 +1331,12 @@ class Autocorrelation:
         if getattr(self, "_acf_mode", None) is None:
             raise RuntimeError("the autocovariance is off: construct the sampler with acf='cold' or 'all'")
         temps = acf_temps(self._acf_mode, len(getattr(self, "beta_ladder", [1.0])))
-        if isinstance(temperature, bool) or not isinstance(temperature, (int, np.integer)) or not 0 <= temperature < temps:
-            raise ValueError(f"temperature must be in 0..{temps - 1} (the autocovariance covers the first {temps}), got {temperature!r}")
+        t = covered_temperature(temperature, temps, "the autocovariance covers")
         run = getattr(self, "_run", None)
         if run is None or run.autocorr_sums() is None:  # nothing run yet, or reset(): empty sums
             z = torch.zeros(self._acf_max_lag + 1, self.dim, dtype=torch.float64)
             return z, z.clone(), z.clone(), torch.zeros(self._acf_max_lag + 1, dtype=torch.int64)
         a = run.autocorr_sums()
-        t = int(temperature)
         return a["sxy"][t].cpu(), a["head"][t].cpu(), a["tail"][t].cpu(), a["pairs"].cpu()
 
     def autocovariance(self, temperature: int = 0) -> torch.Tensor:
@@ -1460,14 +1459,12 @@ class PosteriorCovariance:
         if getattr(self, "_cov_mode", None) is None:
             raise RuntimeError("the covariance is off: construct the sampler with cov='cold' or 'all'")
         temps = cov_temps(self._cov_mode, len(getattr(self, "beta_ladder", [1.0])))
-        if isinstance(temperature, bool) or not isinstance(temperature, (int, np.integer)) or not 0 <= temperature < temps:
-            raise ValueError(f"temperature must be in 0..{temps - 1} (the covariance covers the first {temps}), got {temperature!r}")
+        t = covered_temperature(temperature, temps, "the covariance covers")
         run = getattr(self, "_run", None)
         if run is None or run.covariance_sums() is None:  # nothing run yet, or reset(): empty sums
             return (torch.zeros(self.dim, self.dim, dtype=torch.float64), torch.zeros(self.dim, dtype=torch.float64),
                     torch.zeros(1, dtype=torch.int64))
         a = run.covariance_sums()
-        t = int(temperature)
         return a["sxx"][t].cpu(), a["sx"][t].cpu(), a["count"].cpu()
 
     @property
@@ -1622,13 +1619,12 @@ class MarginalHistograms:
         run = getattr(self, "_run", None)
         n_temps = len(getattr(self, "beta_ladder", [1.0]))
         temps = hist_temps(self._hist_mode, n_temps)
-        if isinstance(temperature, bool) or not isinstance(temperature, (int, np.integer)) or not 0 <= temperature < temps:
-            raise ValueError(f"temperature must be in 0..{temps - 1} (the histograms cover the first {temps}), got {temperature!r}")
+        t = covered_temperature(temperature, temps, "the histograms cover")
         if run is None or run.histogram() is None:  # nothing run yet, or reset(): empty counters
             lo, hi = check_hist_range(self._hist_range, self.dim)
             return torch.zeros(self.dim, self._hist_bins + 2, dtype=torch.int64), hist_edges(lo, hi, self._hist_bins)
         h = run.histogram()
-        return h["counts"][int(temperature)].cpu(), h["edges"]
+        return h["counts"][t].cpu(), h["edges"]
 
     def marginal_histogram(self, temperature: int = 0) -> tuple:
         """(counts [dim, bins + 2] int64, edges [dim, bins + 1] float64) of `temperature`, pooled over every replica and every

@@ -11,6 +11,7 @@
 #include "hist.h"
 #include "precond.h"
 #include "schedule.h"
+#include "snapshot.h"
 #include "variants.h"
 
 namespace ptrwm {
@@ -667,12 +668,10 @@ struct SplitMomentsArgs {  // (of both kernels)
   long long n_chains, step, burn_in, every;
   const long long *device_step;
   int n_temps, dim, temps;
-  // is the step just performed an accumulated one?  (grid-uniform)
-  __device__ bool step_counts() const { return periodic_step_due((device_step != nullptr ? *device_step + step : step) + 1, burn_in, every); }
 };
 
 __global__ void __launch_bounds__(256) split_moments_kernel(SplitMomentsArgs a) {
-  if (!a.step_counts()) return;
+  if (!snapshot_step_due(a.step, a.device_step, a.burn_in, a.every)) return;  // (is the step just performed an accumulated one?)
   const long long c0 = (long long)blockIdx.x * kSplitMomChains;
   const long long c1 = (a.n_chains - c0 < kSplitMomChains) ? a.n_chains : c0 + kSplitMomChains;
   const int td = a.temps * a.dim;
@@ -701,7 +700,7 @@ __global__ void __launch_bounds__(256) split_moments_kernel(SplitMomentsArgs a) 
 // Per-chain moments of one split step (ptrwm_split_chain_moments): one thread per (chain, t < temps, d), a plain
 // read-modify-write of its own two elements - the same sequential fp64 sums as the fused kernels' (v * v is exact in fp64).
 __global__ void __launch_bounds__(256) split_chain_moments_kernel(SplitMomentsArgs a) {
-  if (!a.step_counts()) return;
+  if (!snapshot_step_due(a.step, a.device_step, a.burn_in, a.every)) return;  // (is the step just performed an accumulated one?)
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const int td = a.temps * a.dim;
   if (i >= a.n_chains * td) return;
@@ -724,19 +723,17 @@ __global__ void __launch_bounds__(256) split_chain_moments_kernel(SplitMomentsAr
 // LDS: up to five workgroups per CU.  `direct` (n_bins + 2 > kHistLdsCounters / kHistMinCols: fewer than a wavefront's worth
 // of columns would fit): no LDS, every sample is one global atomic.  The constants and the host's choice of `cols` and
 // `direct` are hist.h's (hist_geometry).
-struct HistSnapArgs {
-  const void *state;  // float or double [n_chains, n_temps, dim]
+struct HistOwn {
   const float *lo, *scale;
   long long *counts, *count;
-  long long n_chains, step, burn_in, every;
-  const long long *device_step;
-  int n_temps, dim, temps, n_bins, cols, direct;
+};
+struct HistSnapArgs : SnapHead<HistOwn> {
+  int temps, n_bins, cols, direct;
 };
 
 template <class state_t>
 __global__ void __launch_bounds__(256) hist_snapshot_kernel(HistSnapArgs a) {
-  // is the step just performed a due one?  (grid-uniform, as SplitMomentsArgs::step_counts)
-  if (!periodic_step_due((a.device_step != nullptr ? *a.device_step + a.step : a.step) + 1, a.burn_in, a.every)) return;
+  if (!a.due()) return;  // (snapshot.h)
   __shared__ unsigned s_cnt[kHistLdsCounters];
   const int tid = (int)threadIdx.x, nbp = a.n_bins + 2, td = a.temps * a.dim;
   const int k0 = (int)blockIdx.y * a.cols;
@@ -751,12 +748,12 @@ __global__ void __launch_bounds__(256) hist_snapshot_kernel(HistSnapArgs a) {
   const int per = 256 / cols, sub = tid / cols, kk = tid - sub * cols;  // chains in flight; this thread's; its column
   if (sub < per) {
     const int k = k0 + kk;
-    const float lo = a.lo[k % a.dim], sc = a.scale[k % a.dim];
+    const float lo = a.own.lo[k % a.dim], sc = a.own.scale[k % a.dim];
     const long long run = (long long)a.n_temps * a.dim;
     const state_t *__restrict__ p = reinterpret_cast<const state_t *>(a.state) + k;
     for (long long c = c0 + sub; c < c1; c += per) {
       const int b = hist_bin(static_cast<float>(p[c * run]), lo, sc, a.n_bins);
-      if (direct) count_add(&a.counts[(long long)k * nbp + b], 1ll);
+      if (direct) count_add(&a.own.counts[(long long)k * nbp + b], 1ll);
       else atomicAdd(&s_cnt[kk * nbp + b], 1u);
     }
   }
@@ -764,11 +761,11 @@ __global__ void __launch_bounds__(256) hist_snapshot_kernel(HistSnapArgs a) {
     __syncthreads();
     for (int i = tid; i < cols * nbp; i += 256) {
       const unsigned v = s_cnt[i];
-      if (v != 0u) count_add(&a.counts[(long long)k0 * nbp + i], (long long)v);
+      if (v != 0u) count_add(&a.own.counts[(long long)k0 * nbp + i], (long long)v);
     }
   }
-  if (blockIdx.y == 0 && a.count != nullptr)
-    for (int t = tid; t < a.temps; t += 256) count_add(&a.count[t], c1 - c0);
+  if (blockIdx.y == 0 && a.own.count != nullptr)
+    for (int t = tid; t < a.temps; t += 256) count_add(&a.own.count[t], c1 - c0);
 }
 
 // Pooled lagged autocovariance (ptrwm_autocorr, and the snapshots of ptrwm_run_with_autocorr; acf.h states the rule and the
@@ -781,21 +778,19 @@ __global__ void __launch_bounds__(256) hist_snapshot_kernel(HistSnapArgs a) {
 // in turn: one barrier per lag), and the column's first thread flushes the tile's three sums, one no-return fp64 atomic per
 // non-zero sum.  (head: the sum of x_j, the same for every lag - it is the lag-0 `tail`.)  Then the thread overwrites its
 // elements of slot j % max_lag: nobody else reads or writes them.
-struct AcfSnapArgs {
-  const void *state;  // float or double [n_chains, n_temps, dim]
-  void *ring;         // the same type [max_lag, n_chains, temps * dim]
+struct AcfOwn {
+  void *ring;  // the state's type [max_lag, n_chains, temps * dim]
   double *sxy, *head, *tail;
   long long *pairs;
-  long long n_chains, step, burn_in, every;
-  const long long *device_step;
-  int n_temps, dim, temps, max_lag, cols, per, chains;
+};
+struct AcfSnapArgs : SnapHead<AcfOwn> {
+  int temps, max_lag, cols, per, chains;
 };
 
 template <class state_t>
 __global__ void __launch_bounds__(kAcfThreads) acf_snapshot_kernel(AcfSnapArgs a) {
-  // is the step just performed a due one?  (grid-uniform, as SplitMomentsArgs::step_counts)
-  const long long sc = (a.device_step != nullptr ? *a.device_step + a.step : a.step) + 1;
-  if (!periodic_step_due(sc, a.burn_in, a.every)) return;
+  long long sc;
+  if (!a.due(&sc)) return;  // (snapshot.h)
   constexpr int R = kAcfChainsPerThread;
   __shared__ double s_red[2][2][kAcfThreads];  // [buffer][sxy, tail][column of the group]
   const long long j = periodic_step_number(sc, a.burn_in, a.every);
@@ -820,7 +815,7 @@ __global__ void __launch_bounds__(kAcfThreads) acf_snapshot_kernel(AcfSnapArgs a
 #pragma unroll
     for (int i = 0; i < R; ++i) x[i] = i < nv ? p[(long long)i * a.per * run] : state_t(0);
   }
-  state_t *ring = reinterpret_cast<state_t *>(a.ring);
+  state_t *ring = reinterpret_cast<state_t *>(a.own.ring);
   const int t = k / a.dim, d = k - t * a.dim;
   const long long acc0 = (long long)t * (a.max_lag + 1) * a.dim + d;  // element [t, 0, d] of the sums
   double hsum = 0.0;
@@ -862,9 +857,9 @@ __global__ void __launch_bounds__(kAcfThreads) acf_snapshot_kernel(AcfSnapArgs a
     if (first) {
       if (lag == 0) hsum = tl;
       const long long e = acc0 + (long long)lag * a.dim;
-      if (sx != 0.0) unsafeAtomicAdd(a.sxy + e, sx);
-      if (hsum != 0.0) unsafeAtomicAdd(a.head + e, hsum);
-      if (tl != 0.0) unsafeAtomicAdd(a.tail + e, tl);
+      if (sx != 0.0) unsafeAtomicAdd(a.own.sxy + e, sx);
+      if (hsum != 0.0) unsafeAtomicAdd(a.own.head + e, hsum);
+      if (tl != 0.0) unsafeAtomicAdd(a.own.tail + e, tl);
     }
   }
   if (nv > 0) {
@@ -874,7 +869,7 @@ __global__ void __launch_bounds__(kAcfThreads) acf_snapshot_kernel(AcfSnapArgs a
       if (i < nv) w[(long long)i * cstep] = x[i];
   }
   if (blockIdx.x == 0 && blockIdx.y == 0)
-    for (int lag = tid; lag <= lags; lag += kAcfThreads) count_add(&a.pairs[lag], a.n_chains);
+    for (int lag = tid; lag <= lags; lag += kAcfThreads) count_add(&a.own.pairs[lag], a.n_chains);
 }
 
 // Pooled posterior covariance (ptrwm_covariance, and the snapshots of ptrwm_run_with_covariance; cov.h states the rule and the
@@ -889,22 +884,17 @@ __global__ void __launch_bounds__(kAcfThreads) acf_snapshot_kernel(AcfSnapArgs a
 // compile-time maximum and guarded wave-uniformly, so that the accumulators are indexed statically (registers, no scratch).
 // Flush: one no-return fp64 atomic per non-zero (i, j), j <= i < dim, and per sx element.
 // The kernel only reads `state`.
-struct CovSnapArgs {
-  const void *state;  // float or double [n_chains, n_temps, dim]
+struct CovOwn {
   double *sxx, *sx;
   long long *count;
-  long long n_chains, step, burn_in, every;
-  const long long *device_step;
-  int n_temps, dim;
 };
+struct CovSnapArgs : SnapHead<CovOwn> {};
 
 typedef double cov_acc_t __attribute__((ext_vector_type(4)));
 
 template <class state_t>
 __global__ void __launch_bounds__(kCovThreads, 2) cov_snapshot_kernel(CovSnapArgs a) {
-  // is the step just performed a due one?  (grid-uniform, as SplitMomentsArgs::step_counts)
-  const long long sc = (a.device_step != nullptr ? *a.device_step + a.step : a.step) + 1;
-  if (!periodic_step_due(sc, a.burn_in, a.every)) return;
+  if (!a.due()) return;  // (snapshot.h)
   extern __shared__ double s_cov[];  // [kCovSubTile][cov_row_stride(dim)]
   const int tid = (int)threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -949,7 +939,7 @@ __global__ void __launch_bounds__(kCovThreads, 2) cov_snapshot_kernel(CovSnapArg
         }
     }
   }
-  double *__restrict__ sxx = a.sxx + (long long)t * dim * dim;
+  double *__restrict__ sxx = a.own.sxx + (long long)t * dim * dim;
 #pragma unroll
   for (int q = 0; q < kCovPairsPerWave; ++q)
     if (q < nq) {
@@ -964,10 +954,10 @@ __global__ void __launch_bounds__(kCovThreads, 2) cov_snapshot_kernel(CovSnapArg
         double m = s[q];           // (the four K-quarters of a column meet: lanes l, l + 16, l + 32, l + 48)
         m += __shfl_xor(m, 16);
         m += __shfl_xor(m, 32);
-        if (cov_sx_flushed(bi[q], lane, dim) && m != 0.0) unsafeAtomicAdd(a.sx + (long long)t * dim + kCovBlock * bi[q] + lane, m);
+        if (cov_sx_flushed(bi[q], lane, dim) && m != 0.0) unsafeAtomicAdd(a.own.sx + (long long)t * dim + kCovBlock * bi[q] + lane, m);
       }
     }
-  if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) count_add(a.count, a.n_chains);
+  if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) count_add(a.own.count, a.n_chains);
 }
 
 // ---- preconditioned Gaussian proposals (precond.h; include/ptrwm.h ptrwm_split_propose_precond) -----------------------------------
@@ -1482,11 +1472,19 @@ static int32_t check_flow(const ptrwm_run_args *args, const ptrwm_flow_args *flo
   return PTRWM_OK;
 }
 
+// what the three snapshot blocks' checks open with: the struct's size, then the covered temperatures and the period
+template <class Block>
+static int32_t check_snapshot_block(const ptrwm_run_args *args, const Block *b) {
+  if (b->struct_size != sizeof(Block)) return PTRWM_E_STRUCT;
+  if (b->temps < 1 || b->temps > args->n_temps || b->every < 1) return PTRWM_E_ARG;
+  return PTRWM_OK;
+}
+
 // the histogram checks shared by ptrwm_run_with_histogram and ptrwm_histogram (args already checked); none: ok
 static int32_t check_hist(const ptrwm_run_args *args, const ptrwm_hist_args *h) {
   if (h == nullptr) return PTRWM_OK;
-  if (h->struct_size != sizeof(ptrwm_hist_args)) return PTRWM_E_STRUCT;
-  if (h->temps < 1 || h->temps > args->n_temps || h->every < 1 || h->n_bins < 1 || h->n_bins > PTRWM_HIST_MAX_BINS) return PTRWM_E_ARG;
+  if (int rc = check_snapshot_block(args, h)) return rc;
+  if (h->n_bins < 1 || h->n_bins > PTRWM_HIST_MAX_BINS) return PTRWM_E_ARG;
   if (h->lo == nullptr || h->scale == nullptr || h->counts == nullptr) return PTRWM_E_NULL;
   return PTRWM_OK;
 }
@@ -1496,38 +1494,23 @@ static_assert(PTRWM_HIST_MAX_BINS == kHistMaxBins, "hist.h and include/ptrwm.h: 
 static int32_t launch_hist(const ptrwm_run_args *args, int32_t dim, const ptrwm_hist_args *h, long long step,
                            const long long *device_step, hipStream_t stream) {
   HistSnapArgs a;
-  a.state = args->state;
-  a.lo = h->lo;
-  a.scale = h->scale;
-  a.counts = (long long *)h->counts;
-  a.count = (long long *)h->count;
-  a.n_chains = args->n_chains;
-  a.step = step;
-  a.burn_in = args->burn_in;
-  a.every = h->every;
-  a.device_step = device_step;
-  a.n_temps = args->n_temps;
-  a.dim = dim;
+  fill_snap_head(a, args, dim, h->every, step, device_step);
+  a.own = {h->lo, h->scale, (long long *)h->counts, (long long *)h->count};
   a.temps = h->temps;
   a.n_bins = h->n_bins;
   const HistGeometry g = hist_geometry(h->n_bins, h->temps * dim);
   a.direct = g.direct;
   a.cols = g.cols;
   const long long gx = (args->n_chains + kHistChains - 1) / kHistChains;
-  if (gx > 0x7fffffffll) return PTRWM_E_ARG;
-  const dim3 grid((unsigned)gx, (unsigned)g.groups);  // (y <= 256 * 104 / 64)
-  if (args->state_f64 == 1)
-    hipLaunchKernelGGL(hist_snapshot_kernel<double>, grid, dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(hist_snapshot_kernel<float>, grid, dim3(256), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+  return launch_snapshot(hist_snapshot_kernel<float>, hist_snapshot_kernel<double>, args->state_f64 == 1, gx, (unsigned)g.groups /* <= 256 * 104 / 64 */,
+                         256, 0, stream, a);
 }
 
 // the autocovariance checks shared by ptrwm_run_with_autocorr and ptrwm_autocorr (args already checked); none: ok
 static int32_t check_acf(const ptrwm_run_args *args, const ptrwm_acf_args *ac) {
   if (ac == nullptr) return PTRWM_OK;
-  if (ac->struct_size != sizeof(ptrwm_acf_args)) return PTRWM_E_STRUCT;
-  if (ac->temps < 1 || ac->temps > args->n_temps || ac->every < 1 || ac->max_lag < 1 || ac->max_lag > PTRWM_ACF_MAX_LAG) return PTRWM_E_ARG;
+  if (int rc = check_snapshot_block(args, ac)) return rc;
+  if (ac->max_lag < 1 || ac->max_lag > PTRWM_ACF_MAX_LAG) return PTRWM_E_ARG;
   if (ac->ring == nullptr || ac->sxy == nullptr || ac->head == nullptr || ac->tail == nullptr || ac->pairs == nullptr) return PTRWM_E_NULL;
   return PTRWM_OK;
 }
@@ -1537,19 +1520,8 @@ static_assert(PTRWM_ACF_MAX_LAG == kAcfMaxLag, "acf.h and include/ptrwm.h: one l
 static int32_t launch_acf(const ptrwm_run_args *args, int32_t dim, const ptrwm_acf_args *ac, long long step,
                           const long long *device_step, hipStream_t stream) {
   AcfSnapArgs a;
-  a.state = args->state;
-  a.ring = ac->ring;
-  a.sxy = ac->sxy;
-  a.head = ac->head;
-  a.tail = ac->tail;
-  a.pairs = (long long *)ac->pairs;
-  a.n_chains = args->n_chains;
-  a.step = step;
-  a.burn_in = args->burn_in;
-  a.every = ac->every;
-  a.device_step = device_step;
-  a.n_temps = args->n_temps;
-  a.dim = dim;
+  fill_snap_head(a, args, dim, ac->every, step, device_step);
+  a.own = {ac->ring, ac->sxy, ac->head, ac->tail, (long long *)ac->pairs};
   a.temps = ac->temps;
   a.max_lag = ac->max_lag;
   const AcfGeometry g = acf_geometry(ac->temps * dim);
@@ -1557,20 +1529,14 @@ static int32_t launch_acf(const ptrwm_run_args *args, int32_t dim, const ptrwm_a
   a.per = g.per;
   a.chains = g.chains;
   const long long gx = (args->n_chains + g.chains - 1) / g.chains;
-  if (gx > 0x7fffffffll) return PTRWM_E_ARG;
-  const dim3 grid((unsigned)gx, (unsigned)g.groups);  // (y <= 104)
-  if (args->state_f64 == 1)
-    hipLaunchKernelGGL(acf_snapshot_kernel<double>, grid, dim3(kAcfThreads), 0, stream, a);
-  else
-    hipLaunchKernelGGL(acf_snapshot_kernel<float>, grid, dim3(kAcfThreads), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+  return launch_snapshot(acf_snapshot_kernel<float>, acf_snapshot_kernel<double>, args->state_f64 == 1, gx, (unsigned)g.groups /* <= 104 */,
+                         kAcfThreads, 0, stream, a);
 }
 
 // the covariance checks shared by ptrwm_run_with_covariance and ptrwm_covariance (args already checked); none: ok
 static int32_t check_cov(const ptrwm_run_args *args, const ptrwm_cov_args *cv) {
   if (cv == nullptr) return PTRWM_OK;
-  if (cv->struct_size != sizeof(ptrwm_cov_args)) return PTRWM_E_STRUCT;
-  if (cv->temps < 1 || cv->temps > args->n_temps || cv->every < 1) return PTRWM_E_ARG;
+  if (int rc = check_snapshot_block(args, cv)) return rc;
   if (cv->sxx == nullptr || cv->sx == nullptr || cv->count == nullptr) return PTRWM_E_NULL;
   return PTRWM_OK;
 }
@@ -1580,26 +1546,12 @@ static_assert(PTRWM_MAX_DIM == kCovMaxDim, "cov.h and include/ptrwm.h: one large
 static int32_t launch_cov(const ptrwm_run_args *args, int32_t dim, const ptrwm_cov_args *cv, long long step,
                           const long long *device_step, hipStream_t stream) {
   CovSnapArgs a;
-  a.state = args->state;
-  a.sxx = cv->sxx;
-  a.sx = cv->sx;
-  a.count = (long long *)cv->count;
-  a.n_chains = args->n_chains;
-  a.step = step;
-  a.burn_in = args->burn_in;
-  a.every = cv->every;
-  a.device_step = device_step;
-  a.n_temps = args->n_temps;
-  a.dim = dim;
+  fill_snap_head(a, args, dim, cv->every, step, device_step);
+  a.own = {cv->sxx, cv->sx, (long long *)cv->count};
   const CovGeometry g = cov_geometry(dim);
   const long long gx = (args->n_chains + g.chains - 1) / g.chains;
-  if (gx > 0x7fffffffll) return PTRWM_E_ARG;
-  const dim3 grid((unsigned)gx, (unsigned)cv->temps);  // (y <= 256)
-  if (args->state_f64 == 1)
-    hipLaunchKernelGGL(cov_snapshot_kernel<double>, grid, dim3(kCovThreads), (size_t)g.lds_bytes, stream, a);
-  else
-    hipLaunchKernelGGL(cov_snapshot_kernel<float>, grid, dim3(kCovThreads), (size_t)g.lds_bytes, stream, a);
-  return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
+  return launch_snapshot(cov_snapshot_kernel<float>, cov_snapshot_kernel<double>, args->state_f64 == 1, gx, (unsigned)cv->temps /* <= 256 */,
+                         kCovThreads, (size_t)g.lds_bytes, stream, a);
 }
 
 // the adaptation checks shared by ptrwm_run_with_adaptation, ptrwm_adapt_reduce and ptrwm_adapt_update (none: ok); what
@@ -1717,10 +1669,42 @@ static bool tuning_fits_run(const Tuning *tu, const ptrwm_run_args *args, const 
          (tu->defer_update == 0 || request_within_window({tu->every, tu->until}, args->step0, args->n_steps));
 }
 
+// The optional blocks of a run (NULL / no moments: off), in the order the ptrwm_run_with_* entry points grew them
+struct RunBlocks {
+  MomSpec spec;
+  const ptrwm_flow_args *flow = nullptr;
+  const ptrwm_hist_args *hist = nullptr;
+  const ptrwm_adapt_args *adapt = nullptr;
+  const ptrwm_ladder_args *ladder = nullptr;
+  const ptrwm_acf_args *acf = nullptr;
+  const ptrwm_cov_args *cov = nullptr;
+};
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist = nullptr,
-                        const ptrwm_adapt_args *adapt = nullptr, const ptrwm_ladder_args *ladder = nullptr,
-                        const ptrwm_acf_args *acf = nullptr, const ptrwm_cov_args *cov = nullptr);
+                        const RunBlocks &blocks, void *hip_stream);
+// ... as the entry points that take both kinds of moments hand them over: one accumulator, pooled or per chain
+static int32_t run_with_blocks(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                               const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments, RunBlocks blocks,
+                               void *stream) {
+  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;
+  blocks.spec = chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments);
+  return run_impl(target, proposal, args, blocks, stream);
+}
+// ptrwm_histogram, ptrwm_autocorr, ptrwm_covariance: one snapshot of `state` if the step just performed is due (Check: the
+// block's check_*, Launch: its launch_*)
+template <auto Check, auto Launch, class Block>
+static int32_t snapshot_call(const ptrwm_run_args *args, int32_t dim, const Block *block, void *stream) {
+  if (args == nullptr || block == nullptr) return PTRWM_E_NULL;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
+  if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
+  if (!is_flag(args->state_f64) || args->n_chains < 0 || args->step0 < 0 || args->burn_in < 0) return PTRWM_E_ARG;
+  if (int rc = Check(args, block)) return rc;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->state == nullptr) return PTRWM_E_NULL;
+  if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, block->every))
+    return PTRWM_OK;  // (known on the host: no snapshot is due)
+  return Launch(args, dim, block, args->step0, (const long long *)args->device_step, (hipStream_t)stream);
+}
 static int32_t swap_sweep_impl(const ptrwm_run_args *args, int32_t dim, int64_t event_index, int32_t rng_stream,
                                const ptrwm_flow_args *flow, void *stream);
 static int32_t split_accept_impl(const ptrwm_run_args *args, int32_t dim, float *proposals, const float *accept_u,
@@ -1825,39 +1809,36 @@ int32_t ptrwm_has_variant(int32_t target_kind, int32_t proposal_kind, int32_t di
 
 int32_t ptrwm_run(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                   void *hip_stream) {
-  return run_impl(target, proposal, args, MomSpec(), nullptr, hip_stream);
+  return run_impl(target, proposal, args, RunBlocks{}, hip_stream);
 }
 
 int32_t ptrwm_run_with_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
                                const ptrwm_run_args *args, const ptrwm_moments_args *moments, void *stream) {
-  return run_impl(target, proposal, args, moments, nullptr, stream);
+  return run_impl(target, proposal, args, RunBlocks{moments}, stream);
 }
 
 int32_t ptrwm_run_with_chain_moments(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
                                      const ptrwm_run_args *args, const ptrwm_chain_moments_args *chain_moments, void *stream) {
-  return run_impl(target, proposal, args, chain_moments, nullptr, stream);
+  return run_impl(target, proposal, args, RunBlocks{chain_moments}, stream);
 }
 
 int32_t ptrwm_run_with_diagnostics(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                                    const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
                                    const ptrwm_flow_args *flow, void *stream) {
-  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // one accumulator, pooled or per chain
-  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream);
+  return run_with_blocks(target, proposal, args, moments, chain_moments, {{}, flow}, stream);
 }
 
 int32_t ptrwm_run_with_histogram(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                                  const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
                                  const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, void *stream) {
-  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // (as ptrwm_run_with_diagnostics)
-  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist);
+  return run_with_blocks(target, proposal, args, moments, chain_moments, {{}, flow, hist}, stream);
 }
 
 int32_t ptrwm_run_with_adaptation(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                                   const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
                                   const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt,
                                   void *stream) {
-  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // (as ptrwm_run_with_diagnostics)
-  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist, adapt);
+  return run_with_blocks(target, proposal, args, moments, chain_moments, {{}, flow, hist, adapt}, stream);
 }
 
 int32_t ptrwm_adapt_reduce(const ptrwm_run_args *args, const ptrwm_adapt_args *adapt, void *stream) {
@@ -1875,24 +1856,21 @@ int32_t ptrwm_run_with_ladder(const ptrwm_target_desc *target, const ptrwm_propo
                               const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
                               const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt,
                               const ptrwm_ladder_args *ladder, void *stream) {
-  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // (as ptrwm_run_with_diagnostics)
-  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist, adapt, ladder);
+  return run_with_blocks(target, proposal, args, moments, chain_moments, {{}, flow, hist, adapt, ladder}, stream);
 }
 
 int32_t ptrwm_run_with_autocorr(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                                 const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
                                 const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt,
                                 const ptrwm_ladder_args *ladder, const ptrwm_acf_args *acf, void *stream) {
-  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // (as ptrwm_run_with_diagnostics)
-  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist, adapt, ladder, acf);
+  return run_with_blocks(target, proposal, args, moments, chain_moments, {{}, flow, hist, adapt, ladder, acf}, stream);
 }
 
 int32_t ptrwm_run_with_covariance(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                                   const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
                                   const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt,
                                   const ptrwm_ladder_args *ladder, const ptrwm_acf_args *acf, const ptrwm_cov_args *cov, void *stream) {
-  if (moments != nullptr && chain_moments != nullptr) return PTRWM_E_ARG;  // (as ptrwm_run_with_diagnostics)
-  return run_impl(target, proposal, args, chain_moments != nullptr ? MomSpec(chain_moments) : MomSpec(moments), flow, stream, hist, adapt, ladder, acf, cov);
+  return run_with_blocks(target, proposal, args, moments, chain_moments, {{}, flow, hist, adapt, ladder, acf, cov}, stream);
 }
 
 int32_t ptrwm_ladder_probe(const ptrwm_run_args *args, const ptrwm_ladder_args *ladder, void *stream) {
@@ -1910,45 +1888,15 @@ int32_t ptrwm_ladder_update(const ptrwm_ladder_args *ladder, int32_t n_temps, in
 }
 
 int32_t ptrwm_histogram(const ptrwm_run_args *args, int32_t dim, const ptrwm_hist_args *hist, void *stream) {
-  if (args == nullptr || hist == nullptr) return PTRWM_E_NULL;
-  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
-  if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
-  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
-  if (!is_flag(args->state_f64) || args->n_chains < 0 || args->step0 < 0 || args->burn_in < 0) return PTRWM_E_ARG;
-  if (int rc = check_hist(args, hist)) return rc;
-  if (args->n_chains == 0) return PTRWM_OK;
-  if (args->state == nullptr) return PTRWM_E_NULL;
-  if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, hist->every))
-    return PTRWM_OK;  // (known on the host: no snapshot is due)
-  return launch_hist(args, dim, hist, args->step0, (const long long *)args->device_step, (hipStream_t)stream);
+  return snapshot_call<check_hist, launch_hist>(args, dim, hist, stream);
 }
 
 int32_t ptrwm_autocorr(const ptrwm_run_args *args, int32_t dim, const ptrwm_acf_args *acf, void *stream) {
-  if (args == nullptr || acf == nullptr) return PTRWM_E_NULL;
-  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
-  if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
-  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
-  if (!is_flag(args->state_f64) || args->n_chains < 0 || args->step0 < 0 || args->burn_in < 0) return PTRWM_E_ARG;
-  if (int rc = check_acf(args, acf)) return rc;
-  if (args->n_chains == 0) return PTRWM_OK;
-  if (args->state == nullptr) return PTRWM_E_NULL;
-  if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, acf->every))
-    return PTRWM_OK;  // (known on the host: no snapshot is due)
-  return launch_acf(args, dim, acf, args->step0, (const long long *)args->device_step, (hipStream_t)stream);
+  return snapshot_call<check_acf, launch_acf>(args, dim, acf, stream);
 }
 
 int32_t ptrwm_covariance(const ptrwm_run_args *args, int32_t dim, const ptrwm_cov_args *cov, void *stream) {
-  if (args == nullptr || cov == nullptr) return PTRWM_E_NULL;
-  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
-  if (dim < 1 || dim > PTRWM_MAX_DIM) return PTRWM_E_DIM;
-  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
-  if (!is_flag(args->state_f64) || args->n_chains < 0 || args->step0 < 0 || args->burn_in < 0) return PTRWM_E_ARG;
-  if (int rc = check_cov(args, cov)) return rc;
-  if (args->n_chains == 0) return PTRWM_OK;
-  if (args->state == nullptr) return PTRWM_E_NULL;
-  if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, cov->every))
-    return PTRWM_OK;  // (known on the host: no snapshot is due)
-  return launch_cov(args, dim, cov, args->step0, (const long long *)args->device_step, (hipStream_t)stream);
+  return snapshot_call<check_cov, launch_cov>(args, dim, cov, stream);
 }
 
 }  // extern "C"
@@ -2149,9 +2097,8 @@ static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_de
 }
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
-                        const MomSpec &spec, const ptrwm_flow_args *flow, void *hip_stream, const ptrwm_hist_args *hist,
-                        const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder, const ptrwm_acf_args *acf,
-                        const ptrwm_cov_args *cov) {
+                        const RunBlocks &blocks, void *hip_stream) {
+  const auto &[spec, flow, hist, adapt, ladder, acf, cov] = blocks;
   bool empty = false;
   if (int rc = check_run(target, proposal, args, spec, flow, hist, &empty)) return rc;
   // the two tunings (adapt.h, ladder.h): their own checks after the existing ones, all before anything is enqueued
@@ -2187,17 +2134,15 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   const long long trace_row = args->trace != nullptr ? args->trace_chains * (long long)args->trace_temps : 0;
   const auto countdown = [](int steps) { return (unsigned)(steps < kNoStepInLaunch ? steps : kNoStepInLaunch); };  // (a launch: <= 2^16 steps)
   for (long long done = 0; done < args->n_steps; done += k.n_steps) {
-    // (histograms: a launch also ends at every due snapshot step - the snapshot kernel reads the state between launches)
-    long long to_snap = hist != nullptr ? steps_to_next_due(args->step0 + done, args->burn_in, hist->every) : cap;
-    // (the autocovariance: likewise, at its own period)
-    if (acf != nullptr) to_snap = std::min(to_snap, steps_to_next_due(args->step0 + done, args->burn_in, acf->every));
-    if (cov != nullptr) to_snap = std::min(to_snap, steps_to_next_due(args->step0 + done, args->burn_in, cov->every));
+    // (a launch also ends at the nearest due step of a snapshot block, each at its own period: snapshot.h)
+    const long long s0 = args->step0 + done, b0 = args->burn_in;
+    const long long to_snap = std::min({steps_to_snapshot(hist, s0, b0, cap), steps_to_snapshot(acf, s0, b0, cap), steps_to_snapshot(cov, s0, b0, cap)});
     // (the tunings, schedule.h warmup_launch_at: a launch inside an adapting window of the scale ends with the window at the
     // latest - the reduce and update kernels run between two launches - and is the production kernel told to count from its
     // first step, into the window scratch, and that no multiple of swap_every lies in it: count_on holds and swap_due never
     // does, kernel.h.  One that starts in an adapting window of the ladder ends behind the next probe step at the latest - the
     // probe kernel reads logp between two launches - and is otherwise told nothing: an ordinary burn-in launch)
-    const WarmupLaunch wl = warmup_launch_at(args->step0 + done, launch_steps(req, done, to_snap < cap ? to_snap : cap), scale_w,
+    const WarmupLaunch wl = warmup_launch_at(args->step0 + done, launch_steps(req, done, to_snap), scale_w,
                                              adapt != nullptr && adapt->defer_update == 1, ladder_w,
                                              ladder != nullptr ? ladder->probe_every : 1, ladder != nullptr && ladder->defer_update == 1);
     const LaunchCut cut = launch_at(req, done, wl.n);
@@ -2221,12 +2166,11 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
       k.full.steps_to_mom = countdown(cut.steps_to_mom);
     }
     if (c.fn(k, c.n_blocks, c.mode, (hipStream_t)hip_stream) != hipSuccess) return PTRWM_E_LAUNCH;
-    if (hist != nullptr && periodic_step_due(cut.step0 + cut.n, args->burn_in, hist->every))
-      if (int rc = launch_hist(args, target->dim, hist, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
-    if (acf != nullptr && periodic_step_due(cut.step0 + cut.n, args->burn_in, acf->every))
-      if (int rc = launch_acf(args, target->dim, acf, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
-    if (cov != nullptr && periodic_step_due(cut.step0 + cut.n, args->burn_in, cov->every))
-      if (int rc = launch_cov(args, target->dim, cov, cut.step0 + cut.n - 1, nullptr, (hipStream_t)hip_stream)) return rc;
+    // (whatever snapshot is due behind this cut: histogram, autocovariance, covariance, in front of the tunings' kernels)
+    const long long sc = cut.step0 + cut.n;
+    if (int rc = snapshot_if_due<launch_hist>(hist, args, target->dim, sc, (hipStream_t)hip_stream)) return rc;
+    if (int rc = snapshot_if_due<launch_acf>(acf, args, target->dim, sc, (hipStream_t)hip_stream)) return rc;
+    if (int rc = snapshot_if_due<launch_cov>(cov, args, target->dim, sc, (hipStream_t)hip_stream)) return rc;
     if (wl.scale_reduce)
       if (int rc = launch_adapt_reduce(adapt, args->n_chains, args->n_temps, (hipStream_t)hip_stream)) return rc;
     if (wl.scale_update)

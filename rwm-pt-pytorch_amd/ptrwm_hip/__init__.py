@@ -762,6 +762,10 @@ class RunPlan:
     _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
                      "chain": ("chain moments", ChainMomentsArgs, "ptrwm_run_with_chain_moments", "ptrwm_split_chain_moments")}
 
+    # launch(): the first entry point that takes _flow, _hist, _adapt, _ladder, _acf, _cov - in this order - and all before it
+    _RUN_WITH = ("ptrwm_run_with_diagnostics", "ptrwm_run_with_histogram", "ptrwm_run_with_adaptation", "ptrwm_run_with_ladder",
+                 "ptrwm_run_with_autocorr", "ptrwm_run_with_covariance")
+
     def _bind_moments(self, kind, lead, sum, sum_sq, sum_logp, count, every) -> None:
         """The one accumulator of the plan: ``sum`` / ``sum_sq`` are [*lead, temps, dim], ``sum_logp`` [*lead, temps],
         ``count`` [temps].  ``sum`` None switches an accumulator of this kind off; anything else replaces what was set."""
@@ -842,6 +846,36 @@ class RunPlan:
         f.n_down = _opt(n_down, "flow n_down", torch.int64)
         self._flow = (f, C.byref(f), (walker, round_trips, n_up, n_down))
 
+    def _bind_block(self, what: str, struct, scalars: dict, pointers) -> tuple:
+        """(struct, byref, tensors) of a snapshot block (`what` starts its messages): every tensor of `pointers` - (field,
+        tensor or None, dtype), shapes already checked - sits on the plan's device and is marshalled into its field."""
+        for name, t, _ in pointers:
+            if t is not None and t.device != self.device:
+                raise ValueError(f"{what} {name} is on {t.device}, state on {self.device}")
+        b = struct()
+        b.struct_size = C.sizeof(struct)
+        for name, v in scalars.items():
+            setattr(b, name, v)
+        for name, t, dtype in pointers:
+            setattr(b, name, _opt(t, f"{what} {name}", dtype))
+        return (b, C.byref(b), tuple(t for _, t, _ in pointers))
+
+    def _split_call(self, name: str, block, step: int) -> None:
+        """A stand-alone accumulator call behind the split step ``step``: ``name``(args, dim, block, stream)"""
+        self._a.step0 = step
+        with self._guard:
+            rc = getattr(self._lib, name)(self._refs[4], self.shape[2], block, _stream(self.device))
+        if rc != 0:
+            raise PTRWMError(rc, name)
+
+    def split_snapshots(self, step: int) -> None:
+        """Every accumulator bound, behind the split step ``step`` just performed: moments, histogram, autocovariance,
+        covariance, in this order (the library skips the steps that are not due)."""
+        self.split_moments(step)
+        self.split_histogram(step)
+        self.split_autocorr(step)
+        self.split_covariance(step)
+
     def set_histogram(self, counts: Optional[torch.Tensor], lo: Optional[torch.Tensor] = None,
                       scale: Optional[torch.Tensor] = None, *, n_bins: int = 0, temps: int = 0, every: int = 1,
                       count: Optional[torch.Tensor] = None) -> None:
@@ -868,17 +902,9 @@ class RunPlan:
         for name, t in (("lo", lo), ("scale", scale)):
             if t is None or tuple(t.shape) != (D,):
                 raise ValueError(f"histogram {name} must be a [{D}] float32 tensor")
-        for name, t in (("counts", counts), ("lo", lo), ("scale", scale), ("count", count)):
-            if t is not None and t.device != self.device:
-                raise ValueError(f"histogram {name} is on {t.device}, state on {self.device}")
-        h = HistArgs()
-        h.struct_size = C.sizeof(HistArgs)
-        h.temps, h.every, h.n_bins = temps, every, n_bins
-        h.lo = _require_device(lo, "histogram lo", torch.float32)
-        h.scale = _require_device(scale, "histogram scale", torch.float32)
-        h.counts = _require_device(counts, "histogram counts", torch.int64)
-        h.count = _opt(count, "histogram count", torch.int64)
-        self._hist = (h, C.byref(h), (counts, lo, scale, count))
+        self._hist = self._bind_block("histogram", HistArgs, dict(temps=temps, every=every, n_bins=n_bins),
+                                      (("counts", counts, torch.int64), ("lo", lo, torch.float32), ("scale", scale, torch.float32),
+                                       ("count", count, torch.int64)))
 
     def set_autocorr(self, ring: Optional[torch.Tensor], sxy: Optional[torch.Tensor] = None, head: Optional[torch.Tensor] = None,
                      tail: Optional[torch.Tensor] = None, pairs: Optional[torch.Tensor] = None, *, every: int = 1) -> None:
@@ -906,31 +932,17 @@ class RunPlan:
                 raise ValueError(f"autocorr {name} must be [{temps}, {max_lag + 1}, {D}]")
         if pairs is None or tuple(pairs.shape) != (max_lag + 1,):
             raise ValueError(f"autocorr pairs must be [{max_lag + 1}]")
-        for name, t in (("ring", ring), ("sxy", sxy), ("head", head), ("tail", tail), ("pairs", pairs)):
-            if t.device != self.device:
-                raise ValueError(f"autocorr {name} is on {t.device}, state on {self.device}")
-        ac = AcfArgs()
-        ac.struct_size = C.sizeof(AcfArgs)
-        ac.temps, ac.every, ac.max_lag = temps, every, max_lag
-        ac.ring = _require_device(ring, "autocorr ring", self.state_dtype)
-        ac.sxy = _require_device(sxy, "autocorr sxy", torch.float64)
-        ac.head = _require_device(head, "autocorr head", torch.float64)
-        ac.tail = _require_device(tail, "autocorr tail", torch.float64)
-        ac.pairs = _require_device(pairs, "autocorr pairs", torch.int64)
-        self._acf = (ac, C.byref(ac), (ring, sxy, head, tail, pairs))
+        self._acf = self._bind_block("autocorr", AcfArgs, dict(temps=temps, every=every, max_lag=max_lag),
+                                     (("ring", ring, self.state_dtype), ("sxy", sxy, torch.float64), ("head", head, torch.float64),
+                                      ("tail", tail, torch.float64), ("pairs", pairs, torch.int64)))
 
     def split_autocorr(self, step: int) -> None:
         """Autocovariance snapshot of the state after the split step ``step`` just performed (ptrwm_autocorr; device-step mode:
         counter + step - decided on the device, so the call can sit in a captured block).  Enqueue after ``split_accept``
         (and ``split_histogram``), behind EVERY step: the library skips the steps that are not due.  No-op without an
         accumulator."""
-        if self._acf is None:
-            return
-        self._a.step0 = step
-        with self._guard:
-            rc = self._lib.ptrwm_autocorr(self._refs[4], self.shape[2], self._acf[1], _stream(self.device))
-        if rc != 0:
-            raise PTRWMError(rc, "ptrwm_autocorr")
+        if self._acf is not None:
+            self._split_call("ptrwm_autocorr", self._acf[1], step)
 
     def set_covariance(self, sxx: Optional[torch.Tensor], sx: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
                        *, every: int = 1) -> None:
@@ -954,29 +966,16 @@ class RunPlan:
             raise ValueError(f"covariance sx must be [{temps}, {D}]")
         if count is None or tuple(count.shape) != (1,):
             raise ValueError("covariance count must be [1]")
-        for name, t in (("sxx", sxx), ("sx", sx), ("count", count)):
-            if t.device != self.device:
-                raise ValueError(f"covariance {name} is on {t.device}, state on {self.device}")
-        cv = CovArgs()
-        cv.struct_size = C.sizeof(CovArgs)
-        cv.temps, cv.every = temps, every
-        cv.sxx = _require_device(sxx, "covariance sxx", torch.float64)
-        cv.sx = _require_device(sx, "covariance sx", torch.float64)
-        cv.count = _require_device(count, "covariance count", torch.int64)
-        self._cov = (cv, C.byref(cv), (sxx, sx, count))
+        self._cov = self._bind_block("covariance", CovArgs, dict(temps=temps, every=every),
+                                     (("sxx", sxx, torch.float64), ("sx", sx, torch.float64), ("count", count, torch.int64)))
 
     def split_covariance(self, step: int) -> None:
         """Covariance snapshot of the state after the split step ``step`` just performed (ptrwm_covariance; device-step mode:
         counter + step - decided on the device, so the call can sit in a captured block).  Enqueue after ``split_accept``
         (and ``split_histogram`` / ``split_autocorr``), behind every step: the library skips the steps that are not due.
         No-op without an accumulator."""
-        if self._cov is None:
-            return
-        self._a.step0 = step
-        with self._guard:
-            rc = self._lib.ptrwm_covariance(self._refs[4], self.shape[2], self._cov[1], _stream(self.device))
-        if rc != 0:
-            raise PTRWMError(rc, "ptrwm_covariance")
+        if self._cov is not None:
+            self._split_call("ptrwm_covariance", self._cov[1], step)
 
     def _tuning_windows(self, what: str, every, until) -> tuple:
         """every, until and K = until // every of a warm-up tuning (`what` starts its messages), checked against the plan"""
@@ -1115,13 +1114,8 @@ class RunPlan:
         """Histogram snapshot of the state after the split step ``step`` just performed (ptrwm_histogram; device-step mode:
         counter + step - decided on the device, so the call can sit in a captured block).  Enqueue after ``split_accept``.
         No-op without a histogram."""
-        if self._hist is None:
-            return
-        self._a.step0 = step
-        with self._guard:
-            rc = self._lib.ptrwm_histogram(self._refs[4], self.shape[2], self._hist[1], _stream(self.device))
-        if rc != 0:
-            raise PTRWMError(rc, "ptrwm_histogram")
+        if self._hist is not None:
+            self._split_call("ptrwm_histogram", self._hist[1], step)
 
     def init_states(self, lo: torch.Tensor, hi: torch.Tensor, *, attempt: int = 0, per_temperature: bool = False,
                     fallback: Optional[torch.Tensor] = None) -> None:
@@ -1150,14 +1144,8 @@ class RunPlan:
         """Moments of the split step ``step`` just performed, pooled or per chain as set (ptrwm_split_moments /
         ptrwm_split_chain_moments; device-step mode: counter + step).  Enqueue after ``split_accept``.  No-op without an
         accumulator."""
-        if self._mom is None:
-            return
-        name = self._MOMENT_KINDS[self._mom[0]][3]
-        self._a.step0 = step
-        with self._guard:
-            rc = getattr(self._lib, name)(self._refs[4], self.shape[2], self._mom[2], _stream(self.device))
-        if rc != 0:
-            raise PTRWMError(rc, name)
+        if self._mom is not None:
+            self._split_call(self._MOMENT_KINDS[self._mom[0]][3], self._mom[2], step)
 
     def launch(
         self,
@@ -1228,11 +1216,11 @@ class RunPlan:
         # first of ptrwm_run_with_diagnostics / _histogram / _adaptation / _ladder / _autocorr / _covariance that takes all that is bound: each
         # takes what the one before it takes and one struct more, behind the two accumulators (pooled, per chain)
         name, opt = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
-        if any(b is not None for b in (self._flow, self._hist, self._adapt, self._ladder, self._acf, self._cov)):
-            more = [b[1] if b is not None else None for b in (self._flow, self._hist, self._adapt, self._ladder, self._acf, self._cov)]
+        blocks = (self._flow, self._hist, self._adapt, self._ladder, self._acf, self._cov)
+        if any(b is not None for b in blocks):
+            more = [b[1] if b is not None else None for b in blocks]
             last = max(i for i, b in enumerate(more) if b is not None)
-            name = ("ptrwm_run_with_diagnostics", "ptrwm_run_with_histogram", "ptrwm_run_with_adaptation", "ptrwm_run_with_ladder",
-                    "ptrwm_run_with_autocorr", "ptrwm_run_with_covariance")[last]
+            name = self._RUN_WITH[last]
             kind, mom = (self._mom[0], self._mom[2]) if self._mom is not None else (None, None)
             opt = (mom if kind == "pooled" else None, mom if kind == "chain" else None, *more[:last + 1])
         with self._guard:
@@ -1381,14 +1369,11 @@ class RunPlan:
             raise RuntimeError("precond_probe: no update bound (set_precond_update)")
         a = self._a
         burn_in, dstep = a.burn_in, a.device_step
-        a.step0, a.burn_in, a.device_step = step, 0, None
+        a.burn_in, a.device_step = 0, None
         try:
-            with self._guard:
-                rc = self._lib.ptrwm_covariance(self._refs[4], self.shape[2], bound[4], _stream(self.device))
+            self._split_call("ptrwm_covariance", bound[4], step)
         finally:
             a.burn_in, a.device_step = burn_in, dstep
-        if rc != 0:
-            raise PTRWMError(rc, "ptrwm_covariance")
 
     def precond_update(self, window: int) -> None:
         """The factor's update of window ``window`` from the bound sums (ptrwm_precond_update): the bound ``chol`` is rewritten
