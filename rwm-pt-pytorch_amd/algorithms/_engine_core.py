@@ -32,7 +32,7 @@ csrc/hist.h - are the plan's):
     counts       int64   [hist_temps, dim, hist_bins + 2]   bin 0 underflow (and NaN), bin hist_bins + 1 overflow
     count        int64   [hist_temps]                       (replica, step) pairs added per temperature
 
-and, with adapt_scale=True, the arrays of the warm-up tuning of the proposal scale (`_adapt`, a ScaleTuning; include/ptrwm.h
+and, with adapt_scale=True, the arrays of the warm-up tuning of the proposal scale (`_adapt`, a WarmupTuning; include/ptrwm.h
 ptrwm_adapt_args), used by two small kernels between launches at the end of every adaptation window of burn-in:
 
     window_accept  int64   [n_replicas, n_temps]      acceptances of the current window (scratch, zero between windows)
@@ -189,29 +189,42 @@ def _number(name, v) -> float:
     return float(v)
 
 
-def check_warmup_args(flag: str, name: str, burn_in: int, every, until, gain, decay, adapt_sync, pooled: str, idle: str, own) -> dict:
-    """What the arguments of the two warm-up tunings share (`flag` switches the tuning on, `name` prefixes its keywords): an
-    integer period, `until` in 0..burn_in (default: burn_in), a finite gain > 0, a decay in 0..1, adapt_sync None or a callable
-    (applied to the `pooled` tensor), windows = until // every, and a warning when that is none (the tuning is `idle`).
-    `own(every)` checks the tuning's other arguments once the period stands and returns their entries of the dict."""
+def check_warmup_args(flag: str, name: str, burn_in: int, every, until, adapt_sync, synced: str, idle: str, own) -> dict:
+    """What the arguments of the three warm-up tunings share (`flag` switches the tuning on, `name` prefixes its keywords): an
+    integer period, `until` in 0..burn_in (default: burn_in), adapt_sync None or a callable (applied to `synced`), windows =
+    until // every, and a warning when that is none (the tuning is `idle`).  `own(every)` checks the tuning's other arguments
+    once the period stands - they are reported after `until` and before adapt_sync - and returns their entries of the dict."""
     every = _integer(f"{name}_every", every, 1)
     if until is None:
         until = burn_in
     if isinstance(until, bool) or not isinstance(until, (int, np.integer)) or not 0 <= until <= burn_in:
         raise ValueError(f"{name}_until must be an integer in 0..burn_in = {burn_in}, got {until!r}")
     rest = own(every)
+    if adapt_sync is not None and not callable(adapt_sync):
+        raise ValueError(f"adapt_sync must be None or a callable applied to the {synced}")
+    windows = int(until) // every
+    if windows == 0:
+        warnings.warn(f"{flag}=True but no window of {name}_every = {every} steps ends within the first "
+                      f"{until} burn-in steps: {idle}")
+    return {"every": every, "until": int(until), "sync": adapt_sync, "windows": windows, **rest}
+
+
+def _gain_decay(name: str, gain, decay) -> dict:
+    """... of the scale's and the ladder's tuning: a finite gain > 0, a decay in 0..1"""
     g, d = _number(f"{name}_gain", gain), _number(f"{name}_decay", decay)
     if not g > 0.0:
         raise ValueError(f"{name}_gain must be positive, got {gain!r}")
     if not 0.0 <= d <= 1.0:
         raise ValueError(f"{name}_decay must lie in 0..1, got {decay!r}")
-    if adapt_sync is not None and not callable(adapt_sync):
-        raise ValueError(f"adapt_sync must be None or a callable applied to the {pooled}")
-    windows = int(until) // every
-    if windows == 0:
-        warnings.warn(f"{flag}=True but no window of {name}_every = {every} steps ends within the first "
-                      f"{until} burn-in steps: {idle}")
-    return {"every": every, "until": int(until), "gain": g, "decay": d, "sync": adapt_sync, "windows": windows, **rest}
+    return {"gain": g, "decay": d}
+
+
+def _probe_every(name: str, every: int, probe_every) -> dict:
+    """... of the ladder's and the factor's tuning: the probe period, an integer >= 1 that divides the window (default: the window)"""
+    probe = every if probe_every is None else _integer(f"{name}_probe_every", probe_every, 1)
+    if every % probe != 0:
+        raise ValueError(f"{name}_probe_every must divide {name}_every = {every}, got {probe_every!r}")
+    return {"probe_every": probe}
 
 
 def check_adapt_args(adapt_scale, burn_in: int, adapt_every=50, adapt_until=None, adapt_target=0.234, adapt_gain=3.0,
@@ -235,9 +248,9 @@ def check_adapt_args(adapt_scale, burn_in: int, adapt_every=50, adapt_until=None
         lo, hi = _number("adapt_scale_bounds lo", lo), _number("adapt_scale_bounds hi", hi)
         if not 0.0 < lo <= hi:
             raise ValueError(f"adapt_scale_bounds must satisfy 0 < lo <= hi, got {adapt_scale_bounds!r}")
-        return {"target": target, "bounds": (lo, hi)}
+        return {"target": target, "bounds": (lo, hi), **_gain_decay("adapt", adapt_gain, adapt_decay)}
 
-    return check_warmup_args("adapt_scale", "adapt", int(burn_in), adapt_every, adapt_until, adapt_gain, adapt_decay, adapt_sync,
+    return check_warmup_args("adapt_scale", "adapt", int(burn_in), adapt_every, adapt_until, adapt_sync,
                              "pooled [n_temps + 1] int64 tensor", "nothing will adapt", own)
 
 
@@ -253,18 +266,16 @@ def check_ladder_args(adapt_ladder, burn_in: int, beta_ladder=None, ladder_every
         return None
 
     def own(every):
-        probe_every = every if ladder_probe_every is None else _integer("ladder_probe_every", ladder_probe_every, 1)
-        if every % probe_every != 0:
-            raise ValueError(f"ladder_probe_every must divide ladder_every = {every}, got {ladder_probe_every!r}")
+        probe = _probe_every("ladder", every, ladder_probe_every)
         if beta_ladder is not None:
             b = np.asarray(list(beta_ladder), np.float32)
             if b.size < 3:
                 raise ValueError(f"adapt_ladder=True moves the interior temperatures: beta_ladder needs at least 3, got {b.size}")
             if not (b > 0).all() or not (b[:-1] > b[1:]).all():
                 raise ValueError("adapt_ladder=True needs a beta_ladder that is positive and strictly decreasing in float32")
-        return {"probe_every": probe_every}
+        return {**probe, **_gain_decay("ladder", ladder_gain, ladder_decay)}
 
-    return check_warmup_args("adapt_ladder", "ladder", int(burn_in), ladder_every, ladder_until, ladder_gain, ladder_decay, adapt_sync,
+    return check_warmup_args("adapt_ladder", "ladder", int(burn_in), ladder_every, ladder_until, adapt_sync,
                              "pooled int64 tensor", "the ladder will not move", own)
 
 
@@ -316,29 +327,21 @@ def check_cov_adapt_args(adapt_cov, burn_in: int, dim: int, cov_adapt_every=200,
         raise ValueError(f"adapt_cov must be True or False, got {adapt_cov!r}")
     if not adapt_cov:
         return None
-    every = _integer("cov_adapt_every", cov_adapt_every, 1)
-    until = burn_in if cov_adapt_until is None else cov_adapt_until
-    if isinstance(until, bool) or not isinstance(until, (int, np.integer)) or not 0 <= until <= burn_in:
-        raise ValueError(f"cov_adapt_until must be an integer in 0..burn_in = {burn_in}, got {until!r}")
-    probe_every = every if cov_adapt_probe_every is None else _integer("cov_adapt_probe_every", cov_adapt_probe_every, 1)
-    if every % probe_every != 0:
-        raise ValueError(f"cov_adapt_probe_every must divide cov_adapt_every = {every}, got {cov_adapt_probe_every!r}")
-    memory, jitter = _number("cov_adapt_memory", cov_adapt_memory), _number("cov_adapt_jitter", cov_adapt_jitter)
-    if not 0.0 < memory <= 1.0:
-        raise ValueError(f"cov_adapt_memory must lie in (0, 1], got {cov_adapt_memory!r}")
-    if jitter < 0.0:
-        raise ValueError(f"cov_adapt_jitter must be >= 0, got {cov_adapt_jitter!r}")
-    min_count = float(4 * dim) if cov_adapt_min_count is None else _number("cov_adapt_min_count", cov_adapt_min_count)
-    if not min_count >= 1.0:
-        raise ValueError(f"cov_adapt_min_count must be >= 1, got {cov_adapt_min_count!r}")
-    if adapt_sync is not None and not callable(adapt_sync):
-        raise ValueError("adapt_sync must be None or a callable applied to the window's covariance sums")
-    windows = int(until) // every
-    if windows == 0:
-        warnings.warn(f"adapt_cov=True but no window of cov_adapt_every = {every} steps ends within the first "
-                      f"{until} burn-in steps: the proposal factor will not move")
-    return {"every": every, "until": int(until), "probe_every": probe_every, "memory": memory, "jitter": jitter,
-            "min_count": min_count, "sync": adapt_sync, "windows": windows}
+
+    def own(every):
+        probe = _probe_every("cov_adapt", every, cov_adapt_probe_every)
+        memory, jitter = _number("cov_adapt_memory", cov_adapt_memory), _number("cov_adapt_jitter", cov_adapt_jitter)
+        if not 0.0 < memory <= 1.0:
+            raise ValueError(f"cov_adapt_memory must lie in (0, 1], got {cov_adapt_memory!r}")
+        if jitter < 0.0:
+            raise ValueError(f"cov_adapt_jitter must be >= 0, got {cov_adapt_jitter!r}")
+        min_count = float(4 * dim) if cov_adapt_min_count is None else _number("cov_adapt_min_count", cov_adapt_min_count)
+        if not min_count >= 1.0:
+            raise ValueError(f"cov_adapt_min_count must be >= 1, got {cov_adapt_min_count!r}")
+        return {**probe, "memory": memory, "jitter": jitter, "min_count": min_count}
+
+    return check_warmup_args("adapt_cov", "cov_adapt", burn_in, cov_adapt_every, cov_adapt_until, adapt_sync,
+                             "window's covariance sums", "the proposal factor will not move", own)
 
 
 def check_init_attempts(init_attempts) -> int:
@@ -368,44 +371,33 @@ def check_class_starts(dim: int, n_replicas: int, n_temps: int, initial_states, 
 
 
 class WarmupTuning:
-    """One warm-up tuning of a run - the ladder's as it stands, the proposal scale's as ScaleTuning: windows of `every` steps that
-    end at or before `until`, the last of them at step `end`; `pooled`, the current window's counts on the device; `sync`, the
-    caller's all-reduce of them (None: the library updates by itself); the tuning's other arrays as attributes."""
+    """One warm-up tuning of a run, as the host loop sees it: windows of `every` steps that end at or before
+    `until`, the last of them at step `end`.  Split steps stop every `cut_every` steps of an adapting window - the window for the
+    scale, the probe period for the ladder and the factor - and call `probe(step)` there where the tuning has one; every window
+    ends with window_end.  `sync` is the caller's all-reduce (None: the library updates by itself), applied to each tensor of
+    `synced`, the window's counts on the device; `reduce` (None: the launch has done it) sums per-replica scratch into them,
+    `update(window)` is the plan's stand-alone update kernel, `after_sync(tuning, window)` what only this tuning records of the
+    synced counts.  `warm_steps`: the split steps inside its windows follow the warm-up recipe (RunPlan.split_warmup).  The tuning's
+    arrays are attributes."""
 
-    def __init__(self, args: dict, pooled: torch.Tensor, update, **arrays):
+    def __init__(self, args: dict, update, synced: tuple, *, cut_every: Optional[int] = None, probe=None, reduce=None,
+                 after_sync=None, warm_steps: bool = False, **arrays):
         self.every, self.until, self.end, self.sync = args["every"], args["until"], args["windows"] * args["every"], args["sync"]
-        self.pooled, self.update = pooled, update  # (update: the plan's stand-alone update kernel of one window)
+        self.cut_every = self.every if cut_every is None else cut_every
+        self.probe, self.reduce, self.update, self.synced, self.after_sync = probe, reduce, update, synced, after_sync
+        self.warm_steps = warm_steps
         self.__dict__.update(arrays)
 
     def window_end(self, window: int) -> None:
         """What follows the last step of adapting window `window` where the library does not do it itself (split steps; with
-        adapt_sync): the caller's all-reduce of `pooled`, the update kernel."""
-        if self.sync is not None:
-            self.sync(self.pooled)
-        self.update(window)
-
-
-class ScaleTuning(WarmupTuning):
-    """... of the proposal scale.  `reduce`: the plan's stand-alone kernel that sums the window's per-replica counts into `pooled`
-    (split steps; None where launch() has done it)."""
-
-    def window_end(self, window: int) -> None:
+        adapt_sync): the reduction, the caller's all-reduce of the window's counts, the update kernel."""
         if self.reduce is not None:
             self.reduce()
         if self.sync is not None:
-            self.sync(self.pooled)
-            self.count_history[window] = self.pooled[-1]  # chain-steps of every shard
-        self.update(window)
-
-
-class FactorTuning(WarmupTuning):
-    """... of the proposal factor (include/ptrwm.h ptrwm_precond_update_args).  There is no pooled row: the window's counts are
-    the covariance sums `sxx`, `sx`, `count` of temperature 0, and `sync` is applied to each of the three."""
-
-    def window_end(self, window: int) -> None:
-        if self.sync is not None:
-            for t in (self.sxx, self.sx, self.count):
+            for t in self.synced:
                 self.sync(t)
+            if self.after_sync is not None:
+                self.after_sync(self, window)
         self.update(window)
 
 
@@ -526,7 +518,7 @@ class EngineRun:
         self.steps_done = 0
         self.manual_sweeps = 0  # stand-alone swap events (swap_sweep) performed so far
         self.use_graph = True   # split steps: replay a captured HIP graph where no per-step trace is asked for
-        self._graph = None
+        self._graph, self._graph_key, self._graph_failed, self._dstep = None, None, False, None  # (_advance_split_graph)
         self.beta = torch.tensor(list(beta_ladder), device=device, dtype=torch.float32)
         if dtype not in (torch.float32, torch.float64):
             raise TypeError(f"state dtype must be torch.float32 or torch.float64, got {dtype}")
@@ -617,73 +609,95 @@ class EngineRun:
         if cov_on:
             c = self._cov = {"sxx": zeros(self.cov_temps, dim, dim), "sx": zeros(self.cov_temps, dim), "count": zeros(1, dtype=torch.int64)}
             self._plan.set_covariance(c["sxx"], c["sx"], c["count"], every=self.cov_every)
-        # warm-up tuning of the proposal scale, per temperature, by two small kernels between launches (off: None)
+        # The warm-up tunings (WarmupTuning, each None when off), in the order the host loop serves them - the library's own:
+        # the scale's update and the ladder's rescaling both write temp_scale, and the fused loop runs the scale's kernels
+        # before the ladder's.  `beta` and `chol` are the run's own tensors: the update kernels rewrite them in place (so
+        # captured blocks of split steps keep working).
         self.init_scales = self.proposal.temp_scale.clone()
-        self._adapt = None
-        if adapt is not None:
-            K, W = adapt["windows"], adapt["every"]
-            # the bounds are factors on the initial scales; the library clamps every temperature to one range
-            tiny, huge = float(np.finfo(np.float32).tiny), float(np.finfo(np.float32).max)
-            lo = min(max(adapt["bounds"][0] * float(self.init_scales.min().item()), tiny), huge)
-            hi = min(max(adapt["bounds"][1] * float(self.init_scales.max().item()), lo), huge)
-            self._adapt = ScaleTuning(
-                adapt, torch.zeros(n_temps + 1, device=device, dtype=torch.int64), self._plan.adapt_update,
-                reduce=self._plan.adapt_reduce if self.split else None,
-                window_accept=torch.zeros(shape, device=device, dtype=torch.int64),
-                scale_history=torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
-                accept_history=torch.zeros(K, n_temps, device=device, dtype=torch.int64),
-                # chain-steps behind every row of accept_history (with adapt_sync: of every shard, recorded)
-                count_history=torch.full((K,), 0 if adapt["sync"] is not None else n_replicas * W, device=device, dtype=torch.int64))
-            self._adapt.scale_history[0] = self.init_scales
-            self._plan.set_adaptation(self._adapt.window_accept, self._adapt.pooled, every=W, until=adapt["until"],
-                                      target=adapt["target"], gain=adapt["gain"], decay=adapt["decay"], min_scale=lo,
-                                      max_scale=hi, defer_update=adapt["sync"] is not None,
-                                      scale_history=self._adapt.scale_history, accept_history=self._adapt.accept_history)
-        # warm-up tuning of the temperature ladder, by two more small kernels between launches (off: None).  `beta` is the
-        # run's own tensor: the update kernel rewrites it in place.
+        self._adapt = self._scale_tuning(adapt)
         self.init_beta = self.beta.clone()
-        self._ladder = None
-        if ladder is not None:
-            K, V = ladder["windows"], ladder["every"]
-            self._ladder = WarmupTuning(
-                ladder, torch.zeros(n_temps, device=device, dtype=torch.int64), self._plan.ladder_update,
-                probe_every=ladder["probe_every"],
-                beta_history=torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
-                # row j: the pooled row of window j - pair sums, and chain-probes in the last column
-                rate_history=torch.zeros(K, n_temps, device=device, dtype=torch.int64),
-                skipped=torch.zeros(1, device=device, dtype=torch.int64))
-            self._ladder.beta_history[0] = self.init_beta
-            self._plan.set_ladder(self._ladder.pooled, every=V, probe_every=ladder["probe_every"], until=ladder["until"],
-                                  gain=ladder["gain"], decay=ladder["decay"], rescale_scales=True,
-                                  defer_update=ladder["sync"] is not None, beta_history=self._ladder.beta_history,
-                                  rate_history=self._ladder.rate_history, skipped=self._ladder.skipped)
-        # the proposal factor (off: None), and its warm-up tuning by a covariance probe of temperature 0 and one update kernel
-        # between steps (off: None).  `chol` is the run's own tensor: the update kernel rewrites it in place, so captured
-        # blocks of split steps keep working.
-        self.chol = self.init_chol = self._factor = None
+        self._ladder = self._ladder_tuning(ladder)
+        self.chol = self.init_chol = None  # the proposal factor (off: None)
         if chol is not None:
             self.chol = torch.from_numpy(chol).to(device)
             self.init_chol = self.chol.clone()
             self._plan.set_preconditioner(self.chol)
-        if factor is not None:
-            K = factor["windows"]
-            f64 = lambda *s: torch.zeros(*s, device=device, dtype=torch.float64)  # noqa: E731
-            self._factor = FactorTuning(
-                factor, None, self._plan.precond_update, probe_every=factor["probe_every"],
-                # the window's sums - the tuning's own, never the user's cov= ones - and the running triple
-                sxx=f64(dim, dim), sx=f64(dim), count=torch.zeros(1, device=device, dtype=torch.int64),
-                run_xx=f64(dim, dim), run_x=f64(dim), run_w=f64(1),
-                chol_history=torch.full((K + 1, dim, dim), float("nan"), device=device, dtype=torch.float32),
-                weight_history=torch.full((K,), float("nan"), device=device, dtype=torch.float64),
-                skipped=torch.zeros(1, device=device, dtype=torch.int64))
-            fa = self._factor
-            fa.chol_history[0] = self.init_chol
-            self._plan.set_precond_update(fa.sxx, fa.sx, fa.count, fa.run_xx, fa.run_x, fa.run_w, windows=max(K, 1),
-                                          probe_every=fa.probe_every, memory=factor["memory"], jitter=factor["jitter"],
-                                          min_count=factor["min_count"], chol_history=fa.chol_history if K else None,
-                                          weight_history=fa.weight_history if K else None, skipped=fa.skipped)
+        self._factor = self._factor_tuning(factor)
+        self._tunings = [tu for tu in (self._adapt, self._ladder, self._factor) if tu is not None]
         if box is not None:
             self._draw_starts(box, x0.to(torch.float32).contiguous(), bool(init_per_temperature), attempts)
+
+    # ---- warm-up tunings: each builder allocates the tuning's arrays, writes row 0 of its history and binds it to the plan --------
+    def _scale_tuning(self, adapt: Optional[dict]) -> Optional[WarmupTuning]:
+        """... of the proposal scale, per temperature, by two small kernels between launches"""
+        if adapt is None:
+            return None
+        device, n_temps, K, W = self.device, self.n_temps, adapt["windows"], adapt["every"]
+        # the bounds are factors on the initial scales; the library clamps every temperature to one range
+        tiny, huge = float(np.finfo(np.float32).tiny), float(np.finfo(np.float32).max)
+        lo = min(max(adapt["bounds"][0] * float(self.init_scales.min().item()), tiny), huge)
+        hi = min(max(adapt["bounds"][1] * float(self.init_scales.max().item()), lo), huge)
+        pooled = torch.zeros(n_temps + 1, device=device, dtype=torch.int64)
+
+        def record_counts(tu, window):
+            tu.count_history[window] = tu.pooled[-1]  # chain-steps of every shard
+
+        tu = WarmupTuning(
+            adapt, self._plan.adapt_update, (pooled,), reduce=self._plan.adapt_reduce if self.split else None,
+            after_sync=record_counts, warm_steps=True, pooled=pooled,
+            window_accept=torch.zeros(self.n_replicas, n_temps, device=device, dtype=torch.int64),
+            scale_history=torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
+            accept_history=torch.zeros(K, n_temps, device=device, dtype=torch.int64),
+            # chain-steps behind every row of accept_history (with adapt_sync: of every shard, recorded)
+            count_history=torch.full((K,), 0 if adapt["sync"] is not None else self.n_replicas * W, device=device, dtype=torch.int64))
+        tu.scale_history[0] = self.init_scales
+        self._plan.set_adaptation(tu.window_accept, pooled, every=W, until=adapt["until"], target=adapt["target"],
+                                  gain=adapt["gain"], decay=adapt["decay"], min_scale=lo, max_scale=hi,
+                                  defer_update=adapt["sync"] is not None, scale_history=tu.scale_history,
+                                  accept_history=tu.accept_history)
+        return tu
+
+    def _ladder_tuning(self, ladder: Optional[dict]) -> Optional[WarmupTuning]:
+        """... of the temperature ladder, by two more small kernels between launches: a probe and an update"""
+        if ladder is None:
+            return None
+        device, n_temps, K, plan = self.device, self.n_temps, ladder["windows"], self._plan
+        pooled = torch.zeros(n_temps, device=device, dtype=torch.int64)
+        tu = WarmupTuning(
+            ladder, plan.ladder_update, (pooled,), cut_every=ladder["probe_every"], probe=lambda step: plan.ladder_probe(),
+            pooled=pooled,
+            beta_history=torch.full((K + 1, n_temps), float("nan"), device=device, dtype=torch.float32),
+            # row j: the pooled row of window j - pair sums, and chain-probes in the last column
+            rate_history=torch.zeros(K, n_temps, device=device, dtype=torch.int64),
+            skipped=torch.zeros(1, device=device, dtype=torch.int64))
+        tu.beta_history[0] = self.init_beta
+        self._plan.set_ladder(pooled, every=ladder["every"], probe_every=ladder["probe_every"], until=ladder["until"],
+                              gain=ladder["gain"], decay=ladder["decay"], rescale_scales=True,
+                              defer_update=ladder["sync"] is not None, beta_history=tu.beta_history,
+                              rate_history=tu.rate_history, skipped=tu.skipped)
+        return tu
+
+    def _factor_tuning(self, factor: Optional[dict]) -> Optional[WarmupTuning]:
+        """... of the proposal factor, by a covariance probe of temperature 0 and one update kernel between steps.  There is no
+        pooled row: the window's counts are the covariance sums sxx, sx, count - the tuning's own, never the user's cov= ones."""
+        if factor is None:
+            return None
+        device, dim, K = self.device, self.dim, factor["windows"]
+        f64 = lambda *s: torch.zeros(*s, device=device, dtype=torch.float64)  # noqa: E731
+        sums = {"sxx": f64(dim, dim), "sx": f64(dim), "count": torch.zeros(1, device=device, dtype=torch.int64)}
+        tu = WarmupTuning(
+            factor, self._plan.precond_update, tuple(sums.values()), cut_every=factor["probe_every"],
+            probe=self._plan.precond_probe, **sums,
+            run_xx=f64(dim, dim), run_x=f64(dim), run_w=f64(1),  # the running triple
+            chol_history=torch.full((K + 1, dim, dim), float("nan"), device=device, dtype=torch.float32),
+            weight_history=torch.full((K,), float("nan"), device=device, dtype=torch.float64),
+            skipped=torch.zeros(1, device=device, dtype=torch.int64))
+        tu.chol_history[0] = self.init_chol
+        self._plan.set_precond_update(tu.sxx, tu.sx, tu.count, tu.run_xx, tu.run_x, tu.run_w, windows=max(K, 1),
+                                      probe_every=factor["probe_every"], memory=factor["memory"], jitter=factor["jitter"],
+                                      min_count=factor["min_count"], chol_history=tu.chol_history if K else None,
+                                      weight_history=tu.weight_history if K else None, skipped=tu.skipped)
+        return tu
 
     def proposal_factor(self) -> Optional[torch.Tensor]:
         """The current proposal factor: float32 [dim, dim] on the device, zeros above the diagonal (a copy); None without one."""
@@ -745,9 +759,9 @@ class EngineRun:
         if self.split:
             self._advance_split(n_steps, trace, trace_logp, trace_row0, max(1, int(trace_every)))
             return
-        # adapt_sync: one launch up to the nearer pending window end of either tuning (the library refuses to step past a pending
-        # update), the caller's all-reduce of that window's `pooled` and the update in between - the scale's before the
-        # ladder's where both end at the same step; ordinary launches from the end of warm-up
+        # adapt_sync: one launch up to the nearest pending window end of any tuning (the library refuses to step past a pending
+        # update), the caller's all-reduce of that window's counts and the update in between - in the order of the list where
+        # several end at the same step; ordinary launches from the end of warm-up
         while n_steps > 0:
             s, pending = self.steps_done, self._pending_sync()
             if not pending:
@@ -764,8 +778,10 @@ class EngineRun:
             self._launch(n_steps, trace, trace_logp, trace_row0, trace_every)
 
     def _pending_sync(self) -> list:
-        """The tunings (scale, ladder) that defer their update to the caller and still have a window to end."""
-        return [tu for tu in (self._adapt, self._ladder) if tu is not None and tu.sync is not None and self.steps_done < tu.end]
+        """The tunings that defer their update to the caller and still have a window to end, for fused steps: a proposal factor
+        makes every step a split step, so its tuning is never among them."""
+        assert not self.split
+        return [tu for tu in self._tunings if tu.sync is not None and self.steps_done < tu.end]
 
     def _launch(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> None:
         if trace is None and trace_logp is None:
@@ -839,9 +855,9 @@ class EngineRun:
 
     def _advance_split_graph(self, n_steps: int) -> bool:
         """n_steps split steps by graph replay; False if the density cannot be captured (the caller falls back)."""
-        if getattr(self, "_graph_failed", False):
+        if self._graph_failed:
             return False
-        if getattr(self, "_dstep", None) is None:
+        if self._dstep is None:
             self._dstep = torch.zeros(1, dtype=torch.int64, device=self.device)
         self._dstep.fill_(self.steps_done)
         self._plan.set_device_step(self._dstep)
@@ -856,7 +872,7 @@ class EngineRun:
                     self._split_step_on_device_counter()
 
             key = (self.manual_sweeps, block)  # (baked into the captured launches)
-            if getattr(self, "_graph_key", None) != key:
+            if self._graph_key != key:
                 self._graph = None
             if self._graph is None:
                 # one step outside capture first, on a side stream (lazy initialisations of whatever the density calls
@@ -901,29 +917,22 @@ class EngineRun:
 
     def _advance_split(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> None:
         """n_steps split steps; traced steps (step_counter a multiple of trace_every) are copied with torch."""
-        ad, ld, fa = self._adapt, self._ladder, self._factor
         while n_steps > 0:
-            # the host loop - and with it every captured block - ends with every adapting window of the scale and behind
-            # every probe step of an adapting window of the ladder and of the proposal factor; the stand-alone kernels follow
-            # in the library's order: the scale's reduce and update, the ladder's probe and, at a window's end, its update,
-            # then the factor's probe and update
+            # the host loop - and with it every captured block - ends every cut_every steps of an adapting window of each
+            # tuning (WarmupTuning); the stand-alone kernels follow in the order of the list, the library's: each tuning's probe
+            # and, at a window's end, its reduction and update
             s = self.steps_done
-            warm, probing = ad is not None and s < ad.end, ld is not None and s < ld.end
-            learning = fa is not None and s < fa.end
-            k = min([n_steps] + ([ad.every - s % ad.every] if warm else []) + ([ld.probe_every - s % ld.probe_every] if probing else [])
-                    + ([fa.probe_every - s % fa.probe_every] if learning else []))
-            trace_row0 += (self._split_steps(k, trace, trace_logp, trace_row0, trace_every, warmup=True) if warm else
+            live = [tu for tu in self._tunings if s < tu.end]
+            k = min([n_steps] + [tu.cut_every - s % tu.cut_every for tu in live])
+            trace_row0 += (self._split_steps(k, trace, trace_logp, trace_row0, trace_every, warmup=True)
+                           if any(tu.warm_steps for tu in live) else
                            self._advance_split_plain(k, trace, trace_logp, trace_row0, trace_every))
-            if warm and (s + k) % ad.every == 0:
-                ad.window_end((s + k) // ad.every - 1)
-            if probing and (s + k) % ld.probe_every == 0:
-                self._plan.ladder_probe()
-                if (s + k) % ld.every == 0:
-                    ld.window_end((s + k) // ld.every - 1)
-            if learning and (s + k) % fa.probe_every == 0:
-                self._plan.precond_probe(s + k - 1)
-                if (s + k) % fa.every == 0:
-                    fa.window_end((s + k) // fa.every - 1)
+            for tu in live:
+                if (s + k) % tu.cut_every == 0:
+                    if tu.probe is not None:
+                        tu.probe(s + k - 1)
+                    if (s + k) % tu.every == 0:
+                        tu.window_end((s + k) // tu.every - 1)
             n_steps -= k
 
     def _advance_split_plain(self, n_steps, trace, trace_logp, trace_row0, trace_every) -> int:
@@ -1311,7 +1320,10 @@ def sokal_window(rho, c: float = 5.0) -> tuple:
 class Autocorrelation:
     """Estimates from the pooled lagged autocovariance (include/ptrwm.h ptrwm_acf_args, csrc/acf.h): how correlated successive
     snapshots of a coordinate are, pooled over every replica of the run.  The host class calls `_check_acf_ctor` in its
-    constructor, passes `_acf_kwargs(n_temps)` to EngineRun and owns `_run`.  Every read synchronises; results are CPU tensors."""
+    constructor, passes `_acf_kwargs(n_temps)` to EngineRun and owns `_run`.  Every read synchronises; results are CPU tensors.
+
+    The keywords: acf='cold' or 'all' temperatures, a snapshot every acf_every-th step past burn-in, lags 0..acf_max_lag in
+    snapshots; acf_ring_limit overrides the largest ring (elements) the constructor accepts."""
 
     def _check_acf_ctor(self, dim: int, acf, acf_every, acf_max_lag, acf_ring_limit=None) -> None:
         """The constructor's autocovariance arguments, checked before anything is built (no GPU needed; the ring's size is
@@ -1441,7 +1453,9 @@ def cov_condition(cov) -> float:
 class PosteriorCovariance:
     """Estimates from the pooled covariance sums (include/ptrwm.h ptrwm_cov_args, csrc/cov.h): how the coordinates move
     together, pooled over every replica of the run.  The host class calls `_check_cov_ctor` in its constructor, passes
-    `_cov_kwargs(n_temps)` to EngineRun and owns `_run`.  Every read synchronises; results are CPU tensors."""
+    `_cov_kwargs(n_temps)` to EngineRun and owns `_run`.  Every read synchronises; results are CPU tensors.
+
+    The keywords: cov='cold' or 'all' temperatures, a snapshot every cov_every-th step past burn-in."""
 
     def _check_cov_ctor(self, cov, cov_every) -> None:
         """The constructor's covariance arguments, checked before anything is built (no GPU needed)."""
@@ -1598,7 +1612,10 @@ def hist_mode_weights(counts, edges, boundaries) -> torch.Tensor:
 class MarginalHistograms:
     """Estimates from the pooled marginal histograms (include/ptrwm.h ptrwm_hist_args): the marginal distribution of every
     coordinate over every replica of the run.  The host class sets `_hist_mode` / `_hist_every` / `_hist_bins` /
-    `_hist_range` and owns `_run` (an EngineRun).  Every read synchronises; results are CPU tensors."""
+    `_hist_range` and owns `_run` (an EngineRun).  Every read synchronises; results are CPU tensors.
+
+    The keywords: hist='cold' or 'all' temperatures, hist_range=(lo, hi) the range of the hist_bins bins, a snapshot every
+    hist_every-th step past burn-in."""
 
     def _check_hist_ctor(self, dim: int, hist, hist_range, hist_bins, hist_every) -> None:
         """The constructor's histogram arguments, checked before anything is built (no GPU needed)."""
@@ -1662,16 +1679,45 @@ class MarginalHistograms:
         return {"hist_out_of_range": (int(c[..., 0].sum().item()) + int(c[..., -1].sum().item())) / total if total else float("nan")}
 
 
-# ---- warm-up tuning of the proposal scale in the drop-in classes ----------------------------------------------------------
-class ScaleAdaptation:
+# ---- the warm-up tunings in the drop-in classes ------------------------------------------------------------------------------
+class WarmupKeywords:
+    """What the mixins of the three warm-up tunings share.  `adapt_sync` is one keyword for all of them - a callable applied to a
+    window's counts at every window end, which makes shards of one run tune together (algorithms.sharding.adaptation_sync): the
+    host class stores it once, as `_adapt_sync`, before it calls a mixin's `_check_*_ctor`, and passes it to EngineRun once, as
+    adapt_sync=, next to the mixins' `_*_kwargs()` (EngineRun ignores it where no tuning is on)."""
+
+    def _check_tuning(self, key: str, flag: str, check, *args, **kw) -> None:
+        """One tuning's constructor keywords `kw`, checked before anything is built (no GPU needed) by `check`: its dict (None:
+        off) is kept as `_<key>_args`, EngineRun's keywords - `flag` and `kw`; off: none - as `_<key>_kw`."""
+        checked = check(*args, **kw, adapt_sync=self._adapt_sync)
+        setattr(self, f"_{key}_args", checked)
+        setattr(self, f"_{key}_kw", {flag: True, **kw} if checked is not None else {})
+
+    @staticmethod
+    def _history_before_run(first: torch.Tensor, windows: int) -> torch.Tensor:
+        """A tuning's history where nothing has run yet, or after reset(): float32 [windows + 1, *first.shape] on `first`'s
+        device, row 0 `first`, the rows of the windows still to run NaN."""
+        rows = torch.full((windows + 1, *first.shape), float("nan"), device=first.device, dtype=torch.float32)
+        rows[0] = first
+        return rows
+
+    @staticmethod
+    def _rows_before_run(windows: int, *shape, device=None) -> torch.Tensor:
+        """... and what it records per window: float64 [windows, *shape], NaN."""
+        return torch.full((windows, *shape), float("nan"), device=device, dtype=torch.float64)
+
+
+class ScaleAdaptation(WarmupKeywords):
     """Readers of the per-temperature proposal scales and of their warm-up tuning (include/ptrwm.h ptrwm_adapt_args).  The
     host class calls `_check_adapt_ctor` in its constructor, passes `_adapt_kwargs()` to EngineRun, owns `_run` and defines
-    `_initial_proposal()` (the engine proposal a fresh run starts from).  Every read synchronises."""
+    `_initial_proposal()` (the engine proposal a fresh run starts from).  Every read synchronises.
+
+    The keywords: adapt_scale=True tunes the scale of every temperature towards the acceptance rate adapt_target in windows of
+    adapt_every steps up to adapt_until (default: all of burn-in), with adapt_gain and adapt_decay; adapt_scale_bounds are
+    factors on the initial scales; adapt_sync (WarmupKeywords) is applied to the pooled [T + 1] counts."""
 
     def _check_adapt_ctor(self, burn_in: int, adapt_scale, **kw) -> None:
-        """The constructor's adaptation arguments, checked before anything is built (no GPU needed)."""
-        self._adapt_args = check_adapt_args(adapt_scale, max(0, int(burn_in)), **kw)
-        self._adapt_kw = {"adapt_scale": bool(adapt_scale), **kw} if self._adapt_args is not None else {}
+        self._check_tuning("adapt", "adapt_scale", check_adapt_args, adapt_scale, max(0, int(burn_in)), **kw)
 
     def _adapt_kwargs(self) -> dict:
         """EngineRun's adaptation arguments."""
@@ -1697,28 +1743,32 @@ class ScaleAdaptation:
         if run is not None:
             h = run.adaptation_history()
             return {"scales": h["scales"], "acceptance": h["acceptance"]}
-        init = self._init_scales()
-        K, T = self._adapt_args["windows"], init.numel()
-        scales = torch.full((K + 1, T), float("nan"), device=init.device, dtype=torch.float32)
-        scales[0] = init
-        return {"scales": scales, "acceptance": torch.full((K, T), float("nan"), device=init.device, dtype=torch.float64)}
+        init, K = self._init_scales(), self._adapt_args["windows"]
+        return {"scales": self._history_before_run(init, K),
+                "acceptance": self._rows_before_run(K, init.numel(), device=init.device)}
 
     def _adapt_diagnostics(self) -> dict:
         return {"adapted_scales": self.proposal_scales().cpu().tolist(), "init_scales": self._init_scales().cpu().tolist()}
 
 
 # ---- preconditioned proposals in the drop-in classes ------------------------------------------------------------------------------
-class Preconditioning:
+class Preconditioning(WarmupKeywords):
     """`proposal_cov=` and `adapt_cov=` of the sampler classes, and the readers of the proposal factor (include/ptrwm.h
     ptrwm_split_propose_precond / ptrwm_precond_update, csrc/precond.h).  The host class calls `_check_precond_ctor` in its
     constructor, passes `_precond_kwargs()` to EngineRun and owns `_run` and `dim`.  Every read synchronises; results are CPU
-    tensors."""
+    tensors.
+
+    The keywords: proposal_cov, a [dim, dim] covariance factored on the host, gives increments N(0, (var / beta_t) proposal_cov);
+    adapt_cov=True learns the factor during burn-in from the cold chain's covariance, in windows of cov_adapt_every steps probed
+    every cov_adapt_probe_every steps (default: one probe per window), up to cov_adapt_until (default: all of burn-in), with
+    cov_adapt_memory, cov_adapt_jitter and cov_adapt_min_count of include/ptrwm.h; adapt_sync (WarmupKeywords) is applied to the
+    window's covariance sums.  Such runs are split steps."""
 
     def _check_precond_ctor(self, dim: int, burn_in: int, proposal_cov, adapt_cov, proposal_distribution, dtype, **kw) -> None:
         """The constructor's arguments, checked before anything is built (no GPU needed).  `proposal_distribution`: the
         proposal object the caller passed (None: the class builds a Normal one)."""
         chol = check_proposal_cov(proposal_cov, int(dim))
-        self._factor_args = check_cov_adapt_args(adapt_cov, max(0, int(burn_in)), int(dim), **kw)
+        self._check_tuning("factor", "adapt_cov", check_cov_adapt_args, adapt_cov, max(0, int(burn_in)), int(dim), **kw)
         on = chol is not None or self._factor_args is not None
         if on and proposal_distribution is not None and type(proposal_distribution).__name__ != "NormalProposal":
             raise ValueError("proposal_cov / adapt_cov precondition the Normal proposal: "
@@ -1729,19 +1779,10 @@ class Preconditioning:
         if on and chol is None:
             chol = np.eye(int(dim), dtype=np.float32)
         self._init_chol = chol
-        self._precond_kw = {}
-        if on:
-            self._precond_kw = {"proposal_chol": chol}
-            if self._factor_args is not None:
-                self._precond_kw.update(adapt_cov=True, **{k: v for k, v in kw.items() if k != "adapt_sync"})
 
-    def _precond_kwargs(self, *others: dict) -> dict:
-        """EngineRun's arguments; `others`: the dicts of the other tunings (adapt_sync travels with one of them where it is
-        on, else with this one)."""
-        kw = dict(self._precond_kw)
-        if self._factor_args is not None and not any("adapt_sync" in o for o in others):
-            kw["adapt_sync"] = self._factor_args["sync"]
-        return kw
+    def _precond_kwargs(self) -> dict:
+        """EngineRun's arguments: the factor where there is one, and its tuning's."""
+        return {"proposal_chol": self._init_chol, **self._factor_kw} if self._init_chol is not None else {}
 
     def _precond_on(self) -> None:
         if getattr(self, "_init_chol", None) is None:
@@ -1770,10 +1811,9 @@ class Preconditioning:
         if run is not None:
             h = run.preconditioner_history()
             return {"factors": h["factors"].cpu(), "weights": h["weights"].cpu(), "skipped": h["skipped"]}
-        K, D = self._factor_args["windows"], self._init_chol.shape[0]
-        factors = torch.full((K + 1, D, D), float("nan"), dtype=torch.float32)
-        factors[0] = torch.from_numpy(self._init_chol)
-        return {"factors": factors, "weights": torch.full((K,), float("nan"), dtype=torch.float64), "skipped": 0}
+        K = self._factor_args["windows"]
+        return {"factors": self._history_before_run(torch.from_numpy(self._init_chol), K), "weights": self._rows_before_run(K),
+                "skipped": 0}
 
     def _precond_diagnostics(self) -> dict:
         if getattr(self, "_init_chol", None) is None:
@@ -1789,18 +1829,22 @@ class Preconditioning:
 
 
 # ---- warm-up tuning of the temperature ladder in the PT class ---------------------------------------------------------------
-class LadderAdaptation:
+class LadderAdaptation(WarmupKeywords):
     """Readers of the temperature ladder and of its warm-up tuning (include/ptrwm.h ptrwm_ladder_args).  The host class calls
     `_check_ladder_ctor` in its constructor once `beta_ladder` stands, passes `_ladder_kwargs()` to EngineRun and owns `_run`
-    and `beta_ladder` (a list, refreshed from the run while the ladder moves).  Every read synchronises."""
+    and `beta_ladder` (a list, refreshed from the run while the ladder moves).  Every read synchronises.
+
+    The keywords: adapt_ladder=True moves the interior betas towards equal swap rates between neighbours in windows of
+    ladder_every steps up to ladder_until (default: all of burn-in), with ladder_gain and ladder_decay, from a probe of every
+    replica behind every ladder_probe_every-th step (default: one per window); both ends stay, the proposal scales follow their
+    temperature, and adapt_sync (WarmupKeywords) is applied to the pooled [T] row."""
 
     def _check_ladder_ctor(self, burn_in: int, adapt_ladder, beta_ladder, **kw) -> None:
-        self._ladder_args = check_ladder_args(adapt_ladder, max(0, int(burn_in)), beta_ladder, **kw)
-        self._ladder_kw = ({"adapt_ladder": True, **{k: v for k, v in kw.items() if k != "adapt_sync"}}
-                           if self._ladder_args is not None else {})
+        self._check_tuning("ladder", "adapt_ladder", check_ladder_args, adapt_ladder, max(0, int(burn_in)), beta_ladder, **kw)
         self._init_beta_ladder = list(beta_ladder)
 
     def _ladder_kwargs(self) -> dict:
+        """EngineRun's ladder arguments."""
         return dict(self._ladder_kw)
 
     def _refresh_beta_ladder(self, steps_before: int) -> None:
@@ -1827,10 +1871,8 @@ class LadderAdaptation:
         if run is not None:
             h = run.ladder_history()
             return {"betas": h["betas"], "rates": h["rates"], "probes": h["probes"]}
-        K, T = self._ladder_args["windows"], len(self._init_beta_ladder)
-        betas = torch.full((K + 1, T), float("nan"), dtype=torch.float32)
-        betas[0] = torch.tensor(self._init_beta_ladder, dtype=torch.float32)
-        return {"betas": betas, "rates": torch.full((K, T - 1), float("nan"), dtype=torch.float64),
+        K, init = self._ladder_args["windows"], torch.tensor(self._init_beta_ladder, dtype=torch.float32)
+        return {"betas": self._history_before_run(init, K), "rates": self._rows_before_run(K, init.numel() - 1),
                 "probes": torch.zeros(K, dtype=torch.int64)}
 
     def _ladder_diagnostics(self) -> dict:

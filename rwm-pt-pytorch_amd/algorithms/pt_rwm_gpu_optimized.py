@@ -73,32 +73,20 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
                  cov_adapt_until: Optional[int] = None, cov_adapt_probe_every: Optional[int] = None,
                  cov_adapt_memory: float = 0.5, cov_adapt_jitter: float = 1e-6, cov_adapt_min_count: Optional[float] = None):
         super().__init__(dim, var, target_dist, symmetric)
-        # warm-up tuning of the proposal scale per temperature (include/ptrwm.h ptrwm_adapt_args): adapt_scale=True tunes towards
-        # adapt_target in windows of adapt_every steps up to adapt_until (default: all of burn-in); adapt_scale_bounds are factors
-        # on the initial scales; adapt_sync, a callable applied to the pooled [T + 1] counts at every window end, makes shards
-        # of one run adapt together (algorithms.sharding.adaptation_sync)
+        # The optional blocks, checked before anything is built.  What the keywords of each mean stands once, in the docstring of
+        # the mixin that owns them (algorithms/_engine_core.py): ScaleAdaptation, MarginalHistograms, Autocorrelation,
+        # PosteriorCovariance, Preconditioning and - below, once the ladder stands - LadderAdaptation; adapt_sync, the one
+        # keyword the tunings share, in WarmupKeywords.
+        self._adapt_sync = adapt_sync
         self._check_adapt_ctor(burn_in, adapt_scale, adapt_every=adapt_every, adapt_until=adapt_until, adapt_target=adapt_target,
-                               adapt_gain=adapt_gain, adapt_decay=adapt_decay, adapt_scale_bounds=adapt_scale_bounds,
-                               adapt_sync=adapt_sync)
-        # pooled marginal histograms over every replica (include/ptrwm.h ptrwm_hist_args): hist='cold' or 'all' temperatures,
-        # hist_range=(lo, hi) the range of the hist_bins bins, a snapshot every hist_every-th step past burn-in
+                               adapt_gain=adapt_gain, adapt_decay=adapt_decay, adapt_scale_bounds=adapt_scale_bounds)
         self._check_hist_ctor(dim, hist, hist_range, hist_bins, hist_every)
-        # pooled lagged autocovariance over every replica (include/ptrwm.h ptrwm_acf_args): acf='cold' or 'all' temperatures, a
-        # snapshot every acf_every-th step past burn-in, lags 0..acf_max_lag in snapshots; acf_ring_limit overrides the largest
-        # ring (elements) the constructor accepts
         self._check_acf_ctor(dim, acf, acf_every, acf_max_lag, acf_ring_limit)
-        # pooled posterior covariance over every replica (include/ptrwm.h ptrwm_cov_args): cov='cold' or 'all' temperatures,
-        # a snapshot every cov_every-th step past burn-in
         self._check_cov_ctor(cov, cov_every)
-        # preconditioned proposals (include/ptrwm.h ptrwm_split_propose_precond): proposal_cov, a [dim, dim] covariance factored on
-        # the host, gives increments N(0, (var / beta_t) proposal_cov); adapt_cov=True learns the factor during burn-in from the
-        # cold chain's covariance, in windows of cov_adapt_every steps probed every cov_adapt_probe_every steps, up to
-        # cov_adapt_until (default: all of burn-in).  Such runs are split steps.
         self._check_precond_ctor(dim, burn_in, proposal_cov, adapt_cov, proposal_distribution, dtype,
                                  cov_adapt_every=cov_adapt_every, cov_adapt_until=cov_adapt_until,
-                                 cov_adapt_probe_every=cov_adapt_probe_every,
-                                 cov_adapt_memory=cov_adapt_memory, cov_adapt_jitter=cov_adapt_jitter,
-                                 cov_adapt_min_count=cov_adapt_min_count, adapt_sync=adapt_sync)
+                                 cov_adapt_probe_every=cov_adapt_probe_every, cov_adapt_memory=cov_adapt_memory,
+                                 cov_adapt_jitter=cov_adapt_jitter, cov_adapt_min_count=cov_adapt_min_count)
         self._flow_on = bool(flow)
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         self._moments_mode, self._moments_every = moments, int(moments_every)
@@ -147,14 +135,8 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
             if not geom_temp_spacing:
                 warnings.warn("No specific ladder construction method chosen. Using geometric spacing as default.")
 
-        # warm-up tuning of the ladder itself (include/ptrwm.h ptrwm_ladder_args): adapt_ladder=True moves the interior betas
-        # towards equal swap rates between neighbours in windows of ladder_every steps up to ladder_until (default: all of
-        # burn-in), from a probe of every replica behind every ladder_probe_every-th step (default: one per window); both ends
-        # stay, the proposal scales follow their temperature, and adapt_sync serves this tuning as it serves the scale's
         self._check_ladder_ctor(self.burn_in, adapt_ladder, self.beta_ladder, ladder_every=ladder_every, ladder_until=ladder_until,
-                                ladder_probe_every=ladder_probe_every, ladder_gain=ladder_gain, ladder_decay=ladder_decay,
-                                adapt_sync=adapt_sync)
-        self._ladder_sync = adapt_sync
+                                ladder_probe_every=ladder_probe_every, ladder_gain=ladder_gain, ladder_decay=ladder_decay)
         self.num_chains = len(self.beta_ladder)  # = number of temperatures, as in the reference
         if self._flow_on and self.num_chains < 2:
             raise ValueError("flow=True tracks replicas through a ladder: it needs at least two temperatures")
@@ -299,9 +281,9 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
             swap_mode=self._swap_mode, swap_order=self._swap_order, seed=self._seed, chain_offset=self._chain_offset,
             dtype=self.dtype, moments_temps=moments_temps(self._moments_mode, len(self.beta_ladder), self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, flow=self._flow_on,
-            **self._hist_kwargs(len(self.beta_ladder)), **self._adapt_kwargs(), **self._ladder_run_kwargs(),
-            **self._acf_kwargs(len(self.beta_ladder)), **self._cov_kwargs(len(self.beta_ladder)),
-            **self._precond_kwargs(self._adapt_kwargs(), self._ladder_run_kwargs()))
+            adapt_sync=self._adapt_sync, **self._hist_kwargs(len(self.beta_ladder)), **self._adapt_kwargs(),
+            **self._ladder_kwargs(), **self._acf_kwargs(len(self.beta_ladder)), **self._cov_kwargs(len(self.beta_ladder)),
+            **self._precond_kwargs())
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
         self.current_log_densities = self._run.logp[0] if self.num_replicas == 1 else self._run.logp
@@ -313,13 +295,6 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
 
     def _initial_proposal(self):
         return self.proposal_dist.engine_proposal(self._init_beta_ladder)
-
-    def _ladder_run_kwargs(self) -> dict:
-        """EngineRun's ladder arguments (adapt_sync travels with the scale's where that is on too)."""
-        kw = self._ladder_kwargs()
-        if kw and "adapt_sync" not in self._adapt_kwargs():
-            kw["adapt_sync"] = self._ladder_sync
-        return kw
 
     def _advance(self, n_steps: int):
         self._ensure_started()

@@ -73,32 +73,20 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
         if adapt_ladder:
             raise ValueError("adapt_ladder=True tunes a temperature ladder: RandomWalkMH_GPU_Optimized has none "
                              "(use ParallelTemperingRWM_GPU_Optimized)")
-        # warm-up tuning of the proposal scale per temperature (include/ptrwm.h ptrwm_adapt_args): adapt_scale=True tunes towards
-        # adapt_target in windows of adapt_every steps up to adapt_until (default: all of burn-in); adapt_scale_bounds are factors
-        # on the initial scales; adapt_sync, a callable applied to the pooled [T + 1] counts at every window end, makes shards
-        # of one run adapt together (algorithms.sharding.adaptation_sync)
+        # The optional blocks, checked before anything is built.  What the keywords of each mean stands once, in the docstring of
+        # the mixin that owns them (algorithms/_engine_core.py): ScaleAdaptation, MarginalHistograms, Autocorrelation,
+        # PosteriorCovariance, Preconditioning; adapt_sync, the one keyword the tunings share, in WarmupKeywords.  With one
+        # temperature, 'cold' and 'all' are the same.
+        self._adapt_sync = adapt_sync
         self._check_adapt_ctor(burn_in, adapt_scale, adapt_every=adapt_every, adapt_until=adapt_until, adapt_target=adapt_target,
-                               adapt_gain=adapt_gain, adapt_decay=adapt_decay, adapt_scale_bounds=adapt_scale_bounds,
-                               adapt_sync=adapt_sync)
-        # pooled marginal histograms over every chain (include/ptrwm.h ptrwm_hist_args): hist='cold' (= 'all' here: one
-        # temperature), hist_range=(lo, hi) the range of the hist_bins bins, a snapshot every hist_every-th step past burn-in
+                               adapt_gain=adapt_gain, adapt_decay=adapt_decay, adapt_scale_bounds=adapt_scale_bounds)
         self._check_hist_ctor(dim, hist, hist_range, hist_bins, hist_every)
-        # pooled lagged autocovariance over every replica (include/ptrwm.h ptrwm_acf_args): acf='cold' (= 'all' here: one temperature), a
-        # snapshot every acf_every-th step past burn-in, lags 0..acf_max_lag in snapshots; acf_ring_limit overrides the largest
-        # ring (elements) the constructor accepts
         self._check_acf_ctor(dim, acf, acf_every, acf_max_lag, acf_ring_limit)
-        # pooled posterior covariance over every replica (include/ptrwm.h ptrwm_cov_args): cov='cold' (= 'all' here: one
-        # temperature), a snapshot every cov_every-th step past burn-in
         self._check_cov_ctor(cov, cov_every)
-        # preconditioned proposals (include/ptrwm.h ptrwm_split_propose_precond): proposal_cov, a [dim, dim] covariance factored on
-        # the host, gives increments N(0, (var / beta_t) proposal_cov); adapt_cov=True learns the factor during burn-in from the
-        # cold chain's covariance, in windows of cov_adapt_every steps probed every cov_adapt_probe_every steps, up to
-        # cov_adapt_until (default: all of burn-in).  Such runs are split steps.
         self._check_precond_ctor(dim, burn_in, proposal_cov, adapt_cov, proposal_distribution, torch.float32,
                                  cov_adapt_every=cov_adapt_every, cov_adapt_until=cov_adapt_until,
-                                 cov_adapt_probe_every=cov_adapt_probe_every,
-                                 cov_adapt_memory=cov_adapt_memory, cov_adapt_jitter=cov_adapt_jitter,
-                                 cov_adapt_min_count=cov_adapt_min_count, adapt_sync=adapt_sync)
+                                 cov_adapt_probe_every=cov_adapt_probe_every, cov_adapt_memory=cov_adapt_memory,
+                                 cov_adapt_jitter=cov_adapt_jitter, cov_adapt_min_count=cov_adapt_min_count)
         # where the chains start (EngineRun's docstring): by default all from the reference's one point; `initial_states`
         # [num_chains, dim] (or [dim] / [num_chains, 1, dim]) gives every chain its own - a warm restart is
         # initial_states=previous.current_states; `init_box` = (lo, hi) draws over-dispersed starts in the library, redrawing
@@ -212,8 +200,8 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
             burn_in=self.burn_in, swap_every=1, swap_mode="exchange", swap_order="sequential", seed=self._seed,
             chain_offset=self._chain_offset, moments_temps=moments_temps(self._moments_mode, 1, self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, init_box=self._init_box,
-            init_attempts=self._init_attempts, **self._hist_kwargs(1), **self._adapt_kwargs(), **self._acf_kwargs(1),
-            **self._cov_kwargs(1), **self._precond_kwargs(self._adapt_kwargs()),
+            init_attempts=self._init_attempts, adapt_sync=self._adapt_sync, **self._hist_kwargs(1), **self._adapt_kwargs(),
+            **self._acf_kwargs(1), **self._cov_kwargs(1), **self._precond_kwargs(),
         )
         self.current_state = self._run.state[0, 0]  # views: always the live values
         self.current_states = self._run.state[:, 0]

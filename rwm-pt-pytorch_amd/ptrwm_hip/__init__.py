@@ -755,8 +755,10 @@ class RunPlan:
         self._ladder = None  # warm-up tuning of the temperature ladder: (struct, byref, tensors)
         self._acf = None  # pooled lagged autocovariance: (struct, byref, tensors)
         self._cov = None  # pooled posterior covariance: (struct, byref, tensors)
-        self._precond = None  # preconditioned proposals: (struct, byref, chol)
-        self._precond_update = None  # ... and the factor's update: (struct, byref, tensors)
+        self._precond = None  # preconditioned proposals: (struct, byref, tensors)
+        self._precond_update = None  # warm-up tuning of the factor, the update: (struct, byref, tensors)
+        self._precond_probe = None  # ... and its probe, a covariance block of temperature 0: (struct, byref, tensors)
+        self._warm_saved = None  # split_warmup: the run arguments it has set aside while on
 
     # kind of accumulator -> (words of its messages, struct, entry point of launch(), entry point of split_moments())
     _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
@@ -847,8 +849,9 @@ class RunPlan:
         self._flow = (f, C.byref(f), (walker, round_trips, n_up, n_down))
 
     def _bind_block(self, what: str, struct, scalars: dict, pointers) -> tuple:
-        """(struct, byref, tensors) of a snapshot block (`what` starts its messages): every tensor of `pointers` - (field,
-        tensor or None, dtype), shapes already checked - sits on the plan's device and is marshalled into its field."""
+        """(struct, byref, tensors) of a bound block - a snapshot accumulator, a warm-up tuning - whose messages start with
+        `what`: `scalars` go into their fields as they are, every tensor of `pointers` - (field, tensor or None, dtype), shapes
+        already checked - sits on the plan's device and is marshalled into its field."""
         for name, t, _ in pointers:
             if t is not None and t.device != self.device:
                 raise ValueError(f"{what} {name} is on {t.device}, state on {self.device}")
@@ -986,19 +989,21 @@ class RunPlan:
             raise ValueError(f"{what} until must be in 0..burn_in = {self._a.burn_in}, got {until}")
         return every, until, until // every
 
-    def _tuning_tensors(self, what: str, tensors) -> None:
-        """(name, tensor, shape, required) of a warm-up tuning: every tensor given - and every required one - has its shape and
-        sits on the plan's device"""
-        for name, t, shape, required in tensors:
+    def _tuning_tensors(self, what: str, tensors) -> list:
+        """The shape check in front of _bind_block: (field, tensor, dtype, shape, required) of a warm-up tuning - every tensor
+        given, and every required one, is there in its shape (one message, which names the device too) - as _bind_block's
+        `pointers`"""
+        for name, t, _, shape, required in tensors:
             if (t is None and required) or (t is not None and (tuple(t.shape) != shape or t.device != self.device)):
                 raise ValueError(f"{what} {name} must be a {list(shape)} tensor on {self.device}")
+        return [spec[:3] for spec in tensors]
 
-    def _tuning_call(self, name: str, bound, missing: str, window: Optional[int] = None) -> None:
+    def _tuning_call(self, name: str, bound, missing: str, window: Optional[int] = None, extent: int = 1) -> None:
         """A stand-alone kernel of a warm-up tuning, ptrwm_<name>: the ones between launches take the run's arguments, the
-        updates (`window` given) n_temps and the window"""
+        updates (`window` given) an extent of the plan's shape - n_temps, or with `extent` = 2 dim - and the window"""
         if bound is None:
             raise RuntimeError(f"{name}: no {missing}")
-        args = (self._refs[4], bound[1]) if window is None else (bound[1], self.shape[1], int(window))
+        args = (self._refs[4], bound[1]) if window is None else (bound[1], self.shape[extent], int(window))
         with self._guard:
             rc = getattr(self._lib, "ptrwm_" + name)(*args, _stream(self.device))
         if rc != 0:
@@ -1019,22 +1024,14 @@ class RunPlan:
             return
         Cn, T, _ = self.shape
         every, until, K = self._tuning_windows("adaptation", every, until)
-        scale = self._keep[1].temp_scale
-        self._tuning_tensors("adaptation", (("window_accept", window_accept, (Cn, T), True), ("pooled", pooled, (T + 1,), True),
-                                            ("scale_history", scale_history, (K + 1, T), False),
-                                            ("accept_history", accept_history, (K, T), False)))
-        ad = AdaptArgs()
-        ad.struct_size = C.sizeof(AdaptArgs)
-        ad.every, ad.until = every, until
-        ad.target, ad.gain, ad.decay = float(target), float(gain), float(decay)
-        ad.min_scale, ad.max_scale = float(min_scale), float(max_scale)
-        ad.defer_update = 1 if defer_update else 0
-        ad.temp_scale = _require_device(scale, "proposal.temp_scale", torch.float32)
-        ad.window_accept = _require_device(window_accept, "adaptation window_accept", torch.int64)
-        ad.pooled = _require_device(pooled, "adaptation pooled", torch.int64)
-        ad.scale_history = _opt(scale_history, "adaptation scale_history", torch.float32)
-        ad.accept_history = _opt(accept_history, "adaptation accept_history", torch.int64)
-        self._adapt = (ad, C.byref(ad), (scale, window_accept, pooled, scale_history, accept_history))
+        pointers = self._tuning_tensors("adaptation", (
+            ("window_accept", window_accept, torch.int64, (Cn, T), True), ("pooled", pooled, torch.int64, (T + 1,), True),
+            ("scale_history", scale_history, torch.float32, (K + 1, T), False),
+            ("accept_history", accept_history, torch.int64, (K, T), False)))
+        # (temp_scale: the plan's own tensor, checked and marshalled with the proposal)
+        self._adapt = self._bind_block("adaptation", AdaptArgs, dict(
+            every=every, until=until, target=float(target), gain=float(gain), decay=float(decay), min_scale=float(min_scale),
+            max_scale=float(max_scale), defer_update=1 if defer_update else 0, temp_scale=self._p.temp_scale), pointers)
 
     def adapt_reduce(self) -> None:
         """The end of an adapting window, stand-alone (ptrwm_adapt_reduce): ``window_accept`` summed over chains into
@@ -1067,24 +1064,17 @@ class RunPlan:
         probe_every = every if probe_every is None else int(probe_every)
         if probe_every < 1 or every % probe_every != 0:
             raise ValueError(f"ladder probe_every must be >= 1 and divide every = {every}, got {probe_every}")
-        beta, scale = self._keep[4], self._keep[1].temp_scale
-        self._tuning_tensors("ladder", (("pooled", pooled, (T,), True), ("beta_history", beta_history, (K + 1, T), False),
-                                        ("rate_history", rate_history, (K, T), False), ("skipped", skipped, (1,), False)))
-        b = beta.detach().cpu().numpy()
+        pointers = self._tuning_tensors("ladder", (
+            ("pooled", pooled, torch.int64, (T,), True), ("beta_history", beta_history, torch.float32, (K + 1, T), False),
+            ("rate_history", rate_history, torch.int64, (K, T), False), ("skipped", skipped, torch.int64, (1,), False)))
+        b = self._keep[4].detach().cpu().numpy()
         if not (b > 0).all() or not (b[:-1] > b[1:]).all():
             raise ValueError("the ladder's tuning needs a positive, strictly decreasing beta ladder")
-        ld = LadderArgs()
-        ld.struct_size = C.sizeof(LadderArgs)
-        ld.every, ld.probe_every, ld.until = every, probe_every, until
-        ld.gain, ld.decay = float(gain), float(decay)
-        ld.rescale_scales, ld.defer_update = (1 if rescale_scales else 0), (1 if defer_update else 0)
-        ld.beta = _require_device(beta, "beta", torch.float32)
-        ld.temp_scale = _require_device(scale, "proposal.temp_scale", torch.float32)
-        ld.pooled = _require_device(pooled, "ladder pooled", torch.int64)
-        ld.beta_history = _opt(beta_history, "ladder beta_history", torch.float32)
-        ld.rate_history = _opt(rate_history, "ladder rate_history", torch.int64)
-        ld.skipped = _opt(skipped, "ladder skipped", torch.int64)
-        self._ladder = (ld, C.byref(ld), (beta, scale, pooled, beta_history, rate_history, skipped))
+        # (beta, temp_scale: the plan's own tensors, checked and marshalled with the run's arguments and the proposal)
+        self._ladder = self._bind_block("ladder", LadderArgs, dict(
+            every=every, probe_every=probe_every, until=until, gain=float(gain), decay=float(decay),
+            rescale_scales=1 if rescale_scales else 0, defer_update=1 if defer_update else 0, beta=self._a.beta,
+            temp_scale=self._p.temp_scale), pointers)
 
     def ladder_probe(self) -> None:
         """One probe of the current log-densities, stand-alone (ptrwm_ladder_probe): every pair's quantised swap probability
@@ -1103,10 +1093,10 @@ class RunPlan:
         if on:
             if self._adapt is None:
                 raise RuntimeError("split_warmup: no adaptation set (set_adaptation)")
-            if getattr(self, "_warm_saved", None) is None:
+            if self._warm_saved is None:
                 self._warm_saved = (a.burn_in, a.swap_every, a.n_accept, a.sq_jump)
             a.burn_in, a.swap_every, a.n_accept, a.sq_jump = 0, 2**31 - 1, self._adapt[0].window_accept, None
-        elif getattr(self, "_warm_saved", None) is not None:
+        elif self._warm_saved is not None:
             a.burn_in, a.swap_every, a.n_accept, a.sq_jump = self._warm_saved
             self._warm_saved = None
 
@@ -1305,12 +1295,8 @@ class RunPlan:
         D = self.shape[2]
         if self.proposal_kind != PROPOSAL_NORMAL:
             raise ValueError("a preconditioner needs the Normal proposal")
-        if tuple(chol.shape) != (D, D) or chol.device != self.device:
-            raise ValueError(f"preconditioner chol must be a [{D}, {D}] tensor on {self.device}")
-        pa = PrecondArgs()
-        pa.struct_size = C.sizeof(PrecondArgs)
-        pa.chol = _require_device(chol, "preconditioner chol", torch.float32)
-        self._precond = (pa, C.byref(pa), chol)
+        self._precond = self._bind_block("preconditioner", PrecondArgs, {}, self._tuning_tensors(
+            "preconditioner", (("chol", chol, torch.float32, (D, D), True),)))
 
     def set_precond_update(self, sxx: Optional[torch.Tensor], sx: Optional[torch.Tensor] = None, count: Optional[torch.Tensor] = None,
                            run_xx: Optional[torch.Tensor] = None, run_x: Optional[torch.Tensor] = None,
@@ -1324,7 +1310,7 @@ class RunPlan:
         float32, ``weight_history`` [windows] float64 and ``skipped`` [1] int64 are optional records.  ``probe_every`` is the
         period of ``precond_probe``.  ``None`` switches it off."""
         if sxx is None:
-            self._precond_update = None
+            self._precond_update = self._precond_probe = None
             return
         if int(probe_every) < 1:
             raise ValueError("preconditioner probe_every must be >= 1")
@@ -1333,45 +1319,32 @@ class RunPlan:
         D, K = self.shape[2], int(windows)
         if K < 1:
             raise ValueError("preconditioner windows must be >= 1")
-        self._tuning_tensors("preconditioner", (("sxx", sxx, (D, D), True), ("sx", sx, (D,), True), ("count", count, (1,), True),
-                                                ("run_xx", run_xx, (D, D), True), ("run_x", run_x, (D,), True),
-                                                ("run_w", run_w, (1,), True), ("chol_history", chol_history, (K + 1, D, D), False),
-                                                ("weight_history", weight_history, (K,), False), ("skipped", skipped, (1,), False)))
-        up = PrecondUpdateArgs()
-        up.struct_size = C.sizeof(PrecondUpdateArgs)
-        up.chol = self._precond[0].chol
-        up.sxx = _require_device(sxx, "preconditioner sxx", torch.float64)
-        up.sx = _require_device(sx, "preconditioner sx", torch.float64)
-        up.count = _require_device(count, "preconditioner count", torch.int64)
-        up.run_xx = _require_device(run_xx, "preconditioner run_xx", torch.float64)
-        up.run_x = _require_device(run_x, "preconditioner run_x", torch.float64)
-        up.run_w = _require_device(run_w, "preconditioner run_w", torch.float64)
-        up.memory, up.jitter = float(memory), float(jitter)
-        up.min_count = float(4 * D if min_count is None else min_count)
-        up.windows = K
-        up.chol_history = _opt(chol_history, "preconditioner chol_history", torch.float32)
-        up.weight_history = _opt(weight_history, "preconditioner weight_history", torch.float64)
-        up.skipped = _opt(skipped, "preconditioner skipped", torch.int64)
-        # the probe: ptrwm_covariance of temperature 0 into the window's sums (their layout with temps = 1)
-        cv = CovArgs()
-        cv.struct_size = C.sizeof(CovArgs)
-        cv.temps, cv.every = 1, int(probe_every)
-        cv.sxx, cv.sx, cv.count = up.sxx, up.sx, up.count
-        self._precond_update = (up, C.byref(up), (sxx, sx, count, run_xx, run_x, run_w, chol_history, weight_history, skipped),
-                                cv, C.byref(cv))
+        f64, i64 = torch.float64, torch.int64
+        pointers = self._tuning_tensors("preconditioner", (
+            ("sxx", sxx, f64, (D, D), True), ("sx", sx, f64, (D,), True), ("count", count, i64, (1,), True),
+            ("run_xx", run_xx, f64, (D, D), True), ("run_x", run_x, f64, (D,), True), ("run_w", run_w, f64, (1,), True),
+            ("chol_history", chol_history, torch.float32, (K + 1, D, D), False),
+            ("weight_history", weight_history, f64, (K,), False), ("skipped", skipped, i64, (1,), False)))
+        self._precond_update = self._bind_block("preconditioner", PrecondUpdateArgs, dict(
+            chol=self._precond[0].chol, memory=float(memory), jitter=float(jitter),
+            min_count=float(4 * D if min_count is None else min_count), windows=K), pointers)
+        # the probe: ptrwm_covariance of temperature 0 into the window's sums (their layout with temps = 1; the update's block
+        # has checked them and keeps them alive)
+        up = self._precond_update[0]
+        self._precond_probe = self._bind_block("preconditioner", CovArgs, dict(
+            temps=1, every=int(probe_every), sxx=up.sxx, sx=up.sx, count=up.count), ())
 
     def precond_probe(self, step: int) -> None:
         """One probe of the factor's tuning behind step ``step`` (ptrwm_covariance on temperature 0 into the bound window sums,
         driven with burn-in 0 and ``every`` = the probe period: a step whose step counter is no multiple of it adds nothing).
         Host-step mode: the call sits between blocks of steps, never inside a captured one."""
-        bound = self._precond_update
-        if bound is None:
+        if self._precond_probe is None:
             raise RuntimeError("precond_probe: no update bound (set_precond_update)")
         a = self._a
         burn_in, dstep = a.burn_in, a.device_step
         a.burn_in, a.device_step = 0, None
         try:
-            self._split_call("ptrwm_covariance", bound[4], step)
+            self._split_call("ptrwm_covariance", self._precond_probe[1], step)
         finally:
             a.burn_in, a.device_step = burn_in, dstep
 
@@ -1379,13 +1352,7 @@ class RunPlan:
         """The factor's update of window ``window`` from the bound sums (ptrwm_precond_update): the bound ``chol`` is rewritten
         in place - or kept, and ``skipped`` counted, where the sums do not give a positive-definite matrix - and the window
         sums are left zero.  Enqueues one small kernel."""
-        bound = self._precond_update
-        if bound is None:
-            raise RuntimeError("precond_update: no update bound (set_precond_update)")
-        with self._guard:
-            rc = self._lib.ptrwm_precond_update(bound[1], self.shape[2], int(window), _stream(self.device))
-        if rc != 0:
-            raise PTRWMError(rc, "ptrwm_precond_update")
+        self._tuning_call("precond_update", self._precond_update, "update bound (set_precond_update)", window, extent=2)
 
     def split_accept(self, step: int, logp_proposed: torch.Tensor, ext_swap_u: Optional[torch.Tensor] = None,
                      accept_flags: Optional[torch.Tensor] = None, swap_event_offset: int = 0, no_sweep: bool = False) -> None:
