@@ -2306,10 +2306,9 @@ int32_t ptrwm_split_propose_precond(const ptrwm_proposal_desc *proposal, const p
                           prec_lds_bytes(PTRWM_MAX_DIM), raised_mask) != hipSuccess)
       return PTRWM_E_LAUNCH;
   }
-  // a workgroup stages the factor once and walks tiles: no more workgroups than keep every compute unit busy
+  // a workgroup stages the factor once and walks tiles (precond.h prec_grid)
   const long long tiles = (a.n_reps + kPrecRows - 1) / kPrecRows;
-  const long long cap = 8ll * (device_cus() > 0 ? device_cus() : 256);
-  hipLaunchKernelGGL(precond_propose_kernel, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(kPrecThreads), lds,
+  hipLaunchKernelGGL(precond_propose_kernel, dim3((unsigned)prec_grid(tiles, device_cus())), dim3(kPrecThreads), lds,
                      (hipStream_t)stream, a);
   return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }

@@ -48,6 +48,12 @@ constexpr int kPrecWaves = kPrecThreads / 64;
 constexpr int kPrecRows = kPrecBlock * kPrecWaves;  // 64
 constexpr int kPrecMaxDim = 104;                    // PTRWM_MAX_DIM of include/ptrwm.h
 
+// the launch: workgroup b walks tiles b, b + grid, ... - no more workgroups than keep every compute unit busy, since each stages
+// the factor once (cus: the device's compute units; 256 where the count is unknown)
+constexpr int kPrecGroupsPerCu = 8;
+PTRWM_HD constexpr long long prec_grid_cap(int cus) { return (long long)kPrecGroupsPerCu * (cus > 0 ? cus : 256); }
+PTRWM_HD constexpr long long prec_grid(long long n_tiles, int cus) { return n_tiles < prec_grid_cap(cus) ? n_tiles : prec_grid_cap(cus); }
+
 PTRWM_HD constexpr int prec_blocks(int dim) { return (dim + kPrecBlock - 1) / kPrecBlock; }
 PTRWM_HD constexpr int prec_padded(int dim) { return kPrecBlock * prec_blocks(dim); }
 // one past the last k the chain of coordinate i visits, and the K-steps of block bi

@@ -44,6 +44,19 @@ def chain_end(i: int) -> int:
     return BLOCK * (i // BLOCK + 1)
 
 
+ROWS = 64  # replica rows per tile (precond.h kPrecRows)
+GROUPS_PER_CU = 8  # (precond.h kPrecGroupsPerCu)
+
+
+def grid(n_tiles: int, cus: int) -> int:
+    """Workgroups the proposal kernel is launched with (precond.h prec_grid): workgroup b walks tiles b, b + grid, ..."""
+    return min(n_tiles, GROUPS_PER_CU * (cus if cus > 0 else 256))
+
+
+def tiles(n_rows: int) -> int:
+    return -(-n_rows // ROWS)
+
+
 def propose_rows(x, chol, z, scale, exact_libm: bool = False):
     """y [n, dim] of the rule: inc_i = the fmaf chain over k = 0 .. chain_end(i) - 1 ascending of L[i][k] z[k] from +0 (L zero
     above the diagonal, z zero at and past dim), y_i = fmaf(s, inc_i, x_i).  x, z [n, dim] float32, chol [dim, dim] (only k <= i

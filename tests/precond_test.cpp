@@ -6,11 +6,13 @@
 //  2. a replay of the kernel - staging of the factor, the states and the normals through an LDS image, the K-steps in the matrix
 //     instruction's operand and result layout (k ascending inside an instruction), the epilogue in place - against the direct
 //     chain of the rule, bit for bit;
-//  3. the update rule: L L^T against A within float rounding plus Cholesky's backward error, the three skips, `memory`.
+//  3. the update rule: L L^T against A within float rounding plus Cholesky's backward error, the three skips, `memory`;
+//  4. the launch: 1 <= prec_grid <= n_tiles and prec_grid <= 8 cus (256 compute units where the count is unknown).
 // With "update" it reads cases from stdin (one per line: dim memory jitter min_count count, then as bit patterns sxx, sx,
 // run_xx, run_x, run_w (uint64) and chol (uint32)) and prints "outcome zeroed chol.. run_xx.. run_x.. run_w" per case; with
 // "propose" lines "dim n s_bits x.. chol.. z.." (uint32 bit patterns, x and z [n, dim]) give "y.." of the REPLAY and of the
-// direct chain; with "geometry" dims give "blocks padded stride lds_bytes z_items l_passes".
+// direct chain; with "geometry" dims give "blocks padded stride lds_bytes z_items l_passes"; with "grid" pairs "n_tiles cus"
+// give the workgroups of the launch.
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
@@ -163,6 +165,17 @@ static std::vector<float> replay_tile(int dim, int n_rows, int head, const float
 
 static const int kDims[] = {1, 3, 4, 5, 16, 17, 30, 33, 64, 104};
 static const int kRows[] = {1, 5, 64};
+
+// the launch: at least one workgroup, none without a tile, at most kPrecGroupsPerCu per compute unit (256 where unknown)
+static void test_grid() {
+  static_assert(kPrecGroupsPerCu == 8, "the launch");
+  for (int cus : {-1, 0, 1, 2, 7, 64, 256, 304, 1 << 20})
+    for (long long n_tiles : {1ll, 2ll, 15ll, 16ll, 17ll, 2047ll, 2048ll, 2049ll, 4134ll, 32768ll, 1ll << 31, 1ll << 40}) {
+      const long long g = prec_grid(n_tiles, cus), cap = 8ll * (cus > 0 ? cus : 256);
+      CHECK(1 <= g && g <= n_tiles && g <= cap, "grid(%lld, %d) = %lld", n_tiles, cus, g);
+      CHECK(g == n_tiles || g == cap, "grid(%lld, %d) = %lld: neither every tile nor the cap", n_tiles, cus, g);
+    }
+}
 
 static void test_maps_and_replay() {
   static_assert(kPrecRows == 64 && kPrecThreads == 256 && kPrecBlock == 16 && kPrecK == 4, "the tile");
@@ -412,6 +425,13 @@ int main(int argc, char **argv) {
       std::printf("%d %d %d %d %d %d\n", prec_blocks(dim), prec_padded(dim), prec_stride(dim), prec_lds_bytes(dim), prec_z_items(dim), prec_l_passes(dim));
     return 0;
   }
+  if (argc > 1 && std::strcmp(argv[1], "grid") == 0) {
+    long long n_tiles;
+    int cus;
+    while (std::scanf("%lld %d", &n_tiles, &cus) == 2) std::printf("%lld\n", prec_grid(n_tiles, cus));
+    return 0;
+  }
+  test_grid();
   test_maps_and_replay();
   test_update();
   std::printf("precond ok: %lld checks\n", g_checks);

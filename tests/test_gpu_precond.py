@@ -148,10 +148,14 @@ def _run_update(device, dim, sxx, sx, n, run_xx, run_x, run_w, chol, *, memory, 
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("dim", [1, 5, 30, 104])
+@pytest.mark.parametrize("dim", [1, 2, 5, 30, 63, 64, 65, 104])
 def test_update_kernel_against_python_floats_bitwise(device, dim):
-    """Integer-valued sums, then generic ones with a running triple and memory 0.5, then the three skips: the kernel's factor,
-    history row, weight, running triple, zeroed window sums and skip count equal precond_reference, bit for bit."""
+    """Integer-valued sums, then generic ones with a running triple and memory 0.5, then the skips: the kernel's factor, history
+    row, weight, running triple, zeroed window sums and skip count equal precond_reference, bit for bit.  The kernel runs one
+    thread per row with barriers inside the column loop: dims 63, 64 and 65 put the last row in front of, on and behind a wave
+    boundary.  Among the skips: a factor whose entries are finite as doubles and infinite as floats (sums scaled to entries of
+    about 1e40), a running weight that is not a number, and a pivot that fails at column 0 (coordinate 0 identically zero, no
+    jitter).  Last, K = 1 with window 0: both history rows are written by the one call."""
     rng = np.random.default_rng(4000 + dim)
     bits = lambda a: np.ascontiguousarray(a).view(np.uint32 if np.asarray(a).dtype == np.float32 else np.uint64)  # noqa: E731
     n = 6 * dim + 7
@@ -168,6 +172,14 @@ def test_update_kernel_against_python_floats_bitwise(device, dim):
     bad = sxx.copy()
     bad[dim // 2, 0] = np.inf
     cases.append(("infinite sum", bad, sx, n, np.zeros((dim, dim)), np.zeros(dim), 0.0, dict(memory=1.0, jitter=1e-6, min_count=4.0 * dim), PR.NOT_POSITIVE))
+    cases.append(("float overflow", sxx * 1e80, sx * 1e40, n, np.zeros((dim, dim)), np.zeros(dim), 0.0, dict(memory=1.0, jitter=1e-6, min_count=4.0 * dim), PR.NOT_POSITIVE))
+    cases.append(("weight not a number", sxx, sx, n, rxx, rx, float("nan"), dict(memory=0.5, jitter=1e-6, min_count=4.0 * dim), PR.FEW_DRAWS))
+    bad = sxx.copy()
+    bad[:, 0] = 0.0
+    bad[0, 1:] = 123.0  # (above the diagonal: never read)
+    bad_x = sx.copy()
+    bad_x[0] = 0.0
+    cases.append(("pivot 0", bad, bad_x, n, np.zeros((dim, dim)), np.zeros(dim), 0.0, dict(memory=1.0, jitter=0.0, min_count=4.0 * dim), PR.NOT_POSITIVE))
     for name, sxx, sx, n, rxx, rx, rw, kw, expect in cases:
         chol0 = _nan_upper(rng.standard_normal((dim, dim)))
         outcome, want, want_xx, want_x, want_w = PR.update(sxx, sx, n, rxx, rx, rw, chol=chol0, **kw)
@@ -192,6 +204,20 @@ def test_update_kernel_against_python_floats_bitwise(device, dim):
                          min_count=4.0 * dim, window=0)
     assert np.array_equal(bits(t["chol_history"][0]), bits(np.tril(np.nan_to_num(chol0, nan=0.0))))
     assert np.array_equal(bits(t["chol_history"][1]), bits(np.tril(np.nan_to_num(got, nan=0.0))))
+    # ... and with K = 1 that call writes the whole record: both history rows and the one weight
+    chol0 = _nan_upper(rng.standard_normal((dim, dim)))
+    sxx, sx = _sums(rng, dim, n, integer=False)
+    kw = dict(memory=1.0, jitter=1e-6, min_count=4.0 * dim)
+    outcome, want, want_xx, want_x, want_w = PR.update(sxx, sx, n, np.zeros((dim, dim)), np.zeros(dim), 0.0, chol=chol0, **kw)
+    assert outcome == PR.UPDATED
+    got, t = _run_update(device, dim, sxx, sx, n, np.zeros((dim, dim)), np.zeros(dim), 0.0, chol0, **kw, window=0, K=1)
+    assert np.array_equal(bits(got), bits(want)) and t["skipped"].tolist() == [0]
+    assert t["chol_history"].shape == (2, dim, dim) and t["weight_history"].shape == (1,)
+    assert np.array_equal(bits(t["chol_history"][0]), bits(np.tril(np.nan_to_num(chol0, nan=0.0))))
+    assert np.array_equal(bits(t["chol_history"][1]), bits(np.tril(np.nan_to_num(want, nan=0.0))))
+    assert bits(t["weight_history"])[0] == bits(np.array([want_w]))[0] == bits(t["run_w"])[0]
+    assert np.array_equal(bits(t["run_xx"]), bits(want_xx)) and np.array_equal(bits(t["run_x"]), bits(want_x))
+    assert t["count"].tolist() == [0] and not t["sx"].any() and not np.tril(t["sxx"]).any()
 
 
 # ---- 5. invariance with a fixed factor --------------------------------------------------------------------------------------------
@@ -227,17 +253,24 @@ def _fixed_factor(dim, seed, lo=0.25, hi=2.5):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("fkey", ["sgauss", "rc15", "user"])
+@pytest.mark.parametrize("fkey", ["sgauss", "rc15", "user", "sgauss-rounds"])
 def test_fixed_factor_leaves_the_tempered_laws_invariant(device, fkey):
     """tests/invariance_reference.py as it stands, with its own P_MIN / Z_MAX: a fixed dense factor of condition 10, a ladder of 4
     with swaps, every replica from an exact draw, the final states hold the tempered law at every rung.  sgauss and rc15 are
     targets with a fused kernel - the split route with the library's density - and `user` a density in plain torch.  The steps
-    run as captured blocks."""
+    run as captured blocks.  32 768 ladders x 4 are 2 048 tiles of the proposal kernel, one per workgroup on 256 compute units;
+    sgauss-rounds has 65 536 ladders, so that every workgroup walks at least two tiles in every one of the 300 steps
+    (precond_reference.grid; tests/test_gpu_precond_rounds.py)."""
     from algorithms._engine_core import EngineRun
 
-    dim, T, Cn, se = 4, 4, 32768, 2
+    case, rounds = f"gpu-precond-{fkey}", fkey.endswith("-rounds")  # (the seed comes from the case's name)
+    fkey = fkey.split("-")[0]
+    dim, T, Cn, se = 4, 4, 65536 if rounds else 32768, 2
+    if rounds:
+        cus = torch.cuda.get_device_properties(device).multi_processor_count
+        assert cus >= 2 and -(-PR.tiles(Cn * T) // PR.grid(PR.tiles(Cn * T), cus)) >= 2
     fam = R.family("gauss" if fkey == "user" else fkey, dim)
-    s = R.setup_case(f"gpu-precond-{fkey}", fam, "Normal", T, 0.1, Cn)
+    s = R.setup_case(case, fam, "Normal", T, 0.1, Cn)
     if fkey == "user":
         mu = torch.tensor(fam.mu, device=device, dtype=torch.float32)
         prec = torch.tensor(1.0 / fam.var, device=device, dtype=torch.float32)
@@ -256,7 +289,7 @@ def test_fixed_factor_leaves_the_tempered_laws_invariant(device, fkey):
     out = {"state": run.state.cpu().numpy(), "n_accept": run.n_accept.cpu().numpy(), "swap_accept": run.swap_accept.cpu().numpy()}
     rates = R.power_conditions(out, fam, N_STEPS, se)
     r = R.check(out["state"], s["betas"], fam)
-    print(f"READINGS precond-{fkey}: {R.describe(r)}; acceptance {rates['accept'].min():.2f}..{rates['accept'].max():.2f}, "
+    print(f"READINGS {case[4:]}: {R.describe(r)}; acceptance {rates['accept'].min():.2f}..{rates['accept'].max():.2f}, "
           f"swaps {rates['swap'].min():.2f}..{rates['swap'].max():.2f}")
     assert R.inside(r), R.describe(r)
     assert np.array_equal(run.proposal_factor().cpu().numpy(), chol)  # a fixed factor stays what it was
@@ -383,6 +416,113 @@ def test_adaptation_follows_the_reference_window_by_window(device):
     run.advance(20)
     torch.cuda.synchronize()
     assert np.array_equal(run.proposal_factor().cpu().numpy(), factor) and len(calls) == 6
+
+
+@pytest.mark.gpu
+def test_adaptation_with_a_ladder_learns_from_temperature_0_only(device):
+    """The window-by-window test with a ladder [1, 0.5, 0.25] (the probe is then ptrwm_covariance with temps = 1 on a [C, T, D]
+    state): the library's diagonal Gaussian in dim 5 - so that eager and captured densities are the same bits - 4096 ladders,
+    every replica from an exact draw of its own tempered law, two windows of 80 steps probed every 40 (all inside burn-in: no
+    swap event), a trace whose second extent is 1: temperature 0 at the probe steps.
+      * After each window the factor is within one float32 ulp of precond_reference on the math.fsum sums of that trace, the
+        weight is probes x ladders as the schedule implies (memory 0.5: 8 192, then 12 288) and nothing is skipped.  The device's
+        sums differ from fsum's by the order of n = 8 192 fp64 additions: to first order the factor moves by
+        (n + dim) 2^-53 kappa(A) relative, with kappa(A) < 8 here (variances 0.5 .. 2) below 8e-12 - asserted, from the reference's
+        own A, to lie below half a float32 ulp, 2^-25 = 3e-8 - so one ulp covers a rounding that falls the other way.
+      * The control that gives the test its point: a twin run with a full trace has the same temperature-0 rows bit for bit, and
+        the same sums taken from its rung 1 (variance Sigma / 0.5) give a factor sqrt 2 larger, far more than one ulp away.  A
+        probe that read another rung, or all rungs, fails the first check.
+      * A third run, same seed, use_graph left on and no trace: every chunk of 40 steps replays captured blocks.  At the end of
+        window 0 its states equal the eager run's bit for bit - the factor was the identity for both - and its window-0 factor
+        is within one ulp of the same reference.  Nothing is claimed about window 1 between the two runs: their factors may
+        differ by an ulp."""
+    import math
+
+    from algorithms._engine_core import EngineRun
+
+    dim, Cn, T, W, P = 5, 4096, 3, 80, 40
+    fam = R.family("gauss", dim)
+    betas = np.array([1.0, 0.5, 0.25], np.float32)
+    x0 = R.exact_starts(fam, np.random.default_rng(78), betas, Cn)
+    scales = (2.38 / math.sqrt(dim) * 0.8 / np.sqrt(betas)).astype(np.float32)
+
+    def make():
+        prop = E.Proposal(E.PROPOSAL_NORMAL, torch.tensor(scales, device=device))
+        with pytest.warns(UserWarning, match="split steps"):
+            return EngineRun(target_dist=_EngineTarget(fam.spec().engine(device)), proposal=prop, beta_ladder=[float(b) for b in betas],
+                             dim=dim, device=device, n_replicas=Cn, initial_state=x0, burn_in=2 * W, swap_every=1, swap_mode="exchange",
+                             swap_order="sequential", seed=6, adapt_cov=True, cov_adapt_every=W, cov_adapt_probe_every=P)
+
+    def sums_of(rows):
+        sxx = np.array([[math.fsum(rows[:, i] * rows[:, j]) if j <= i else 0.0 for j in range(dim)] for i in range(dim)])
+        return sxx, np.array([math.fsum(rows[:, i]) for i in range(dim)])
+
+    ulps = lambda a, b: np.abs(a.view(np.int32).astype(np.int64) - b.view(np.int32).astype(np.int64))  # noqa: E731
+    tri = np.tril_indices(dim)
+    run = make()
+    assert run.split and run.density_fn is None
+    assert np.array_equal(run.proposal_factor().cpu().numpy(), np.eye(dim, dtype=np.float32))
+    rxx, rx, rw, factor = np.zeros((dim, dim)), np.zeros(dim), 0.0, np.eye(dim, dtype=np.float32)
+    wants, cold0, state0, logp0 = [], None, None, None
+    for window in range(2):
+        tr = torch.empty(W // P, Cn, 1, dim, device=device)
+        run.advance(W, trace=tr, trace_every=P)
+        torch.cuda.synchronize()
+        assert run._graph is None  # (a traced chunk runs step by step)
+        rows = tr.cpu().numpy().reshape(-1, dim).astype(np.float64)
+        n = rows.shape[0]
+        assert n == (W // P) * Cn
+        sxx, sx = sums_of(rows)
+        outcome, want, rxx, rx, rw = PR.update(sxx, sx, n, rxx, rx, rw, 0.5, 1e-6, 4.0 * dim, factor)
+        assert outcome == PR.UPDATED
+        m = rx / rw
+        kappa = np.linalg.cond(np.tril(rxx) / rw + np.tril(rxx, -1).T / rw - np.outer(m, m))
+        bound = (n + dim) * 2.0 ** -53 * kappa
+        assert kappa < 8.0 and bound < 2.0 ** -25
+        h = run.preconditioner_history()
+        assert h["skipped"] == 0
+        assert float(h["weights"][window]) == rw == (8192.0 if window == 0 else 12288.0)
+        got = run.proposal_factor().cpu().numpy()
+        worst = int(ulps(got[tri], want[tri]).max())
+        print(f"READINGS ladder adaptation window {window}: factor within {worst} float32 ulp(s) of the reference, weight {rw:.0f}, "
+              f"kappa {kappa:.2f}, bound {bound:.2e} against half an ulp {2.0 ** -25:.2e}")
+        assert worst <= 1
+        assert np.array_equal(h["factors"][window + 1].cpu().numpy(), got) and not np.triu(got, 1).any()
+        wants.append(want)
+        if window == 0:
+            cold0, state0, logp0 = tr.clone(), run.state.clone(), run.logp.clone()
+        factor = got  # (the next window ran with the device's own factor)
+    # the control: rung 1 of a full trace
+    twin = make()
+    full = torch.empty(W // P, Cn, T, dim, device=device)
+    twin.advance(W, trace=full, trace_every=P)
+    torch.cuda.synchronize()
+    assert torch.equal(full[:, :, :1], cold0)
+    got0 = twin.proposal_factor().cpu().numpy()
+    assert int(ulps(got0[tri], wants[0][tri]).max()) <= 1
+    sxx, sx = sums_of(full[:, :, 1].cpu().numpy().reshape(-1, dim).astype(np.float64))
+    outcome, hot, _, _, _ = PR.update(sxx, sx, (W // P) * Cn, np.zeros((dim, dim)), np.zeros(dim), 0.0, 0.5, 1e-6, 4.0 * dim,
+                                      np.eye(dim, dtype=np.float32))
+    ratio = np.diag(hot) / np.diag(got0)
+    print(f"READINGS ladder adaptation control: the factor of rung 1's sums is {ratio.min():.3f}..{ratio.max():.3f} times the device's, "
+          f"{int(ulps(got0[tri], hot[tri]).max())} ulps away")
+    assert outcome == PR.UPDATED and int(ulps(got0[tri], hot[tri]).max()) > 1
+    assert np.all((ratio > 1.3) & (ratio < 1.55))  # sqrt 2, within the sampling error of 8 192 draws (1 %) many times over
+    # captured blocks
+    graph = make()
+    assert graph.use_graph
+    graph.advance(W)
+    torch.cuda.synchronize()
+    assert graph._graph is not None
+    assert torch.equal(graph.state.view(torch.int32), state0.view(torch.int32)) and torch.equal(graph.logp.view(torch.int32), logp0.view(torch.int32))
+    g0 = graph.proposal_factor().cpu().numpy()
+    assert int(ulps(g0[tri], wants[0][tri]).max()) <= 1
+    h = graph.preconditioner_history()
+    assert h["skipped"] == 0 and float(h["weights"][0]) == 8192.0
+    graph.advance(W)
+    torch.cuda.synchronize()
+    h = graph.preconditioner_history()
+    assert h["skipped"] == 0 and float(h["weights"][1]) == 12288.0 and not bool(torch.isnan(h["factors"]).any())
 
 
 @pytest.mark.gpu

@@ -50,6 +50,34 @@ def test_geometry_of_the_gpu_shapes(precond_exe):
     assert geo[104][5] == 28
 
 
+def test_launch_grid_mirror_is_the_headers(precond_exe):
+    """precond_reference.grid, from which the GPU tests prove that their batches take a second and a third round, against
+    precond.h prec_grid (what ptrwm_split_propose_precond launches with): 256 compute units with every tile count the GPU tests
+    use - the round cases of tests/test_gpu_precond_rounds.py, the 4 tiles of the alignment tests, the 2 048 and 4 096 tiles of
+    the invariance cases - the same for other device sizes, an unknown count, and the cap's neighbours."""
+    import test_gpu_precond_rounds as RD
+
+    pairs = []
+    for cus in (2, 64, 256, 304):
+        G = PR.grid(RD.HUGE, cus)
+        assert G == 8 * cus
+        tiles = {1, 4, 2048, 4096, G - 1, G, G + 1, 2 * G, RD.HUGE}
+        for dim, k, T in RD.CASES.values():
+            G2, r, n_tiles, Cn = RD.plan_rounds(k, T, cus)
+            assert G2 == G and 0 < r < G and r % 4 != 0 and n_tiles == k * G + r
+            assert Cn * T == 64 * (n_tiles - 1) + 5 and PR.tiles(Cn * T) == n_tiles  # the last tile holds 5 rows
+            assert -(-n_tiles // PR.grid(n_tiles, cus)) == k + 1
+            tiles.add(n_tiles)
+        pairs += [(t, cus) for t in sorted(tiles)]
+    pairs += [(t, cus) for cus in (0, -1) for t in (1, 2047, 2048, 2049, 4134)]  # (unknown: 256 compute units)
+    assert (PR.tiles(210), PR.tiles(32768 * 4), PR.tiles(65536 * 4), PR.tiles(64), PR.tiles(65)) == (4, 2048, 4096, 1, 2)
+    out = subprocess.run([precond_exe, "grid"], input="".join(f"{t} {c}\n" for t, c in pairs), capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = [int(ln) for ln in out.stdout.splitlines()]
+    assert got == [PR.grid(t, c) for t, c in pairs]
+    assert PR.grid(4134, 256) == 2048 == PR.grid(4134, 0) and PR.grid(5, 256) == 5 and PR.grid(RD.HUGE, 2) == 16
+
+
 def test_fmaf_vec_is_libm_fmaf():
     """The array form of the reference's fused multiply-add against libm's, on random triples, on products that cancel against
     the addend and on sums constructed to lie next to a float32 rounding tie (where rounding twice would go wrong)."""
