@@ -3,36 +3,26 @@ launch cuts and the kernel geometry against brute force, the struct's C layout, 
 that returns before a HIP call, the estimators on hand-made sums, and Sokal's window on the exact AR(1) sequence."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import ptrwm_hip as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+from host_harness import assert_layout, c_layout, run_exe, sanitized_exe, valid_args
 
 
 @pytest.fixture(scope="module")
 def acf_exe(tmp_path_factory):
     """tests/acf_test.cpp, a program of its own, compiled as plain C++ under AddressSanitizer and UBSan."""
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "acf_test.cpp")
-    exe = str(tmp_path_factory.mktemp("acf") / "acf_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", src, "-o", exe])
-    return exe
+    return sanitized_exe(tmp_path_factory.mktemp("acf"), "acf_test.cpp")
 
 
 def test_rule_cuts_and_geometry_against_brute_force(acf_exe):
     """csrc/acf.h and the cut of csrc/schedule.h in tests/acf_test.cpp: snapshot numbers and ring slots against a replay that
     counts, for burn_in that is and is not a multiple of every; the lags before and after the ring fills; the cuts with a
     histogram at another period; acf_geometry for every temps * dim in 1..26 624."""
-    out = subprocess.run([acf_exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "acf ok:" in out.stdout
+    run_exe(acf_exe, ok="acf ok:")
 
 
 def test_gpu_cases_have_the_geometry_they_are_named_for(acf_exe):
@@ -41,10 +31,9 @@ def test_gpu_cases_have_the_geometry_they_are_named_for(acf_exe):
     from test_gpu_acf import EQUALITY_CASES
 
     lines = "".join(f"{c['temps'] * c['dim']}\n" for c in EQUALITY_CASES)
-    out = subprocess.run([acf_exe, "geometry"], input=lines, capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    out = run_exe(acf_exe, "geometry", input=lines, timeout=60)
     geo = {c["name"]: dict(zip(("cols", "groups", "per", "chains", "last"), map(int, ln.split())), **c)
-           for c, ln in zip(EQUALITY_CASES, out.stdout.splitlines())}
+           for c, ln in zip(EQUALITY_CASES, out.splitlines())}
     assert len(geo) == len(EQUALITY_CASES)
     g = geo["partial_tile"]  # 70 chains: one tile, not full
     assert g["groups"] == 1 and g["per"] > 1 and g["Cn"] == 70 < g["chains"]
@@ -63,8 +52,8 @@ def test_gpu_cases_have_the_geometry_they_are_named_for(acf_exe):
 def test_launch_cuts_with_a_histogram_at_another_period(acf_exe):
     """The launches of ptrwm_run_with_autocorr replayed step by step in Python: acf every 7, histogram every 5, burn_in 11."""
     step0, n, burn, ae, he, cap = 3, 60, 11, 7, 5, 1000
-    out = subprocess.run([acf_exe, "cuts", *map(str, (step0, n, burn, ae, he, cap))], capture_output=True, text=True, timeout=60)
-    got = [tuple(int(v) for v in ln.split()) for ln in out.stdout.splitlines()]
+    out = run_exe(acf_exe, "cuts", step0, n, burn, ae, he, cap, timeout=60)
+    got = [tuple(int(v) for v in ln.split()) for ln in out.splitlines()]
     want, start = [], step0
     for s in range(step0, step0 + n):  # step s has step counter s + 1
         sc = s + 1
@@ -75,52 +64,22 @@ def test_launch_cuts_with_a_histogram_at_another_period(acf_exe):
     assert got == want and sum(c[2] for c in got) == 8 and sum(c[3] for c in got) == 10  # step counters 14 .. 63; 15 .. 60
     assert any(c[2] and c[3] for c in got)  # step counter 35: both
     # no histogram, nothing due: one launch
-    out = subprocess.run([acf_exe, "cuts", "0", "10", "10", "3", "0", "1000"], capture_output=True, text=True, timeout=60)
-    assert out.stdout.split() == ["0", "10", "0", "0"]
+    assert run_exe(acf_exe, "cuts", 0, 10, 10, 3, 0, 1000, timeout=60).split() == ["0", "10", "0", "0"]
 
 
 def test_acf_struct_layout_matches_the_c_header(tmp_path):
     fields = [f[0] for f in E.AcfArgs._fields_]
     assert fields == ["struct_size", "temps", "every", "max_lag", "ring", "sxy", "head", "tail", "pairs"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){",
-             'printf("size %zu\\n", sizeof(ptrwm_acf_args));']
-    lines += [f'printf("{f} %zu\\n", offsetof(ptrwm_acf_args, {f}));' for f in fields]
-    lines.append('printf("abi %d\\n", PTRWM_ABI_VERSION);')
-    lines.append('printf("maxlag %d\\n", PTRWM_ACF_MAX_LAG);')
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert C.sizeof(E.AcfArgs) == int(got["size"])
-    for f in fields:
-        assert getattr(E.AcfArgs, f).offset == int(got[f]), f
-    assert int(got["abi"]) == E.ABI_VERSION == 3  # additive: the version stays
-    assert int(got["maxlag"]) == E.ACF_MAX_LAG == 1024
+    got = c_layout(tmp_path, {"ptrwm_acf_args": fields}, macros=("PTRWM_ABI_VERSION", "PTRWM_ACF_MAX_LAG"))
+    assert_layout(E.AcfArgs, "ptrwm_acf_args", fields, got)
+    assert got["PTRWM_ABI_VERSION"] == E.ABI_VERSION == 3  # additive: the version stays
+    assert got["PTRWM_ACF_MAX_LAG"] == E.ACF_MAX_LAG == 1024
     assert "ptrwm_autocorr" in E.SYMBOLS and "ptrwm_run_with_autocorr" in E.SYMBOLS
 
 
 def _valid(n_temps=4):
-    """Arguments both entry points accept up to their first HIP call (the pointers point at host memory a refused call never
-    reads)."""
-    buf = C.create_string_buffer(64)
-    ptr = C.cast(buf, C.c_void_p)
-    td, pd, ra, ac = E.TargetDesc(), E.ProposalDesc(), E.RunArgs(), E.AcfArgs()
-    td.kind, td.dim = E.TARGET_ROUGH_CARPET, 30
-    pd.kind, pd.temp_scale = E.PROPOSAL_NORMAL, ptr
-    ra.struct_size, ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = C.sizeof(E.RunArgs), n_temps, 4, 10, 1
-    ra.state = ra.logp = ra.beta = ptr
-    ac.struct_size, ac.temps, ac.every, ac.max_lag = C.sizeof(E.AcfArgs), 1, 1, 8
-    ac.ring = ac.sxy = ac.head = ac.tail = ac.pairs = ptr
-    hi, ad, ld = E.HistArgs(), E.AdaptArgs(), E.LadderArgs()
-    hi.struct_size, hi.temps, hi.every, hi.n_bins = C.sizeof(E.HistArgs), 1, 1, 64
-    hi.lo = hi.scale = hi.counts = ptr
-    ad.struct_size, ad.every, ad.until, ad.target, ad.gain, ad.decay = C.sizeof(E.AdaptArgs), 5, 0, 0.234, 3.0, 0.5
-    ad.min_scale, ad.max_scale, ad.temp_scale, ad.window_accept, ad.pooled = 1e-3, 1e3, ptr, ptr, ptr
-    ld.struct_size, ld.every, ld.probe_every, ld.until, ld.gain, ld.decay = C.sizeof(E.LadderArgs), 10, 5, 0, 2.0, 0.5
-    ld.beta, ld.temp_scale, ld.pooled = ptr, ptr, ptr
-    return {"buf": buf, "ptr": ptr, "td": td, "pd": pd, "ra": ra, "ac": ac, "hi": hi, "ad": ad, "ld": ld}
+    """Arguments both entry points accept up to their first HIP call, with every block that check_acf comes after."""
+    return valid_args("ac", "hi", "ad", "ld", n_temps=n_temps)  # ld.every == 10: "3 does not divide 10" below
 
 
 def test_acf_validation_needs_no_gpu():

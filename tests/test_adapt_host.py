@@ -3,31 +3,20 @@ and the launch / reduce / update sequence against brute force, the update rule a
 every validation code of the three entry points that returns before a HIP call, the classes' constructor checks, and
 adaptation_sync over two gloo ranks."""
 import ctypes as C
-import os
-import socket
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import ptrwm_hip as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+from host_harness import assert_layout, c_layout, gloo_world, run_exe, sanitized_exe, valid_args
 
 
 @pytest.fixture(scope="module")
 def adapt_exe(tmp_path_factory):
     """tests/adapt_test.cpp, a program of its own, compiled as plain C++ under AddressSanitizer and UBSan."""
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "adapt_test.cpp")
-    exe = str(tmp_path_factory.mktemp("adapt") / "adapt_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", src, "-o", exe])
-    return exe
+    return sanitized_exe(tmp_path_factory.mktemp("adapt"), "adapt_test.cpp")
 
 
 def test_window_helpers_and_cuts_against_brute_force(adapt_exe):
@@ -36,9 +25,7 @@ def test_window_helpers_and_cuts_against_brute_force(adapt_exe):
     and cut into single steps, against a loop over the windows - each step covered once, no adapting launch across a window
     end, the same (reduce, update) sequence whatever the cut.  (The window helpers themselves: schedule_test.cpp,
     test_host_logic.py.)"""
-    out = subprocess.run([adapt_exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "adapt ok:" in out.stdout
+    run_exe(adapt_exe, ok="adapt ok:")
 
 
 def _bits(x):
@@ -66,9 +53,8 @@ def test_update_rule_against_numpy_float64(adapt_exe):
     lo, hi = np.minimum(lo, hi), np.maximum(lo, hi)
     lines = "".join(f"{sb} {a} {c} {g!r} {t!r} {l} {h}\n" for sb, a, c, g, t, l, h in
                     zip(_bits(s_old), accepted, counted, gain_k.tolist(), target.tolist(), _bits(lo), _bits(hi)))
-    out = subprocess.run([adapt_exe, "update"], input=lines, capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stderr[-2000:]
-    got = np.array([int(v) for v in out.stdout.split()], np.uint32).view(np.float32)
+    out = run_exe(adapt_exe, "update", input=lines, timeout=120)
+    got = np.array([int(v) for v in out.split()], np.uint32).view(np.float32)
     assert got.shape == (n,)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         rate = accepted.astype(np.float64) / counted.astype(np.float64)
@@ -91,37 +77,16 @@ FIELDS = ["struct_size", "every", "until", "target", "gain", "decay", "min_scale
 
 def test_adapt_struct_layout_matches_the_c_header(tmp_path):
     assert [f[0] for f in E.AdaptArgs._fields_] == FIELDS
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){",
-             'printf("size %zu\\n", sizeof(ptrwm_adapt_args));']
-    lines += [f'printf("{f} %zu\\n", offsetof(ptrwm_adapt_args, {f}));' for f in FIELDS]
-    lines.append('printf("abi %d\\n", PTRWM_ABI_VERSION);')
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert C.sizeof(E.AdaptArgs) == int(got["size"])
-    for f in FIELDS:
-        assert getattr(E.AdaptArgs, f).offset == int(got[f]), f
-    assert int(got["abi"]) == E.ABI_VERSION == 3  # additive: the version stays
+    got = c_layout(tmp_path, {"ptrwm_adapt_args": FIELDS}, macros=("PTRWM_ABI_VERSION",))
+    assert_layout(E.AdaptArgs, "ptrwm_adapt_args", FIELDS, got)
+    assert got["PTRWM_ABI_VERSION"] == E.ABI_VERSION == 3  # additive: the version stays
 
 
-def _valid(n_temps=4, burn_in=100):
-    """Arguments the entry points accept up to their first HIP call (the pointers point at host memory a refused call never
-    reads)."""
-    buf = C.create_string_buffer(64)
-    ptr = C.cast(buf, C.c_void_p)
-    td, pd, ra, ad = E.TargetDesc(), E.ProposalDesc(), E.RunArgs(), E.AdaptArgs()
-    td.kind, td.dim = E.TARGET_ROUGH_CARPET, 30
-    pd.kind, pd.temp_scale = E.PROPOSAL_NORMAL, ptr
-    ra.struct_size, ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = C.sizeof(E.RunArgs), n_temps, 4, 10, 1
-    ra.burn_in = burn_in
-    ra.state = ra.logp = ra.beta = ptr
-    ad.struct_size, ad.every, ad.until = C.sizeof(E.AdaptArgs), 10, burn_in
-    ad.target, ad.gain, ad.decay, ad.min_scale, ad.max_scale = 0.234, 3.0, 0.5, 1e-6, 1e6
-    ad.temp_scale = ad.window_accept = ad.pooled = ptr
-    return {"buf": buf, "ptr": ptr, "td": td, "pd": pd, "ra": ra, "ad": ad}
+def _valid(n_temps=4):
+    """Arguments the three entry points accept up to their first HIP call."""
+    # burn_in 100, so ad.until == 100 in windows of ad.every == 10: "until = 101 past burn_in", "window 9 ends after step 99"
+    # and the update's K = 10 windows below
+    return valid_args("ad", n_temps=n_temps, burn_in=100)
 
 
 def test_adapt_validation_needs_no_gpu():
@@ -247,17 +212,13 @@ def _pooled_shard(rank):
     return p
 
 
-def _sync_worker(rank, world, port, q):
+def _sync_worker(rank):
     from algorithms.sharding import adaptation_sync
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     p = _pooled_shard(rank)
     out = adaptation_sync()(p)
     assert out is p and p.dtype == torch.int64  # in place
-    q.put((rank, p.numpy()))
-    dist.barrier()
-    dist.destroy_process_group()
+    return p.numpy()
 
 
 def test_adaptation_sync_over_two_ranks_is_the_sum_of_the_shards():
@@ -267,18 +228,7 @@ def test_adaptation_sync_over_two_ranks_is_the_sum_of_the_shards():
 
     alone = _pooled_shard(0)
     assert torch.equal(adaptation_sync()(alone), _pooled_shard(0))
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_sync_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=180) for _ in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    got = gloo_world(_sync_worker)
     want = (_pooled_shard(0) + _pooled_shard(1)).numpy()
     assert int(want[1]) == (1 << 32) + 7
     assert sorted(r for r, _ in got) == [0, 1]

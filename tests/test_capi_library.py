@@ -8,8 +8,7 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+from host_harness import HEADER, ROOT, assert_layout, c_layout, valid_args
 
 
 @pytest.fixture(scope="module")
@@ -41,7 +40,7 @@ def test_header_functions_are_all_exported_and_bound(engine):
 
 
 def test_struct_layouts_match_the_c_header(engine, tmp_path):
-    """Compile a probe with gcc against the real header and compare sizeof/offsetof with the ctypes mirrors
+    """A probe compiled with gcc against the real header: every struct's size and field offsets against the ctypes mirrors
     (both the product binding and the oracle's)."""
     from oracle import oracle as O
 
@@ -50,23 +49,11 @@ def test_struct_layouts_match_the_c_header(engine, tmp_path):
         "ptrwm_proposal_desc": ["kind", "inv_dim", "temp_scale", "dim_scale"],
         "ptrwm_run_args": [f[0] for f in engine.RunArgs._fields_],
     }
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){"]
-    for s, fs in fields.items():
-        lines.append(f'printf("{s} %zu\\n", sizeof({s}));')
-        for f in fs:
-            lines.append(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));')
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)], text=True).splitlines())
+    got = c_layout(tmp_path, fields)
     for mod in (engine, O):
         for cname, cls in (("ptrwm_target_desc", mod.TargetDesc), ("ptrwm_proposal_desc", mod.ProposalDesc),
                            ("ptrwm_run_args", mod.RunArgs)):
-            assert C.sizeof(cls) == int(got[cname])
-            for f in fields[cname]:
-                assert getattr(cls, f).offset == int(got[f"{cname}.{f}"]), (mod.__name__, cname, f)
+            assert_layout(cls, cname, fields[cname], got)
     hdr = open(HEADER).read()
     assert int(re.search(r"#define PTRWM_MAX_DIM (\d+)", hdr).group(1)) == engine.MAX_DIM
     assert int(re.search(r"#define PTRWM_MAX_TEMPS (\d+)", hdr).group(1)) == engine.MAX_TEMPS
@@ -190,16 +177,9 @@ TWO_DEFECT_CODES = {
 def two_defect_code(engine, lib, entry, defects):
     """`entry` called with arguments that are valid but for `defects` (the pointers point at host memory that a refused call
     never reads)."""
-    buf = C.create_string_buffer(64)
-    ptr = C.cast(buf, C.c_void_p)
-    td, pd, ra, init = engine.TargetDesc(), engine.ProposalDesc(), engine.RunArgs(), engine.InitArgs()
-    mom = (engine.ChainMomentsArgs if "chain" in entry else engine.MomentsArgs)()
-    td.kind, td.dim = engine.TARGET_ROUGH_CARPET, 30
-    pd.kind, pd.temp_scale = engine.PROPOSAL_NORMAL, ptr
-    ra.struct_size, ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = C.sizeof(engine.RunArgs), 4, 4, 10, 1
-    ra.state = ra.logp = ra.beta = ptr
-    mom.struct_size, mom.temps, mom.every, mom.sum, mom.sum_sq = C.sizeof(mom), 1, 1, ptr, ptr
-    init.struct_size, init.lo, init.hi = C.sizeof(engine.InitArgs), ptr, ptr
+    mk = "cmom" if "chain" in entry else "mom"
+    v = valid_args(mk, "init")
+    ptr, td, pd, ra, mom, init = v["ptr"], v["td"], v["pd"], v["ra"], v[mk], v["init"]
     dim = 30
     for d in defects:
         if d == "T":

@@ -4,18 +4,13 @@ two entry points before the first HIP call, the classes' argument check, and all
 two against the single-process estimate.  CPU only."""
 import ctypes as C
 import os
-import socket
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+from host_harness import ROOT, assert_layout, c_layout, gloo_world, valid_args
 
 
 @pytest.fixture(scope="module")
@@ -91,18 +86,7 @@ def test_new_symbols_exist_and_the_mirror_has_the_c_layout(engine, tmp_path):
     for name in ("ptrwm_run_with_chain_moments", "ptrwm_split_chain_moments"):
         assert name in engine.SYMBOLS and getattr(lib, name) is not None
     fs = [f[0] for f in engine.ChainMomentsArgs._fields_]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("size %zu\\n", sizeof(ptrwm_chain_moments_args));']
-    lines += [f'printf("{f} %zu\\n", offsetof(ptrwm_chain_moments_args, {f}));' for f in fs]
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert int(got["size"]) == C.sizeof(engine.ChainMomentsArgs)
-    for f in fs:
-        assert int(got[f]) == getattr(engine.ChainMomentsArgs, f).offset, f
+    assert_layout(engine.ChainMomentsArgs, "ptrwm_chain_moments_args", fs, c_layout(tmp_path, {"ptrwm_chain_moments_args": fs}))
     assert fs == ["struct_size", "temps", "every", "sum", "sum_sq", "sum_logp", "count"]
 
 
@@ -117,83 +101,73 @@ def test_the_two_accumulator_structs_are_one_layout(engine):
         assert getattr(a, name).offset == getattr(b, name).offset and getattr(a, name).size == getattr(b, name).size, name
 
 
-def _run_args(engine, n_temps, n_chains=4, n_steps=10):
-    ra = engine.RunArgs()
-    ra.struct_size = C.sizeof(engine.RunArgs)
-    ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = n_temps, n_chains, n_steps, 1
-    # never dereferenced: every case below is refused before anything is enqueued
-    ra.state, ra.logp, ra.beta = 0x1000, 0x2000, 0x3000
-    return ra
-
-
-def _cm(engine, temps, every=1, sums=True):
-    m = engine.ChainMomentsArgs()
-    m.struct_size = C.sizeof(engine.ChainMomentsArgs)
+def _cm(temps, every=1, sums=True):
+    """A fresh accumulator block (no pointer of these tests is ever dereferenced: every case is refused, or has nothing to
+    do, before anything is enqueued)."""
+    m = valid_args("cmom")["cmom"]
     m.temps, m.every = temps, every
-    if sums:
-        m.sum, m.sum_sq = 0x4000, 0x5000
+    if not sums:
+        m.sum = m.sum_sq = None
     return m
 
 
 def test_chain_moments_refusals_need_no_gpu(engine):
     lib = engine.load_library()
-    td, pd = engine.TargetDesc(), engine.ProposalDesc()
-    td.kind, td.dim = engine.TARGET_ROUGH_CARPET, 30
+    v = valid_args(n_temps=8)
+    td, pd, ra = v["td"], v["pd"], v["ra"]
     td.p[0], td.p[1], td.p[2] = -15.0, 0.0, 15.0
-    pd.kind, pd.temp_scale = engine.PROPOSAL_NORMAL, 0x6000
-    ra = _run_args(engine, 8)
     run = lambda m: lib.ptrwm_run_with_chain_moments(C.byref(td), C.byref(pd), C.byref(ra), m, None)  # noqa: E731
-    m = _cm(engine, 1)
+    m = _cm(1)
     m.struct_size = 8
     assert run(C.byref(m)) == -6  # PTRWM_E_STRUCT
     for temps, every in ((0, 1), (9, 1), (-1, 1), (1, 0), (8, -3)):
-        assert run(C.byref(_cm(engine, temps, every))) == -5, (temps, every)  # PTRWM_E_ARG
-    assert run(C.byref(_cm(engine, 1, sums=False))) == -1  # PTRWM_E_NULL
-    m = _cm(engine, 1)
+        assert run(C.byref(_cm(temps, every))) == -5, (temps, every)  # PTRWM_E_ARG
+    assert run(C.byref(_cm(1, sums=False))) == -1  # PTRWM_E_NULL
+    m = _cm(1)
     m.sum_sq = None
     assert run(C.byref(m)) == -1
     # the run's own checks come first, as in ptrwm_run
     ra.swap_every = 0
-    assert run(C.byref(_cm(engine, 1))) == -5
+    assert run(C.byref(_cm(1))) == -5
     ra.swap_every = 1
     ra.n_steps = 0
-    assert run(C.byref(_cm(engine, 1))) == 0  # empty: nothing to do
+    assert run(C.byref(_cm(1))) == 0  # empty: nothing to do
     # the LDS limit.  RWM (one temperature) at dim 32: 4 waves x 64 chains x 65 doubles on top of the thread form's own
     # 40 960 bytes are more than 160 KiB, 4 x 16 x 65 in the lane-split form are not - a pinned thread form is refused, and
     # so is a shape neither form holds
     td.dim = 32
-    ra = _run_args(engine, 1)
+    ra = valid_args(n_temps=1)["ra"]
     assert engine.has_thread_variant(td.kind, pd.kind, 32) and engine.has_quad_variant(td.kind, pd.kind, 32, 1)
     with engine.kernel_form(engine.FORM_THREAD):
-        assert run(C.byref(_cm(engine, 1))) == -5
+        assert run(C.byref(_cm(1))) == -5
     td.dim = 60
-    ra = _run_args(engine, 256)  # thread form only; 256 x 121 doubles on top of 256 rows
+    ra = valid_args(n_temps=256)["ra"]  # thread form only; 256 x 121 doubles on top of 256 rows
     assert not engine.has_quad_variant(td.kind, pd.kind, 60, 256)
-    assert run(C.byref(_cm(engine, 256))) == -5
+    assert run(C.byref(_cm(256))) == -5
 
     # split steps: the same argument checks
-    sp = _run_args(engine, 8)
+    sp = valid_args(n_temps=8)["ra"]
     assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, None, None) == -1
-    assert lib.ptrwm_split_chain_moments(None, 30, C.byref(_cm(engine, 1)), None) == -1
-    m = _cm(engine, 1)
+    assert lib.ptrwm_split_chain_moments(None, 30, C.byref(_cm(1)), None) == -1
+    m = _cm(1)
     m.struct_size = 0
     assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(m), None) == -6
-    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(engine, 9)), None) == -5
-    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(engine, 0)), None) == -5
-    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(engine, 1, every=0)), None) == -5
-    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(engine, 1, sums=False)), None) == -1
-    m = _cm(engine, 1)
+    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(9)), None) == -5
+    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(0)), None) == -5
+    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(1, every=0)), None) == -5
+    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(1, sums=False)), None) == -1
+    m = _cm(1)
     m.sum_sq = None
     assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(m), None) == -1
-    assert lib.ptrwm_split_chain_moments(C.byref(sp), 0, C.byref(_cm(engine, 1)), None) == -2
+    assert lib.ptrwm_split_chain_moments(C.byref(sp), 0, C.byref(_cm(1)), None) == -2
     sp.n_chains = 0
-    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(engine, 1)), None) == 0  # empty batch
+    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(1)), None) == 0  # empty batch
     # a step that does not count is known on the host: nothing is enqueued
-    sp = _run_args(engine, 8)
+    sp = valid_args(n_temps=8)["ra"]
     sp.burn_in, sp.step0 = 10, 3
-    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(engine, 1)), None) == 0
+    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(1)), None) == 0
     sp.burn_in, sp.step0 = 0, 4  # step_counter 5, every 2
-    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(engine, 1, every=2)), None) == 0
+    assert lib.ptrwm_split_chain_moments(C.byref(sp), 30, C.byref(_cm(1, every=2)), None) == 0
 
 
 def test_the_classes_want_a_moments_mode_for_per_chain_moments(engine):
@@ -226,36 +200,21 @@ def _shard(rank, chains):
     return cm, x
 
 
-def _worker(rank, world, port, q):
+def _worker(rank):
     from algorithms.sharding import allreduce_chain_summary
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     cm, _ = _shard(rank, 5 + 3 * rank)
     kept = {k: v.clone() for k, v in cm.items() if torch.is_tensor(v)}
     out = allreduce_chain_summary(cm)
     assert all(torch.equal(cm[k], v) for k, v in kept.items())  # inputs untouched
-    q.put((rank, {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in out.items()}))
-    dist.barrier()
-    dist.destroy_process_group()
+    return {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in out.items()}
 
 
 def test_allreduce_chain_summary_over_two_ranks_equals_one_process():
     from algorithms._engine_core import rhat_ess_from_chain_sums
     from algorithms.sharding import allreduce_chain_summary
 
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=180) for _ in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    got = gloo_world(_worker)
     (a, xa), (b, xb) = _shard(0, 5), _shard(1, 8)
     whole = {k: torch.cat([a[k], b[k]]) for k in ("sum", "sum_sq")}
     x = np.concatenate([xa, xb])

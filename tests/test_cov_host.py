@@ -4,39 +4,26 @@ of the two entry points that returns before a HIP call; the estimators on hand-m
 of two."""
 import ctypes as C
 import math
-import os
-import socket
-import subprocess
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import ptrwm_hip as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+from host_harness import assert_layout, c_layout, gloo_world, run_exe, sanitized_exe, valid_args
 
 
 @pytest.fixture(scope="module")
 def cov_exe(tmp_path_factory):
     """tests/cov_test.cpp, a program of its own, compiled as plain C++ under AddressSanitizer and UBSan."""
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cov_test.cpp")
-    exe = str(tmp_path_factory.mktemp("cov") / "cov_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", src, "-o", exe])
-    return exe
+    return sanitized_exe(tmp_path_factory.mktemp("cov"), "cov_test.cpp")
 
 
 def test_geometry_replay_and_cuts_against_brute_force(cov_exe):
     """csrc/cov.h and the cut of csrc/schedule.h in tests/cov_test.cpp: one owner per (i, j), j <= i < dim, and no pad element
     flushed, for every dim in 1..104; the CPU replay of the kernel on integer states; the cuts with a histogram and an
     autocovariance at other periods."""
-    out = subprocess.run([cov_exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "cov ok:" in out.stdout
+    run_exe(cov_exe, ok="cov ok:")
 
 
 def test_gpu_cases_have_the_geometry_they_are_named_for(cov_exe):
@@ -45,10 +32,9 @@ def test_gpu_cases_have_the_geometry_they_are_named_for(cov_exe):
     from test_gpu_cov import EQUALITY_CASES
 
     lines = "".join(f"{c['dim']}\n" for c in EQUALITY_CASES)
-    out = subprocess.run([cov_exe, "geometry"], input=lines, capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    out = run_exe(cov_exe, "geometry", input=lines, timeout=60)
     keys = ("blocks", "pairs", "stride", "lds_bytes", "chains", "sub_tile", "k", "waves")
-    geo = {c["name"]: dict(zip(keys, map(int, ln.split())), **c) for c, ln in zip(EQUALITY_CASES, out.stdout.splitlines())}
+    geo = {c["name"]: dict(zip(keys, map(int, ln.split())), **c) for c, ln in zip(EQUALITY_CASES, out.splitlines())}
     assert len(geo) == len(EQUALITY_CASES) == 9
     # the issue's table, row by row
     assert [(c["dim"], c["T"], c["temps"], c["Cn"]) for c in EQUALITY_CASES[:8]] == [
@@ -78,8 +64,8 @@ def test_launch_cuts_with_a_histogram_and_an_autocovariance_at_other_periods(cov
     """The launches of ptrwm_run_with_covariance replayed step by step in Python: covariance every 7, autocovariance every 4,
     histogram every 5, burn_in 11."""
     step0, n, burn, ce, ae, he, cap = 3, 60, 11, 7, 4, 5, 1000
-    out = subprocess.run([cov_exe, "cuts", *map(str, (step0, n, burn, ce, ae, he, cap))], capture_output=True, text=True, timeout=60)
-    got = [tuple(int(v) for v in ln.split()) for ln in out.stdout.splitlines()]
+    out = run_exe(cov_exe, "cuts", step0, n, burn, ce, ae, he, cap, timeout=60)
+    got = [tuple(int(v) for v in ln.split()) for ln in out.splitlines()]
     want, start = [], step0
     for s in range(step0, step0 + n):  # step s has step counter s + 1
         sc = s + 1
@@ -90,52 +76,21 @@ def test_launch_cuts_with_a_histogram_and_an_autocovariance_at_other_periods(cov
     assert got == want and sum(c[2] for c in got) == 8  # step counters 14 .. 63
     assert any(c[2] and c[3] for c in got) and any(c[2] and c[4] for c in got)  # step counters 28 and 35: two kernels behind one launch
     # nothing else bound, nothing due: one launch
-    out = subprocess.run([cov_exe, "cuts", "0", "10", "10", "3", "0", "0", "1000"], capture_output=True, text=True, timeout=60)
-    assert out.stdout.split() == ["0", "10", "0", "0", "0"]
+    assert run_exe(cov_exe, "cuts", 0, 10, 10, 3, 0, 0, 1000, timeout=60).split() == ["0", "10", "0", "0", "0"]
 
 
 def test_cov_struct_layout_matches_the_c_header(tmp_path):
     fields = [f[0] for f in E.CovArgs._fields_]
     assert fields == ["struct_size", "temps", "every", "sxx", "sx", "count"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){",
-             'printf("size %zu\\n", sizeof(ptrwm_cov_args));']
-    lines += [f'printf("{f} %zu\\n", offsetof(ptrwm_cov_args, {f}));' for f in fields]
-    lines.append('printf("abi %d\\n", PTRWM_ABI_VERSION);')
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert C.sizeof(E.CovArgs) == int(got["size"])
-    for f in fields:
-        assert getattr(E.CovArgs, f).offset == int(got[f]), f
-    assert int(got["abi"]) == E.ABI_VERSION == 3  # additive: the version stays
+    got = c_layout(tmp_path, {"ptrwm_cov_args": fields}, macros=("PTRWM_ABI_VERSION",))
+    assert_layout(E.CovArgs, "ptrwm_cov_args", fields, got)
+    assert got["PTRWM_ABI_VERSION"] == E.ABI_VERSION == 3  # additive: the version stays
     assert "ptrwm_covariance" in E.SYMBOLS and "ptrwm_run_with_covariance" in E.SYMBOLS
 
 
 def _valid(n_temps=4):
-    """Arguments both entry points accept up to their first HIP call (the pointers point at host memory a refused call never
-    reads)."""
-    buf = C.create_string_buffer(64)
-    ptr = C.cast(buf, C.c_void_p)
-    td, pd, ra, cv, ac = E.TargetDesc(), E.ProposalDesc(), E.RunArgs(), E.CovArgs(), E.AcfArgs()
-    td.kind, td.dim = E.TARGET_ROUGH_CARPET, 30
-    pd.kind, pd.temp_scale = E.PROPOSAL_NORMAL, ptr
-    ra.struct_size, ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = C.sizeof(E.RunArgs), n_temps, 4, 10, 1
-    ra.state = ra.logp = ra.beta = ptr
-    cv.struct_size, cv.temps, cv.every = C.sizeof(E.CovArgs), 1, 1
-    cv.sxx = cv.sx = cv.count = ptr
-    ac.struct_size, ac.temps, ac.every, ac.max_lag = C.sizeof(E.AcfArgs), 1, 1, 8
-    ac.ring = ac.sxy = ac.head = ac.tail = ac.pairs = ptr
-    hi, ad, ld = E.HistArgs(), E.AdaptArgs(), E.LadderArgs()
-    hi.struct_size, hi.temps, hi.every, hi.n_bins = C.sizeof(E.HistArgs), 1, 1, 64
-    hi.lo = hi.scale = hi.counts = ptr
-    ad.struct_size, ad.every, ad.until, ad.target, ad.gain, ad.decay = C.sizeof(E.AdaptArgs), 5, 0, 0.234, 3.0, 0.5
-    ad.min_scale, ad.max_scale, ad.temp_scale, ad.window_accept, ad.pooled = 1e-3, 1e3, ptr, ptr, ptr
-    ld.struct_size, ld.every, ld.probe_every, ld.until, ld.gain, ld.decay = C.sizeof(E.LadderArgs), 10, 5, 0, 2.0, 0.5
-    ld.beta, ld.temp_scale, ld.pooled = ptr, ptr, ptr
-    return {"buf": buf, "ptr": ptr, "td": td, "pd": pd, "ra": ra, "cv": cv, "ac": ac, "hi": hi, "ad": ad, "ld": ld}
+    """Arguments both entry points accept up to their first HIP call, with every block that check_cov comes after."""
+    return valid_args("cv", "ac", "hi", "ad", "ld", n_temps=n_temps)  # ld.every == 10: "3 does not divide 10" below
 
 
 def test_cov_validation_needs_no_gpu():
@@ -338,36 +293,21 @@ def _shard(rank):
     return {"sxx": sxx, "sx": x.sum(0), "count": torch.tensor([5 + rank]), "every": 5, "x": x}
 
 
-def _worker(rank, world, port, q):
+def _worker(rank):
     from algorithms.sharding import allreduce_covariance
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     shard = _shard(rank)
     shard.pop("x")
     kept = {k: v.clone() for k, v in shard.items() if torch.is_tensor(v)}
     total = allreduce_covariance(shard)
     assert all(torch.equal(shard[k], v) for k, v in kept.items())  # inputs untouched
-    q.put((rank, {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in total.items()}))
-    dist.barrier()
-    dist.destroy_process_group()
+    return {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in total.items()}
 
 
 def test_allreduce_covariance_over_two_ranks_is_the_covariance_of_the_whole_job():
     from algorithms.sharding import allreduce_covariance
 
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=180) for _ in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    got = gloo_world(_worker)
     a, b = _shard(0), _shard(1)
     x = torch.cat([a["x"], b["x"]]).numpy()  # the whole job's draws
     for _, total in got:

@@ -3,68 +3,33 @@ restatement, the struct's C layout, every validation code of the three entry poi
 arithmetic of the class accessors and of the shards' all-reduce on hand-made tensors."""
 import ctypes as C
 import math
-import os
-import socket
-import subprocess
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import ptrwm_hip as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+from host_harness import assert_layout, c_layout, gloo_world, run_exe, sanitized_exe, valid_args
 
 
 def test_flow_header_against_a_literal_restatement(tmp_path):
     """csrc/flow.h compiled as plain C++ under AddressSanitizer and UBSan into tests/flow_test.cpp, a program of its own:
     random accept patterns for T in {2, 3, 5, 8, 64, 70, 256}, both modes and both orders; flow words moved through src[t] as
     the kernels move them against explicit id / direction arrays and sequential transpositions or copies, after every event."""
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "flow_test.cpp")
-    exe = str(tmp_path / "flow_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "flow ok: 62400 events, 7 ladder lengths x 2 modes x 2 orders x 3 acceptance rates" in out.stdout
+    run_exe(sanitized_exe(tmp_path, "flow_test.cpp"),
+            ok="flow ok: 62400 events, 7 ladder lengths x 2 modes x 2 orders x 3 acceptance rates")
 
 
 def test_flow_struct_layout_matches_the_c_header(tmp_path):
     fields = [f[0] for f in E.FlowArgs._fields_]
     assert fields == ["struct_size", "reserved", "walker", "round_trips", "n_up", "n_down"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){",
-             'printf("size %zu\\n", sizeof(ptrwm_flow_args));']
-    lines += [f'printf("{f} %zu\\n", offsetof(ptrwm_flow_args, {f}));' for f in fields]
-    lines.append('printf("abi %d\\n", PTRWM_ABI_VERSION);')
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert C.sizeof(E.FlowArgs) == int(got["size"])
-    for f in fields:
-        assert getattr(E.FlowArgs, f).offset == int(got[f]), f
-    assert int(got["abi"]) == E.ABI_VERSION == 3  # additive: the version stays
+    got = c_layout(tmp_path, {"ptrwm_flow_args": fields}, macros=("PTRWM_ABI_VERSION",))
+    assert_layout(E.FlowArgs, "ptrwm_flow_args", fields, got)
+    assert got["PTRWM_ABI_VERSION"] == E.ABI_VERSION == 3  # additive: the version stays
 
 
 def _valid(n_temps=4):
-    """Arguments every entry point accepts up to its first HIP call (the pointers point at host memory a refused call never
-    reads)."""
-    buf = C.create_string_buffer(64)
-    ptr = C.cast(buf, C.c_void_p)
-    td, pd, ra, fl = E.TargetDesc(), E.ProposalDesc(), E.RunArgs(), E.FlowArgs()
-    td.kind, td.dim = E.TARGET_ROUGH_CARPET, 30
-    pd.kind, pd.temp_scale = E.PROPOSAL_NORMAL, ptr
-    ra.struct_size, ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = C.sizeof(E.RunArgs), n_temps, 4, 10, 1
-    ra.state = ra.logp = ra.beta = ptr
-    fl.struct_size, fl.walker = C.sizeof(E.FlowArgs), ptr
-    mom, cmom = E.MomentsArgs(), E.ChainMomentsArgs()
-    for m in (mom, cmom):
-        m.struct_size, m.temps, m.every, m.sum, m.sum_sq = C.sizeof(m), 1, 1, ptr, ptr
-    return {"buf": buf, "ptr": ptr, "td": td, "pd": pd, "ra": ra, "fl": fl, "mom": mom, "cmom": cmom}
+    """Arguments every entry point accepts up to its first HIP call, with both accumulators, whose checks come before flow's."""
+    return valid_args("fl", "mom", "cmom", n_temps=n_temps)
 
 
 def test_flow_validation_needs_no_gpu():
@@ -198,18 +163,14 @@ def _flow_shard(rank):
             "n_down": torch.randint(0, 50, (n, FLOW_TEMPS), generator=g, dtype=torch.int64), "events": FLOW_EVENTS}
 
 
-def _flow_worker(rank, world, port, q):
+def _flow_worker(rank):
     from algorithms.sharding import allreduce_flow
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     shard = _flow_shard(rank)
     kept = {k: v.clone() for k, v in shard.items() if torch.is_tensor(v)}
     total = allreduce_flow(shard)
     assert all(torch.equal(shard[k], v) for k, v in kept.items())  # inputs untouched
-    q.put((rank, {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in total.items()}))
-    dist.barrier()
-    dist.destroy_process_group()
+    return {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in total.items()}
 
 
 def test_allreduce_flow_over_two_ranks_is_the_flow_of_the_whole():
@@ -217,18 +178,7 @@ def test_allreduce_flow_over_two_ranks_is_the_flow_of_the_whole():
     the up-fraction and round-trip rate computed from those."""
     from algorithms.sharding import flow_round_trip_rate, flow_up_fraction
 
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_flow_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=180) for _ in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    got = gloo_world(_flow_worker)
     a, b = _flow_shard(0), _flow_shard(1)
     whole = {k: torch.cat([a[k], b[k]]) for k in ("round_trips", "n_up", "n_down")}
     assert whole["n_up"].shape == (8, FLOW_TEMPS)

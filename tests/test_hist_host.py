@@ -3,53 +3,40 @@ against brute force, the struct's C layout, every validation code of the two ent
 NumPy replay of the rule that the GPU tests rely on, and the arithmetic of the class accessors on hand-made counts."""
 import ctypes as C
 import math
-import os
-import socket
 import subprocess
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import ptrwm_hip as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+from host_harness import ROOT, assert_layout, c_layout, gloo_world, run_exe, sanitized_exe, valid_args
 
 
-def _build_hist_test(tmp_path):
+@pytest.fixture(scope="module")
+def hist_exe(tmp_path_factory):
     """tests/hist_test.cpp, a program of its own, compiled as plain C++ under AddressSanitizer and UBSan."""
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hist_test.cpp")
-    exe = str(tmp_path / "hist_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", src, "-o", exe])
-    return exe
+    return sanitized_exe(tmp_path_factory.mktemp("hist"), "hist_test.cpp")
 
 
-def test_bin_rule_and_cuts_against_brute_force(tmp_path):
+def test_bin_rule_and_cuts_against_brute_force(hist_exe):
     """csrc/hist.h and the histogram helper of csrc/schedule.h in tests/hist_test.cpp: the rule against a double-precision
     restatement (lo, hi, their neighbours, +-inf, NaN, denormals; 1, 2, 7, 64 and 1024 bins), the cuts of
     ptrwm_run_with_histogram replayed step by step, and hist_geometry - the snapshot kernel's tiling of the covered columns -
     for every n_bins in 1..1024 and every temps * dim in 1..26 624."""
-    out = subprocess.run([_build_hist_test(tmp_path)], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "hist ok:" in out.stdout
+    run_exe(hist_exe, ok="hist ok:")
 
 
-def test_gpu_geometry_cases_force_the_geometry_they_are_named_for(tmp_path):
+def test_gpu_geometry_cases_force_the_geometry_they_are_named_for(hist_exe):
     """The table of tests/test_gpu_hist.py through hist_geometry itself (the program's "geometry" mode): every case has more
     than one group of columns and the strategy, group width, group count and last group its row states - so a change of a
     constant of csrc/hist.h cannot quietly turn the GPU cases back into single-group ones - and, case by case, the property
     it is there for."""
     from test_gpu_hist import GEOMETRY_CASES
 
-    exe = _build_hist_test(tmp_path)
     lines = "".join(f"{c[4]} {c[3] * c[1]}\n" for c in GEOMETRY_CASES)
-    out = subprocess.run([exe, "geometry"], input=lines, capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    got = [tuple(int(v) for v in ln.split()) for ln in out.stdout.splitlines()]
+    out = run_exe(hist_exe, "geometry", input=lines, timeout=60)
+    got = [tuple(int(v) for v in ln.split()) for ln in out.splitlines()]
     assert len(got) == len(GEOMETRY_CASES) == 7
     geo = {}
     for (name, dim, T, temps, _, Cn, direct, cols, groups, last, _), g in zip(GEOMETRY_CASES, got):
@@ -106,48 +93,22 @@ def test_numpy_replay_agrees_with_the_header(tmp_path):
         want.append(numpy_bins(xs, lo32, scale, nb))
         for x in xs:
             lines.append(f"{x.view(np.uint32):x} {lo32.view(np.uint32):x} {scale.view(np.uint32):x} {nb}")
-    out = subprocess.run([str(exe)], input="\n".join(lines), capture_output=True, text=True, timeout=60)
-    got = np.array([int(v) for v in out.stdout.split()], np.int64)
+    got = np.array([int(v) for v in run_exe(exe, input="\n".join(lines), timeout=60).split()], np.int64)
     assert np.array_equal(got, np.concatenate(want))
 
 
 def test_hist_struct_layout_matches_the_c_header(tmp_path):
     fields = [f[0] for f in E.HistArgs._fields_]
     assert fields == ["struct_size", "temps", "every", "n_bins", "lo", "scale", "counts", "count"]
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){",
-             'printf("size %zu\\n", sizeof(ptrwm_hist_args));']
-    lines += [f'printf("{f} %zu\\n", offsetof(ptrwm_hist_args, {f}));' for f in fields]
-    lines.append('printf("abi %d\\n", PTRWM_ABI_VERSION);')
-    lines.append('printf("maxbins %d\\n", PTRWM_HIST_MAX_BINS);')
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert C.sizeof(E.HistArgs) == int(got["size"])
-    for f in fields:
-        assert getattr(E.HistArgs, f).offset == int(got[f]), f
-    assert int(got["abi"]) == E.ABI_VERSION == 3  # additive: the version stays
-    assert int(got["maxbins"]) == E.HIST_MAX_BINS == 1024
+    got = c_layout(tmp_path, {"ptrwm_hist_args": fields}, macros=("PTRWM_ABI_VERSION", "PTRWM_HIST_MAX_BINS"))
+    assert_layout(E.HistArgs, "ptrwm_hist_args", fields, got)
+    assert got["PTRWM_ABI_VERSION"] == E.ABI_VERSION == 3  # additive: the version stays
+    assert got["PTRWM_HIST_MAX_BINS"] == E.HIST_MAX_BINS == 1024
 
 
 def _valid(n_temps=4):
-    """Arguments both entry points accept up to their first HIP call (the pointers point at host memory a refused call never
-    reads)."""
-    buf = C.create_string_buffer(64)
-    ptr = C.cast(buf, C.c_void_p)
-    td, pd, ra, hi = E.TargetDesc(), E.ProposalDesc(), E.RunArgs(), E.HistArgs()
-    td.kind, td.dim = E.TARGET_ROUGH_CARPET, 30
-    pd.kind, pd.temp_scale = E.PROPOSAL_NORMAL, ptr
-    ra.struct_size, ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = C.sizeof(E.RunArgs), n_temps, 4, 10, 1
-    ra.state = ra.logp = ra.beta = ptr
-    hi.struct_size, hi.temps, hi.every, hi.n_bins = C.sizeof(E.HistArgs), 1, 1, 64
-    hi.lo = hi.scale = hi.counts = ptr
-    fl, mom = E.FlowArgs(), E.MomentsArgs()
-    fl.struct_size, fl.walker = C.sizeof(E.FlowArgs), ptr
-    mom.struct_size, mom.temps, mom.every, mom.sum, mom.sum_sq = C.sizeof(mom), 1, 1, ptr, ptr
-    return {"buf": buf, "ptr": ptr, "td": td, "pd": pd, "ra": ra, "hi": hi, "fl": fl, "mom": mom}
+    """Arguments both entry points accept up to their first HIP call, with the blocks whose checks come before check_hist."""
+    return valid_args("hi", "fl", "mom", n_temps=n_temps)
 
 
 def test_hist_validation_needs_no_gpu():
@@ -370,35 +331,20 @@ def _hist_shard(rank):
     return {"counts": counts, "count": count, "edges": edges}
 
 
-def _hist_worker(rank, world, port, q):
+def _hist_worker(rank):
     from algorithms.sharding import allreduce_histogram
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     shard = _hist_shard(rank)
     kept = {k: v.clone() for k, v in shard.items()}
     total = allreduce_histogram(shard)
     assert all(torch.equal(shard[k], v) for k, v in kept.items())  # inputs untouched
     assert total["counts"].dtype == torch.int64 and total["count"].dtype == torch.int64
-    q.put((rank, {k: v.numpy() for k, v in total.items()}))
-    dist.barrier()
-    dist.destroy_process_group()
+    return {k: v.numpy() for k, v in total.items()}
 
 
 def test_allreduce_histogram_over_two_ranks_is_the_sum_of_the_shards():
     """gloo, two spawned ranks, CPU tensors: counts and count add up exactly on both ranks, the edges pass through."""
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_hist_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=180) for _ in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    got = gloo_world(_hist_worker)
     a, b = _hist_shard(0), _hist_shard(1)
     assert int((a["counts"] + b["counts"])[1, 2, 3]) == (1 << 32) + 11 and int((a["count"] + b["count"]).min()) > 0
     assert sorted(r for r, _ in got) == [0, 1]

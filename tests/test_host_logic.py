@@ -7,6 +7,7 @@ import torch
 
 import helpers as H
 import ptrwm_hip
+from host_harness import run_exe, sanitized_exe
 from algorithms import (ParallelTemperingRWM_GPU_Optimized, RandomWalkMH_GPU_Optimized, RWM_GPU_Optimized,
                         geometric_beta_ladder)
 from algorithms.sharding import pack_summary, shard_range, unpack_summary
@@ -482,16 +483,7 @@ def test_step_schedule_header_against_brute_force(tmp_path):
     of a grid of requests (burn-in x the three periods x step0 x n_steps x the cut) step by step, and every helper of the
     warm-up windows (every in {1, 6, 7, 50}, until from 0 to past four windows, every divisor as the probe period) against a
     loop over the windows."""
-    import os
-    import subprocess
-
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "schedule_test.cpp")
-    exe = str(tmp_path / "schedule_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "schedule ok: 2092800 launches, 3024 window positions" in out.stdout
+    run_exe(sanitized_exe(tmp_path, "schedule_test.cpp"), ok="schedule ok: 2092800 launches, 3024 window positions")
 
 
 def test_rng_layout_header_against_literal_restatements(tmp_path):
@@ -499,13 +491,4 @@ def test_rng_layout_header_against_literal_restatements(tmp_path):
     exchange group, as every kernel and host path of csrc/ builds them - compiled as plain C++ under AddressSanitizer and
     UBSan into tests/rng_layout_test.cpp, a program of its own that checks each helper against a literal restatement over a
     grid crossing the 32-bit boundaries of the step index and the chain id."""
-    import os
-    import subprocess
-
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "rng_layout_test.cpp")
-    exe = str(tmp_path / "rng_layout_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "rng layout ok: " in out.stdout
+    run_exe(sanitized_exe(tmp_path, "rng_layout_test.cpp"), ok="rng layout ok: ")

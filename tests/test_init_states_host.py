@@ -4,17 +4,14 @@ classes on device="cpu", and the properties of the NumPy restatement (tests/init
 against.  CPU only."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+from host_harness import ROOT, assert_layout, c_layout, valid_args
 from init_reference import expected_box_starts
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
 
 E_NULL, E_DIM, E_TEMPS, E_ARG, E_STRUCT = -1, -2, -3, -5, -6
 
@@ -37,35 +34,22 @@ def test_the_symbol_exists_and_the_mirror_has_the_c_layout(engine, tmp_path):
     assert lib.ptrwm_abi_version() == 3  # a new symbol, no change to anything that existed
     fs = [f[0] for f in engine.InitArgs._fields_]
     assert fs == ["struct_size", "per_temperature", "attempt", "lo", "hi", "fallback"]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("size %zu\\n", sizeof(ptrwm_init_args));']
-    lines += [f'printf("{f} %zu\\n", offsetof(ptrwm_init_args, {f}));' for f in fs]
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert int(got["size"]) == C.sizeof(engine.InitArgs)
-    for f in fs:
-        assert int(got[f]) == getattr(engine.InitArgs, f).offset, f
+    assert_layout(engine.InitArgs, "ptrwm_init_args", fs, c_layout(tmp_path, {"ptrwm_init_args": fs}))
 
 
-def _run_args(engine, n_temps=4, n_chains=8):
-    ra = engine.RunArgs()
-    ra.struct_size = C.sizeof(engine.RunArgs)
-    ra.n_temps, ra.n_chains, ra.swap_every = n_temps, n_chains, 1
-    # never dereferenced: every case below is refused before anything is enqueued
-    ra.state, ra.logp = 0x1000, 0x2000
+def _run_args(n_temps=4, n_chains=8):
+    """(No pointer of these tests is ever dereferenced: every case is refused, or has nothing to do, before anything is
+    enqueued.)"""
+    ra = valid_args(n_temps=n_temps)["ra"]
+    ra.n_chains = n_chains
     return ra
 
 
-def _init(engine, attempt=0, per_temperature=0, bounds=True):
-    i = engine.InitArgs()
-    i.struct_size = C.sizeof(engine.InitArgs)
+def _init(attempt=0, per_temperature=0, bounds=True):
+    i = valid_args("init")["init"]
     i.attempt, i.per_temperature = attempt, per_temperature
-    if bounds:
-        i.lo, i.hi = 0x3000, 0x4000
+    if not bounds:
+        i.lo = i.hi = None
     return i
 
 
@@ -74,49 +58,49 @@ def test_init_states_refusals_need_no_gpu(engine):
     call = lambda ra, dim, i: lib.ptrwm_init_states(None if ra is None else C.byref(ra), dim,  # noqa: E731
                                                     None if i is None else C.byref(i), None)
     # NULL structs
-    assert call(None, 30, _init(engine)) == E_NULL
-    assert call(_run_args(engine), 30, None) == E_NULL
+    assert call(None, 30, _init()) == E_NULL
+    assert call(_run_args(), 30, None) == E_NULL
     # struct sizes, either struct
-    ra = _run_args(engine)
+    ra = _run_args()
     ra.struct_size = 8
-    assert call(ra, 30, _init(engine)) == E_STRUCT
-    i = _init(engine)
+    assert call(ra, 30, _init()) == E_STRUCT
+    i = _init()
     i.struct_size = C.sizeof(engine.InitArgs) - 8
-    assert call(_run_args(engine), 30, i) == E_STRUCT
+    assert call(_run_args(), 30, i) == E_STRUCT
     # dim and ladder length, as the split steps check them
     for dim in (0, -1, engine.MAX_DIM + 1):
-        assert call(_run_args(engine), dim, _init(engine)) == E_DIM, dim
+        assert call(_run_args(), dim, _init()) == E_DIM, dim
     for T in (0, -2, engine.MAX_TEMPS + 1):
-        assert call(_run_args(engine, n_temps=T), 30, _init(engine)) == E_TEMPS, T
+        assert call(_run_args(n_temps=T), 30, _init()) == E_TEMPS, T
     # attempt and per_temperature ranges
     for attempt in (-1, 65536, 2**20):
-        assert call(_run_args(engine), 30, _init(engine, attempt=attempt)) == E_ARG, attempt
+        assert call(_run_args(), 30, _init(attempt=attempt)) == E_ARG, attempt
     for pt in (-1, 2):
-        assert call(_run_args(engine), 30, _init(engine, per_temperature=pt)) == E_ARG, pt
-    assert call(_run_args(engine, n_chains=-1), 30, _init(engine)) == E_ARG
-    ra = _run_args(engine)
+        assert call(_run_args(), 30, _init(per_temperature=pt)) == E_ARG, pt
+    assert call(_run_args(n_chains=-1), 30, _init()) == E_ARG
+    ra = _run_args()
     ra.state_f64 = 2
-    assert call(ra, 30, _init(engine)) == E_ARG
+    assert call(ra, 30, _init()) == E_ARG
     # required arrays
-    ra = _run_args(engine)
+    ra = _run_args()
     ra.state = None
-    assert call(ra, 30, _init(engine)) == E_NULL
-    assert call(_run_args(engine), 30, _init(engine, bounds=False)) == E_NULL
+    assert call(ra, 30, _init()) == E_NULL
+    assert call(_run_args(), 30, _init(bounds=False)) == E_NULL
     for missing in ("lo", "hi"):
-        i = _init(engine)
+        i = _init()
         setattr(i, missing, None)
-        assert call(_run_args(engine), 30, i) == E_NULL, missing
-    ra = _run_args(engine)
+        assert call(_run_args(), 30, i) == E_NULL, missing
+    ra = _run_args()
     ra.logp = None
-    assert call(ra, 30, _init(engine, attempt=1)) == E_NULL  # a redraw reads logp ...
-    assert call(ra, 30, _init(engine, attempt=65535, bounds=False)) == E_NULL
+    assert call(ra, 30, _init(attempt=1)) == E_NULL  # a redraw reads logp ...
+    assert call(ra, 30, _init(attempt=65535, bounds=False)) == E_NULL
     # ... and the largest valid attempt / per_temperature values pass the range checks (refused for the NULL logp only)
     # an empty batch is fine, with or without arrays
     for attempt in (0, 3):
-        assert call(_run_args(engine, n_chains=0), 30, _init(engine, attempt=attempt, per_temperature=1)) == 0
-    ra = _run_args(engine, n_chains=0)
+        assert call(_run_args(n_chains=0), 30, _init(attempt=attempt, per_temperature=1)) == 0
+    ra = _run_args(n_chains=0)
     ra.state = ra.logp = None
-    assert call(ra, 104, _init(engine, bounds=False)) == 0
+    assert call(ra, 104, _init(bounds=False)) == 0
 
 
 # ---- constructors ---------------------------------------------------------------------------------------------------

@@ -3,32 +3,21 @@ probe helpers and the launch / probe / update sequence against brute force, the 
 restatement of tests/ladder_reference.py, the struct's C layout, every validation code of the three entry points that returns
 before a HIP call, the classes' constructor checks, and adaptation_sync over two gloo ranks on a [n_temps] tensor."""
 import ctypes as C
-import os
-import socket
-import subprocess
 import warnings
 
 import numpy as np
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import ladder_reference as LR
 import ptrwm_hip as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+from host_harness import assert_layout, c_layout, gloo_world, run_exe, sanitized_exe, valid_args
 
 
 @pytest.fixture(scope="module")
 def ladder_exe(tmp_path_factory):
     """tests/ladder_test.cpp, a program of its own, compiled as plain C++ under AddressSanitizer and UBSan."""
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ladder_test.cpp")
-    exe = str(tmp_path_factory.mktemp("ladder") / "ladder_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", src, "-o", exe])
-    return exe
+    return sanitized_exe(tmp_path_factory.mktemp("ladder"), "ladder_test.cpp")
 
 
 def test_window_helpers_and_cuts_against_brute_force(ladder_exe):
@@ -38,9 +27,7 @@ def test_window_helpers_and_cuts_against_brute_force(ladder_exe):
     across a probe step, the same (probe, update) sequence whatever the cut; with the scale's adaptation at W = 7 next to V = 6
     the order scale reduce, scale update, ladder probe, ladder update at shared ends.  (The window helpers themselves:
     schedule_test.cpp, test_host_logic.py.)"""
-    out = subprocess.run([ladder_exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "ladder ok:" in out.stdout
+    run_exe(ladder_exe, ok="ladder ok:")
 
 
 def _bits(x):
@@ -80,9 +67,7 @@ def test_update_rule_against_numpy_float64(ladder_exe):
         cases.append((T, gain_j, beta, pooled, scale))
     lines = "".join(f"{T} {g!r} {' '.join(map(str, _bits(b)))} {' '.join(map(str, p))} {' '.join(map(str, _bits(s)))}\n"
                     for T, g, b, p, s in cases)
-    out = subprocess.run([ladder_exe, "update"], input=lines, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rows = out.stdout.splitlines()
+    rows = run_exe(ladder_exe, "update", input=lines).splitlines()
     assert len(rows) == n
     outcomes, worst, worst_s, exact = [0, 0, 0], 0, 0, 0
     for (T, g, beta, pooled, scale), row in zip(cases, rows):
@@ -113,37 +98,16 @@ FIELDS = ["struct_size", "every", "probe_every", "until", "gain", "decay", "resc
 
 def test_ladder_struct_layout_matches_the_c_header(tmp_path):
     assert [f[0] for f in E.LadderArgs._fields_] == FIELDS
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){",
-             'printf("size %zu\\n", sizeof(ptrwm_ladder_args));']
-    lines += [f'printf("{f} %zu\\n", offsetof(ptrwm_ladder_args, {f}));' for f in FIELDS]
-    lines.append('printf("abi %d\\n", PTRWM_ABI_VERSION);')
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert C.sizeof(E.LadderArgs) == int(got["size"])
-    for f in FIELDS:
-        assert getattr(E.LadderArgs, f).offset == int(got[f]), f
-    assert int(got["abi"]) == E.ABI_VERSION == 3  # additive: the version stays
+    got = c_layout(tmp_path, {"ptrwm_ladder_args": FIELDS}, macros=("PTRWM_ABI_VERSION",))
+    assert_layout(E.LadderArgs, "ptrwm_ladder_args", FIELDS, got)
+    assert got["PTRWM_ABI_VERSION"] == E.ABI_VERSION == 3  # additive: the version stays
 
 
-def _valid(n_temps=4, burn_in=100):
-    """Arguments the entry points accept up to their first HIP call (the pointers point at host memory a refused call never
-    reads)."""
-    buf = C.create_string_buffer(64)
-    ptr = C.cast(buf, C.c_void_p)
-    td, pd, ra, ld = E.TargetDesc(), E.ProposalDesc(), E.RunArgs(), E.LadderArgs()
-    td.kind, td.dim = E.TARGET_ROUGH_CARPET, 30
-    pd.kind, pd.temp_scale = E.PROPOSAL_NORMAL, ptr
-    ra.struct_size, ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = C.sizeof(E.RunArgs), n_temps, 4, 10, 1
-    ra.burn_in = burn_in
-    ra.state = ra.logp = ra.beta = ptr
-    ld.struct_size, ld.every, ld.probe_every, ld.until = C.sizeof(E.LadderArgs), 10, 5, burn_in
-    ld.gain, ld.decay, ld.rescale_scales = 2.0, 0.5, 1
-    ld.beta = ld.temp_scale = ld.pooled = ptr
-    return {"buf": buf, "ptr": ptr, "td": td, "pd": pd, "ra": ra, "ld": ld}
+def _valid(n_temps=4):
+    """Arguments the three entry points accept up to their first HIP call."""
+    # burn_in 100, so ld.until == 100 in windows of ld.every == 10: "until = 101 past burn_in", "window 9 ends after step 99"
+    # and the update's K = 10 windows below
+    return valid_args("ld", n_temps=n_temps, burn_in=100)
 
 
 def test_ladder_validation_needs_no_gpu():
@@ -288,34 +252,19 @@ def _pooled_shard(rank):
     return p
 
 
-def _sync_worker(rank, world, port, q):
+def _sync_worker(rank):
     from algorithms.sharding import adaptation_sync
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     p = _pooled_shard(rank)
     out = adaptation_sync()(p)
     assert out is p and p.dtype == torch.int64  # in place
-    q.put((rank, p.numpy()))
-    dist.barrier()
-    dist.destroy_process_group()
+    return p.numpy()
 
 
 def test_adaptation_sync_over_two_ranks_on_a_ladder_row():
     """gloo, two spawned ranks, CPU tensors of the ladder's [n_temps] shape: every rank ends with the same integers, the sum of
     the shards' pooled rows."""
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_sync_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=180) for _ in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    got = gloo_world(_sync_worker)
     want = (_pooled_shard(0) + _pooled_shard(1)).numpy()
     assert int(want[1]) == (1 << 53) + 7
     assert sorted(r for r, _ in got) == [0, 1]

@@ -3,17 +3,12 @@ of the two entry points returns before the first HIP call, the drop-in classes r
 allreduce_moments over a gloo world of two equals the sum of the shards.  CPU only."""
 import ctypes as C
 import os
-import socket
-import subprocess
 import sys
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+from host_harness import ROOT, assert_layout, c_layout, gloo_world, valid_args
 
 
 @pytest.fixture(scope="module")
@@ -30,88 +25,67 @@ def engine():
 
 def test_moments_args_mirror_has_the_c_layout(engine, tmp_path):
     fs = [f[0] for f in engine.MomentsArgs._fields_]
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){",
-             'printf("size %zu\\n", sizeof(ptrwm_moments_args));']
-    lines += [f'printf("{f} %zu\\n", offsetof(ptrwm_moments_args, {f}));' for f in fs]
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(l.split() for l in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert int(got["size"]) == C.sizeof(engine.MomentsArgs)
-    for f in fs:
-        assert int(got[f]) == getattr(engine.MomentsArgs, f).offset, f
+    assert_layout(engine.MomentsArgs, "ptrwm_moments_args", fs, c_layout(tmp_path, {"ptrwm_moments_args": fs}))
     assert fs == ["struct_size", "temps", "every", "sum", "sum_sq", "sum_logp", "count"]
 
 
-def _run_args(engine, n_temps, n_chains=4, n_steps=10):
-    ra = engine.RunArgs()
-    ra.struct_size = C.sizeof(engine.RunArgs)
-    ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = n_temps, n_chains, n_steps, 1
-    # never dereferenced: every case below is refused before anything is enqueued
-    ra.state, ra.logp, ra.beta = 0x1000, 0x2000, 0x3000
-    return ra
-
-
-def _moments(engine, temps, every=1, sums=True):
-    m = engine.MomentsArgs()
-    m.struct_size = C.sizeof(engine.MomentsArgs)
+def _moments(temps, every=1, sums=True):
+    """A fresh accumulator block (no pointer of these tests is ever dereferenced: every case is refused, or has nothing to
+    do, before anything is enqueued)."""
+    m = valid_args("mom")["mom"]
     m.temps, m.every = temps, every
-    if sums:
-        m.sum, m.sum_sq = 0x4000, 0x5000
+    if not sums:
+        m.sum = m.sum_sq = None
     return m
 
 
 def test_moments_refusals_need_no_gpu(engine):
     lib = engine.load_library()
-    td, pd = engine.TargetDesc(), engine.ProposalDesc()
-    td.kind, td.dim = engine.TARGET_ROUGH_CARPET, 30
+    v = valid_args(n_temps=8)
+    td, pd, ra = v["td"], v["pd"], v["ra"]
     td.p[0], td.p[1], td.p[2] = -15.0, 0.0, 15.0
-    pd.kind, pd.temp_scale = engine.PROPOSAL_NORMAL, 0x6000
-    ra = _run_args(engine, 8)
     run = lambda m: lib.ptrwm_run_with_moments(C.byref(td), C.byref(pd), C.byref(ra), m, None)  # noqa: E731
-    m = _moments(engine, 1)
+    m = _moments(1)
     m.struct_size = 8
     assert run(C.byref(m)) == -6  # PTRWM_E_STRUCT
     for temps, every in ((0, 1), (9, 1), (-1, 1), (1, 0), (8, -3)):
-        assert run(C.byref(_moments(engine, temps, every))) == -5, (temps, every)  # PTRWM_E_ARG
-    assert run(C.byref(_moments(engine, 1, sums=False))) == -1  # PTRWM_E_NULL
-    m = _moments(engine, 1)
+        assert run(C.byref(_moments(temps, every))) == -5, (temps, every)  # PTRWM_E_ARG
+    assert run(C.byref(_moments(1, sums=False))) == -1  # PTRWM_E_NULL
+    m = _moments(1)
     m.sum_sq = None
     assert run(C.byref(m)) == -1
     # the run's own checks come first, as in ptrwm_run
     ra.swap_every = 0
-    assert run(C.byref(_moments(engine, 1))) == -5
+    assert run(C.byref(_moments(1))) == -5
     ra.swap_every = 1
     ra.n_steps = 0
-    assert run(C.byref(_moments(engine, 1))) == 0  # empty: nothing to do
+    assert run(C.byref(_moments(1))) == 0  # empty: nothing to do
     # an accumulator too big for the kernel's LDS: every temperature of a 256-rung ladder at dim 60 (thread form)
     td.dim = 60
-    ra = _run_args(engine, 256)
+    ra = valid_args(n_temps=256)["ra"]
     assert engine.has_thread_variant(td.kind, pd.kind, 60) and not engine.has_quad_variant(td.kind, pd.kind, 60, 256)
     with engine.kernel_form(engine.FORM_THREAD):
-        assert run(C.byref(_moments(engine, 256))) == -5
+        assert run(C.byref(_moments(256))) == -5
 
     # split steps: the same argument checks
-    sp = _run_args(engine, 8)
+    sp = valid_args(n_temps=8)["ra"]
     assert lib.ptrwm_split_moments(C.byref(sp), 30, None, None) == -1
-    assert lib.ptrwm_split_moments(None, 30, C.byref(_moments(engine, 1)), None) == -1
-    m = _moments(engine, 1)
+    assert lib.ptrwm_split_moments(None, 30, C.byref(_moments(1)), None) == -1
+    m = _moments(1)
     m.struct_size = 0
     assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(m), None) == -6
-    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(engine, 9)), None) == -5
-    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(engine, 1, every=0)), None) == -5
-    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(engine, 1, sums=False)), None) == -1
-    assert lib.ptrwm_split_moments(C.byref(sp), 0, C.byref(_moments(engine, 1)), None) == -2
+    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(9)), None) == -5
+    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(1, every=0)), None) == -5
+    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(1, sums=False)), None) == -1
+    assert lib.ptrwm_split_moments(C.byref(sp), 0, C.byref(_moments(1)), None) == -2
     sp.n_chains = 0
-    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(engine, 1)), None) == 0  # empty batch
+    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(1)), None) == 0  # empty batch
     # a step that does not count is known on the host: nothing is enqueued
-    sp = _run_args(engine, 8)
+    sp = valid_args(n_temps=8)["ra"]
     sp.burn_in, sp.step0 = 10, 3
-    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(engine, 1)), None) == 0
+    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(1)), None) == 0
     sp.burn_in, sp.step0 = 0, 4  # step_counter 5, every 2
-    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(engine, 1, every=2)), None) == 0
+    assert lib.ptrwm_split_moments(C.byref(sp), 30, C.byref(_moments(1, every=2)), None) == 0
 
 
 def test_the_classes_reject_bad_moments_arguments(engine):
@@ -144,35 +118,20 @@ def _shard(rank):
             "count": torch.randint(0, 1 << 40, (TEMPS,), generator=g, dtype=torch.int64), "every": 5}
 
 
-def _worker(rank, world, port, q):
+def _worker(rank):
     from algorithms.sharding import allreduce_moments
 
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     shard = _shard(rank)
     kept = {k: v.clone() for k, v in shard.items() if torch.is_tensor(v)}
     total = allreduce_moments(shard)
     assert all(torch.equal(shard[k], v) for k, v in kept.items())  # inputs untouched
-    q.put((rank, {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in total.items()}))
-    dist.barrier()
-    dist.destroy_process_group()
+    return {k: (v.numpy() if torch.is_tensor(v) else v) for k, v in total.items()}
 
 
 def test_allreduce_moments_over_two_ranks_is_the_sum_of_the_shards():
     from algorithms.sharding import allreduce_moments
 
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.get_context("spawn")
-    q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
-    got = [q.get(timeout=180) for _ in procs]
-    for p in procs:
-        p.join(60)
-        assert p.exitcode == 0
+    got = gloo_world(_worker)
     a, b = _shard(0), _shard(1)
     for _, total in got:
         for k in ("sum", "sum_sq", "sum_logp"):

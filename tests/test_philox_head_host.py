@@ -1,7 +1,6 @@
 """csrc/philox_head.h on the CPU (no GPU needed): the head / tail split of a Philox block that the production step kernel of
 the headline shape runs, the launch cut that keeps a parked head valid, and the one-fma u01_open0."""
-import os
-import subprocess
+from host_harness import run_exe, sanitized_exe
 
 
 def test_philox_head_and_tail_are_the_plain_block(tmp_path):
@@ -10,10 +9,5 @@ def test_philox_head_and_tail_are_the_plain_block(tmp_path):
     on 10^6 random (key, step, chain, temperature, stream, block) tuples and on the crossed corners - every block index
     0..26, steps and chain ids on both sides of 2^32, streams 0 and 1; u01_open0 equals its former two-operation form on all
     2^24 inputs; csrc/schedule.h lets no launch hold steps with different high words, and cuts nothing else."""
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "philox_head_test.cpp")
-    exe = str(tmp_path / "philox_head_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=all", src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "philox head ok: 1045363 blocks, 16777216 u01_open0 inputs, 22320 launches" in out.stdout
+    run_exe(sanitized_exe(tmp_path, "philox_head_test.cpp"),
+            ok="philox head ok: 1045363 blocks, 16777216 u01_open0 inputs, 22320 launches")

@@ -3,28 +3,20 @@ GPU: the proposal kernel's index maps and a CPU replay of it against the rule's 
 skips (tests/precond_test.cpp under ASan and UBSan); the header held to tests/precond_reference.py bit for bit; the structs'
 C layout; every validation code of the two entry points that returns before a HIP call."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import precond_reference as PR
 import ptrwm_hip as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ptrwm.h")
+from host_harness import assert_layout, c_layout, run_exe, sanitized_exe, valid_args
 
 
 @pytest.fixture(scope="module")
 def precond_exe(tmp_path_factory):
-    """tests/precond_test.cpp, a program of its own, compiled as plain C++ under AddressSanitizer and UBSan (-ffp-contract=off:
-    the header's operations are rounded one by one)."""
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "precond_test.cpp")
-    exe = str(tmp_path_factory.mktemp("precond") / "precond_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe])
-    return exe
+    """tests/precond_test.cpp, a program of its own, compiled as plain C++ under AddressSanitizer and UBSan."""
+    # -ffp-contract=off: the header's operations are rounded one by one (the bitwise tests below hold it to Python floats)
+    return sanitized_exe(tmp_path_factory.mktemp("precond"), "precond_test.cpp", "-ffp-contract=off")
 
 
 def test_maps_replay_and_update_rule(precond_exe):
@@ -32,15 +24,13 @@ def test_maps_replay_and_update_rule(precond_exe):
     read inside the slabs on a written element, the LDS byte count what the maps touch; (b) the replay of staging, K-steps and
     epilogue equals the direct chain; (c) L L^T within (2^-23 + 2^-48 + (dim + 1) 2^-52) (|L| |L^T|)_ij of A, and a non-positive
     pivot, a sum that is not finite and w < min_count each leave the factor's bits alone; `memory` applied as stated."""
-    out = subprocess.run([precond_exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert "precond ok:" in out.stdout
+    run_exe(precond_exe, ok="precond ok:")
 
 
 def test_geometry_of_the_gpu_shapes(precond_exe):
     dims = [1, 3, 4, 5, 16, 17, 30, 33, 64, 104]
-    out = subprocess.run([precond_exe, "geometry"], input="".join(f"{d}\n" for d in dims), capture_output=True, text=True, timeout=60)
-    rows = [tuple(map(int, ln.split())) for ln in out.stdout.splitlines()]
+    out = run_exe(precond_exe, "geometry", input="".join(f"{d}\n" for d in dims), timeout=60)
+    rows = [tuple(map(int, ln.split())) for ln in out.splitlines()]
     assert len(rows) == len(dims)
     geo = dict(zip(dims, rows))
     assert [geo[d][0] for d in dims] == [1, 1, 1, 1, 1, 2, 2, 3, 4, 7]  # blocks: 17 and 33 open a block with one coordinate
@@ -71,9 +61,8 @@ def test_launch_grid_mirror_is_the_headers(precond_exe):
         pairs += [(t, cus) for t in sorted(tiles)]
     pairs += [(t, cus) for cus in (0, -1) for t in (1, 2047, 2048, 2049, 4134)]  # (unknown: 256 compute units)
     assert (PR.tiles(210), PR.tiles(32768 * 4), PR.tiles(65536 * 4), PR.tiles(64), PR.tiles(65)) == (4, 2048, 4096, 1, 2)
-    out = subprocess.run([precond_exe, "grid"], input="".join(f"{t} {c}\n" for t, c in pairs), capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stderr[-2000:]
-    got = [int(ln) for ln in out.stdout.splitlines()]
+    out = run_exe(precond_exe, "grid", input="".join(f"{t} {c}\n" for t, c in pairs), timeout=60)
+    got = [int(ln) for ln in out.splitlines()]
     assert got == [PR.grid(t, c) for t, c in pairs]
     assert PR.grid(4134, 256) == 2048 == PR.grid(4134, 0) and PR.grid(5, 256) == 5 and PR.grid(RD.HUGE, 2) == 16
 
@@ -152,9 +141,7 @@ def test_update_rule_against_python_floats_bitwise(precond_exe):
     for dim, memory, jitter, min_count, n, sxx, sx, run_xx, run_x, run_w, chol in cases:
         nums = [*_bits64(sxx), *_bits64(sx), *_bits64(run_xx), *_bits64(run_x), *_bits64([run_w]), *_bits32(chol)]
         lines.append(f"{dim} {memory!r} {jitter!r} {min_count!r} {n} " + " ".join(map(str, nums)) + "\n")
-    out = subprocess.run([precond_exe, "update"], input="".join(lines), capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    rows = out.stdout.splitlines()
+    rows = run_exe(precond_exe, "update", input="".join(lines), timeout=600).splitlines()
     assert len(rows) == len(cases)
     outcomes = [0, 0, 0]
     for (dim, memory, jitter, min_count, n, sxx, sx, run_xx, run_x, run_w, chol), row in zip(cases, rows):
@@ -191,9 +178,7 @@ def test_proposal_rule_against_libm_fmaf_bitwise(precond_exe):
         chol_in = np.where(np.isnan(chol), np.float32(777), chol)  # (text cannot carry the NaN's payload; the maps never read it)
         nums = [*_bits32(scale), *_bits32(x), *_bits32(chol_in), *_bits32(z)]
         lines.append(f"{dim} {n} " + " ".join(map(str, nums)) + "\n")
-    out = subprocess.run([precond_exe, "propose"], input="".join(lines), capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    rows = out.stdout.splitlines()
+    rows = run_exe(precond_exe, "propose", input="".join(lines)).splitlines()
     assert len(rows) == len(cases)
     for (dim, n, x, z, chol, scale), row in zip(cases, rows):
         v = np.array(row.split(), np.uint32)
@@ -312,38 +297,16 @@ UPDATE_FIELDS = ["struct_size", "reserved", "chol", "sxx", "sx", "count", "run_x
 
 def test_struct_layouts_match_the_c_header(tmp_path):
     assert [f[0] for f in E.PrecondArgs._fields_] == PRECOND_FIELDS and [f[0] for f in E.PrecondUpdateArgs._fields_] == UPDATE_FIELDS
-    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){",
-             'printf("size_p %zu\\n", sizeof(ptrwm_precond_args));', 'printf("size_u %zu\\n", sizeof(ptrwm_precond_update_args));']
-    lines += [f'printf("p_{f} %zu\\n", offsetof(ptrwm_precond_args, {f}));' for f in PRECOND_FIELDS]
-    lines += [f'printf("u_{f} %zu\\n", offsetof(ptrwm_precond_update_args, {f}));' for f in UPDATE_FIELDS]
-    lines.append('printf("abi %d\\n", PTRWM_ABI_VERSION);')
-    lines.append("return 0;}")
-    src = tmp_path / "probe.c"
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "probe"
-    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
-    got = dict(ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())
-    assert C.sizeof(E.PrecondArgs) == int(got["size_p"]) and C.sizeof(E.PrecondUpdateArgs) == int(got["size_u"])
-    for f in PRECOND_FIELDS:
-        assert getattr(E.PrecondArgs, f).offset == int(got["p_" + f]), f
-    for f in UPDATE_FIELDS:
-        assert getattr(E.PrecondUpdateArgs, f).offset == int(got["u_" + f]), f
-    assert int(got["abi"]) == E.ABI_VERSION == 3  # additive: the version stays
+    got = c_layout(tmp_path, {"ptrwm_precond_args": PRECOND_FIELDS, "ptrwm_precond_update_args": UPDATE_FIELDS},
+                   macros=("PTRWM_ABI_VERSION",))
+    assert_layout(E.PrecondArgs, "ptrwm_precond_args", PRECOND_FIELDS, got)
+    assert_layout(E.PrecondUpdateArgs, "ptrwm_precond_update_args", UPDATE_FIELDS, got)
+    assert got["PTRWM_ABI_VERSION"] == E.ABI_VERSION == 3  # additive: the version stays
     assert "ptrwm_split_propose_precond" in E.SYMBOLS and "ptrwm_precond_update" in E.SYMBOLS
 
 
 def _valid(n_temps=4):
-    buf = C.create_string_buffer(64)
-    ptr = C.cast(buf, C.c_void_p)
-    pd, ra, pa, up = E.ProposalDesc(), E.RunArgs(), E.PrecondArgs(), E.PrecondUpdateArgs()
-    pd.kind, pd.temp_scale = E.PROPOSAL_NORMAL, ptr
-    ra.struct_size, ra.n_temps, ra.n_chains, ra.n_steps, ra.swap_every = C.sizeof(E.RunArgs), n_temps, 4, 1, 1
-    ra.state = ra.logp = ra.beta = ptr
-    pa.struct_size, pa.chol = C.sizeof(E.PrecondArgs), ptr
-    up.struct_size = C.sizeof(E.PrecondUpdateArgs)
-    up.chol = up.sxx = up.sx = up.count = up.run_xx = up.run_x = up.run_w = ptr
-    up.memory, up.jitter, up.min_count, up.windows = 0.5, 1e-6, 20.0, 3
-    return {"buf": buf, "ptr": ptr, "pd": pd, "ra": ra, "pa": pa, "up": up}
+    return valid_args("pa", "up", n_temps=n_temps)
 
 
 def test_validation_needs_no_gpu():

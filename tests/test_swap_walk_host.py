@@ -1,7 +1,6 @@
 """csrc/swap_walk.h on the CPU (no GPU needed): the lane-mask walk that decides the sequential exchange sweep of the step
 kernel's one-wavefront exchange groups, against a literal restatement of the sweep."""
-import os
-import subprocess
+from host_harness import run_exe, sanitized_exe
 
 
 def test_swap_walk_is_the_sequential_scan(tmp_path):
@@ -11,11 +10,8 @@ def test_swap_walk_is_the_sequential_scan(tmp_path):
     Random: T in {7, 8, 16, 21, 31, 32, 63, 64}, every number of ladders per wavefront, random bits in the idle lanes'
     mask positions, the threshold and the literal rule mixed per ladder within a wavefront.  For every position: the
     source lane, the travelled log-density (bit for bit) and pair_acc equal the scan's."""
-    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "swap_walk_test.cpp")
-    exe = str(tmp_path / "swap_walk_test")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-g", "-Wall", "-Wextra", "-Werror", "-ffp-contract=off", "-pthread",
-                           "-fsanitize=address,undefined", "-fno-sanitize-recover=all", src, "-o", exe])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
-    assert ("swap walk ok: 2018521043 ladders exhaustive (T = 2..6, seven values), 18000 random wavefronts of 63000 ladders"
-            in out.stdout)
+    # -ffp-contract=off: the literal rule of a pair is four products summed left to right, each rounded on its own;
+    # -O2 and -pthread: two billion exhaustive ladders, which the program spreads over 16 std::threads
+    exe = sanitized_exe(tmp_path, "swap_walk_test.cpp", "-ffp-contract=off", "-pthread", opt="-O2")
+    run_exe(exe, timeout=600, ok="swap walk ok: 2018521043 ladders exhaustive (T = 2..6, seven values), 18000 random wavefronts "
+                                 "of 63000 ladders")
