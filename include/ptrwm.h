@@ -736,6 +736,76 @@ int32_t ptrwm_run_with_covariance(const ptrwm_target_desc *target, const ptrwm_p
                                   const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder,
                                   const ptrwm_acf_args *acf, const ptrwm_cov_args *cov, void *stream);
 
+/* ---- pooled log-density sums along the ladder: normalising-constant ratios and the energy per rung, without a trace ------------
+ * What is log Z(beta_a) / Z(beta_b), Z(beta) = integral of pi(x)^beta dx, and where does the ladder need rungs?  A snapshot is
+ * due at every step whose step_counter > burn_in and step_counter % every == 0 (the histograms', the autocovariance's and the
+ * covariance's rule).  At a due step, for every local chain c and temperature t, with l = logp[c, t] - the float32 log-density
+ * after the whole step, swap event included - and g = (chain_offset + c) mod groups, the chain's group by its global id:
+ *   l not finite:  nonfinite[0] += 1 and nothing else.
+ *   otherwise, with x = (double) l and y = x - ref[t] (one double subtraction):
+ *     count[g, t] += 1      s1[g, t] += x      s2[g, t] += x * x
+ *     t >= 1:            colder[g, t] += exp(((double) beta[t - 1] - (double) beta[t]) * y)
+ *     t <= n_temps - 2:  hotter[g, t] += exp(((double) beta[t + 1] - (double) beta[t]) * y)
+ * colder[:, 0] and hotter[:, n_temps - 1] are never written; with n_temps = 1 neither array is touched.  An overflowing exp
+ * leaves inf in its sum.  Only the order of the additions is free (tile sums are flushed with fp64 atomics, the counters with
+ * integer atomics).
+ * ref, the level the exponential sums are taken against, keeps an unnormalised log-density (one offset by -1e6, say) from
+ * overflowing or underflowing.  While ref_set[0] is 0, a due snapshot first sets ref[t] to the largest finite l of temperature
+ * t over the local chains at that snapshot (0 where none is finite) and ref_set[0] to 1 - a maximum, so ref is deterministic;
+ * a non-zero flag leaves ref alone.  A caller may pin ref and pre-set the flag: shards that share a pinned ref have sums that
+ * add directly; shards with their own ref rescale colder / hotter to a common one on the host before they add.
+ * The groups are disjoint sets of independent chains - a sharded run puts every chain in the group the unsharded run does -
+ * and the delete-one-group jackknife over them gives error bars that hold whatever the chains' autocorrelation in time.
+ * On the host, with n[t] = sum_g count[g, t] and the sums added over g, for t = 1 .. n_temps - 1:
+ *   forward[t] =   log(colder[t] / n[t])         + (beta[t-1] - beta[t]) ref[t]
+ *   reverse[t] = -(log(hotter[t-1] / n[t-1])     + (beta[t] - beta[t-1]) ref[t-1])
+ * both estimate log Z(beta[t-1]) / Z(beta[t]) (stepping stones; E forward <= truth <= E reverse), and s1 / n, s2 / n give the
+ * mean and variance of l per rung: thermodynamic integration, and the heat capacity beta^2 Var(l).
+ * The rule is csrc/energy.h's.  Everything is added to (+=): launches, calls and shards compose.  ptrwm_swap_sweep events are
+ * not steps and add nothing.  beta is read at the snapshot: after a ladder tuning it is the final ladder (past burn-in nothing
+ * adapts).  The accumulators must be ordinary device memory of the current device.
+ * How: NOT in the step kernels.  Two small kernels read logp between launches: one workgroup that sets ref (it returns at once
+ * where the flag is set), and the accumulating kernel - a workgroup serves chains of one group, lanes run along the rows of
+ * logp, partial sums per temperature sit in LDS and are flushed once per workgroup.  It reads n_chains * n_temps floats. */
+#define PTRWM_ENERGY_MAX_GROUPS 64
+typedef struct ptrwm_energy_args {
+  uint32_t struct_size; /* sizeof(ptrwm_energy_args) */
+  int32_t groups;       /* 1..PTRWM_ENERGY_MAX_GROUPS */
+  int32_t every;        /* >= 1: a snapshot at every step past burn-in whose step_counter is a multiple */
+  double *ref;          /* device [n_temps]; written once while *ref_set == 0, else only read */
+  int32_t *ref_set;     /* device [1]; 0: the next due snapshot sets ref and this flag */
+  int64_t *count;       /* device [groups, n_temps], += */
+  int64_t *nonfinite;   /* device [1], +=; may be NULL */
+  double *s1;           /* device [groups, n_temps], += */
+  double *s2;           /* device [groups, n_temps], += */
+  double *colder;       /* device [groups, n_temps], += on t >= 1; may be NULL with n_temps = 1 */
+  double *hotter;       /* device [groups, n_temps], += on t <= n_temps - 2; may be NULL with n_temps = 1 */
+} ptrwm_energy_args;
+
+/* One snapshot: logp as it stands after step args->step0 (device-step mode: *device_step + step0 - read on the device, as is
+ * ref_set, so the call can sit inside a captured block of split steps, after ptrwm_split_accept); a step that is not due adds
+ * nothing.  Reads from `args`: n_temps, n_chains, chain_offset, logp, beta, burn_in, step0, device_step.
+ * Checked, in this order, before anything is enqueued: PTRWM_E_NULL for a NULL args / energy; PTRWM_E_STRUCT for a wrong
+ * struct_size of args; PTRWM_E_TEMPS as everywhere; PTRWM_E_ARG for a negative n_chains, step0 or burn_in; then
+ * the block's own checks as below; an empty batch returns PTRWM_OK; PTRWM_E_NULL for a NULL logp or beta. */
+int32_t ptrwm_energy(const ptrwm_run_args *args, const ptrwm_energy_args *energy, void *stream);
+
+/* ptrwm_run_with_covariance, plus the log-density sums.  energy == NULL: exactly ptrwm_run_with_covariance.
+ * A launch of the request additionally ends at every step whose step_counter is past burn_in and a multiple of energy->every,
+ * and the two kernels are enqueued right after it on `stream` (behind the histogram's, the autocovariance's and the
+ * covariance's, where those are due at the same step); a request without such a step performs exactly the launches it performs
+ * without `energy`.  No step kernel is told about it, and everything else of the run is bit-identical with and without
+ * `energy`, with the one exception that holds for any change of where a run is cut into launches (ptrwm_run_args.sq_jump above).
+ * Checked before anything is enqueued, after every other block's checks: PTRWM_E_STRUCT for a wrong energy->struct_size;
+ * PTRWM_E_ARG for groups outside 1..PTRWM_ENERGY_MAX_GROUPS or every < 1; PTRWM_E_NULL for a NULL ref, ref_set, count, s1 or
+ * s2, and for a NULL colder or hotter with n_temps >= 2 (nonfinite may be NULL).  An empty batch returns PTRWM_OK. */
+int32_t ptrwm_run_with_energy(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal,
+                              const ptrwm_run_args *args, const ptrwm_moments_args *moments,
+                              const ptrwm_chain_moments_args *chain_moments, const ptrwm_flow_args *flow,
+                              const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt, const ptrwm_ladder_args *ladder,
+                              const ptrwm_acf_args *acf, const ptrwm_cov_args *cov, const ptrwm_energy_args *energy,
+                              void *stream);
+
 /* One stand-alone swap event over the current states: what the reference's
  * ParallelTemperingRWM_GPU_Optimized._attempt_all_swaps() does when called on its own
  * (pt_rwm_gpu_optimized.py:594-633; tests/debug_pt_performance.py:156).  Exactly the swap part of a ptrwm_run step:

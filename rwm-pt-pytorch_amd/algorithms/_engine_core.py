@@ -63,6 +63,16 @@ to by a snapshot kernel between launches at every cov_every-th step past burn-in
     sx     float64 [cov_temps, dim]        sums of x_i
     count  int64   [1]                     (replica, snapshot) pairs added
 
+and, with energy=True, the pooled log-density sums along the ladder (`_energy`, a dict; include/ptrwm.h ptrwm_energy_args,
+csrc/energy.h), added to by two small kernels between launches at every energy_every-th step past burn-in, per group g of chains
+(global replica id mod energy_groups), with `_energy_ref` [n_temps] float64, the level the exponential sums are taken against, and
+`_energy_ref_set` [1] int32, its flag:
+
+    count           int64   [groups, n_temps]   finite log-densities added
+    s1, s2          float64 [groups, n_temps]   sums of l and of l^2
+    colder, hotter  float64 [groups, n_temps]   sums of exp((beta[t -+ 1] - beta[t]) (l - ref[t])); column 0 / n_temps - 1 unused
+    nonfinite       int64   [1]                 log-densities that were not finite (added nowhere else)
+
 `n_replicas` is the axis the reference does not have: independent copies of the whole chain /
 ladder, one Philox subsequence each (global replica id = chain_offset + local index), so a run is
 invariant to how replicas are sharded over GPUs.
@@ -428,7 +438,8 @@ class EngineRun:
                  acf_ring_limit: Optional[int] = None, cov_temps: int = 0, cov_every: int = 1, proposal_chol=None,
                  adapt_cov: bool = False, cov_adapt_every: int = 200, cov_adapt_until: Optional[int] = None,
                  cov_adapt_probe_every: Optional[int] = None, cov_adapt_memory: float = 0.5, cov_adapt_jitter: float = 1e-6,
-                 cov_adapt_min_count: Optional[float] = None):
+                 cov_adapt_min_count: Optional[float] = None, energy: bool = False, energy_every: int = 1,
+                 energy_groups: int = 16, energy_ref=None):
         adapt = check_adapt_args(adapt_scale, max(0, int(burn_in)), adapt_every, adapt_until, adapt_target, adapt_gain,
                                  adapt_decay, adapt_scale_bounds, adapt_sync)
         ladder = check_ladder_args(adapt_ladder, max(0, int(burn_in)), beta_ladder, ladder_every, ladder_until,
@@ -465,6 +476,7 @@ class EngineRun:
         hist_box = check_hist_args(hist_temps, hist_every, hist_bins, hist_range, n_temps, dim)
         acf_on = check_acf_args(acf_temps, acf_every, acf_max_lag, n_temps, dim, n_replicas, acf_ring_limit)
         cov_on = check_cov_args(cov_temps, cov_every, n_temps)
+        energy_on = check_energy_args(energy, energy_every, energy_groups, energy_ref, n_temps)
         # the starts (host-side checks, before the device is asked for: bad arguments fail the same way without a GPU)
         axes = start_shape(initial_state, dim, n_replicas, n_temps)
         box = check_init_box(init_box, dim)
@@ -583,8 +595,8 @@ class EngineRun:
                           **{k: torch.empty(shape, device=device, dtype=torch.int64) for k in ("round_trips", "n_up", "n_down")}}
             self.reset_flow()
             self._plan.set_flow(self._flow["walker"], self._flow["round_trips"], self._flow["n_up"], self._flow["n_down"])
-        # The snapshot accumulators - pooled marginal histograms, lagged autocovariance, posterior covariance - each added to by
-        # a snapshot kernel between launches.  One description each: the dict of its sums under the attribute's name, zeroed by
+        # The snapshot accumulators - pooled marginal histograms, lagged autocovariance, posterior covariance, log-density sums
+        # along the ladder - each added to by a snapshot kernel between launches.  One description each: the dict of its sums under the attribute's name, zeroed by
         # _reset_snapshot and read out by _snapshot_sums (off: None); scratch - the bin rule's constants, the ring - stays out of it.
         self.hist_temps, self.hist_every, self.hist_bins = int(hist_temps), int(hist_every), int(hist_bins)
         self.acf_temps, self.acf_every, self.acf_max_lag = int(acf_temps), int(acf_every), int(acf_max_lag)
@@ -593,7 +605,7 @@ class EngineRun:
         def zeros(*shape, dtype=torch.float64):
             return torch.zeros(*shape, device=device, dtype=dtype)
 
-        self._hist = self._acf = self._cov = None
+        self._hist = self._acf = self._cov = self._energy = None
         if hist_box is not None:
             lo, hi = hist_box
             self._hist_edges = hist_edges(lo, hi, self.hist_bins)
@@ -609,6 +621,18 @@ class EngineRun:
         if cov_on:
             c = self._cov = {"sxx": zeros(self.cov_temps, dim, dim), "sx": zeros(self.cov_temps, dim), "count": zeros(1, dtype=torch.int64)}
             self._plan.set_covariance(c["sxx"], c["sx"], c["count"], every=self.cov_every)
+        if energy_on is not None:
+            # (the level and its flag stay out of the dict of sums: a reset leaves a pinned level where it is)
+            G = self.energy_groups = energy_on["groups"]
+            self.energy_every, self._energy_pinned = energy_on["every"], energy_on["ref"] is not None
+            e = self._energy = {"count": zeros(G, n_temps, dtype=torch.int64), **{k: zeros(G, n_temps) for k in ("s1", "s2", "colder", "hotter")},
+                                "nonfinite": zeros(1, dtype=torch.int64)}
+            self._energy_ref, self._energy_ref_set = zeros(n_temps), zeros(1, dtype=torch.int32)
+            if self._energy_pinned:
+                self._energy_ref.copy_(torch.from_numpy(energy_on["ref"]))
+                self._energy_ref_set.fill_(1)
+            self._plan.set_energy(e["count"], e["s1"], e["s2"], e["colder"], e["hotter"], ref=self._energy_ref,
+                                  ref_set=self._energy_ref_set, nonfinite=e["nonfinite"], every=self.energy_every)
         # The warm-up tunings (WarmupTuning, each None when off), in the order the host loop serves them - the library's own:
         # the scale's update and the ladder's rescaling both write temp_scale, and the fused loop runs the scale's kernels
         # before the ladder's.  `beta` and `chol` are the run's own tensors: the update kernels rewrite them in place (so
@@ -1048,6 +1072,23 @@ class EngineRun:
     def reset_covariance(self) -> None:
         """Zero the covariance sums (the chains keep their states)."""
         self._reset_snapshot("_cov")
+
+    def energy_sums(self) -> Optional[dict]:
+        """The pooled log-density sums of this shard, or None when they are off: count [groups, n_temps] int64, s1 / s2 / colder /
+        hotter [groups, n_temps] float64, nonfinite [1] int64, ref [n_temps] float64, ref_set [1] int32 and beta [n_temps]
+        float32 - the ladder as it stands - (device tensors, no synchronisation), and every, pinned."""
+        if self._energy is None:
+            return None
+        return self._snapshot_sums("_energy", ref=self._energy_ref, ref_set=self._energy_ref_set, beta=self.beta,
+                                   every=self.energy_every, pinned=self._energy_pinned)
+
+    def reset_energy(self) -> None:
+        """Zero the log-density sums (the chains keep their states); a level the run chose itself is chosen anew by the next
+        due snapshot, a pinned one (energy_ref=) stays."""
+        self._reset_snapshot("_energy")
+        if self._energy is not None and not self._energy_pinned:
+            self._energy_ref_set.zero_()
+            self._energy_ref.zero_()
 
     def flow(self) -> Optional[dict]:
         """Replica flow of this shard (device tensors, no synchronisation), or None when flow is off: walker (int32 flow
@@ -1503,6 +1544,228 @@ class PosteriorCovariance:
         if getattr(self, "_cov_mode", None) is None:
             return {}
         return {"cov_condition": cov_condition(self.posterior_covariance(0)), "cov_count": self.covariance_count}
+
+
+# ---- pooled log-density sums along the ladder: estimators and the drop-in classes' readers ---------------------------------------
+ENERGY_METHODS = ("forward", "reverse", "thermodynamic", "thermodynamic_corrected")
+
+
+def check_energy_args(energy, energy_every=1, energy_groups=16, energy_ref=None, n_temps: Optional[int] = None) -> Optional[dict]:
+    """EngineRun's arguments of the log-density sums (no GPU needed): None when off, else {"every", "groups", "ref"} - ref None
+    (the first due snapshot chooses the level) or float64 [n_temps] (pinned: a scalar stands for every temperature).  With
+    n_temps None (a class whose ladder is not built yet) a vector's length is left to EngineRun."""
+    if not isinstance(energy, (bool, np.bool_)):
+        raise ValueError(f"energy must be True or False, got {energy!r}")
+    if not energy:
+        if energy_ref is not None:
+            raise ValueError("energy_ref pins the level of energy=True: it does nothing without it")
+        return None
+    every, groups = _integer("energy_every", energy_every, 1), _integer("energy_groups", energy_groups, 1)
+    if groups > ptrwm_hip.ENERGY_MAX_GROUPS:
+        raise ValueError(f"energy_groups must be in 1..{ptrwm_hip.ENERGY_MAX_GROUPS}, got {energy_groups!r}")
+    ref = None
+    if energy_ref is not None:
+        r = energy_ref.detach().cpu().numpy() if torch.is_tensor(energy_ref) else np.asarray(energy_ref)
+        if r.dtype == object or not np.issubdtype(r.dtype, np.number) or np.issubdtype(r.dtype, np.complexfloating):
+            raise ValueError(f"energy_ref must be a number or a [n_temps] vector of numbers, got {energy_ref!r}")
+        ref = np.asarray(r, dtype=np.float64)
+        if ref.ndim > 1 or (ref.ndim == 1 and n_temps is not None and ref.shape[0] != n_temps):
+            raise ValueError(f"energy_ref must be a scalar or a [n_temps] = [{n_temps}] vector, got shape {tuple(ref.shape)}")
+        if not np.isfinite(ref).all():
+            raise ValueError("energy_ref must be finite")
+        if n_temps is not None:
+            ref = np.ascontiguousarray(np.broadcast_to(ref, (n_temps,)))
+    return {"every": every, "groups": groups, "ref": ref}
+
+
+def _f64(x) -> np.ndarray:
+    return torch.as_tensor(x).detach().cpu().to(torch.float64).numpy()
+
+
+def _energy_jackknife(estimate, used: np.ndarray) -> np.ndarray:
+    """The delete-one-group jackknife standard error of estimate(mask), mask a bool [groups] of the groups summed over, over the
+    m groups of `used`: se^2 = (m - 1) / m sum_g (theta_(g) - mean theta_(.))^2, NaN for m < 2."""
+    idx = np.flatnonzero(used)
+    m = len(idx)
+    if m < 2:
+        return np.full_like(np.asarray(estimate(used), dtype=np.float64), np.nan)
+    theta = []
+    for g in idx:
+        mask = used.copy()
+        mask[g] = False
+        theta.append(np.asarray(estimate(mask), dtype=np.float64))
+    theta = np.stack(theta)
+    with np.errstate(invalid="ignore"):
+        return np.sqrt((m - 1) / m * ((theta - theta.mean(0)) ** 2).sum(0))
+
+
+def energy_moments_from_sums(count, s1, s2, beta) -> dict:
+    """Per rung, from the sums [groups, n_temps] added over the groups: "mean" = s1 / n, the mean of l = log pi; "variance" =
+    s2 / n - mean^2 (divided by n, as posterior_variance is); "heat_capacity" = beta^2 variance, whose shape over the ladder
+    says where it needs rungs; "count" = n.  float64 [n_temps] on the CPU (count int64); NaN where n = 0."""
+    n = torch.as_tensor(count).detach().cpu().to(torch.int64).sum(0)
+    nf, a, b, be = n.to(torch.float64).numpy(), _f64(s1).sum(0), _f64(s2).sum(0), _f64(beta)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(nf > 0, a / nf, np.nan)
+        var = np.where(nf > 0, b / nf - mean * mean, np.nan)
+    return {"mean": torch.from_numpy(mean), "variance": torch.from_numpy(var), "heat_capacity": torch.from_numpy(be * be * var),
+            "count": n}
+
+
+def stepping_stones_from_sums(count, colder, hotter, ref, beta) -> dict:
+    """The stepping-stone estimates of log Z(beta[t-1]) / Z(beta[t]), t = 1 .. n_temps - 1 (entry t - 1 of each array), from the
+    sums [groups, n_temps] and the level ref [n_temps] they were taken against:
+        forward[t] =   log(colder[t] / n[t])     + (beta[t-1] - beta[t]) ref[t]        (draws of rung t)
+        reverse[t] = -(log(hotter[t-1] / n[t-1]) + (beta[t] - beta[t-1]) ref[t-1])     (draws of rung t - 1)
+    By Jensen E forward <= truth <= E reverse.  "forward_se" / "reverse_se": the delete-one-group jackknife over the groups that
+    have draws at the rung involved (NaN with fewer than two); "forward_total" / "reverse_total" and their "_se": the sum over
+    the ladder, log Z(beta[0]) / Z(beta[n_temps-1]), jackknifed as a whole over the groups with draws at every rung;
+    "overflow": an exponential sum holds an inf (choose or pin a higher ref).  float64 on the CPU."""
+    n, c, h, r, be = _f64(count), _f64(colder), _f64(hotter), _f64(ref), _f64(beta)
+    T = n.shape[1]
+
+    def forward(mask, t):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.log(c[mask, t].sum() / n[mask, t].sum()) + (be[t - 1] - be[t]) * r[t]
+
+    def reverse(mask, t):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return -(np.log(h[mask, t - 1].sum() / n[mask, t - 1].sum()) + (be[t] - be[t - 1]) * r[t - 1])
+
+    out = {}
+    everywhere = (n > 0).all(1)
+    for name, fn, rung in (("forward", forward, 0), ("reverse", reverse, -1)):
+        used = [n[:, t + rung] > 0 for t in range(1, T)]
+        out[name] = torch.tensor([fn(u, t) for t, u in zip(range(1, T), used)], dtype=torch.float64)
+        out[name + "_se"] = torch.tensor([float(_energy_jackknife(lambda m, t=t: fn(m, t), u)) for t, u in zip(range(1, T), used)],
+                                         dtype=torch.float64)
+        out[name + "_total"] = float(out[name].sum())
+        out[name + "_total_se"] = float(_energy_jackknife(lambda m: sum(fn(m, t) for t in range(1, T)), everywhere)) if T > 1 else float("nan")
+    out["overflow"] = bool(np.isinf(c[:, 1:]).any() or np.isinf(h[:, :-1]).any()) if T > 1 else False
+    return out
+
+
+def thermodynamic_integral_from_sums(count, s1, s2, beta) -> dict:
+    """Thermodynamic integration of log Z(beta[t-1]) / Z(beta[t]) = integral of E_beta[l] d beta, t = 1 .. n_temps - 1 (entry
+    t - 1), with E[t] and V[t] the mean and variance of l at rung t:
+        trapezoid[t] = (beta[t-1] - beta[t]) (E[t-1] + E[t]) / 2
+        corrected[t] = trapezoid[t] - (beta[t-1] - beta[t])^2 (V[t-1] - V[t]) / 12       (Friel, Hurn and Wyse 2014)
+    with "trapezoid_se" / "corrected_se", the delete-one-group jackknife over the groups that have draws at both rungs, and
+    "trapezoid_total" / "corrected_total" with their "_se" (jackknifed as a whole over the groups with draws at every rung).
+    float64 on the CPU."""
+    n, a, b, be = _f64(count), _f64(s1), _f64(s2), _f64(beta)
+    T = n.shape[1]
+
+    def pair(mask, t, corrected):
+        with np.errstate(invalid="ignore", divide="ignore"):
+            nn = n[mask][:, [t - 1, t]].sum(0)
+            e = a[mask][:, [t - 1, t]].sum(0) / nn
+            v = b[mask][:, [t - 1, t]].sum(0) / nn - e * e
+            d = be[t - 1] - be[t]
+            return d * (e[0] + e[1]) / 2 - (d * d * (v[0] - v[1]) / 12 if corrected else 0.0)
+
+    out = {}
+    everywhere = (n > 0).all(1)
+    for name, corrected in (("trapezoid", False), ("corrected", True)):
+        used = [(n[:, t - 1] > 0) & (n[:, t] > 0) for t in range(1, T)]
+        out[name] = torch.tensor([pair(u, t, corrected) for t, u in zip(range(1, T), used)], dtype=torch.float64)
+        out[name + "_se"] = torch.tensor([float(_energy_jackknife(lambda m, t=t: pair(m, t, corrected), u))
+                                          for t, u in zip(range(1, T), used)], dtype=torch.float64)
+        out[name + "_total"] = float(out[name].sum())
+        out[name + "_total_se"] = (float(_energy_jackknife(lambda m: sum(pair(m, t, corrected) for t in range(1, T)), everywhere))
+                                   if T > 1 else float("nan"))
+    return out
+
+
+class LadderEnergies:
+    """Estimates from the pooled log-density sums along the ladder (include/ptrwm.h ptrwm_energy_args, csrc/energy.h): the
+    normalising-constant ratios log Z(beta_a) / Z(beta_b), Z(beta) = integral of pi(x)^beta dx, by stepping stones in both
+    directions and by thermodynamic integration, and the mean, variance and heat capacity of l = log pi per rung.  The host class
+    calls `_check_energy_ctor` in its constructor, passes `_energy_kwargs()` to EngineRun and owns `_run`.  Every read
+    synchronises; results are CPU tensors.
+
+    The keywords: energy=True; a snapshot every energy_every-th step past burn-in; energy_groups (1..64, default 16) disjoint
+    groups of chains, by global replica id, for the jackknife error bars - they hold whatever the chains' autocorrelation in
+    time, and need at least two groups with draws; energy_ref, a scalar or [n_temps], pins the level the exponential sums are
+    taken against (default: the largest finite log-density of each rung at the first snapshot), which shards must share for
+    their sums to add directly.  With one temperature only the moments mean something."""
+
+    def _check_energy_ctor(self, energy, energy_every, energy_groups, energy_ref) -> None:
+        """The constructor's arguments, checked before anything is built (no GPU needed)."""
+        check_energy_args(energy, energy_every, energy_groups, energy_ref)
+        self._energy_on, self._energy_args = bool(energy), (energy_every, energy_groups, energy_ref)
+
+    def _energy_kwargs(self) -> dict:
+        """EngineRun's arguments."""
+        if not self._energy_on:
+            return {}
+        every, groups, ref = self._energy_args
+        return {"energy": True, "energy_every": every, "energy_groups": groups, "energy_ref": ref}
+
+    def _energy_data(self) -> dict:
+        if not getattr(self, "_energy_on", False):
+            raise RuntimeError("the log-density sums are off: construct the sampler with energy=True")
+        run = getattr(self, "_run", None)
+        if run is None or run.energy_sums() is None:  # nothing run yet, or reset(): empty sums
+            G, T = int(self._energy_args[1]), len(getattr(self, "beta_ladder", [1.0]))
+            z = torch.zeros(G, T, dtype=torch.float64)
+            return {"count": torch.zeros(G, T, dtype=torch.int64), "s1": z, "s2": z, "colder": z, "hotter": z,
+                    "nonfinite": torch.zeros(1, dtype=torch.int64), "ref": torch.zeros(T, dtype=torch.float64),
+                    "ref_set": torch.zeros(1, dtype=torch.int32),
+                    "beta": torch.tensor(list(getattr(self, "beta_ladder", [1.0])), dtype=torch.float32)}
+        return {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in run.energy_sums().items()}
+
+    @property
+    def energy_count(self) -> torch.Tensor:
+        """Finite log-densities accumulated per rung, over every group: int64 [n_temps]."""
+        return self._energy_data()["count"].sum(0)
+
+    def _energy_moments(self) -> dict:
+        a = self._energy_data()
+        return energy_moments_from_sums(a["count"], a["s1"], a["s2"], a["beta"])
+
+    def mean_energy(self) -> torch.Tensor:
+        """The mean of l = log pi per rung, pooled over every replica and snapshot: float64 [n_temps]."""
+        return self._energy_moments()["mean"]
+
+    def energy_variance(self) -> torch.Tensor:
+        """The variance of l per rung (divided by n): float64 [n_temps]."""
+        return self._energy_moments()["variance"]
+
+    def heat_capacity(self) -> torch.Tensor:
+        """beta^2 Var_beta(l) per rung: where it peaks, the ladder needs rungs.  float64 [n_temps]."""
+        return self._energy_moments()["heat_capacity"]
+
+    def _energy_estimate(self, method: str) -> tuple:
+        if method not in ENERGY_METHODS:
+            raise ValueError(f"method must be one of {ENERGY_METHODS}, got {method!r}")
+        a = self._energy_data()
+        if method in ("forward", "reverse"):
+            return stepping_stones_from_sums(a["count"], a["colder"], a["hotter"], a["ref"], a["beta"]), method
+        return (thermodynamic_integral_from_sums(a["count"], a["s1"], a["s2"], a["beta"]),
+                "trapezoid" if method == "thermodynamic" else "corrected")
+
+    def log_normalizer_ratios(self, method: str = "forward") -> tuple:
+        """(values, se), float64 [n_temps - 1] each: entry t - 1 estimates log Z(beta[t-1]) / Z(beta[t]) by `method` -
+        "forward" / "reverse" (stepping stones from the hotter / the colder rung's draws; in expectation they bracket the
+        truth from below / above), "thermodynamic" (trapezoid) or "thermodynamic_corrected" - with its jackknife standard error."""
+        est, key = self._energy_estimate(method)
+        return est[key], est[key + "_se"]
+
+    def log_normalizer_ratio(self, method: str = "forward") -> tuple:
+        """(total, se): log Z(beta[0]) / Z(beta[n_temps-1]) by `method`, the sum over the ladder, with its jackknife standard error."""
+        est, key = self._energy_estimate(method)
+        return est[key + "_total"], est[key + "_total_se"]
+
+    def _energy_diagnostics(self) -> dict:
+        if not getattr(self, "_energy_on", False):
+            return {}
+        a = self._energy_data()
+        st = stepping_stones_from_sums(a["count"], a["colder"], a["hotter"], a["ref"], a["beta"])
+        return {"log_z_ratio_forward": st["forward_total"], "log_z_ratio_reverse": st["reverse_total"],
+                "log_z_ratio_se": max(st["forward_total_se"], st["reverse_total_se"]) if not (
+                    np.isnan(st["forward_total_se"]) or np.isnan(st["reverse_total_se"])) else float("nan"),
+                "energy_nonfinite": int(a["nonfinite"][0]), "energy_overflow": st["overflow"]}
 
 
 # ---- pooled marginal histograms of the drop-in classes -------------------------------------------------------------

@@ -32,7 +32,7 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import (Autocorrelation, EngineRun, LadderAdaptation, MarginalHistograms, PosteriorCovariance,
+from ._engine_core import (Autocorrelation, EngineRun, LadderAdaptation, LadderEnergies, MarginalHistograms, PosteriorCovariance,
                            PosteriorMoments, Preconditioning, ScaleAdaptation, check_class_starts, moments_temps, resolve_device)
 from .sharding import flow_round_trip_rate, flow_up_fraction
 
@@ -47,8 +47,8 @@ def geometric_beta_ladder(n_temps: int, beta_min: float = 0.01) -> list:
     return [float(beta_min ** (t / (n_temps - 1))) for t in range(n_temps)]
 
 
-class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, PosteriorCovariance, ScaleAdaptation,
-                                         Preconditioning, LadderAdaptation, MHAlgorithm):
+class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, PosteriorCovariance, LadderEnergies,
+                                         ScaleAdaptation, Preconditioning, LadderAdaptation, MHAlgorithm):
     def __init__(self, dim: int, var: float, target_dist=None, symmetric: bool = True, beta_ladder: list = None,
                  iterative_temp_spacing: bool = False, geom_temp_spacing: bool = False,
                  swap_acceptance_rate: float = 0.234, beta_min_iterative: float = 0.01, N_samples_swap_est: int = 3000,
@@ -71,7 +71,8 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
                  acf_ring_limit: Optional[int] = None, cov: Optional[str] = None, cov_every: int = 1,
                  proposal_cov=None, adapt_cov: bool = False, cov_adapt_every: int = 200,
                  cov_adapt_until: Optional[int] = None, cov_adapt_probe_every: Optional[int] = None,
-                 cov_adapt_memory: float = 0.5, cov_adapt_jitter: float = 1e-6, cov_adapt_min_count: Optional[float] = None):
+                 cov_adapt_memory: float = 0.5, cov_adapt_jitter: float = 1e-6, cov_adapt_min_count: Optional[float] = None,
+                 energy: bool = False, energy_every: int = 1, energy_groups: int = 16, energy_ref=None):
         super().__init__(dim, var, target_dist, symmetric)
         # The optional blocks, checked before anything is built.  What the keywords of each mean stands once, in the docstring of
         # the mixin that owns them (algorithms/_engine_core.py): ScaleAdaptation, MarginalHistograms, Autocorrelation,
@@ -83,6 +84,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
         self._check_hist_ctor(dim, hist, hist_range, hist_bins, hist_every)
         self._check_acf_ctor(dim, acf, acf_every, acf_max_lag, acf_ring_limit)
         self._check_cov_ctor(cov, cov_every)
+        self._check_energy_ctor(energy, energy_every, energy_groups, energy_ref)
         self._check_precond_ctor(dim, burn_in, proposal_cov, adapt_cov, proposal_distribution, dtype,
                                  cov_adapt_every=cov_adapt_every, cov_adapt_until=cov_adapt_until,
                                  cov_adapt_probe_every=cov_adapt_probe_every, cov_adapt_memory=cov_adapt_memory,
@@ -283,6 +285,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, flow=self._flow_on,
             adapt_sync=self._adapt_sync, **self._hist_kwargs(len(self.beta_ladder)), **self._adapt_kwargs(),
             **self._ladder_kwargs(), **self._acf_kwargs(len(self.beta_ladder)), **self._cov_kwargs(len(self.beta_ladder)),
+            **self._energy_kwargs(),
             **self._precond_kwargs())
         # reference shapes for one ladder: [T, dim] / [T]; with replicas: [R, T, dim] / [R, T]
         self.current_states = self._run.state[0] if self.num_replicas == 1 else self._run.state
@@ -525,6 +528,7 @@ class ParallelTemperingRWM_GPU_Optimized(PosteriorMoments, MarginalHistograms, A
             **self._hist_diagnostics(),
             **self._acf_diagnostics(),
             **self._cov_diagnostics(),
+            **self._energy_diagnostics(),
             **self._precond_diagnostics(),
             **self._adapt_diagnostics(),
             **self._ladder_diagnostics(),

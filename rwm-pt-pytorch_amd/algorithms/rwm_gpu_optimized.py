@@ -22,7 +22,7 @@ import ptrwm_hip
 from interfaces import MHAlgorithm, TargetDistribution, TorchTargetDistribution
 from proposal_distributions import LaplaceProposal, NormalProposal, ProposalDistribution, UniformRadiusProposal
 
-from ._engine_core import (Autocorrelation, EngineRun, MarginalHistograms, PosteriorCovariance, PosteriorMoments,
+from ._engine_core import (Autocorrelation, EngineRun, LadderEnergies, MarginalHistograms, PosteriorCovariance, PosteriorMoments,
                            Preconditioning, ScaleAdaptation, check_class_starts, moments_temps, resolve_device)
 
 
@@ -53,7 +53,7 @@ def _rebuild_proposal(p: ProposalDistribution, dim, beta, device, dtype, rng):
     )
 
 
-class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, PosteriorCovariance, ScaleAdaptation,
+class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorrelation, PosteriorCovariance, LadderEnergies, ScaleAdaptation,
                                  Preconditioning, MHAlgorithm):
     def __init__(self, dim: int, var: float = None, target_dist=None, symmetric: bool = True, beta: float = 1.0,
                  burn_in: int = 0, device: str = None, pre_allocate_steps: int = None, use_efficient_rng: bool = True,
@@ -68,7 +68,8 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
                  acf_every: int = 1, acf_max_lag: int = 32, acf_ring_limit: Optional[int] = None, cov: Optional[str] = None,
                  cov_every: int = 1, proposal_cov=None, adapt_cov: bool = False, cov_adapt_every: int = 200,
                  cov_adapt_until: Optional[int] = None, cov_adapt_probe_every: Optional[int] = None,
-                 cov_adapt_memory: float = 0.5, cov_adapt_jitter: float = 1e-6, cov_adapt_min_count: Optional[float] = None):
+                 cov_adapt_memory: float = 0.5, cov_adapt_jitter: float = 1e-6, cov_adapt_min_count: Optional[float] = None,
+                 energy: bool = False, energy_every: int = 1, energy_groups: int = 16, energy_ref=None):
         moments_temps(moments, 1, moments_every)  # (checked before anything is built)
         if adapt_ladder:
             raise ValueError("adapt_ladder=True tunes a temperature ladder: RandomWalkMH_GPU_Optimized has none "
@@ -83,6 +84,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
         self._check_hist_ctor(dim, hist, hist_range, hist_bins, hist_every)
         self._check_acf_ctor(dim, acf, acf_every, acf_max_lag, acf_ring_limit)
         self._check_cov_ctor(cov, cov_every)
+        self._check_energy_ctor(energy, energy_every, energy_groups, energy_ref)
         self._check_precond_ctor(dim, burn_in, proposal_cov, adapt_cov, proposal_distribution, torch.float32,
                                  cov_adapt_every=cov_adapt_every, cov_adapt_until=cov_adapt_until,
                                  cov_adapt_probe_every=cov_adapt_probe_every, cov_adapt_memory=cov_adapt_memory,
@@ -201,7 +203,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
             chain_offset=self._chain_offset, moments_temps=moments_temps(self._moments_mode, 1, self._moments_every),
             moments_every=self._moments_every, moments_per_chain=self._moments_per_chain, init_box=self._init_box,
             init_attempts=self._init_attempts, adapt_sync=self._adapt_sync, **self._hist_kwargs(1), **self._adapt_kwargs(),
-            **self._acf_kwargs(1), **self._cov_kwargs(1), **self._precond_kwargs(),
+            **self._acf_kwargs(1), **self._cov_kwargs(1), **self._energy_kwargs(), **self._precond_kwargs(),
         )
         self.current_state = self._run.state[0, 0]  # views: always the live values
         self.current_states = self._run.state[:, 0]
@@ -298,6 +300,7 @@ class RandomWalkMH_GPU_Optimized(PosteriorMoments, MarginalHistograms, Autocorre
             **self._hist_diagnostics(),
             **self._acf_diagnostics(),
             **self._cov_diagnostics(),
+            **self._energy_diagnostics(),
             **self._precond_diagnostics(),
             **self._adapt_diagnostics(),
         }

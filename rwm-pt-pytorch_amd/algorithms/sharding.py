@@ -226,6 +226,61 @@ def allreduce_covariance(sampler, group: Optional[dist.ProcessGroup] = None) -> 
     return out
 
 
+ENERGY_SUMS = ("count", "nonfinite", "s1", "s2", "colder", "hotter")
+
+
+def energy_rescale(sums: dict, ref_common) -> dict:
+    """A shard's log-density sums (EngineRun.energy_sums()) taken to the level `ref_common` [n_temps], on the host in float64:
+    colder[:, t] *= exp((beta[t-1] - beta[t]) (ref[t] - ref_common[t])), hotter[:, t] *= exp((beta[t+1] - beta[t]) (ref[t] -
+    ref_common[t])); where the two levels agree - a pinned ref - the factor is exactly 1.  A sum that is zero stays zero.
+    New CPU tensors; the shard's own arrays are not modified."""
+    out = {k: (v.detach().cpu().clone() if torch.is_tensor(v) else v) for k, v in sums.items()}
+    beta, ref = out["beta"].to(torch.float64), out["ref"].to(torch.float64)
+    common = torch.as_tensor(ref_common).detach().cpu().to(torch.float64)
+    shift = ref - common
+    n_temps = beta.numel()
+    if n_temps > 1:
+        for name, to, at in (("colder", slice(0, n_temps - 1), slice(1, n_temps)), ("hotter", slice(1, n_temps), slice(0, n_temps - 1))):
+            factor = torch.exp((beta[to] - beta[at]) * shift[at])
+            cols = out[name][:, at]
+            out[name][:, at] = torch.where(cols != 0, cols * factor, cols)
+    out["ref"] = common
+    return out
+
+
+def allreduce_energy(sampler, group: Optional[dist.ProcessGroup] = None) -> dict:
+    """Whole-job log-density sums along the ladder from every rank's shard.  A tiny MAX all-reduce of `ref` gives the common
+    level (a shard that has not chosen one yet stands aside); every shard rescales its two exponential sums to it on the host
+    (energy_rescale: the identity under a pinned ref); ONE float64 SUM all-reduce of the sums packed into one vector follows
+    (the counts ride as doubles: exact below 2^53).  `sampler`: a sampler constructed with energy=True, its EngineRun, or the
+    dict EngineRun.energy_sums() returns.  Returns new tensors {"count", "nonfinite", "s1", "s2", "colder", "hotter", "ref"} on
+    the shards' device plus "beta" and "every" - what algorithms._engine_core's energy_moments_from_sums,
+    stepping_stones_from_sums and thermodynamic_integral_from_sums take; the shard's own arrays are not modified."""
+    a = sampler
+    if not isinstance(a, dict):
+        run = getattr(sampler, "_run", sampler)
+        a = run.energy_sums() if run is not None and hasattr(run, "energy_sums") else None
+        if a is None:
+            raise RuntimeError("allreduce_energy: the log-density sums are off, or nothing has run yet")
+    device = a["count"].device
+    chosen = bool(int(torch.as_tensor(a["ref_set"]).reshape(-1)[0]) != 0)
+    ref = a["ref"].detach().to(torch.float64).clone() if chosen else torch.full_like(a["ref"], float("-inf"), dtype=torch.float64)
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(ref, op=dist.ReduceOp.MAX, group=group)
+    ref = torch.where(torch.isinf(ref), torch.zeros_like(ref), ref)  # (no shard has chosen: nothing has been added anywhere)
+    mine = energy_rescale(a, ref)
+    parts = [mine[k] for k in ENERGY_SUMS]
+    vec = torch.cat([p.reshape(-1).to(torch.float64) for p in parts]).to(device)
+    if dist.is_available() and dist.is_initialized():
+        dist.all_reduce(vec, op=dist.ReduceOp.SUM, group=group)
+    out, at = {"ref": ref.to(device), "ref_set": torch.ones(1, dtype=torch.int32, device=device), "beta": a["beta"],
+               "every": a.get("every")}, 0
+    for k, p in zip(ENERGY_SUMS, parts):
+        out[k] = vec[at:at + p.numel()].view(p.shape).to(p.dtype)
+        at += p.numel()
+    return out
+
+
 # ---- warm-up tuning of the proposal scale and of the ladder (include/ptrwm.h ptrwm_adapt_args, ptrwm_ladder_args) ---------------
 def adaptation_sync(group: Optional[dist.ProcessGroup] = None):
     """The `adapt_sync=` callable of a sharded run, for both tunings: all-reduces (SUM) the pooled int64 counts of a window in

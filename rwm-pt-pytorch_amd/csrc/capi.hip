@@ -7,6 +7,7 @@
 #include "acf.h"
 #include "adapt.h"
 #include "cov.h"
+#include "energy.h"
 #include "ladder.h"
 #include "hist.h"
 #include "precond.h"
@@ -960,6 +961,128 @@ __global__ void __launch_bounds__(kCovThreads, 2) cov_snapshot_kernel(CovSnapArg
   if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) count_add(a.own.count, a.n_chains);
 }
 
+// ---- pooled log-density sums along the ladder (energy.h; include/ptrwm.h ptrwm_energy_args) -----------------------------------------
+// Two kernels behind a due step (ptrwm_energy, and the snapshots of ptrwm_run_with_energy); both only read logp and beta, and
+// both decide on the device whether the step counts (snapshot.h) - the first also whether ref is still to be set - so the pair
+// can sit in a captured block of split steps.  logp is float32 for state_f64 runs too: one instance each.
+struct EnergySnapArgs {
+  const float *logp;  // [n_chains, n_temps]
+  const float *beta;  // [n_temps]
+  double *ref;        // [n_temps]
+  int *ref_set;       // [1]
+  long long *count, *nonfinite;       // [groups, n_temps], [1] or NULL
+  double *s1, *s2, *colder, *hotter;  // [groups, n_temps]
+  long long n_chains, chain_offset, step, burn_in, every;
+  const long long *device_step;
+  int n_temps, groups;
+};
+
+// ref: ONE workgroup, to any effect at most once per run (it need not be fast).  Thread i walks elements i, i + 256, ... of logp
+// and keeps the largest key (energy.h: floats ordered as integers) of the temperature it stands on; the keys meet in LDS by an
+// integer atomic max - a maximum does not depend on the order of evaluation.
+__global__ void __launch_bounds__(kEnergyThreads) energy_ref_kernel(EnergySnapArgs a) {
+  if (!snapshot_step_due(a.step, a.device_step, a.burn_in, a.every)) return;
+  if (*a.ref_set != 0) return;  // (workgroup-uniform: nobody writes the flag in front of the barriers below)
+  __shared__ int s_key[PTRWM_MAX_TEMPS];
+  const int tid = (int)threadIdx.x, T = a.n_temps;
+  for (int t = tid; t < T; t += kEnergyThreads) s_key[t] = kEnergyNoKey;
+  __syncthreads();
+  const long long n = a.n_chains * T;
+  const int stride_t = kEnergyThreads % T;
+  int t = tid % T, cur = t, best = kEnergyNoKey;  // (t == e % T throughout)
+  for (long long e = tid; e < n; e += kEnergyThreads) {
+    if (t != cur) {
+      if (best != kEnergyNoKey) atomicMax(&s_key[cur], best);
+      cur = t, best = kEnergyNoKey;
+    }
+    const float l = a.logp[e];
+    if (energy_finite(l)) {
+      const int key = energy_key(l);
+      best = key > best ? key : best;
+    }
+    t += stride_t;
+    if (t >= T) t -= T;
+  }
+  if (best != kEnergyNoKey) atomicMax(&s_key[cur], best);
+  __syncthreads();
+  for (int u = tid; u < T; u += kEnergyThreads) a.ref[u] = energy_ref_of(s_key[u]);
+  if (tid == 0) *a.ref_set = 1;
+}
+
+// The sums: a workgroup serves one group's chains (blockIdx.y) and a tile of them (blockIdx.x), energy.h's geometry.  A thread
+// keeps the five partial sums of the temperature its elements stand on in registers - for the whole tile where n_temps divides
+// the workgroup - and adds them to the workgroup's LDS table when they move on; one atomic per non-zero (workgroup, sum,
+// temperature) flushes.
+__global__ void __launch_bounds__(kEnergyThreads) energy_snapshot_kernel(EnergySnapArgs a) {
+  if (!snapshot_step_due(a.step, a.device_step, a.burn_in, a.every)) return;
+  const int tid = (int)threadIdx.x, T = a.n_temps, G = a.groups, g = (int)blockIdx.y;
+  const long long members = energy_group_chains(a.n_chains, a.chain_offset, G, g);
+  const int n = energy_tile_elems((long long)blockIdx.x, members, T);  // (1 .. tile_chains * n_temps <= max(kEnergyTileElems, n_temps))
+  if (n == 0) return;  // (workgroup-uniform: the tile lies behind the group's last chain)
+  __shared__ double s_sum[4][PTRWM_MAX_TEMPS];  // s1, s2, colder, hotter
+  __shared__ unsigned long long s_cnt[PTRWM_MAX_TEMPS];
+  __shared__ double s_ref[PTRWM_MAX_TEMPS], s_dc[PTRWM_MAX_TEMPS], s_dh[PTRWM_MAX_TEMPS];
+  __shared__ unsigned s_bad;
+  for (int t = tid; t < T; t += kEnergyThreads) {
+    s_sum[0][t] = s_sum[1][t] = s_sum[2][t] = s_sum[3][t] = 0.0;
+    s_cnt[t] = 0ull;
+    s_ref[t] = a.ref[t];
+    s_dc[t] = t >= 1 ? (double)a.beta[t - 1] - (double)a.beta[t] : 0.0;
+    s_dh[t] = t <= T - 2 ? (double)a.beta[t + 1] - (double)a.beta[t] : 0.0;
+  }
+  if (tid == 0) s_bad = 0u;
+  __syncthreads();
+  const long long first = energy_first_chain(a.chain_offset, G, g);
+  const long long m0 = (long long)blockIdx.x * energy_tile_chains(T);
+  const int stride_t = kEnergyThreads % T, stride_k = kEnergyThreads / T;
+  int t = tid % T, k = tid / T;  // (t == e % T, k == e / T throughout: energy_elem_temp, energy_elem_member)
+  int cur = t;
+  unsigned cnt = 0u, bad = 0u;
+  double v1 = 0.0, v2 = 0.0, vc = 0.0, vh = 0.0;
+  const auto park = [&]() {
+    if (cnt == 0u) return;
+    atomicAdd(&s_cnt[cur], (unsigned long long)cnt);
+    atomicAdd(&s_sum[0][cur], v1);
+    atomicAdd(&s_sum[1][cur], v2);
+    if (cur >= 1) atomicAdd(&s_sum[2][cur], vc);
+    if (cur <= T - 2) atomicAdd(&s_sum[3][cur], vh);
+  };
+  for (int e = tid; e < n; e += kEnergyThreads) {
+    if (t != cur) {
+      park();
+      cur = t, cnt = 0u, v1 = v2 = vc = vh = 0.0;
+    }
+    const long long c = first + (m0 + k) * G;  // (m0 + k < members: c < n_chains)
+    const float l = a.logp[c * T + t];
+    if (energy_finite(l)) {
+      const double x = (double)l, y = x - s_ref[t];
+      ++cnt;
+      v1 += x;
+      v2 += x * x;
+      if (t >= 1) vc += exp(s_dc[t] * y);
+      if (t <= T - 2) vh += exp(s_dh[t] * y);
+    } else {
+      ++bad;
+    }
+    t += stride_t, k += stride_k;
+    if (t >= T) t -= T, ++k;
+  }
+  park();
+  if (bad != 0u) atomicAdd(&s_bad, bad);
+  __syncthreads();
+  const long long row = (long long)g * T;
+  for (int u = tid; u < T; u += kEnergyThreads) {
+    const unsigned long long c = s_cnt[u];
+    if (c == 0ull) continue;
+    count_add(&a.count[row + u], (long long)c);
+    if (s_sum[0][u] != 0.0) unsafeAtomicAdd(&a.s1[row + u], s_sum[0][u]);
+    if (s_sum[1][u] != 0.0) unsafeAtomicAdd(&a.s2[row + u], s_sum[1][u]);
+    if (u >= 1 && s_sum[2][u] != 0.0) unsafeAtomicAdd(&a.colder[row + u], s_sum[2][u]);
+    if (u <= T - 2 && s_sum[3][u] != 0.0) unsafeAtomicAdd(&a.hotter[row + u], s_sum[3][u]);
+  }
+  if (tid == 0 && s_bad != 0u && a.nonfinite != nullptr) count_add(a.nonfinite, (long long)s_bad);
+}
+
 // ---- preconditioned Gaussian proposals (precond.h; include/ptrwm.h ptrwm_split_propose_precond) -----------------------------------
 // ptrwm_split_propose's job for the Normal proposal with increments s_t L z: one run-time-dim kernel.  Geometry and index maps in
 // precond.h.  A workgroup stages the factor into LDS once - zeros above the diagonal and in the pad; the caller's strict upper
@@ -1554,6 +1677,43 @@ static int32_t launch_cov(const ptrwm_run_args *args, int32_t dim, const ptrwm_c
                          kCovThreads, (size_t)g.lds_bytes, stream, a);
 }
 
+// the checks of the log-density sums shared by ptrwm_run_with_energy and ptrwm_energy (args already checked); none: ok
+static int32_t check_energy(const ptrwm_run_args *args, const ptrwm_energy_args *en) {
+  if (en == nullptr) return PTRWM_OK;
+  if (en->struct_size != sizeof(ptrwm_energy_args)) return PTRWM_E_STRUCT;
+  if (en->groups < 1 || en->groups > PTRWM_ENERGY_MAX_GROUPS || en->every < 1) return PTRWM_E_ARG;
+  if (en->ref == nullptr || en->ref_set == nullptr || en->count == nullptr || en->s1 == nullptr || en->s2 == nullptr) return PTRWM_E_NULL;
+  if (args->n_temps >= 2 && (en->colder == nullptr || en->hotter == nullptr)) return PTRWM_E_NULL;
+  return PTRWM_OK;
+}
+static_assert(PTRWM_ENERGY_MAX_GROUPS == kEnergyMaxGroups && PTRWM_MAX_TEMPS == kEnergyMaxTemps, "energy.h and include/ptrwm.h: one set of limits");
+
+// One snapshot of logp after step `step` (device_step != NULL: *device_step + step): the ref kernel, then the sums; everything
+// checked, logp and beta there (`dim`: unused - the signature of the snapshot launchers, snapshot.h)
+static int32_t launch_energy(const ptrwm_run_args *args, int32_t /*dim*/, const ptrwm_energy_args *en, long long step,
+                             const long long *device_step, hipStream_t stream) {
+  EnergySnapArgs a;
+  a.logp = args->logp;
+  a.beta = args->beta;
+  a.ref = en->ref;
+  a.ref_set = en->ref_set;
+  a.count = (long long *)en->count;
+  a.nonfinite = (long long *)en->nonfinite;
+  a.s1 = en->s1, a.s2 = en->s2, a.colder = en->colder, a.hotter = en->hotter;
+  a.n_chains = args->n_chains;
+  a.chain_offset = args->chain_offset;
+  a.step = step;
+  a.burn_in = args->burn_in;
+  a.every = en->every;
+  a.device_step = device_step;
+  a.n_temps = args->n_temps;
+  a.groups = en->groups;
+  const EnergyGeometry g = energy_geometry(args->n_temps, args->n_chains, args->chain_offset, en->groups);
+  if (int rc = launch_snapshot(energy_ref_kernel, energy_ref_kernel, false, 1, 1u, kEnergyThreads, 0, stream, a)) return rc;
+  return launch_snapshot(energy_snapshot_kernel, energy_snapshot_kernel, false, g.tiles, (unsigned)g.groups /* <= 64 */, kEnergyThreads, 0,
+                         stream, a);
+}
+
 // the adaptation checks shared by ptrwm_run_with_adaptation, ptrwm_adapt_reduce and ptrwm_adapt_update (none: ok); what
 // needs the run (until <= burn_in, temp_scale == proposal->temp_scale) is checked by run_impl itself (tuning_fits_run)
 static int32_t check_tuning(const ptrwm_adapt_args *ad) {
@@ -1678,6 +1838,7 @@ struct RunBlocks {
   const ptrwm_ladder_args *ladder = nullptr;
   const ptrwm_acf_args *acf = nullptr;
   const ptrwm_cov_args *cov = nullptr;
+  const ptrwm_energy_args *energy = nullptr;
 };
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                         const RunBlocks &blocks, void *hip_stream);
@@ -1873,6 +2034,14 @@ int32_t ptrwm_run_with_covariance(const ptrwm_target_desc *target, const ptrwm_p
   return run_with_blocks(target, proposal, args, moments, chain_moments, {{}, flow, hist, adapt, ladder, acf, cov}, stream);
 }
 
+int32_t ptrwm_run_with_energy(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
+                              const ptrwm_moments_args *moments, const ptrwm_chain_moments_args *chain_moments,
+                              const ptrwm_flow_args *flow, const ptrwm_hist_args *hist, const ptrwm_adapt_args *adapt,
+                              const ptrwm_ladder_args *ladder, const ptrwm_acf_args *acf, const ptrwm_cov_args *cov,
+                              const ptrwm_energy_args *energy, void *stream) {
+  return run_with_blocks(target, proposal, args, moments, chain_moments, {{}, flow, hist, adapt, ladder, acf, cov, energy}, stream);
+}
+
 int32_t ptrwm_ladder_probe(const ptrwm_run_args *args, const ptrwm_ladder_args *ladder, void *stream) {
   if (int rc = check_tuning_call(ladder, true, args, 0, 0)) return rc;
   if (args->n_temps < 3 || ladder->beta != args->beta) return PTRWM_E_ARG;
@@ -1897,6 +2066,19 @@ int32_t ptrwm_autocorr(const ptrwm_run_args *args, int32_t dim, const ptrwm_acf_
 
 int32_t ptrwm_covariance(const ptrwm_run_args *args, int32_t dim, const ptrwm_cov_args *cov, void *stream) {
   return snapshot_call<check_cov, launch_cov>(args, dim, cov, stream);
+}
+
+int32_t ptrwm_energy(const ptrwm_run_args *args, const ptrwm_energy_args *energy, void *stream) {
+  if (args == nullptr || energy == nullptr) return PTRWM_E_NULL;
+  if (!has_abi_size(args)) return PTRWM_E_STRUCT;
+  if (!temps_in_range(args->n_temps)) return PTRWM_E_TEMPS;
+  if (args->n_chains < 0 || args->step0 < 0 || args->burn_in < 0) return PTRWM_E_ARG;
+  if (int rc = check_energy(args, energy)) return rc;
+  if (args->n_chains == 0) return PTRWM_OK;
+  if (args->logp == nullptr || args->beta == nullptr) return PTRWM_E_NULL;
+  if (args->device_step == nullptr && !periodic_step_due(args->step0 + 1, args->burn_in, energy->every))
+    return PTRWM_OK;  // (known on the host: no snapshot is due)
+  return launch_energy(args, 0, energy, args->step0, (const long long *)args->device_step, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -2098,7 +2280,7 @@ static KArgs fill_kargs(const ptrwm_target_desc *target, const ptrwm_proposal_de
 
 static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_desc *proposal, const ptrwm_run_args *args,
                         const RunBlocks &blocks, void *hip_stream) {
-  const auto &[spec, flow, hist, adapt, ladder, acf, cov] = blocks;
+  const auto &[spec, flow, hist, adapt, ladder, acf, cov, energy] = blocks;
   bool empty = false;
   if (int rc = check_run(target, proposal, args, spec, flow, hist, &empty)) return rc;
   // the two tunings (adapt.h, ladder.h): their own checks after the existing ones, all before anything is enqueued
@@ -2111,6 +2293,7 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   }
   if (int rc = check_acf(args, acf)) return rc;  // (the autocovariance: after every existing block's checks)
   if (int rc = check_cov(args, cov)) return rc;  // (the covariance: after those)
+  if (int rc = check_energy(args, energy)) return rc;  // (the log-density sums: after those)
   if (empty) return PTRWM_OK;
   // (every = 0: no such tuning, schedule.h)
   const WarmupWindows scale_w = adapt != nullptr ? WarmupWindows{adapt->every, adapt->until} : WarmupWindows{0, 0};
@@ -2136,7 +2319,8 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
   for (long long done = 0; done < args->n_steps; done += k.n_steps) {
     // (a launch also ends at the nearest due step of a snapshot block, each at its own period: snapshot.h)
     const long long s0 = args->step0 + done, b0 = args->burn_in;
-    const long long to_snap = std::min({steps_to_snapshot(hist, s0, b0, cap), steps_to_snapshot(acf, s0, b0, cap), steps_to_snapshot(cov, s0, b0, cap)});
+    const long long to_snap = std::min({steps_to_snapshot(hist, s0, b0, cap), steps_to_snapshot(acf, s0, b0, cap), steps_to_snapshot(cov, s0, b0, cap),
+                                        steps_to_snapshot(energy, s0, b0, cap)});
     // (the tunings, schedule.h warmup_launch_at: a launch inside an adapting window of the scale ends with the window at the
     // latest - the reduce and update kernels run between two launches - and is the production kernel told to count from its
     // first step, into the window scratch, and that no multiple of swap_every lies in it: count_on holds and swap_due never
@@ -2166,11 +2350,13 @@ static int32_t run_impl(const ptrwm_target_desc *target, const ptrwm_proposal_de
       k.full.steps_to_mom = countdown(cut.steps_to_mom);
     }
     if (c.fn(k, c.n_blocks, c.mode, (hipStream_t)hip_stream) != hipSuccess) return PTRWM_E_LAUNCH;
-    // (whatever snapshot is due behind this cut: histogram, autocovariance, covariance, in front of the tunings' kernels)
+    // (whatever snapshot is due behind this cut: histogram, autocovariance, covariance, log-density sums, in front of the
+    // tunings' kernels)
     const long long sc = cut.step0 + cut.n;
     if (int rc = snapshot_if_due<launch_hist>(hist, args, target->dim, sc, (hipStream_t)hip_stream)) return rc;
     if (int rc = snapshot_if_due<launch_acf>(acf, args, target->dim, sc, (hipStream_t)hip_stream)) return rc;
     if (int rc = snapshot_if_due<launch_cov>(cov, args, target->dim, sc, (hipStream_t)hip_stream)) return rc;
+    if (int rc = snapshot_if_due<launch_energy>(energy, args, target->dim, sc, (hipStream_t)hip_stream)) return rc;
     if (wl.scale_reduce)
       if (int rc = launch_adapt_reduce(adapt, args->n_chains, args->n_temps, (hipStream_t)hip_stream)) return rc;
     if (wl.scale_update)

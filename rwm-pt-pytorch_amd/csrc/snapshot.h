@@ -59,14 +59,14 @@ inline int32_t launch_snapshot(void (*of_float)(Args), void (*of_double)(Args), 
   return hipGetLastError() == hipSuccess ? PTRWM_OK : PTRWM_E_LAUNCH;
 }
 
-// ptrwm_run's launch loop (block: a ptrwm_hist_args, ptrwm_acf_args or ptrwm_cov_args, or NULL - none): a launch ends at every
+// ptrwm_run's launch loop (block: a ptrwm_hist_args, ptrwm_acf_args, ptrwm_cov_args or ptrwm_energy_args, or NULL - none): a launch ends at every
 // due step of a block, since the snapshot kernel reads the state between launches ...
 template <class Block>
 inline long long steps_to_snapshot(const Block *b, long long step0, long long burn_in, long long cap) {
   return b != nullptr ? std::min(cap, steps_to_next_due(step0, burn_in, b->every)) : cap;
 }
 // ... and behind a launch whose last step has counter `sc`, the block's snapshot if that step is due (Launch: launch_hist,
-// launch_acf or launch_cov of capi.hip)
+// launch_acf, launch_cov or launch_energy of capi.hip)
 template <auto Launch, class Block>
 inline int32_t snapshot_if_due(const Block *b, const ptrwm_run_args *args, int32_t dim, long long sc, hipStream_t stream) {
   if (b == nullptr || !periodic_step_due(sc, args->burn_in, b->every)) return PTRWM_OK;

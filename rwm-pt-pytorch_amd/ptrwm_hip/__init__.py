@@ -239,6 +239,26 @@ class CovArgs(C.Structure):
     ]
 
 
+class EnergyArgs(C.Structure):
+    """ptrwm_energy_args: pooled log-density sums along the ladder, per group of chains (include/ptrwm.h, csrc/energy.h)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("groups", C.c_int32),
+        ("every", C.c_int32),
+        ("ref", C.c_void_p),
+        ("ref_set", C.c_void_p),
+        ("count", C.c_void_p),
+        ("nonfinite", C.c_void_p),
+        ("s1", C.c_void_p),
+        ("s2", C.c_void_p),
+        ("colder", C.c_void_p),
+        ("hotter", C.c_void_p),
+    ]
+
+
+ENERGY_MAX_GROUPS = 64
+
+
 class PrecondArgs(C.Structure):
     """ptrwm_precond_args: the factor of a preconditioned Normal proposal (include/ptrwm.h, csrc/precond.h)."""
     _fields_ = [
@@ -341,6 +361,12 @@ SYMBOLS = {
          C.POINTER(FlowArgs), C.POINTER(HistArgs), C.POINTER(AdaptArgs), C.POINTER(LadderArgs), C.POINTER(AcfArgs),
          C.POINTER(CovArgs), C.c_void_p]),
     "ptrwm_covariance": (C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.POINTER(CovArgs), C.c_void_p]),
+    "ptrwm_run_with_energy": (
+        C.c_int32,
+        [C.POINTER(TargetDesc), C.POINTER(ProposalDesc), C.POINTER(RunArgs), C.POINTER(MomentsArgs), C.POINTER(ChainMomentsArgs),
+         C.POINTER(FlowArgs), C.POINTER(HistArgs), C.POINTER(AdaptArgs), C.POINTER(LadderArgs), C.POINTER(AcfArgs),
+         C.POINTER(CovArgs), C.POINTER(EnergyArgs), C.c_void_p]),
+    "ptrwm_energy": (C.c_int32, [C.POINTER(RunArgs), C.POINTER(EnergyArgs), C.c_void_p]),
     "ptrwm_swap_sweep_with_flow": (
         C.c_int32, [C.POINTER(RunArgs), C.c_int32, C.c_int64, C.c_int32, C.POINTER(FlowArgs), C.c_void_p]),
     "ptrwm_split_accept_with_flow": (
@@ -755,6 +781,7 @@ class RunPlan:
         self._ladder = None  # warm-up tuning of the temperature ladder: (struct, byref, tensors)
         self._acf = None  # pooled lagged autocovariance: (struct, byref, tensors)
         self._cov = None  # pooled posterior covariance: (struct, byref, tensors)
+        self._energy = None  # pooled log-density sums along the ladder: (struct, byref, tensors)
         self._precond = None  # preconditioned proposals: (struct, byref, tensors)
         self._precond_update = None  # warm-up tuning of the factor, the update: (struct, byref, tensors)
         self._precond_probe = None  # ... and its probe, a covariance block of temperature 0: (struct, byref, tensors)
@@ -764,9 +791,9 @@ class RunPlan:
     _MOMENT_KINDS = {"pooled": ("moments", MomentsArgs, "ptrwm_run_with_moments", "ptrwm_split_moments"),
                      "chain": ("chain moments", ChainMomentsArgs, "ptrwm_run_with_chain_moments", "ptrwm_split_chain_moments")}
 
-    # launch(): the first entry point that takes _flow, _hist, _adapt, _ladder, _acf, _cov - in this order - and all before it
+    # launch(): the first entry point that takes _flow, _hist, _adapt, _ladder, _acf, _cov, _energy - in this order - and all before it
     _RUN_WITH = ("ptrwm_run_with_diagnostics", "ptrwm_run_with_histogram", "ptrwm_run_with_adaptation", "ptrwm_run_with_ladder",
-                 "ptrwm_run_with_autocorr", "ptrwm_run_with_covariance")
+                 "ptrwm_run_with_autocorr", "ptrwm_run_with_covariance", "ptrwm_run_with_energy")
 
     def _bind_moments(self, kind, lead, sum, sum_sq, sum_logp, count, every) -> None:
         """The one accumulator of the plan: ``sum`` / ``sum_sq`` are [*lead, temps, dim], ``sum_logp`` [*lead, temps],
@@ -873,11 +900,12 @@ class RunPlan:
 
     def split_snapshots(self, step: int) -> None:
         """Every accumulator bound, behind the split step ``step`` just performed: moments, histogram, autocovariance,
-        covariance, in this order (the library skips the steps that are not due)."""
+        covariance, log-density sums, in this order (the library skips the steps that are not due)."""
         self.split_moments(step)
         self.split_histogram(step)
         self.split_autocorr(step)
         self.split_covariance(step)
+        self.split_energy(step)
 
     def set_histogram(self, counts: Optional[torch.Tensor], lo: Optional[torch.Tensor] = None,
                       scale: Optional[torch.Tensor] = None, *, n_bins: int = 0, temps: int = 0, every: int = 1,
@@ -979,6 +1007,55 @@ class RunPlan:
         No-op without an accumulator."""
         if self._cov is not None:
             self._split_call("ptrwm_covariance", self._cov[1], step)
+
+    def set_energy(self, count: Optional[torch.Tensor], s1: Optional[torch.Tensor] = None, s2: Optional[torch.Tensor] = None,
+                   colder: Optional[torch.Tensor] = None, hotter: Optional[torch.Tensor] = None, *,
+                   ref: Optional[torch.Tensor] = None, ref_set: Optional[torch.Tensor] = None,
+                   nonfinite: Optional[torch.Tensor] = None, every: int = 1) -> None:
+        """Accumulate the pooled log-density sums along the ladder (include/ptrwm.h ptrwm_energy_args) in every following
+        ``launch`` and ``split_energy``: ``count`` [groups, n_temps] int64, ``s1`` / ``s2`` / ``colder`` / ``hotter``
+        [groups, n_temps] float64 (the last two may be None with one temperature), ``ref`` [n_temps] float64 and ``ref_set``
+        [1] int32 (0: the first due snapshot sets ``ref``; pre-set to pin it), ``nonfinite`` [1] int64 (optional), all on the
+        run's device; the sums are added to (+=).  ``groups`` (1..64) is read off ``count``.  ``launch`` then ends a kernel
+        launch at every due step and enqueues the two kernels behind it.  ``set_energy(None)`` switches it off."""
+        if count is None:
+            self._energy = None
+            return
+        T = self.shape[1]
+        if count.dim() != 2 or count.shape[1] != T:
+            raise ValueError(f"energy count must be [groups, {T}]")
+        groups, every = int(count.shape[0]), int(every)
+        if not 1 <= groups <= ENERGY_MAX_GROUPS:
+            raise ValueError(f"energy groups must be in 1..{ENERGY_MAX_GROUPS}, got {groups}")
+        if every < 1:
+            raise ValueError("energy every must be >= 1")
+        for name, t in (("s1", s1), ("s2", s2), ("colder", colder), ("hotter", hotter)):
+            if t is None and name in ("colder", "hotter") and T == 1:
+                continue
+            if t is None or tuple(t.shape) != (groups, T):
+                raise ValueError(f"energy {name} must be [{groups}, {T}]")
+        if ref is None or tuple(ref.shape) != (T,):
+            raise ValueError(f"energy ref must be [{T}]")
+        if ref_set is None or tuple(ref_set.shape) != (1,):
+            raise ValueError("energy ref_set must be [1]")
+        if nonfinite is not None and tuple(nonfinite.shape) != (1,):
+            raise ValueError("energy nonfinite must be [1]")
+        self._energy = self._bind_block("energy", EnergyArgs, dict(groups=groups, every=every),
+                                        (("ref", ref, torch.float64), ("ref_set", ref_set, torch.int32), ("count", count, torch.int64),
+                                         ("nonfinite", nonfinite, torch.int64), ("s1", s1, torch.float64), ("s2", s2, torch.float64),
+                                         ("colder", colder, torch.float64), ("hotter", hotter, torch.float64)))
+
+    def split_energy(self, step: int) -> None:
+        """Log-density sums of the state after the split step ``step`` just performed (ptrwm_energy, which takes no dim;
+        device-step mode: counter + step - decided on the device, as is whether ``ref`` is still to be set, so the call can sit
+        in a captured block).  Enqueue after ``split_accept``, behind every step: the library skips the steps that are not due.
+        No-op without an accumulator."""
+        if self._energy is not None:
+            self._a.step0 = step
+            with self._guard:
+                rc = self._lib.ptrwm_energy(self._refs[4], self._energy[1], _stream(self.device))
+            if rc != 0:
+                raise PTRWMError(rc, "ptrwm_energy")
 
     def _tuning_windows(self, what: str, every, until) -> tuple:
         """every, until and K = until // every of a warm-up tuning (`what` starts its messages), checked against the plan"""
@@ -1203,10 +1280,10 @@ class RunPlan:
             if trace is not None and ext_prop is None and ext_u is None and ext_swap_u is None and accept_flags is None:
                 self._last_trace = (trace, trace_logp, trace_every)
         # ptrwm_run, or the accumulator's entry point with its struct in front of the stream; with anything else bound, the
-        # first of ptrwm_run_with_diagnostics / _histogram / _adaptation / _ladder / _autocorr / _covariance that takes all that is bound: each
+        # first of ptrwm_run_with_diagnostics / _histogram / _adaptation / _ladder / _autocorr / _covariance / _energy that takes all that is bound: each
         # takes what the one before it takes and one struct more, behind the two accumulators (pooled, per chain)
         name, opt = ("ptrwm_run", ()) if self._mom is None else (self._MOMENT_KINDS[self._mom[0]][2], (self._mom[2],))
-        blocks = (self._flow, self._hist, self._adapt, self._ladder, self._acf, self._cov)
+        blocks = (self._flow, self._hist, self._adapt, self._ladder, self._acf, self._cov, self._energy)
         if any(b is not None for b in blocks):
             more = [b[1] if b is not None else None for b in blocks]
             last = max(i for i, b in enumerate(more) if b is not None)
